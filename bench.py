@@ -2,32 +2,40 @@
 """bench.py -- Gorp match-and-extract throughput on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--results {auto,narrow,compact,dense}]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (gx_extract_batch: product-DFA match + capture scan) over one batch of
 synthetic log lines that is already resident in HBM.  Workloads (BASELINE.json `configs`, 1-based as in BASELINE.md):
 
   2  README 3-extraction GET/PUT/Other definition, 10 M x 200-byte lines            (the metric's config: `value`)
-  3  64 syslog-like extractions, 10 M x 200-byte lines                              (N = 1: also.config3, same line)
-  4  config 3's definition, 10 M lines PER GPU, table blob broadcast + final gather  (N > 1: configs3_64_extractions)
-  5  512 extractions, lines of 50-2000 bytes, ~2 GB                                  (N = 1: also.config5, same line)
+  3  64 syslog-like extractions, 10 M x 200-byte lines                              (N = 1, --full: also.config3, same line)
+  4  config 3's definition, 10 M lines PER GPU, table blob broadcast + final gather  (N > 1, --full: configs3_64_extractions)
+  5  512 extractions, lines of 50-2000 bytes, ~2 GB                                  (N = 1, --full: also.config5, same line)
 
-The default run (no --config) times config 2 as the headline and then, at N = 1, configs 3 and 5 with the SAME protocol
-(spin-up, W warm-up steps, K timed steps between barrier + synchronize, two events on the launch stream around the K
-steps) and reports each as a complete object under `also`: ms_per_step, lines_per_s, roofline (achieved, frac, traffic
-from the committed counter passes), cpu_baseline (the oracle on a bounded sample, cores stated) and a bit-exact check of
-the GPU rows against the oracle on that sample.  also.config3 carries a second generator variant beside the lower-case
-one (mixed-case tokens: what a hop table that skips ONE byte interval per state pays for `JohnDoe42`).
+A plain run measures the headline and nothing else: it builds the workload and the tables, spins the device up, runs W
+warm-up steps and times K steps (between barrier + synchronize, two events on the launch stream around the K steps), and
+prints the line: `value` (lines/s), `ms_per_step` (host clock over the K steps / K), the kernel time from the events and
+the roofline derived from it.  --dump-outputs DIR then also writes what the last timed step computed (write_outputs).
+
+--full adds everything else, each after the headline's timed region or in runs of its own: the other result formats,
+the same steps from idle, the spread of single steps, the device's plain read rate (roofline.this_box), the check of the
+timed match ids against the generator's, the CPU baseline with a bit-exact check of every format against the oracle, the
+one-line latency and, with no --config, at N = 1 configs 3 and 5 with the SAME protocol as complete objects under `also`:
+ms_per_step, lines_per_s, roofline (achieved, frac, traffic from the committed counter passes), cpu_baseline (the oracle
+on a bounded sample, cores stated) and a bit-exact check of the GPU rows against the oracle on that sample.
+also.config3 carries a second generator variant beside the lower-case one (mixed-case tokens: what a hop table that
+skips ONE byte interval per state pays for `JohnDoe42`).
 
 Result formats (gx_batch_opts.compact_results): `dense` int32 match id + int32 offsets (4 + 8 G bytes per line), `compact`
 rows of int16 id + uint16 offsets (2 + 4 G), `narrow` rows of int8 id + uint8 offsets (1 + 2 G; for batches whose lines are
 shorter than 255 bytes and definitions of at most 126 extractions).  --results auto takes the narrowest format the workload
-allows; ALL applicable formats are timed with the full step count and reported in `formats`.
+allows; with --full ALL applicable formats are timed with the full step count and reported in `formats`.
 
 Multi-GPU (one rank per GPU, RCCL): rank 0 compiles the tables and broadcasts the packed blob; every rank builds its
 handle from the blob, generates its own shard (seeded by rank) and runs the same steps -- lines are independent, so there
-is no collective inside a step (weak scaling).  After the timed region the per-line results are gathered to rank 0 over
-xGMI; the gather is reported separately (`gather_*_ms`) and, overlapped with the next batch's kernel on a second stream,
-as `value_with_overlapped_gather`.  Any rank whose parity check fails makes the run exit non-zero.
+is no collective inside a step (weak scaling).  With --full, after the timed region the per-line results are gathered to
+rank 0 over xGMI; the gather is reported separately (`gather_*_ms`) and, overlapped with the next batch's kernel on a
+second stream, as `value_with_overlapped_gather`.  Any rank whose parity check fails makes the run exit non-zero.
 
 Prints ONE JSON line on rank 0.
 """
@@ -334,6 +342,31 @@ def side_workload(config, args, dev, stream, timer, variant=None, with_cpu=True)
     return obj
 
 
+DUMP_BYTES = 48 << 20   # what --dump-outputs writes at most (the limit is 64 MB)
+DUMP_SEED = 0
+
+
+def write_outputs(out_dir, n, slots, fetch):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of gx_extract_batch receives it -- the match
+    id of every line and its capture offsets (-1: unset) -- for a fixed, seeded sample of k of the n lines (all of them when
+    they fit in DUMP_BYTES).  fetch(idx int64[k]) -> (match_id int32[k], caps int32[k, slots]).  Writes, in line order:
+      match_id.npy    float32[k]
+      captures.npy    float32[k, slots]
+      line_index.npy  float64[k]   (the sampled lines' numbers in the batch)
+    The same arguments give the same inputs and the same sample, so two builds can be compared file for file."""
+    import numpy as np
+    k = min(n, DUMP_BYTES // (4 * (1 + slots) + 8))
+    if k == n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+    m, c = fetch(idx)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "match_id.npy"), np.asarray(m).astype(np.float32))
+    np.save(os.path.join(out_dir, "captures.npy"), np.asarray(c).astype(np.float32).reshape(k, slots))
+    np.save(os.path.join(out_dir, "line_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -344,14 +377,19 @@ def main():
                          "weak-scaling curve; at N = 1 configs 3 and 5 are measured beside it as `also`, at N > 1 configs[3] as `configs3_64_extractions`)")
     ap.add_argument("--lines", type=int, default=0, help="lines per GPU (0: the config's size)")
     ap.add_argument("--results", default="auto", choices=["auto", "narrow", "compact", "dense"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="N = 1, no --config: skip configs 3 and 5 (the `also` objects)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well (other formats and configs, CPU baseline, parity "
+                         "with the oracle, gathers at N > 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/*.npy (a seeded sample of the lines; write_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-also", action="store_true", help="--full, N = 1, no --config: skip configs 3 and 5 (the `also` objects)")
     ap.add_argument("--side-cpu-budget-s", type=float, default=10.0, help="CPU-seconds of the oracle per `also` workload")
     ap.add_argument("--result-buffer-candidates", type=int, default=1,
                     help="u8 result buffers timed before the timed region; `value` uses the MEDIAN one (1, the default: the buffer as allocated)")
     ap.add_argument("--spin-up-ms", type=float, default=150.0,
                     help="untimed steps for this long before the W warm-up steps of a timed region: the device at its steady clocks (0: none)")
-    ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--no-gather", action="store_true", help="--full, N > 1: skip the gathers")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -364,8 +402,8 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: the launcher's world size and --gpus must agree" % (args.gpus, world))
     config = args.config or 2
-    also_config4 = args.config == 0 and world > 1   # BASELINE.json configs[3]: its hardware run rides along with the scaling curve
-    also_side = args.config == 0 and world == 1 and not args.no_also
+    also_config4 = args.full and args.config == 0 and world > 1   # BASELINE.json configs[3]: its hardware run rides along with the scaling curve
+    also_side = args.full and args.config == 0 and world == 1 and not args.no_also
 
     import numpy as np
     import torch
@@ -466,33 +504,45 @@ def main():
         del cands
 
     runs = {}
-    torch.cuda.synchronize()
-    time.sleep(0.25)                                                         # (an idle device, as a first batch finds it)
-    from_idle = timer(lambda: step(headline), args.steps, args.warmup)       # the same W + K steps from idle: reported beside, never `value`
-    for fmt in [f for f in formats if f != headline]:
-        runs[fmt] = timer(lambda: step(fmt), args.steps, args.warmup, spin_ms=args.spin_up_ms)   # the other result formats, same step count, reported beside
+    if args.full:
+        torch.cuda.synchronize()
+        time.sleep(0.25)                                                         # (an idle device, as a first batch finds it)
+        from_idle = timer(lambda: step(headline), args.steps, args.warmup)       # the same W + K steps from idle: reported beside, never `value`
+        for fmt in [f for f in formats if f != headline]:
+            runs[fmt] = timer(lambda: step(fmt), args.steps, args.warmup, spin_ms=args.spin_up_ms)   # the other result formats, same step count, reported beside
     elapsed, kernel_ms = runs[headline] = timer(lambda: step(headline), args.steps, args.warmup, spin_ms=args.spin_up_ms)   # THE timed region
     own_elapsed = timer.last_own_elapsed
-    _, step_ms = timer(lambda: step(headline), args.steps, 1, per_step=True)                     # (afterwards: the spread of single steps)
 
-    # ---- correctness of what was timed: the generator knows every (uncorrupted) line's answer ----
-    got = {"compact": lambda: rows[:, 0].to(torch.int32), "narrow": lambda: rows8[:, 0].view(torch.int8).to(torch.int32), "dense": lambda: mid}[headline]()
-    ok = bool(torch.equal(got, want)) if known is None else bool(torch.equal(got[known], want[known]))
-    ok = ok and int(overflow.item()) == 0
-    all_ranks_ok(ok, "match ids differ from the generator's expected categories")
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs on the device: the buffers still hold the last timed step's results; N > 1: rank 0's shard)
+        def fetch(idx):
+            sel = torch.from_numpy(idx).to(dev)
+            if headline == "dense":
+                return mid.index_select(0, sel).cpu().numpy(), caps.index_select(0, sel).cpu().numpy()
+            return unpack_rows((rows8 if headline == "narrow" else rows).index_select(0, sel).cpu().numpy())
+        write_outputs(args.dump_outputs, n, 2 * G, fetch)
 
-    # per-rank step times (N > 1: min / max over the ranks), and the world size as the collective library reports it
-    rank_ms = torch.tensor([own_elapsed * 1e3 / args.steps], dtype=torch.float64, device=dev)
-    rank_ms_all = [rank_ms.clone() for _ in range(world)]
-    if distributed:
-        dist.all_gather(rank_ms_all, rank_ms)
-    rank_ms_all = [float(x.item()) for x in rank_ms_all]
+    if args.full:
+        _, step_ms = timer(lambda: step(headline), args.steps, 1, per_step=True)                 # (afterwards: the spread of single steps)
+
+        # ---- correctness of what was timed: the generator knows every (uncorrupted) line's answer ----
+        got = {"compact": lambda: rows[:, 0].to(torch.int32), "narrow": lambda: rows8[:, 0].view(torch.int8).to(torch.int32), "dense": lambda: mid}[headline]()
+        ok = bool(torch.equal(got, want)) if known is None else bool(torch.equal(got[known], want[known]))
+        ok = ok and int(overflow.item()) == 0
+        all_ranks_ok(ok, "match ids differ from the generator's expected categories")
+
+        # per-rank step times (N > 1: min / max over the ranks), and the world size as the collective library reports it
+        rank_ms = torch.tensor([own_elapsed * 1e3 / args.steps], dtype=torch.float64, device=dev)
+        rank_ms_all = [rank_ms.clone() for _ in range(world)]
+        if distributed:
+            dist.all_gather(rank_ms_all, rank_ms)
+        rank_ms_all = [float(x.item()) for x in rank_ms_all]
 
     # ---- final gather of results to rank 0 over xGMI (reported, not in `value`), then the same gather overlapped with the
     # next batch's kernel on a second stream: what a job pays per batch when it gathers every batch ----
     gather_ms = gather_dense_ms = gather_narrow_ms = None
     overlapped = None
-    if distributed and not args.no_gather:
+    if args.full and distributed and not args.no_gather:
         for fmt in formats:
             step(fmt)
         torch.cuda.synchronize()
@@ -611,29 +661,19 @@ def main():
         ms_per_step = elapsed * 1e3 / steps
         value = n * world * steps / elapsed
         k_avg = sum(kernel_ms) / len(kernel_ms)
-        k_sorted = sorted(step_ms)
         algo_read = total_bytes + 4 * (n + 1)            # line bytes + u32 offsets
         write_bytes = {"narrow": n * (1 + 2 * G), "compact": n * (2 + 4 * G), "dense": n * (4 + 8 * G)}
         fmt_desc = {"narrow": "narrow rows (int8 id + uint8 offsets, %d B/line)" % (1 + 2 * G),
                     "compact": "compact rows (int16 id + uint16 offsets, %d B/line)" % (2 + 4 * G),
                     "dense": "dense (int32 id + int32 offsets, %d B/line)" % (4 + 8 * G)}
         achieved = algo_read / (k_avg * 1e-3) / 1e9
-        box_rate = box_read_rate(data) if world == 1 else None   # (after the timed region; the same buffer, the same clocks)
         if config == 2:
             traffic, traffic_src = recorded_traffic(("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json"), algo_read, write_bytes[headline])
         else:
             traffic, traffic_src = recorded_traffic(("r05_config%d_traffic.json" % config,), algo_read, write_bytes[headline])
-        per_format = {}
-        for fmt, (f_elapsed, f_ms) in runs.items():
-            f_avg = sum(f_ms) / len(f_ms)
-            per_format[fmt] = {"results": fmt_desc[fmt], "steps": len(f_ms), "lines_per_s": n * world * len(f_ms) / f_elapsed,
-                               "ms_per_step": f_elapsed * 1e3 / len(f_ms), "kernel_ms_avg": f_avg,
-                               "algorithmic_write_bytes": write_bytes[fmt], "read_gb_per_s": algo_read / (f_avg * 1e-3) / 1e9,
-                               "frac": algo_read / (f_avg * 1e-3) / 1e9 / HBM_PEAK_GBS}
         out = {
             "metric": "lines/sec (Gorp.extract: product-DFA match + capture offsets; results as %s)" % fmt_desc[headline],
             "value": value,
-            "value_compact_rows": per_format["compact"]["lines_per_s"],   # the same workload with u16 rows: the format `value` had in round 2 (a stable key for trends)
             "unit": "lines/s",
             "n_gpus": world,
             "steps": steps,
@@ -656,32 +696,44 @@ def main():
                        "parallelism": "lines sharded by rank (dp%d), no collective in a step" % world},
             "gb_per_s_scanned": total_bytes * world * steps / elapsed / 1e9,
             "kernel_ms": {"avg": k_avg, "clock": "two events on the launch stream around the %d timed steps" % steps,
-                          "spin_up_ms": args.spin_up_ms,   # untimed steps before the W warm-up steps: the device at its steady clocks (see Timer)
-                          "from_idle": {"avg": sum(from_idle[1]) / len(from_idle[1]), "ms_per_step": from_idle[0] * 1e3 / steps,
-                                        "lines_per_s": n * world * steps / from_idle[0],
-                                        "protocol": "0.25 s of idling, then the same W + K steps without the spin-up"},
-                          "single_steps_after": {"min": k_sorted[0], "median": k_sorted[len(k_sorted) // 2], "max": k_sorted[-1],
-                                                 "clock": "an event behind every step, a second run of %d steps" % steps}},
+                          "spin_up_ms": args.spin_up_ms},   # untimed steps before the W warm-up steps: the device at its steady clocks (see Timer)
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "frac_by_wall_clock": algo_read / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,   # (the same bytes over ms_per_step, the host's clock around barrier + synchronize)
                          "traffic": traffic, "traffic_unit": "bytes/launch",
                          "traffic_source": traffic_src,
                          "algorithmic_read_bytes": algo_read, "algorithmic_write_bytes": write_bytes[headline],
-                         "frac_of_measured_copy_ceiling": achieved / 6290.0,
-                         "this_box": None if box_rate is None else {
-                             "plain_read_gb_per_s": box_rate, "frac_of_it": achieved / box_rate,
-                             "what": "a torch int64 sum over the same 2 GB buffer right after the timed steps: what a read-only sweep reaches on this device"}},
-            "formats": per_format,
+                         "frac_of_measured_copy_ceiling": achieved / 6290.0},
             "setup_s": setup_s,
             "table_bcast_ms": bcast_ms,
-            "gather_ms": gather_ms,
-            "gather_dense_ms": gather_dense_ms,
-            "gather_narrow_ms": gather_narrow_ms,
         }
         if distributed:
             out["collective_world_size"] = dist.get_world_size()   # as the process group (RCCL) reports it
             out["collective_backend"] = dist.get_backend()
+    if rank == 0 and args.full:
+        k_sorted = sorted(step_ms)
+        box_rate = box_read_rate(data) if world == 1 else None   # (after the timed region; the same buffer, the same clocks)
+        per_format = {}
+        for fmt, (f_elapsed, f_ms) in runs.items():
+            f_avg = sum(f_ms) / len(f_ms)
+            per_format[fmt] = {"results": fmt_desc[fmt], "steps": len(f_ms), "lines_per_s": n * world * len(f_ms) / f_elapsed,
+                               "ms_per_step": f_elapsed * 1e3 / len(f_ms), "kernel_ms_avg": f_avg,
+                               "algorithmic_write_bytes": write_bytes[fmt], "read_gb_per_s": algo_read / (f_avg * 1e-3) / 1e9,
+                               "frac": algo_read / (f_avg * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        out["value_compact_rows"] = per_format["compact"]["lines_per_s"]   # the same workload with u16 rows: the format `value` had in round 2 (a stable key for trends)
+        out["kernel_ms"]["from_idle"] = {"avg": sum(from_idle[1]) / len(from_idle[1]), "ms_per_step": from_idle[0] * 1e3 / steps,
+                                         "lines_per_s": n * world * steps / from_idle[0],
+                                         "protocol": "0.25 s of idling, then the same W + K steps without the spin-up"}
+        out["kernel_ms"]["single_steps_after"] = {"min": k_sorted[0], "median": k_sorted[len(k_sorted) // 2], "max": k_sorted[-1],
+                                                  "clock": "an event behind every step, a second run of %d steps" % steps}
+        out["roofline"]["this_box"] = None if box_rate is None else {
+            "plain_read_gb_per_s": box_rate, "frac_of_it": achieved / box_rate,
+            "what": "a torch int64 sum over the same 2 GB buffer right after the timed steps: what a read-only sweep reaches on this device"}
+        out["formats"] = per_format
+        out["gather_ms"] = gather_ms
+        out["gather_dense_ms"] = gather_dense_ms
+        out["gather_narrow_ms"] = gather_narrow_ms
+        if distributed:
             out["ms_per_step_by_rank"] = {"min": min(rank_ms_all), "max": max(rank_ms_all), "all": rank_ms_all}
             if overlapped is not None:
                 out["value_with_overlapped_gather"] = overlapped["value"]

@@ -755,8 +755,8 @@ def test_bench_ranks_self_launched(ranks, lines):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GORP_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--lines", str(lines), "--steps", "3", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--lines", str(lines), "--steps", "3", "--warmup", "1",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     out_lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(out_lines) == 1, r.stdout[-2000:]
@@ -774,8 +774,8 @@ def test_bench_ranks_self_launched(ranks, lines):
     if ranks == 2:
         # one rank's parity check fails: every rank leaves, the launcher's exit code -- and the parent's -- is not zero, no line is printed
         env["GORP_BENCH_FAIL_RANK"] = "1"
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--lines", "100000", "--steps", "2", "--warmup", "1", "--no-gather"],
-                           env=env, capture_output=True, text=True, timeout=900, cwd=root)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--lines", "100000", "--steps", "2", "--warmup", "1", "--no-gather",
+                            "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
         assert r.returncode != 0 and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")], (r.returncode, r.stdout[-500:])
 
 

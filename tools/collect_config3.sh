@@ -8,10 +8,10 @@ root=$(pwd)
 out=$root/gpurun_out/${tag}_config3
 mkdir -p "$out"
 export TMPDIR=/tmp
-python3 bench.py --config 3 --steps 20 --warmup 3 > "$out/bench.json"
+python3 bench.py --full --config 3 --steps 20 --warmup 3 > "$out/bench.json"
 echo "bench done"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --config 3 --steps 20 --warmup 3 --no-cpu-baseline > "$out/bench_under_rocprof.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --full --config 3 --steps 20 --warmup 3 --no-cpu-baseline > "$out/bench_under_rocprof.json"
 echo "kernel-trace done"
 cd "$root"
 find "$out/stats" -type f ! -name "*kernel_stats.csv" -delete

@@ -11,11 +11,11 @@ out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 
-python3 bench.py --steps 20 --warmup 3 > "$out/bench.json"
+python3 bench.py --full --steps 20 --warmup 3 > "$out/bench.json"
 echo "bench done"
 
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --steps 20 --warmup 3 > "$out/bench_under_rocprof.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --full --steps 20 --warmup 3 > "$out/bench_under_rocprof.json"
 echo "kernel-trace done"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch" -o fetch -- python3 "$root/tools/traffic_target.py" > /dev/null
 echo "fetch pass done"

@@ -8,12 +8,12 @@ root=$(pwd)
 out=$root/gpurun_out/r03x
 mkdir -p "$out"
 export TMPDIR=/tmp
-python3 bench.py --config 3 --no-cpu-baseline > "$out/config3_bench.json"
-python3 bench.py --config 5 --no-cpu-baseline > "$out/config5_bench.json"
+python3 bench.py --full --config 3 --no-cpu-baseline > "$out/config3_bench.json"
+python3 bench.py --full --config 5 --no-cpu-baseline > "$out/config5_bench.json"
 echo "bench lines done"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c3stats" -o c3 -- python3 "$root/bench.py" --config 3 --no-cpu-baseline > /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c5stats" -o c5 -- python3 "$root/bench.py" --config 5 --no-cpu-baseline > /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c3stats" -o c3 -- python3 "$root/bench.py" --full --config 3 --no-cpu-baseline > /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c5stats" -o c5 -- python3 "$root/bench.py" --full --config 5 --no-cpu-baseline > /dev/null
 cd "$root"
 cp "$(find "$out/c3stats" -name '*kernel_stats.csv' | head -1)" "$out/config3_kernel_stats.csv"
 cp "$(find "$out/c5stats" -name '*kernel_stats.csv' | head -1)" "$out/config5_kernel_stats.csv"

@@ -11,10 +11,10 @@ out=$root/gpurun_out/r04
 mkdir -p "$out"
 export TMPDIR=/tmp
 if [ "$part" = headline ] || [ "$part" = all ]; then
-  python3 bench.py --steps 20 --warmup 5 > "$out/bench.json"
+  python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json"
   echo "bench done"
   cd /tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_under_rocprofv3.json"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_under_rocprofv3.json"
   cp "$(find "$out/stats" -name '*kernel_stats.csv' | head -1)" "$out/kernel_stats.csv"; rm -rf "$out/stats"
   echo "kernel-trace done"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch" -o fetch -- python3 "$root/tools/traffic_target.py" > /dev/null
@@ -30,11 +30,11 @@ if [ "$part" = headline ] || [ "$part" = all ]; then
   echo "headline done"
 fi
 if [ "$part" = configs ] || [ "$part" = all ]; then
-  python3 bench.py --config 3 --no-cpu-baseline > "$out/config3_bench.json"
-  python3 bench.py --config 5 --no-cpu-baseline > "$out/config5_bench.json"
+  python3 bench.py --full --config 3 --no-cpu-baseline > "$out/config3_bench.json"
+  python3 bench.py --full --config 5 --no-cpu-baseline > "$out/config5_bench.json"
   cd /tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c3stats" -o c3 -- python3 "$root/bench.py" --config 3 --no-cpu-baseline > /dev/null
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c5stats" -o c5 -- python3 "$root/bench.py" --config 5 --no-cpu-baseline > /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c3stats" -o c3 -- python3 "$root/bench.py" --full --config 3 --no-cpu-baseline > /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c5stats" -o c5 -- python3 "$root/bench.py" --full --config 5 --no-cpu-baseline > /dev/null
   cd "$root"
   cp "$(find "$out/c3stats" -name '*kernel_stats.csv' | head -1)" "$out/config3_kernel_stats.csv"; rm -rf "$out/c3stats"
   cp "$(find "$out/c5stats" -name '*kernel_stats.csv' | head -1)" "$out/config5_kernel_stats.csv"; rm -rf "$out/c5stats"

@@ -10,10 +10,10 @@ out=$root/gpurun_out/r05
 mkdir -p "$out"
 export TMPDIR=/tmp
 if [ "$part" = bench ] || [ "$part" = all ]; then
-  python3 bench.py --steps 20 --warmup 5 > "$out/bench.json"
+  python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json"
   echo "bench done"
   cd /tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_under_rocprofv3.json"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 "$root/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_under_rocprofv3.json"
   cd "$root"
   cp "$(find "$out/stats" -name '*kernel_stats.csv' | head -1)" "$out/kernel_stats.csv"; rm -rf "$out/stats"
   echo "kernel-trace done"
@@ -22,8 +22,8 @@ if [ "$part" = configs ] || [ "$part" = all ]; then
   # configs 3 and 5 alone: their kernel statistics are not mixed with the other workloads' launches of the same kernel
   cd /tmp
   for c in 3 5; do
-    python3 "$root/bench.py" --config $c --no-cpu-baseline > "$out/config${c}_bench.json"
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c${c}stats" -o c$c -- python3 "$root/bench.py" --config $c --no-cpu-baseline > /dev/null
+    python3 "$root/bench.py" --full --config $c --no-cpu-baseline > "$out/config${c}_bench.json"
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c${c}stats" -o c$c -- python3 "$root/bench.py" --full --config $c --no-cpu-baseline > /dev/null
     cp "$(find "$out/c${c}stats" -name '*kernel_stats.csv' | head -1)" "$out/config${c}_kernel_stats.csv"; rm -rf "$out/c${c}stats"
   done
   cd "$root"
