@@ -1259,7 +1259,7 @@ k_extract_hop_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, co
 
 }  // namespace
 
-// lds: a layout from plan_hop_slice_launch (gx_api.cpp): the hop tier's tables, per wave a register block and a [64][144]-byte piece buffer
+// lds: a layout from plan_hop_slice_launch (gx_images.cpp): the hop tier's tables, per wave a register block and a [64][144]-byte piece buffer
 namespace {
 uint64_t hop_slices_blocks(uint64_t n, uint32_t nwaves, int num_cus) {
     uint64_t blocks = static_cast<uint64_t>(num_cus);

@@ -352,7 +352,7 @@ uint32_t lanes_sorted_tickets(uint64_t n, uint32_t chunk_lines, int num_cus) {
     return static_cast<uint32_t>(nchunks + (static_cast<uint64_t>(num_cus) < nchunks ? static_cast<uint64_t>(num_cus) : nchunks));
 }
 
-// lds: a layout from plan_lanes_launch (gx_api.cpp): tables, then per wave the register block with the result rows
+// lds: a layout from plan_lanes_launch (gx_images.cpp): tables, then per wave the register block with the result rows
 // behind it.  Needs tables in global memory (tier 1 or 3) and, for captures, the fused automaton.
 hipError_t launch_extract_lanes(const GxDev& dev, const GxLds& lds, const uint8_t* lds_image, const uint8_t* at_global, int num_cus,
                                 const GxBatch& b, hipStream_t stream, unsigned long long* dev_stamps) {

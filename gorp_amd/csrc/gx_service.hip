@@ -126,7 +126,7 @@ k_one_service(GxLds L, const uint8_t* __restrict__ image, const uint32_t* __rest
 
 }  // namespace
 
-// lds: the handle's dense-rows image laid out for one wave (gx_api.cpp: plan_service); mode 0 / 1 as above
+// lds: the handle's dense-rows image laid out for one wave (gx_images.cpp: plan_service); mode 0 / 1 as above
 hipError_t launch_one_service(int mode, const GxLds& lds, const uint8_t* lds_image, const uint32_t* mailbox, int32_t* answer, uint32_t* state,
                               uint32_t last_seq, int max_groups, unsigned long long idle_ticks, unsigned long long life_ticks, hipStream_t stream) {
     if (mode == 0) {

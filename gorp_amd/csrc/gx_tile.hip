@@ -68,7 +68,7 @@ hipError_t launch_extract_tile(const GxDev& dev, const GxLds& lds, const uint8_t
     const bool want_caps = b.match_only == 0 && dev.has_capture;
     const int mode = !want_caps ? 0 : (lds.u_start != 0xFFFFFFFFu && lds.simple_ops) ? 1 : 2;
     const bool off64 = b.offsets64 != 0;
-    if (b.wide) {   // UTF-16 code units: dense rows in LDS, or the hop tier (the other tiers take the narrowed copy: gx_api.cpp)
+    if (b.wide) {   // UTF-16 code units: dense rows in LDS, or the hop tier (the other tiers take the narrowed copy: gx_images.cpp: plan_batch)
         if (!b.wide_flags || !b.wide_any) return hipErrorInvalidValue;
         if (lds.tier == 4) return (at_global && mode != 2) ? launch_tile_hop_w(mode, off64, lds, &io, grid, block, stream) : hipErrorInvalidValue;
         if (at_global || lds.tier != 0) return hipErrorInvalidValue;

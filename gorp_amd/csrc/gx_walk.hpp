@@ -99,7 +99,7 @@ __device__ __forceinline__ uint32_t window_mask(uint32_t start, uint32_t end, ui
 // Where the automaton rows live.  TIER_LDS: dense rows in LDS, a state is the LDS byte address of its row (the host
 // bakes the table's position into every successor field).  TIER_L2: dense rows in global memory (they stay resident
 // in the XCD's L2), a state is its index and the row address is index * row_bytes.  TIER_REC: sparse range records
-// in LDS (gx_api.cpp: records_from_dense), a state is the index of its first 8-byte record.
+// in LDS (gx_images.cpp: records_from_dense), a state is the index of its first 8-byte record.
 // TIER_RECG: the same records in global memory (64 KB - 512 KB: they live in the CUs' vector L1 and the XCD's L2, and
 // LDS is left to the waves' staging areas).
 // TIER_HOP: hop records (run + chain per state) over dense rows in global memory; the staging area holds class ids
@@ -117,7 +117,7 @@ struct WalkTab {
     uint32_t indexed;      // TIER_REC: states from this index on keep one record per class (read record [state + class])
 };
 
-// Record tiers (gx_api.cpp: records_from_dense).  The class map at LDS address 0 has 32-bit entries, class | class * 8
+// Record tiers (gx_images.cpp: records_from_dense).  The class map at LDS address 0 has 32-bit entries, class | class * 8
 // << 16 (entry 256, for bytes outside the line: REC_IDC, and 0 in the upper half); the records of the LDS tier follow it
 // at the fixed address REC_AT, so that a record read is "ds_read_b64 index * 8, offset: REC_AT".  Record 0 is the one
 // dead state all automata of the image share.

@@ -1,4 +1,5 @@
-// ASan/UBSan driver for the host-side compiler (no HIP): definitions -> regex strings -> tables -> blob -> tables.
+// ASan/UBSan driver for the host-side compiler (no HIP): definitions -> regex strings -> tables -> blob -> tables; table images
+// and the kernel a batch gets (gx_images.hpp).
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -10,6 +11,7 @@
 #include "gx_compile.hpp"
 #include "gx_dsl.hpp"
 #include "gx_hop.hpp"
+#include "gx_images.hpp"
 using namespace gx;
 
 // ---- the hop tier's tables (gx_hop.hpp) walked on the host exactly as gx_hop_dev.hpp walks them, against the dense fused
@@ -181,11 +183,89 @@ size_t check_hop_tier(const Tables& T, uint64_t seed) {
     (void)iterations; (void)bytes;
     return checked;
 }
+
+// A planned LDS layout fits: its regions in ascending order inside LDS, the table image a multiple of 16 bytes.
+bool layout_fits(const GxLds& L) {
+    if (L.table_bytes % 16 || L.nwaves == 0 || L.total_bytes > LDS_BYTES) return false;
+    uint32_t at = L.table_bytes;
+    for (uint32_t r : {L.regs, L.bitmap, L.counter, L.stage, L.total_bytes}) {
+        if (r == 0) continue;   // (a region the kernel does not have)
+        if (r < at) return false;
+        at = r;
+    }
+    return true;
+}
+
+const uint32_t FLAG_SETS[] = {0u, GX_CREATE_TIER_L2, GX_CREATE_TIER_RECORDS, GX_CREATE_TIER_RECORDS_GLOBAL, GX_CREATE_TIER_HOP, GX_CREATE_NO_FUSED,
+                              GX_CREATE_TIER_RECORDS | GX_CREATE_NO_FUSED};
+
+// choose_tile_images under `flags`, then plan_batch over a grid of batch shapes: every plan uses images that exist, and its layout fits.
+// Returns the number of plans checked.
+size_t check_plans(const Tables& T, uint32_t flags) {
+    const TileImages I = choose_tile_images(T, flags);
+    size_t checked = 0;
+    for (uint32_t hint : {0u, 50u, 200u, 255u, 256u, 1500u, 4000u})
+        for (int shape = 0; shape < 32; ++shape)
+            for (uint32_t kernel = GX_KERNEL_AUTO; kernel <= GX_KERNEL_HOP_SLICES; ++kernel) {
+                BatchShape s;
+                s.line_bytes_hint = hint;
+                s.uneven = shape & 1;
+                s.wide = shape & 2;
+                s.match_only = (shape >> 2) & 1;
+                s.packed = shape & 8;
+                s.want_states = (shape & 16) && s.match_only;
+                s.n = 1u << 20;
+                s.kernel = kernel;
+                const BatchPlan p = plan_batch(I, s, 256);
+                ++checked;
+                if (p.narrow) {
+                    if (!s.wide) throw std::runtime_error("plan_batch: bytes to narrow");
+                    continue;
+                }
+                if (p.kernel == GX_KERNEL_PER_LINE) {
+                    if (p.image >= 0 || p.global >= 0) throw std::runtime_error("plan_batch: the per-line kernel with table images");
+                    continue;
+                }
+                if (p.image < 0 || !I.image(p.image) || (p.global >= 0 && !I.image(p.global)))
+                    throw std::runtime_error("plan_batch: kernel " + std::to_string(p.kernel) + " on an image that does not exist");
+                if (!layout_fits(p.L)) throw std::runtime_error("plan_batch: kernel " + std::to_string(p.kernel) + " with a layout that does not fit LDS");
+            }
+    GxLds L;
+    if (plan_service(I, &L) && !layout_fits(L)) throw std::runtime_error("plan_service: a layout that does not fit LDS");
+    return checked;
+}
+
+// The kernel AUTO gives a few batch shapes (GX_KERNEL_*; n: the UTF-16 units narrowed first), for a test to pin.
+std::string pinned_plans(const Tables& T, uint32_t flags) {
+    const TileImages I = choose_tile_images(T, flags);
+    struct Row { bool wide; int match_only; bool states; uint32_t hint; bool uneven; uint32_t kernel; };
+    const Row rows[] = {{false, 0, false, 200, false, 0}, {false, 0, false, 200, true, 0}, {false, 0, false, 400, false, 0},
+                        {false, 0, false, 1500, false, 0}, {false, 1, false, 200, false, 0}, {false, 1, true, 200, false, 0},
+                        {true, 0, false, 200, false, 0}, {true, 0, false, 1500, false, 0}, {false, 0, false, 200, false, GX_KERNEL_HOP_SLICES},
+                        {false, 0, false, 200, false, GX_KERNEL_PER_LINE}};
+    std::string out;
+    for (const Row& r : rows) {
+        BatchShape s;
+        s.wide = r.wide;
+        s.match_only = r.match_only;
+        s.want_states = r.states;
+        s.line_bytes_hint = r.hint;
+        s.uneven = r.uneven;
+        s.kernel = r.kernel;
+        s.n = 1u << 20;
+        const BatchPlan p = plan_batch(I, s, 256);
+        out += p.narrow ? std::string(" n") : " " + std::to_string(p.kernel);
+    }
+    return out;
+}
 }  // namespace
 int main(int argc, char** argv) {
     int ok = 0, bad = 0, mutated_ok = 0, mutated_bad = 0;
-    size_t hop_lines = 0, hop_defs = 0;
+    size_t hop_lines = 0, hop_defs = 0, plans = 0;
     for (int a = 1; a < argc; ++a) {
+        // --pin FILE: the kernel choice of a few batch shapes for that definition, as "pin FILE FLAGS: ..."
+        const bool pin = strcmp(argv[a], "--pin") == 0 && a + 1 < argc;
+        if (pin) ++a;
         std::ifstream f(argv[a]);
         std::stringstream ss; ss << f.rdbuf();
         const std::string text = ss.str();
@@ -197,6 +277,10 @@ int main(int argc, char** argv) {
             auto blob = pack_blob(T);
             Tables U = unpack_blob(blob.data(), blob.size());
             (void)U;
+            for (uint32_t flags : FLAG_SETS) {
+                plans += check_plans(T, flags);
+                if (pin) printf("pin %s %u:%s\n", argv[a], flags, pinned_plans(T, flags).c_str());
+            }
             const size_t hop_checked = check_hop_tier(T, static_cast<uint64_t>(a));
             hop_lines += hop_checked;
             hop_defs += hop_checked ? 1 : 0;
@@ -232,6 +316,7 @@ int main(int argc, char** argv) {
         } catch (GxError& e) { ++bad; }
     }
     printf("asan driver: %d compiled, %d rejected; damaged blobs: %d accepted, %d refused\n", ok, bad, mutated_ok, mutated_bad);
+    printf("batch plans: %zu checked\n", plans);
     printf("hop tier: %zu definitions, %zu lines agree with the dense automaton (%zu second chances on loop sets)\n", hop_defs, hop_lines, second_chances_total);
     return 0;
 }
