@@ -21,6 +21,7 @@
 #include "gx_dsl.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
+#include "gx_slots.hpp"
 
 using namespace gx;
 
@@ -42,6 +43,136 @@ int fail(int code, const std::string& msg) {
         if (_e != hipSuccess) throw GxError(GX_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// An entry point's body: what it throws leaves the C ABI as an error code and gx_last_error().
+template <typename F> int guarded(F&& body) {
+    try {
+        return body();
+    } catch (GxError& e) { return fail(e.code, e.what()); }
+    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
+    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+}
+
+// Move-only owners of HIP resources.  One that holds null makes no HIP call: host-only handles are created and destroyed on machines
+// without a GPU.
+template <typename P, auto Release> class Owned {
+    P p_{};
+
+  public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() {
+        if (p_) (void)Release(p_);
+        p_ = nullptr;
+    }
+    P* out() { reset(); return &p_; }   // (for the call that creates the resource)
+    P get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+template <typename T = void> using DevMem = Owned<T*, hipFree>;
+template <typename T> using PinnedMem = Owned<T*, hipHostFree>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using MemPool = Owned<hipMemPool_t, hipMemPoolDestroy>;
+
+// Device memory for the length of a call (16 bytes for none).
+template <typename T = void> DevMem<T> dev_alloc(size_t bytes) {
+    DevMem<T> m;
+    GX_HIP(hipMalloc(m.out(), bytes ? bytes : 16));
+    return m;
+}
+
+// Device memory kept between calls and grown as they ask (an allocation and a free per call cost more than the kernels that use it).
+struct GrowBuf {
+    DevMem<> mem;
+    size_t cap = 0;
+    void* get(size_t need) {
+        if (cap < need) {
+            cap = 0;
+            GX_HIP(hipMalloc(mem.out(), need + need / 8 + 256));
+            cap = need + need / 8 + 256;
+        }
+        return mem.get();
+    }
+};
+
+// Puts the calling thread's current device back when the scope ends.
+struct DeviceScope {
+    int saved = 0;
+    DeviceScope() { (void)hipGetDevice(&saved); }
+    ~DeviceScope() { (void)hipSetDevice(saved); }
+};
+
+// n + 1 line offsets in host memory, 32 or 64 bits each.
+struct HostOffsets {
+    const void* p;
+    bool off64;
+    uint64_t n;
+    uint64_t operator[](uint64_t i) const { return off64 ? static_cast<const uint64_t*>(p)[i] : static_cast<const uint32_t*>(p)[i]; }
+    // the first line from `from` on whose start lies at or beyond `at` (n: none)
+    uint64_t lines_at_or_after(uint64_t at, uint64_t from) const {
+        uint64_t lo = from, hi = n;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) / 2;
+            if ((*this)[mid] >= at) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo;
+    }
+};
+
+// offsets[0] and offsets[n] of an offsets array in device memory: a small synchronous read on `stream`.
+std::pair<uint64_t, uint64_t> device_offset_ends(const void* offsets, uint64_t n, bool off64, hipStream_t stream) {
+    const size_t w = off64 ? 8 : 4;
+    uint64_t first = 0, last = 0;
+    GX_HIP(hipMemcpyAsync(&first, offsets, w, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&last, static_cast<const uint8_t*>(offsets) + n * w, w, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    return {first, last};
+}
+
+// Asynchronous device-pointer batches that give no line_bytes_hint: the mean line length of the previous such batch, read back
+// without a synchronisation (two offsets copied to pinned memory, picked up by the next call once its event is done).
+struct HintProbe {
+    std::mutex mu;
+    PinnedMem<uint64_t> ends;   // offsets[0], offsets[n] of the batch being probed
+    Event event;
+    bool pending = false;
+    uint64_t n = 0;
+    bool off64 = false;
+    uint32_t learned = 0;
+    // the hint for a batch (what the previous such batch measured; 0 until one has), and a probe of this batch for the next call
+    uint32_t next(const void* offsets, uint64_t batch_n, bool batch_off64, hipStream_t stream) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!ends) {
+            GX_HIP(hipHostMalloc(ends.out(), 16, hipHostMallocDefault));
+            GX_HIP(hipEventCreateWithFlags(event.out(), hipEventDisableTiming));
+        }
+        uint64_t* e = ends.get();
+        if (pending && hipEventQuery(event.get()) == hipSuccess) {
+            const uint64_t first = off64 ? e[0] : (e[0] & 0xFFFFFFFFull), last = off64 ? e[1] : (e[1] & 0xFFFFFFFFull);
+            if (n && last >= first) learned = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((last - first + n - 1) / n, 4096)));
+            pending = false;
+        }
+        const uint32_t hint = learned;
+        if (!pending) {
+            const size_t w = batch_off64 ? 8 : 4;
+            e[0] = e[1] = 0;
+            GX_HIP(hipMemcpyAsync(&e[0], offsets, w, hipMemcpyDeviceToHost, stream));
+            GX_HIP(hipMemcpyAsync(&e[1], static_cast<const uint8_t*>(offsets) + batch_n * w, w, hipMemcpyDeviceToHost, stream));
+            GX_HIP(hipEventRecord(event.get(), stream));
+            pending = true;
+            n = batch_n;
+            off64 = batch_off64;
+        }
+        return hint;
+    }
+};
+
 }  // namespace
 
 struct gx_handle {
@@ -49,20 +180,23 @@ struct gx_handle {
     std::vector<uint8_t> blob;
     bool on_device = false;
     int device = 0;
-    void* dimage = nullptr;
+    DevMem<> dimage;
     size_t image_bytes = 0;
     GxDev dev{};
     int max_regs = 0;
     // the batch kernels' table images and layouts (gx_images.hpp), and their device copies, by IMG_* id
     TileImages tiles;
-    void* d_img[IMG_COUNT] = {};
+    DevMem<> d_img[IMG_COUNT];
     int num_cus = 256;
     std::vector<dsl::Extraction> meta;  // names / extractor names / append (from definition text or gx_set_extraction_meta)
-    void* one_dev = nullptr;     // scratch of the one-String entry points (device) ...
-    void* one_host = nullptr;    // ... and its pinned host mirror
-    size_t one_cap = 0;
+    // scratch of the one-String entry points: device, and its pinned host mirror (one_line)
+    struct OneScratch {
+        DevMem<uint8_t> dev;
+        PinnedMem<uint8_t> host;
+        size_t cap = 0;
+    } one;
     std::vector<std::vector<std::pair<std::string, std::string>>> append_entries;  // per extraction: (key, value JSON), lazily
-    struct JsonlImage { void* d = nullptr; GxJsonl dev{}; };
+    struct JsonlImage { DevMem<> d; GxJsonl dev{}; };
     std::map<std::string, JsonlImage> jsonl;  // device templates per id_as ("0" = none, "1" + id_as)
     std::mutex mu;  // serialises host-pointer batches that share nothing else
     // Host-pointer batches (what a JNI caller hands over) go through a small pipeline: the batch is cut into chunks of
@@ -71,84 +205,53 @@ struct gx_handle {
     // the bus' two directions.  (Threads, not just streams: a copy from pageable memory holds its host thread.)
     static const int HOST_WORKERS = 4;
     struct HostSlot {
-        hipStream_t stream = nullptr;
-        void* d_bytes = nullptr; size_t cap_bytes = 0;
-        void* d_off = nullptr; size_t cap_off = 0;
-        void* d_res = nullptr; size_t cap_res = 0;      // match ids, or compact rows
-        void* d_caps = nullptr; size_t cap_caps = 0;
-        void* d_states = nullptr; size_t cap_states = 0;
-        unsigned long long* d_over = nullptr;
+        Stream stream;
+        GrowBuf bytes, off, res, caps, states;   // res: match ids, or compact rows
+        DevMem<unsigned long long> over;
     } host_slot[HOST_WORKERS];
     uint32_t create_flags = 0;   // GX_CREATE_* given at creation (kernel choice)
-    // Asynchronous batches that give no line_bytes_hint: the mean line length of the previous such batch, read back
-    // without a synchronisation (two offsets copied to pinned memory, picked up by the next call once its event is done).
-    uint32_t learned_hint = 0;
-    uint64_t* hint_probe = nullptr;   // pinned: offsets[0], offsets[n] of the batch being probed
-    hipEvent_t hint_event = nullptr;
-    bool hint_pending = false;
-    uint64_t hint_n = 0;
-    bool hint_off64 = false;
-    std::mutex hint_mu;
-    // Tile-kernel launches that are in flight share nothing but these slots: one word each, into which a launch
-    // stores its sequence number when it meets a line it cannot stage (gx_device.hpp: GxBatch::oversize_flag).
-    // A slot is reused only after the follow-up kernel of its previous user has run (event).
-    // A slot belongs to ONE STREAM for the life of the handle (launches of a stream run in order, so the word is free again
-    // when the stream's next launch begins: nothing to wait for, nothing to record); the last slot is shared by the streams
-    // that come after N_SLOTS - 1 others and is handed over with an event.
-    static const int N_SLOTS = 32;
-    uint32_t* d_slots = nullptr;          // [N_SLOTS] oversize flags, then [N_SLOTS] chunk counters of the lane kernel, then [N_SLOTS] "a line
-                                          // of this UTF-16 batch holds a unit above 0xFF" words
-    hipStream_t slot_stream[N_SLOTS] = {};
-    bool slot_taken[N_SLOTS] = {};
-    // Batches that promise their longest line (gx_batch_opts.max_line_bytes) have no follow-up launch; their flag word is in
-    // pinned host memory (one per slot; the device writes it only if the promise is broken), so that the host can see it.
-    uint32_t* h_broken = nullptr;         // [N_SLOTS], pinned + mapped
-    uint32_t* d_broken = nullptr;         // the device's address of the same words
-    uint32_t* d_steal[N_SLOTS] = {};      // per slot, at its first tile launch: [2][GX_STEAL_MAX * GX_STEAL_STRIDE], the tile kernel's workgroup counters (GxBatch::steal)
-    uint32_t steal_parity[N_SLOTS] = {};  // the row the slot's next tile-kernel launch draws from
-    uint32_t promise_seq[N_SLOTS] = {};   // the sequence number of the slot's last launch under a promise (0: none)
-    uint32_t broken_seen[N_SLOTS] = {};   // the slot's pinned word as the host last saw it: ANY other value is a promise that broke since --
-                                          // whichever of the stream's batches it was, however many have been enqueued behind it
-    std::atomic<uint64_t> promises_broken{0};
+    HintProbe hint;
+    // the launch slots (gx_slots.hpp): their bookkeeping, under slot_mu, and their device resources
+    LaunchSlots slots;
+    std::mutex slot_mu;
+    DevMem<uint32_t> d_slots;   // [N] oversize flags, then [N] chunk counters of the lane kernel, then [N] "a line of this UTF-16
+                                // batch holds a unit above 0xFF" words
+    PinnedMem<uint32_t> h_broken;   // [N] the words of batches that promised their longest line (LaunchSlots::broken), mapped
+    uint32_t* d_broken = nullptr;   // the device's address of the same words
+    DevMem<uint32_t> d_steal[LaunchSlots::N];   // per slot, at its first tile launch: [2][GX_STEAL_MAX * GX_STEAL_STRIDE], the tile kernel's workgroup counters (GxBatch::steal)
+    Event shared_event;   // the shared slot's "previous user is done"
     // the resident one-line service (gx_service.hip; GX_CREATE_RESIDENT_ONE)
     struct Service {
         bool enabled = false;
         int mode = 0;
         GxLds L{};
-        hipStream_t stream = nullptr;
-        uint32_t* host = nullptr;      // pinned block: mailbox [17 x 16 dwords] | answer [2 + 2 G dwords, padded] | state
-        uint32_t* dev = nullptr;       // the device's address of the same block
+        PinnedMem<uint32_t> host;   // pinned block: mailbox [17 x 16 dwords] | answer [2 + 2 G dwords, padded] | state
+        uint32_t* dev = nullptr;    // the device's address of the same block
+        Stream stream;
         uint32_t seq = 0;
         bool started = false;
         uint64_t launches = 0;
     } svc;
-    int32_t* d_pike_scratch = nullptr;    // thread lists of the lanes that run an extraction's program as it is (GxDev::pike_scratch)
+    DevMem<int32_t> d_pike_scratch;   // thread lists of the lanes that run an extraction's program as it is (GxDev::pike_scratch)
     // ... ONE set of them per handle, a lane's area named by its place in the grid: two per-line kernels of the handle must not run at
     // once (the host pipeline's four streams, a caller's streams, the one-String calls beside a batch).  Every launch of such a
     // handle waits for the one before it, on whatever stream that was (PikeGate).
     std::recursive_mutex pike_mu;
-    hipEvent_t pike_event = nullptr;
+    Event pike_event;
     bool pike_event_set = false;
     int pike_depth = 0;
-    hipStream_t multi_stream = nullptr;   // gx_extract_batch_multi_device: the stream of shards that bring none
-    hipStream_t gather_stream = nullptr;  // gx_gather_rows: this handle's rows leave for the root's device on it (a copy queue of its own: seven peers, seven links)
-    hipEvent_t gather_event = nullptr;    // ... "the shard's kernel is done", recorded on the kernel's stream
+    Stream multi_stream;    // gx_extract_batch_multi_device: the stream of shards that bring none
+    Stream gather_stream;   // gx_gather_rows: this handle's rows leave for the root's device on it (a copy queue of its own: seven peers, seven links)
+    Event gather_event;     // ... "the shard's kernel is done", recorded on the kernel's stream
     size_t peer_image_bytes = 0;          // table bytes that came from another device's copy (gx_create_on_devices; gx_stat(h, 30))
     std::atomic<int> last_kernel{0};      // GX_KERNEL_* of the most recent batch launch (gx_stat(h, 25))
-    // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls and grown as
-    // batches ask: a hipMalloc + hipFree pair per call cost more than the scan kernels.  Used under `mu` only, and every call that
-    // uses it ends with a stream synchronisation.
-    void* scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls.  Used under
+    // `mu` only, and every call that uses it ends with a stream synchronisation.
+    GrowBuf scratch[8];
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
-    hipMemPool_t pool = nullptr;
-    uint32_t chunk_tickets[N_SLOTS] = {};  // what each chunk counter will read when the next launch on its slot begins
-    hipEvent_t shared_event = nullptr;    // the shared slot's "previous user is done"
-    bool shared_used = false;
-    uint32_t next_seq = 1;
-    std::mutex slot_mu;
+    MemPool pool;
 #ifdef GX_DEV
     unsigned long long* dev_stamps = nullptr;  // developer build: device buffer for the tile kernel's phase cycle counts
 #endif
@@ -230,10 +333,10 @@ void upload(gx_handle* h) {
             throw GxError(GX_E_LIMIT, "capture program too large to run as it is (the thread lists of one workgroup beyond 1 GiB)");
     }
 
-    GX_HIP(hipMalloc(&h->dimage, img.bytes.size()));
+    GX_HIP(hipMalloc(h->dimage.out(), img.bytes.size()));
     h->image_bytes = img.bytes.size();
-    put_image(h, h->dimage, img.bytes.data(), img.bytes.size(), g_peer_src ? g_peer_src->dimage : nullptr);
-    const uint8_t* base = static_cast<const uint8_t*>(h->dimage);
+    put_image(h, h->dimage.get(), img.bytes.data(), img.bytes.size(), g_peer_src ? g_peer_src->dimage.get() : nullptr);
+    const uint8_t* base = static_cast<const uint8_t*>(h->dimage.get());
     GxDev& d = h->dev;
     d.cls256 = base + o_cls;
     d.hi_lo = reinterpret_cast<const uint16_t*>(base + o_hilo);
@@ -263,8 +366,8 @@ void upload(gx_handle* h) {
         d.pike_sets = reinterpret_cast<const uint32_t*>(base + o_pike_sets);
         d.pike_lane_ints = pike_lane_ints;
         d.pike_blocks = pike_blocks;
-        GX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_pike_scratch), static_cast<size_t>(pike_lane_ints) * 4u * (256u * pike_blocks + 1u)));
-        d.pike_scratch = h->d_pike_scratch;
+        GX_HIP(hipMalloc(h->d_pike_scratch.out(), static_cast<size_t>(pike_lane_ints) * 4u * (256u * pike_blocks + 1u)));
+        d.pike_scratch = h->d_pike_scratch.get();
     }
 
     h->tiles = choose_tile_images(T, h->create_flags);
@@ -272,17 +375,18 @@ void upload(gx_handle* h) {
     for (int id = 0; id < IMG_COUNT; ++id) {
         const std::vector<uint8_t>* v = I.image(id);
         if (!v) continue;
-        GX_HIP(hipMalloc(&h->d_img[id], v->size()));
-        put_image(h, h->d_img[id], v->data(), v->size(), g_peer_src ? g_peer_src->d_img[id] : nullptr);
+        GX_HIP(hipMalloc(h->d_img[id].out(), v->size()));
+        put_image(h, h->d_img[id].get(), v->data(), v->size(), g_peer_src ? g_peer_src->d_img[id].get() : nullptr);
     }
     if (I.tile_ok || I.hop[0].ok || I.hop[1].ok) {
-        GX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_slots), 3 * gx_handle::N_SLOTS * sizeof(uint32_t)));
-        GX_HIP(hipMemset(h->d_slots, 0, 3 * gx_handle::N_SLOTS * sizeof(uint32_t)));
-        GX_HIP(hipEventCreateWithFlags(&h->shared_event, hipEventDisableTiming));
+        GX_HIP(hipMalloc(h->d_slots.out(), 3 * LaunchSlots::N * sizeof(uint32_t)));
+        GX_HIP(hipMemset(h->d_slots.get(), 0, 3 * LaunchSlots::N * sizeof(uint32_t)));
+        GX_HIP(hipEventCreateWithFlags(h->shared_event.out(), hipEventDisableTiming));
 
-        GX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_broken), gx_handle::N_SLOTS * sizeof(uint32_t), hipHostMallocMapped));
-        for (int q = 0; q < gx_handle::N_SLOTS; ++q) h->h_broken[q] = 0;
-        GX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_broken), h->h_broken, 0));
+        GX_HIP(hipHostMalloc(h->h_broken.out(), LaunchSlots::N * sizeof(uint32_t), hipHostMallocMapped));
+        for (int q = 0; q < LaunchSlots::N; ++q) h->h_broken.get()[q] = 0;
+        h->slots.broken = h->h_broken.get();
+        GX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_broken), h->h_broken.get(), 0));
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->num_cus = cus;
         // the resident one-line service (gx_service.hip)
@@ -290,10 +394,10 @@ void upload(gx_handle* h) {
             gx_handle::Service& sv = h->svc;
             sv.mode = T.has_capture ? 1 : 0;
             const size_t dwords = 17 * 16 + 80 + 16;
-            GX_HIP(hipHostMalloc(reinterpret_cast<void**>(&sv.host), dwords * 4, hipHostMallocMapped));
-            memset(sv.host, 0, dwords * 4);
-            GX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sv.dev), sv.host, 0));
-            GX_HIP(hipStreamCreateWithFlags(&sv.stream, hipStreamNonBlocking));
+            GX_HIP(hipHostMalloc(sv.host.out(), dwords * 4, hipHostMallocMapped));
+            memset(sv.host.get(), 0, dwords * 4);
+            GX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sv.dev), sv.host.get(), 0));
+            GX_HIP(hipStreamCreateWithFlags(sv.stream.out(), hipStreamNonBlocking));
             sv.enabled = true;
         }
     }
@@ -312,76 +416,48 @@ struct Launched {
 };
 
 // The launch's flag word (and the lane kernel's chunk counter): the slot of its stream.  Call under h->slot_mu.
-struct SlotUse { int slot; bool shared; };
-SlotUse take_slot(gx_handle* h, GxBatch& b, hipStream_t stream) {
-    b.seq = h->next_seq++;
-    if (h->next_seq == 0) h->next_seq = 1;
-    int slot = -1;
-    for (int q = 0; q < gx_handle::N_SLOTS - 1 && slot < 0; ++q)
-        if (h->slot_taken[q] && h->slot_stream[q] == stream) slot = q;
-    for (int q = 0; q < gx_handle::N_SLOTS - 1 && slot < 0; ++q)
-        if (!h->slot_taken[q]) { h->slot_taken[q] = true; h->slot_stream[q] = stream; slot = q; }
-    const bool shared = slot < 0;
-    if (shared) {
-        slot = gx_handle::N_SLOTS - 1;
-        if (h->shared_used) GX_HIP(hipStreamWaitEvent(stream, h->shared_event, 0));
-        h->shared_used = true;
-    }
+LaunchSlots::Use take_slot(gx_handle* h, GxBatch& b, hipStream_t stream) {
+    const LaunchSlots::Use u = h->slots.take(stream);
+    b.seq = u.seq;
+    if (u.wait_shared) GX_HIP(hipStreamWaitEvent(stream, h->shared_event.get(), 0));
     // a batch of this stream that promised its longest line, ran without a follow-up launch and met a longer line after all
     // (no_sync batches: nobody has looked yet)
-    // (the word holds the sequence number of the LAST launch that broke its promise; until round 4 it was compared with the newest
-    // promise alone, and a kernel that reached its long line after the next batch had been enqueued was never noticed)
-    const uint32_t word = __atomic_load_n(&h->h_broken[slot], __ATOMIC_RELAXED);
-    if (word != h->broken_seen[slot]) {
-        h->broken_seen[slot] = word;
-        h->promise_seq[slot] = 0;
-        h->promises_broken.fetch_add(1);
+    if (h->slots.consume_broken(u.slot))
         throw GxError(GX_E_ARG, "an earlier no_sync batch on this stream held a line longer than its gx_batch_opts.max_line_bytes: that line was not "
                                 "processed (its result row is unwritten); this batch was not launched");
-    }
-    b.oversize_flag = h->d_slots + slot;
-    if (!h->d_steal[slot]) {   // (the slot's first launch: 768 KB, zeroed once -- every launch leaves the next one's row zeroed)
+    b.oversize_flag = h->d_slots.get() + u.slot;
+    DevMem<uint32_t>& steal = h->d_steal[u.slot];
+    if (!steal) {   // (the slot's first launch: 768 KB, zeroed once -- every launch leaves the next one's row zeroed)
         const size_t bytes = 2 * static_cast<size_t>(GX_STEAL_MAX) * GX_STEAL_STRIDE * sizeof(uint32_t);
-        GX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_steal[slot]), bytes));
-        GX_HIP(hipMemsetAsync(h->d_steal[slot], 0, bytes, stream));   // (on the launch's own stream: in order before its kernel; the shared slot's later users wait for its event)
+        GX_HIP(hipMalloc(steal.out(), bytes));
+        GX_HIP(hipMemsetAsync(steal.get(), 0, bytes, stream));   // (on the launch's own stream: in order before its kernel; the shared slot's later users wait for its event)
     }
-    b.steal = h->d_steal[slot];
-    b.steal_parity = h->steal_parity[slot];
-    return SlotUse{slot, shared};
+    b.steal = steal.get();
+    b.steal_parity = h->slots.steal_parity[u.slot];
+    return u;
 }
 // The follow-up launch for the lines the batch kernel leaves (longer than `limit`: see launch_extract_oversize) -- unless the
 // caller promised that there are none (b.max_line_bytes within `fits`), or the host knows (b.no_followup: the one-line calls).
 // Call before the batch kernel is launched; returns what to launch after it.
-bool plan_followup(gx_handle* h, GxBatch& b, const SlotUse& u, uint32_t fits, Launched* out) {
+bool plan_followup(gx_handle* h, GxBatch& b, const LaunchSlots::Use& u, uint32_t fits, Launched* out) {
     if (out) { out->slot = u.slot; out->seq = b.seq; }
     if (b.no_followup) return false;
     if (b.max_line_bytes != 0 && b.max_line_bytes <= fits) {
         b.no_followup = 1;
         b.oversize_flag = h->d_broken + u.slot;
-        h->promise_seq[u.slot] = b.seq;
         if (out) out->promised = true;
         return false;
     }
-    h->promise_seq[u.slot] = 0;
     return true;
 }
 // Has a batch of this stream broken its promise since anybody looked?  (For the calls that wait for their batches themselves:
 // the word is final once the stream is idle.)  Marks it seen.
 bool promise_broken_since(gx_handle* h, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(h->slot_mu);
-    int slot = gx_handle::N_SLOTS - 1;
-    for (int q = 0; q < gx_handle::N_SLOTS - 1; ++q)
-        if (h->slot_taken[q] && h->slot_stream[q] == stream) { slot = q; break; }
-    if (!h->h_broken) return false;
-    const uint32_t word = __atomic_load_n(&h->h_broken[slot], __ATOMIC_RELAXED);
-    if (word == h->broken_seen[slot]) return false;
-    h->broken_seen[slot] = word;
-    h->promise_seq[slot] = 0;
-    h->promises_broken.fetch_add(1);
-    return true;
+    return h->slots.consume_broken(h->slots.slot_of(stream));
 }
-void done_slot(gx_handle* h, const SlotUse& u, hipStream_t stream) {
-    if (u.shared) GX_HIP(hipEventRecord(h->shared_event, stream));
+void done_slot(gx_handle* h, const LaunchSlots::Use& u, hipStream_t stream) {
+    if (u.shared) GX_HIP(hipEventRecord(h->shared_event.get(), stream));
 }
 
 // Stream-ordered memory out of the handle's own pool (gx_handle::pool) for the length of a scope: freed on the stream when the scope
@@ -398,12 +474,12 @@ struct PoolBuffer {
                 props.handleTypes = hipMemHandleTypeNone;
                 props.location.type = hipMemLocationTypeDevice;
                 props.location.id = h->device;
-                GX_HIP(hipMemPoolCreate(&h->pool, &props));
+                GX_HIP(hipMemPoolCreate(h->pool.out(), &props));
                 uint64_t keep = ~0ull;
-                GX_HIP(hipMemPoolSetAttribute(h->pool, hipMemPoolAttrReleaseThreshold, &keep));
+                GX_HIP(hipMemPoolSetAttribute(h->pool.get(), hipMemPoolAttrReleaseThreshold, &keep));
             }
         }
-        GX_HIP(hipMallocFromPoolAsync(&p, bytes, h->pool, stream));
+        GX_HIP(hipMallocFromPoolAsync(&p, bytes, h->pool.get(), stream));
     }
     ~PoolBuffer() { if (p) (void)hipFreeAsync(p, s); }
     PoolBuffer(const PoolBuffer&) = delete;
@@ -418,13 +494,13 @@ struct PikeGate {
     PikeGate(gx_handle* h_, hipStream_t s_) : h(h_), s(s_), on(h_->T.has_pike()) {
         if (!on) return;
         h->pike_mu.lock();
-        if (h->pike_depth++ == 0 && h->pike_event_set) (void)hipStreamWaitEvent(s, h->pike_event, 0);
+        if (h->pike_depth++ == 0 && h->pike_event_set) (void)hipStreamWaitEvent(s, h->pike_event.get(), 0);
     }
     ~PikeGate() {
         if (!on) return;
         if (--h->pike_depth == 0) {
-            if (!h->pike_event) (void)hipEventCreateWithFlags(&h->pike_event, hipEventDisableTiming);
-            if (h->pike_event && hipEventRecord(h->pike_event, s) == hipSuccess) h->pike_event_set = true;
+            if (!h->pike_event) (void)hipEventCreateWithFlags(h->pike_event.out(), hipEventDisableTiming);
+            if (h->pike_event && hipEventRecord(h->pike_event.get(), s) == hipSuccess) h->pike_event_set = true;
         }
         h->pike_mu.unlock();
     }
@@ -445,11 +521,7 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
             throw GxError(GX_E_ARG, "gx_batch_opts.utf16 with no_sync: this batch would take the narrowed copy of its code units (tables other than dense rows "
                                     "in LDS or hop tables, or a kernel named in gx_batch_opts.kernel), which is sized by a read of the offsets on the host; "
                                     "call it without no_sync");
-        const size_t off_w = b.offsets64 ? 8 : 4;
-        uint64_t first = 0, last = 0;
-        GX_HIP(hipMemcpyAsync(&first, b.offsets, off_w, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&last, static_cast<const uint8_t*>(b.offsets) + b.n * off_w, off_w, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipStreamSynchronize(stream));
+        const auto [first, last] = device_offset_ends(b.offsets, b.n, b.offsets64 != 0, stream);
         const uint64_t units = last >= first ? last - first : 0;
         PoolBuffer tmp_buf(h, units + b.n + 64, stream);
         uint8_t* bytes = static_cast<uint8_t*>(tmp_buf.p);
@@ -466,8 +538,8 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         GX_HIP(e);
         return;
     }
-    const uint8_t* image = p.image >= 0 ? static_cast<const uint8_t*>(h->d_img[p.image]) : nullptr;
-    const uint8_t* at_global = p.global >= 0 ? static_cast<const uint8_t*>(h->d_img[p.global]) : nullptr;
+    const uint8_t* image = p.image >= 0 ? static_cast<const uint8_t*>(h->d_img[p.image].get()) : nullptr;
+    const uint8_t* at_global = p.global >= 0 ? static_cast<const uint8_t*>(h->d_img[p.global].get()) : nullptr;
     if (p.kernel == GX_KERNEL_PER_LINE || p.kernel == GX_KERNEL_SLICES) {   // (no slot: these take every line themselves)
         h->last_kernel = p.kernel;
         if (p.kernel == GX_KERNEL_SLICES) GX_HIP(launch_extract_slices(h->dev, p.L, image, at_global, h->num_cus, b, stream));
@@ -483,18 +555,18 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         // a slot for the "lines I could not stage" word of this launch, free again once its follow-up kernel has run
         // (submission of slot launches is serialised per handle; the launches themselves are asynchronous)
         std::lock_guard<std::mutex> lock(h->slot_mu);
-        const SlotUse u = take_slot(h, b, stream);
+        const LaunchSlots::Use u = take_slot(h, b, stream);
         const bool followup = plan_followup(h, b, u, p.fits, launched);
         if (launched) { launched->limit = p.limit; launched->by_length = p.by_length; }
         if (b.wide) {
             b.wide_flags = static_cast<uint8_t*>(flags->p);
-            b.wide_any = h->d_slots + 2 * gx_handle::N_SLOTS + u.slot;
+            b.wide_any = h->d_slots.get() + 2 * LaunchSlots::N + u.slot;
         }
         // (the pool of chunks the launch's waves share: the slot's chunk counter -- the hop slice kernel, the lane kernel's sorted tiles)
         const bool chunks = p.kernel == GX_KERNEL_HOP_SLICES || (p.kernel == GX_KERNEL_LANES && p.L.sort_chunk);
         if (chunks) {
-            b.chunk_ctr = h->d_slots + gx_handle::N_SLOTS + u.slot;
-            b.chunk_base = h->chunk_tickets[u.slot];
+            b.chunk_ctr = h->d_slots.get() + LaunchSlots::N + u.slot;
+            b.chunk_base = h->slots.chunk_tickets[u.slot];
         }
         unsigned long long* stamps = nullptr;
 #ifdef GX_DEV
@@ -503,13 +575,13 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         h->last_kernel = p.kernel;
         if (p.kernel == GX_KERNEL_TILES || p.kernel == GX_KERNEL_HOPS) {
             e = launch_extract_tile(h->dev, p.L, image, at_global, h->num_cus, b, stream, stamps);
-            if (e == hipSuccess) h->steal_parity[u.slot] ^= 1u;
+            if (e == hipSuccess) h->slots.steal_parity[u.slot] ^= 1u;
         } else if (p.kernel == GX_KERNEL_HOP_SLICES) {
             e = launch_extract_hop_slices(h->dev, p.L, image, at_global, h->num_cus, b, stream, stamps);
-            if (e == hipSuccess) h->chunk_tickets[u.slot] += hop_slices_tickets(b.n, p.L.nwaves, h->num_cus);   // (what the launch will draw)
+            if (e == hipSuccess) h->slots.chunk_tickets[u.slot] += hop_slices_tickets(b.n, p.L.nwaves, h->num_cus);   // (what the launch will draw)
         } else {
             e = launch_extract_lanes(h->dev, p.L, image, at_global, h->num_cus, b, stream, stamps);
-            if (e == hipSuccess && chunks) h->chunk_tickets[u.slot] += lanes_sorted_tickets(b.n, p.L.sort_chunk, h->num_cus);
+            if (e == hipSuccess && chunks) h->slots.chunk_tickets[u.slot] += lanes_sorted_tickets(b.n, p.L.sort_chunk, h->num_cus);
         }
         if (e == hipSuccess && b.wide) e = launch_extract_flagged(h->dev, b, static_cast<const uint8_t*>(flags->p), stream, b.wide_any);
         if (e == hipSuccess && followup) e = launch_extract_oversize(h->dev, b, p.limit, p.by_length, stream);
@@ -527,47 +599,25 @@ int finish_create(std::unique_ptr<gx_handle>& h, uint32_t flags, gx_handle** out
     return GX_OK;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void alloc(size_t bytes) { GX_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
-};
-
-// gx_split_lines has no handle to keep its workspace on (an eighth of the text since the text-read-once split: a hipMalloc + hipFree
+// gx_split_lines has no handle to keep its workspace on (an eighth of the text since the text-read-once split: an allocation and a free
 // of 250 MB per call were 0.1 ms of a 0.7 ms call): one workspace per device, kept between calls, grown as needed; a call holds the
 // lock OF ITS DEVICE while it runs (calls on one device take turns: they would on the device anyway; calls on different devices -- one
 // process, eight GPUs -- do not wait for each other).  gx_release_scratch(device) gives a device's workspace back.
 struct SplitScratch {
     std::mutex mu[64];
-    void* p[64] = {};
-    size_t cap[64] = {};
-    void release(int dev) {
-        if (dev < 0 || dev >= 64) return;
-        std::lock_guard<std::mutex> lock(mu[dev]);
-        if (p[dev]) { (void)hipFree(p[dev]); p[dev] = nullptr; cap[dev] = 0; }
-    }
-    void* get(int dev, size_t bytes) {   // (the caller holds mu[dev])
-        if (dev < 0 || dev >= 64) throw GxError(GX_E_DEVICE, "gx_split_lines: device ordinal beyond 63");
-        if (cap[dev] < bytes) {
-            if (p[dev]) { (void)hipFree(p[dev]); p[dev] = nullptr; cap[dev] = 0; }
-            const size_t want = bytes + bytes / 8 + 256;
-            GX_HIP(hipMalloc(&p[dev], want));
-            cap[dev] = want;
-        }
-        return p[dev];
-    }
+    GrowBuf ws[64];
 };
-SplitScratch g_split_scratch;
+SplitScratch& g_split_scratch = *new SplitScratch;   // (never destroyed: the HIP runtime may be gone when static destructors run)
 
-// the handle's scratch buffer `which`, at least `bytes` long (the caller holds h->mu)
-void* handle_scratch(gx_handle* h, int which, size_t bytes) {
-    if (h->scratch_cap[which] < bytes) {
-        if (h->scratch[which]) { (void)hipFree(h->scratch[which]); h->scratch[which] = nullptr; h->scratch_cap[which] = 0; }
-        const size_t cap = bytes + bytes / 8 + 256;
-        GX_HIP(hipMalloc(&h->scratch[which], cap));
-        h->scratch_cap[which] = cap;
-    }
-    return h->scratch[which];
+// Accepts the current gx_batch_opts and every earlier, shorter layout of it (struct_size says which).
+gx_batch_opts read_opts(const gx_batch_opts* opts) {
+    gx_batch_opts o{};
+    if (!opts) return o;
+    const size_t v1 = offsetof(gx_batch_opts, strip_eol);  // the first layout; later ones only appended fields
+    if (opts->struct_size < v1 || opts->struct_size > sizeof(gx_batch_opts) || (opts->struct_size & 3u))
+        throw GxError(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
+    memcpy(&o, opts, opts->struct_size);
+    return o;
 }
 
 }  // namespace
@@ -577,14 +627,15 @@ extern "C" {
 const char* gx_last_error(void) { return g_last_error.c_str(); }
 
 int gx_release_scratch(int device) {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    DeviceScope scope;
     if (hipSetDevice(device) != hipSuccess) {
         (void)hipGetLastError();   // (the runtime keeps the error for the next hipGetLastError(): a later launch's check would see it)
         return fail(GX_E_DEVICE, "gx_release_scratch: no such device");
     }
-    g_split_scratch.release(device);
-    (void)hipSetDevice(prev);
+    if (device >= 0 && device < 64) {
+        std::lock_guard<std::mutex> lock(g_split_scratch.mu[device]);
+        g_split_scratch.ws[device] = {};
+    }
     return GX_OK;
 }
 
@@ -597,7 +648,7 @@ int gx_device_count(void) {
 int gx_create_from_patterns(const char* const* automaton_rx, const char* const* jdk_rx, int32_t n, uint32_t flags,
                             gx_handle** out) {
     if (!automaton_rx || !out || n <= 0) return fail(GX_E_ARG, "gx_create_from_patterns: bad argument");
-    try {
+    return guarded([&]() -> int {
         std::vector<ustr> a, j;
         for (int32_t i = 0; i < n; ++i) {
             if (!automaton_rx[i] || (jdk_rx && !jdk_rx[i])) return fail(GX_E_ARG, "gx_create_from_patterns: null pattern");
@@ -607,20 +658,16 @@ int gx_create_from_patterns(const char* const* automaton_rx, const char* const* 
         std::unique_ptr<gx_handle> h(new gx_handle());
         h->T = compile_tables(a, jdk_rx ? &j : nullptr);
         return finish_create(h, flags, out);
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 int gx_create_from_blob(const void* blob, size_t size, uint32_t flags, gx_handle** out) {
     if (!blob || !out) return fail(GX_E_ARG, "gx_create_from_blob: bad argument");
-    try {
+    return guarded([&]() -> int {
         std::unique_ptr<gx_handle> h(new gx_handle());
         h->T = unpack_blob(blob, size);
         return finish_create(h, flags, out);
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 size_t gx_blob_size(const gx_handle* h) { return h ? h->blob.size() : 0; }
@@ -633,37 +680,11 @@ int gx_blob_copy(const gx_handle* h, void* dst, size_t cap) {
 
 void gx_destroy(gx_handle* h) {
     if (!h) return;
-    if (h->dimage) (void)hipFree(h->dimage);
-    for (void* q : h->d_img) if (q) (void)hipFree(q);
-    if (h->hint_probe) { (void)hipHostFree(h->hint_probe); (void)hipEventDestroy(h->hint_event); }
-    for (auto& sl : h->host_slot) {
-        for (void* p : {sl.d_bytes, sl.d_off, sl.d_res, sl.d_caps, sl.d_states, static_cast<void*>(sl.d_over)}) if (p) (void)hipFree(p);
-        if (sl.stream) (void)hipStreamDestroy(sl.stream);
+    if (h->svc.started) {   // the resident wave reads the dense image and the mailbox: tell it to leave, wait for it, before they go
+        uint32_t* mb = h->svc.host.get();
+        __atomic_store_n(&mb[1], (mb[1] & 0xFFFFu) | 0x10000u, __ATOMIC_RELEASE);
+        (void)hipStreamSynchronize(h->svc.stream.get());
     }
-    if (h->d_slots) {
-        (void)hipFree(h->d_slots);
-        if (h->shared_event) (void)hipEventDestroy(h->shared_event);
-        if (h->h_broken) (void)hipHostFree(h->h_broken);
-        for (uint32_t* q : h->d_steal) if (q) (void)hipFree(q);
-    }
-    for (auto& e : h->jsonl) if (e.second.d) (void)hipFree(e.second.d);
-    for (void* q : h->scratch) if (q) (void)hipFree(q);
-    if (h->pool) (void)hipMemPoolDestroy(h->pool);
-    if (h->svc.enabled) {
-        if (h->svc.started) {   // tell the wave to leave, wait for it
-            __atomic_store_n(&h->svc.host[1], (h->svc.host[1] & 0xFFFFu) | 0x10000u, __ATOMIC_RELEASE);
-            (void)hipStreamSynchronize(h->svc.stream);
-        }
-        if (h->svc.stream) (void)hipStreamDestroy(h->svc.stream);
-        if (h->svc.host) (void)hipHostFree(h->svc.host);
-    }
-    if (h->multi_stream) (void)hipStreamDestroy(h->multi_stream);
-    if (h->gather_stream) (void)hipStreamDestroy(h->gather_stream);
-    if (h->gather_event) (void)hipEventDestroy(h->gather_event);
-    if (h->d_pike_scratch) (void)hipFree(h->d_pike_scratch);
-    if (h->pike_event) (void)hipEventDestroy(h->pike_event);
-    if (h->one_dev) (void)hipFree(h->one_dev);
-    if (h->one_host) (void)hipHostFree(h->one_host);
     delete h;
 }
 
@@ -700,7 +721,7 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     case 18: { GxLds L; return plan_hop_launch(I, 0, &L) ? static_cast<int64_t>(L.nwaves) : 0; }  // hop tier: waves per CU
     case 20: return I.hop[0].ok ? static_cast<int64_t>(H.full.n_lds_rows) : 0;       // ... whose dense row is in LDS too (branching states)
     case 22: return I.hop[1].ok ? static_cast<int64_t>(I.hop[1].img.n_states) : 0;   // hop tier of the match automaton alone (match-only batches): states
-    case 24: return static_cast<int64_t>(h->promises_broken.load());
+    case 24: return static_cast<int64_t>(h->slots.promises_broken.load());
     case 30: return static_cast<int64_t>(h->peer_image_bytes);   // table bytes copied from another handle's device (gx_create_on_devices)
     case 25: return h->last_kernel.load();
     case 26: return I.hop_reason;
@@ -713,16 +734,6 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     }
 }
 
-// Accepts the current gx_batch_opts and every earlier, shorter layout of it (struct_size says which).
-static bool read_opts(const gx_batch_opts* opts, gx_batch_opts* o) {
-    *o = gx_batch_opts{};
-    if (!opts) return true;
-    const size_t v1 = offsetof(gx_batch_opts, strip_eol);  // the first layout; later ones only appended fields
-    if (opts->struct_size < v1 || opts->struct_size > sizeof(gx_batch_opts) || (opts->struct_size & 3u)) return false;
-    memcpy(o, opts, opts->struct_size);
-    return true;
-}
-
 int gx_split_lines(const uint8_t* bytes, uint64_t size, void* offsets, uint64_t cap_lines, uint64_t* n_lines, uint8_t* line_flags,
                    const gx_batch_opts* opts) {
     return gx_split_lines_max(bytes, size, offsets, cap_lines, n_lines, line_flags, nullptr, opts);
@@ -730,39 +741,39 @@ int gx_split_lines(const uint8_t* bytes, uint64_t size, void* offsets, uint64_t 
 
 int gx_split_lines_max(const uint8_t* bytes, uint64_t size, void* offsets, uint64_t cap_lines, uint64_t* n_lines, uint8_t* line_flags,
                        uint64_t* max_line_bytes, const gx_batch_opts* opts) {
-    if (!offsets || !n_lines || (size && !bytes)) return fail(GX_E_ARG, "gx_split_lines: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    if (!o.offsets64 && size > 0xFFFFFFFFull) return fail(GX_E_ARG, "gx_split_lines: buffers of 4 GiB and more need offsets64");
-    try {
+    return guarded([&]() -> int {
+        if (!offsets || !n_lines || (size && !bytes)) return fail(GX_E_ARG, "gx_split_lines: bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        if (!o.offsets64 && size > 0xFFFFFFFFull) return fail(GX_E_ARG, "gx_split_lines: buffers of 4 GiB and more need offsets64");
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
             throw GxError(GX_E_DEVICE, "no HIP device available (libgorp_hip needs a gfx950 GPU; there is no CPU fallback)");
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
         const size_t off_w = o.offsets64 ? 8 : 4;
-        DevBuf d_bytes, d_off, d_flags;
+        DevMem<> d_bytes, d_off;
+        DevMem<uint8_t> d_flags;
         int dev = 0;
         GX_HIP(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64) return fail(GX_E_DEVICE, "gx_split_lines: device ordinal beyond 63");
         std::lock_guard<std::mutex> ws_lock(g_split_scratch.mu[dev]);
-        struct { void* p; } ws{g_split_scratch.get(dev, split_workspace_bytes(size, line_flags != nullptr))};
+        void* ws = g_split_scratch.ws[dev].get(split_workspace_bytes(size, line_flags != nullptr));
         const uint8_t* src = bytes;
         void* dst_off = offsets;
         uint8_t* dst_flags = line_flags;
         if (o.device_pointers) {
             if (reinterpret_cast<uintptr_t>(bytes) & 15u) return fail(GX_E_ARG, "gx_split_lines: device buffer must be 16-byte aligned");
         } else {
-            d_bytes.alloc(size);
-            d_off.alloc((cap_lines + 1) * off_w);
-            if (line_flags) d_flags.alloc(cap_lines);
-            if (size) GX_HIP(hipMemcpyAsync(d_bytes.p, bytes, size, hipMemcpyHostToDevice, stream));
-            src = static_cast<const uint8_t*>(d_bytes.p);
-            dst_off = d_off.p;
-            dst_flags = line_flags ? static_cast<uint8_t*>(d_flags.p) : nullptr;
+            d_bytes = dev_alloc(size);
+            d_off = dev_alloc((cap_lines + 1) * off_w);
+            if (line_flags) d_flags = dev_alloc<uint8_t>(cap_lines);
+            if (size) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, size, hipMemcpyHostToDevice, stream));
+            src = static_cast<const uint8_t*>(d_bytes.get());
+            dst_off = d_off.get();
+            dst_flags = d_flags.get();
         }
         uint64_t* d_n = nullptr;
         uint64_t* d_max = nullptr;
-        GX_HIP(launch_split_lines(src, size, dst_off, o.offsets64 ? 1 : 0, cap_lines, dst_flags, ws.p, &d_n, stream, max_line_bytes ? &d_max : nullptr));
+        GX_HIP(launch_split_lines(src, size, dst_off, o.offsets64 ? 1 : 0, cap_lines, dst_flags, ws, &d_n, stream, max_line_bytes ? &d_max : nullptr));
         uint64_t n_and_max[2] = {0, 0};   // (n_lines and max_line are neighbours in the workspace)
         GX_HIP(hipMemcpyAsync(n_and_max, d_n, max_line_bytes ? 16 : 8, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
@@ -771,12 +782,11 @@ int gx_split_lines_max(const uint8_t* bytes, uint64_t size, void* offsets, uint6
         if (max_line_bytes) *max_line_bytes = n_and_max[1];
         if (n > cap_lines) return fail(GX_E_LIMIT, "gx_split_lines: the buffer holds more lines than cap_lines");
         if (!o.device_pointers) {
-            GX_HIP(hipMemcpy(offsets, d_off.p, (n + 1) * off_w, hipMemcpyDeviceToHost));
-            if (line_flags && n) GX_HIP(hipMemcpy(line_flags, d_flags.p, n, hipMemcpyDeviceToHost));
+            GX_HIP(hipMemcpy(offsets, d_off.get(), (n + 1) * off_w, hipMemcpyDeviceToHost));
+            if (line_flags && n) GX_HIP(hipMemcpy(line_flags, d_flags.get(), n, hipMemcpyDeviceToHost));
         }
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
+    });
 }
 
 // One JSON template per extraction for ExtractionResult.asMap(idAs) (core/ExtractionResult.java:65-88), uploaded once
@@ -833,9 +843,9 @@ static const GxJsonl& jsonl_templates(gx_handle* h, const char* id_as) {
     const size_t o_seg = img.put(seg_off), o_lo = img.put(lit_off), o_ll = img.put(lit_len), o_g = img.put(group), o_f = img.put(fixed_len),
                  o_l = img.put(lits);
     gx_handle::JsonlImage ji;
-    GX_HIP(hipMalloc(&ji.d, img.bytes.size()));
-    GX_HIP(hipMemcpy(ji.d, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice));
-    const uint8_t* base = static_cast<const uint8_t*>(ji.d);
+    GX_HIP(hipMalloc(ji.d.out(), img.bytes.size()));
+    GX_HIP(hipMemcpy(ji.d.get(), img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice));
+    const uint8_t* base = static_cast<const uint8_t*>(ji.d.get());
     ji.dev.seg_off = reinterpret_cast<const uint32_t*>(base + o_seg);
     ji.dev.lit_off = reinterpret_cast<const uint32_t*>(base + o_lo);
     ji.dev.lit_len = reinterpret_cast<const uint32_t*>(base + o_ll);
@@ -845,58 +855,50 @@ static const GxJsonl& jsonl_templates(gx_handle* h, const char* id_as) {
     ji.dev.lits_bytes = static_cast<uint32_t>(lits.size());
     ji.dev.n_rules = static_cast<uint32_t>(T.n_rules);
     ji.dev.n_segs = static_cast<uint32_t>(group.size());
-    return h->jsonl.emplace(key, ji).first->second.dev;
+    return h->jsonl.emplace(key, std::move(ji)).first->second.dev;
 }
 
 int gx_results_to_jsonl(gx_handle* h, const uint8_t* bytes, const void* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps,
                         const char* id_as, uint8_t* out, uint64_t out_cap, uint64_t* out_size, uint64_t* line_out_offsets,
                         const gx_batch_opts* opts) {
-    if (!h || !offsets || !out_size || (n && !match_id)) return fail(GX_E_ARG, "gx_results_to_jsonl: bad argument");
-    if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    if (n && slots && !caps) return fail(GX_E_ARG, "gx_results_to_jsonl: caps is NULL");
-    if (slots > 128) return fail(GX_E_LIMIT, "gx_results_to_jsonl: more than 64 capture groups per extraction");
-    try {
+    return guarded([&]() -> int {
+        if (!h || !offsets || !out_size || (n && !match_id)) return fail(GX_E_ARG, "gx_results_to_jsonl: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const gx_batch_opts o = read_opts(opts);
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (n && slots && !caps) return fail(GX_E_ARG, "gx_results_to_jsonl: caps is NULL");
+        if (slots > 128) return fail(GX_E_LIMIT, "gx_results_to_jsonl: more than 64 capture groups per extraction");
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         const GxJsonl& tm = jsonl_templates(h, id_as);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
         const size_t off_w = o.offsets64 ? 8 : 4;
-        DevBuf d_bytes, d_off, d_mid, d_caps, d_out;
-        void* ws = handle_scratch(h, 0, jsonl_workspace_bytes(n));
+        DevMem<> d_bytes, d_off, d_mid, d_caps;
+        DevMem<uint8_t> d_out;
+        void* ws = h->scratch[0].get(jsonl_workspace_bytes(n));
         GxBatch b{};
         b.n = n;
         b.offsets64 = o.offsets64 ? 1 : 0;
         uint64_t* loff = line_out_offsets;
+        // mean line length, for the LDS staging of the kernels (device pointers: from the two ends of the offsets array)
+        std::pair<uint64_t, uint64_t> ends{0, 0};
         if (o.device_pointers) {
             b.data = bytes; b.offsets = offsets; b.match_id = const_cast<int32_t*>(match_id); b.caps = const_cast<int32_t*>(caps);
-            if (!loff) loff = static_cast<uint64_t*>(handle_scratch(h, 1, (n + 1) * 8));
+            if (!loff) loff = static_cast<uint64_t*>(h->scratch[1].get((n + 1) * 8));
+            if (n) ends = device_offset_ends(offsets, n, o.offsets64 != 0, stream);
         } else {
-            uint64_t total_in = 0;
-            if (n) total_in = o.offsets64 ? static_cast<const uint64_t*>(offsets)[n] : static_cast<const uint32_t*>(offsets)[n];
-            d_bytes.alloc(total_in); d_off.alloc((n + 1) * off_w); d_mid.alloc(n * 4); d_caps.alloc(n * slots * 4);
-            if (total_in) GX_HIP(hipMemcpyAsync(d_bytes.p, bytes, total_in, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.p, offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_mid.p, match_id, n * 4, hipMemcpyHostToDevice, stream));
-            if (n && slots) GX_HIP(hipMemcpyAsync(d_caps.p, caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            b.data = d_bytes.p; b.offsets = d_off.p; b.match_id = static_cast<int32_t*>(d_mid.p); b.caps = static_cast<int32_t*>(d_caps.p);
-            loff = static_cast<uint64_t*>(handle_scratch(h, 1, (n + 1) * 8));
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const uint64_t total_in = n ? off[n] : 0;
+            d_bytes = dev_alloc(total_in); d_off = dev_alloc((n + 1) * off_w); d_mid = dev_alloc(n * 4); d_caps = dev_alloc(n * slots * 4);
+            if (total_in) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, total_in, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_mid.get(), match_id, n * 4, hipMemcpyHostToDevice, stream));
+            if (n && slots) GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            b.data = d_bytes.get(); b.offsets = d_off.get(); b.match_id = static_cast<int32_t*>(d_mid.get()); b.caps = static_cast<int32_t*>(d_caps.get());
+            loff = static_cast<uint64_t*>(h->scratch[1].get((n + 1) * 8));
+            if (n) ends = {off[0], off[n]};
         }
-        // mean line length, for the LDS staging of the kernels (device pointers: from the two ends of the offsets array)
-        uint64_t first_off = 0, last_off = 0;
-        if (n) {
-            if (o.device_pointers) {
-                GX_HIP(hipMemcpyAsync(&first_off, offsets, off_w, hipMemcpyDeviceToHost, stream));
-                GX_HIP(hipMemcpyAsync(&last_off, static_cast<const uint8_t*>(offsets) + n * off_w, off_w, hipMemcpyDeviceToHost, stream));
-                GX_HIP(hipStreamSynchronize(stream));
-            } else {
-                first_off = o.offsets64 ? static_cast<const uint64_t*>(offsets)[0] : static_cast<const uint32_t*>(offsets)[0];
-                last_off = o.offsets64 ? static_cast<const uint64_t*>(offsets)[n] : static_cast<const uint32_t*>(offsets)[n];
-            }
-        }
-        const uint32_t mean_in = n ? static_cast<uint32_t>(std::min<uint64_t>((last_off - first_off + n - 1) / n, 1u << 20)) : 1u;
+        const uint32_t mean_in = n ? static_cast<uint32_t>(std::min<uint64_t>((ends.second - ends.first + n - 1) / n, 1u << 20)) : 1u;
         GX_HIP(launch_jsonl_sizes(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, loff, ws, stream));
         uint64_t total = 0;
         GX_HIP(hipMemcpyAsync(&total, loff + n, 8, hipMemcpyDeviceToHost, stream));
@@ -906,49 +908,46 @@ int gx_results_to_jsonl(gx_handle* h, const uint8_t* bytes, const void* offsets,
         if (!out) return GX_OK;  // size query
         if (total > out_cap) return fail(GX_E_LIMIT, "gx_results_to_jsonl: out_cap is smaller than the text (see *out_size)");
         uint8_t* dst = out;
-        if (!o.device_pointers) { d_out.alloc(total); dst = static_cast<uint8_t*>(d_out.p); }
+        if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(total); dst = d_out.get(); }
         const uint32_t mean_out = n ? static_cast<uint32_t>(std::min<uint64_t>((total + n - 1) / n, 1u << 20)) : 1u;
         GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, mean_out, loff, dst, ws, stream));
         if (!o.device_pointers && total) GX_HIP(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const char* id_as, uint8_t* out, uint64_t out_cap, uint64_t* out_size,
                      uint64_t* n_lines, uint64_t* n_matched, uint64_t* n_exceptions, const gx_batch_opts* opts) {
-    if (!h || !out_size || (size && !text)) return fail(GX_E_ARG, "gx_text_to_jsonl: bad argument");
-    if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-    if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_to_jsonl: split texts of 4 GiB and more at a line boundary");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    if (slots > 128) return fail(GX_E_LIMIT, "gx_text_to_jsonl: more than 64 capture groups per extraction");
-    try {
+    return guarded([&]() -> int {
+        if (!h || !out_size || (size && !text)) return fail(GX_E_ARG, "gx_text_to_jsonl: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_to_jsonl: split texts of 4 GiB and more at a line boundary");
+        const gx_batch_opts o = read_opts(opts);
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (slots > 128) return fail(GX_E_LIMIT, "gx_text_to_jsonl: more than 64 capture groups per extraction");
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         const GxJsonl& tm = jsonl_templates(h, id_as);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevBuf d_text, d_out;   // (host buffers only; everything between lives in the handle's scratch: 2 split workspace, 3 offsets, 4 ids, 5 captures, 6 counts)
+        DevMem<uint8_t> d_text, d_out;   // (host buffers only; everything between lives in the handle's scratch: 2 split workspace, 3 offsets, 4 ids, 5 captures, 6 counts)
         const uint8_t* src = text;
         if (!o.device_pointers) {
-            d_text.alloc(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.p, text, size, hipMemcpyHostToDevice, stream));
-            src = static_cast<const uint8_t*>(d_text.p);
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
         } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
             return fail(GX_E_ARG, "gx_text_to_jsonl: device text must be 16-byte aligned");
         }
         // 1. lines: offsets for the guess "64 bytes or more per line"; a text with shorter lines is split a second time
-        void* ws_split = handle_scratch(h, 2, split_workspace_bytes(size));
+        void* ws_split = h->scratch[2].get(split_workspace_bytes(size));
         uint64_t cap = size / 64 + 4096;
-        void* d_off2 = handle_scratch(h, 3, (cap + 1) * 4);
+        void* d_off2 = h->scratch[3].get((cap + 1) * 4);
         uint64_t* d_n = nullptr;
         uint64_t* d_max = nullptr;
         // (the split pass also leaves a bit per byte that takes one more byte inside a JSON string, and says whether some byte takes five
         // more -- a control character --: without one, the sizes pass below does not read the text again)
-        uint16_t* esc_bits = static_cast<uint16_t*>(handle_scratch(h, 7, ((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
+        uint16_t* esc_bits = static_cast<uint16_t*>(h->scratch[7].get(((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
         GX_HIP(launch_split_lines(src, size, d_off2, 0, cap, nullptr, ws_split, &d_n, stream, &d_max, esc_bits, o.utf8_passthrough ? 1 : 0));
         uint64_t n_and_max[3] = {0, 0, 0};   // (the line count, the longest line and the control-character word are neighbours in the workspace)
         GX_HIP(hipMemcpyAsync(n_and_max, d_n, 24, hipMemcpyDeviceToHost, stream));
@@ -957,13 +956,13 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         uint64_t longest = n_and_max[1];
         const bool sizes_from_bits = n_and_max[2] == 0;
         if (n > cap) {
-            d_off2 = handle_scratch(h, 3, (n + 1) * 4);
+            d_off2 = h->scratch[3].get((n + 1) * 4);
             GX_HIP(launch_split_lines(src, size, d_off2, 0, n, nullptr, ws_split, &d_n, stream));
             longest = 0;   // (measured over the first `cap` lines only: no promise)
         }
         // 2. the path
-        void* d_mid = handle_scratch(h, 4, n * 4 + 16);
-        void* d_caps = handle_scratch(h, 5, n * slots * 4 + 16);
+        void* d_mid = h->scratch[4].get(n * 4 + 16);
+        void* d_caps = h->scratch[5].get(n * slots * 4 + 16);
         GxBatch b{};
         b.data = src; b.offsets = d_off2; b.n = n; b.match_id = static_cast<int32_t*>(d_mid);
         b.caps = h->T.has_capture ? static_cast<int32_t*>(d_caps) : nullptr;
@@ -974,11 +973,11 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         launch_batch(h, b, mean_in, GX_KERNEL_AUTO, stream);
         if (!h->T.has_capture && n && slots) GX_HIP(hipMemsetAsync(d_caps, 0xFF, n * slots * 4, stream));
         b.caps = static_cast<int32_t*>(d_caps);
-        void* d_counts = handle_scratch(h, 6, 16);
+        void* d_counts = h->scratch[6].get(16);
         GX_HIP(launch_count_outcomes(b.match_id, n, static_cast<unsigned long long*>(d_counts), stream));
         // 3. the text
-        void* ws_json = handle_scratch(h, 0, jsonl_workspace_bytes(n));
-        uint64_t* loff = static_cast<uint64_t*>(handle_scratch(h, 1, (n + 1) * 8));
+        void* ws_json = h->scratch[0].get(jsonl_workspace_bytes(n));
+        uint64_t* loff = static_cast<uint64_t*>(h->scratch[1].get((n + 1) * 8));
         GX_HIP(launch_jsonl_sizes(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, loff, ws_json, stream,
                                   sizes_from_bits ? reinterpret_cast<const uint32_t*>(esc_bits) : nullptr));
         uint64_t total = 0;
@@ -995,57 +994,51 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         if (!out) return GX_OK;
         if (total > out_cap) return fail(GX_E_LIMIT, "gx_text_to_jsonl: out_cap is smaller than the text (see *out_size)");
         uint8_t* dst = out;
-        if (!o.device_pointers) { d_out.alloc(total); dst = static_cast<uint8_t*>(d_out.p); }
+        if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(total); dst = d_out.get(); }
         const uint32_t mean_out = n ? static_cast<uint32_t>(std::min<uint64_t>((total + n - 1) / n, 1u << 20)) : 1u;
         GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, mean_out, loff, dst, ws_json, stream));
         if (!o.device_pointers && total) GX_HIP(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 int gx_pack_results(const int32_t* match_id, const int32_t* caps, uint64_t n, int32_t slots, uint16_t* packed, uint64_t* n_overflow,
                     const gx_batch_opts* opts) {
-    if (slots < 0 || !n_overflow || (n && (!match_id || !packed || (slots && !caps)))) return fail(GX_E_ARG, "gx_pack_results: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    try {
+    return guarded([&]() -> int {
+        if (slots < 0 || !n_overflow || (n && (!match_id || !packed || (slots && !caps)))) return fail(GX_E_ARG, "gx_pack_results: bad argument");
+        const gx_batch_opts o = read_opts(opts);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevBuf cnt;
-        cnt.alloc(8);
-        GX_HIP(launch_pack_results(match_id, caps, n, slots, packed, static_cast<unsigned long long*>(cnt.p), stream));
+        const DevMem<unsigned long long> cnt = dev_alloc<unsigned long long>(8);
+        GX_HIP(launch_pack_results(match_id, caps, n, slots, packed, cnt.get(), stream));
         unsigned long long over = 0;
-        GX_HIP(hipMemcpyAsync(&over, cnt.p, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&over, cnt.get(), 8, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         *n_overflow = over;
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
+    });
 }
 
 int gx_unpack_results(const uint16_t* packed, uint64_t n, int32_t slots, int32_t* match_id, int32_t* caps, const gx_batch_opts* opts) {
-    if (slots < 0 || (n && (!match_id || !packed || (slots && !caps)))) return fail(GX_E_ARG, "gx_unpack_results: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    try {
+    return guarded([&]() -> int {
+        if (slots < 0 || (n && (!match_id || !packed || (slots && !caps)))) return fail(GX_E_ARG, "gx_unpack_results: bad argument");
+        const gx_batch_opts o = read_opts(opts);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
         GX_HIP(launch_unpack_results(packed, n, slots, match_id, caps, stream));
         if (!o.no_sync) GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
+    });
 }
 
 int gx_unpack_results8(const uint8_t* rows, uint64_t n, int32_t slots, int32_t* match_id, int32_t* caps, const gx_batch_opts* opts) {
-    if (slots < 0 || (n && (!match_id || !rows || (slots && !caps)))) return fail(GX_E_ARG, "gx_unpack_results8: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    try {
+    return guarded([&]() -> int {
+        if (slots < 0 || (n && (!match_id || !rows || (slots && !caps)))) return fail(GX_E_ARG, "gx_unpack_results8: bad argument");
+        const gx_batch_opts o = read_opts(opts);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
         GX_HIP(launch_unpack_results8(rows, n, slots, match_id, caps, stream));
         if (!o.no_sync) GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
+    });
 }
 
 int gx_set_extraction_meta(gx_handle* h, int32_t k, const char* name, const char* const* extractor_names, int32_t n_names,
@@ -1053,44 +1046,38 @@ int gx_set_extraction_meta(gx_handle* h, int32_t k, const char* name, const char
     if (!h || !name || k < 0 || k >= h->T.n_rules || n_names < 0 || (n_names && !extractor_names))
         return fail(GX_E_ARG, "gx_set_extraction_meta: bad argument");
     if (n_names != h->T.rules[k].n_groups) return fail(GX_E_ARG, "gx_set_extraction_meta: n_names must equal gx_num_groups(h, k)");
-    try {
+    return guarded([&]() -> int {
         std::lock_guard<std::mutex> lock(h->mu);
         if (static_cast<int>(h->meta.size()) != h->T.n_rules) h->meta.assign(h->T.n_rules, dsl::Extraction());
         dsl::Extraction& x = h->meta[k];
         x.name = name;
         x.extractor_names.assign(extractor_names, extractor_names + n_names);
         x.append_json = append_json ? dsl::canonical_json_object(append_json) : std::string();
-        for (auto& e : h->jsonl) if (e.second.d) (void)hipFree(e.second.d);
         h->jsonl.clear();
         h->append_entries.clear();
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 // One host-pointer batch through the workers of gx_handle::host_slot.  `proto` carries the batch's modes (wide,
 // offsets64, match_only, strip_eol); lines [0, n) are cut into chunks of whole lines of about chunk_bytes, chunk c goes
 // to worker c % HOST_WORKERS.  A chunk's lines keep their offsets: the kernels get a data pointer moved back by the
 // chunk's first offset instead of rebased offsets.
-static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* bytes, const void* offsets, uint64_t n, uint64_t total,
+static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* bytes, const HostOffsets& off, uint64_t total,
                           int32_t* match_id, int32_t* caps, int32_t* states, bool compact, bool match_only, uint32_t hint, uint32_t kernel,
                           bool uneven, uint64_t* over_total) {
+    const uint64_t n = off.n;
     if (n == 0) return;
     const size_t unit = proto.wide ? 2 : 1, off_w = proto.offsets64 ? 8 : 4;
     const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    auto off_at = [&](uint64_t i) -> uint64_t {
-        return proto.offsets64 ? static_cast<const uint64_t*>(offsets)[i] : static_cast<const uint32_t*>(offsets)[i];
-    };
     // chunks: large enough to amortise a launch, small enough that the pipeline has several in flight
     const uint64_t total_bytes = total * unit;
     uint64_t chunk_bytes = std::max<uint64_t>(total_bytes / (4 * gx_handle::HOST_WORKERS), 8ull << 20);
     chunk_bytes = std::min<uint64_t>(chunk_bytes, 128ull << 20);
     std::vector<uint64_t> cuts(1, 0);
     while (cuts.back() < n) {
-        const uint64_t a = cuts.back(), want = off_at(a) * unit + chunk_bytes;
-        uint64_t lo = a + 1, hi = n;  // first line index whose start lies at or beyond `want` (at least one line per chunk)
-        while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (off_at(mid) * unit >= want) hi = mid; else lo = mid + 1; }
-        uint64_t b_ = lo;
+        const uint64_t a = cuts.back();
+        uint64_t b_ = off.lines_at_or_after(off[a] + (chunk_bytes + unit - 1) / unit, a + 1);   // (at least one line per chunk)
         if (b_ - a > 0x7FFFFFF0ull) b_ = a + 0x7FFFFFF0ull;
         cuts.push_back(std::min<uint64_t>(b_, n));
     }
@@ -1101,62 +1088,51 @@ static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* byt
     int err_code = GX_OK;
     std::string err_msg;
     auto work = [&](int w) {
-        try {
+        const int rc = guarded([&]() -> int {
             GX_HIP(hipSetDevice(h->device));
             gx_handle::HostSlot& sl = h->host_slot[w];
-            if (!sl.stream) GX_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-            auto grow = [&](void*& p, size_t& cap, size_t need) {
-                if (need <= cap) return;
-                if (p) GX_HIP(hipFree(p));
-                p = nullptr; cap = 0;
-                GX_HIP(hipMalloc(&p, need + need / 8 + 256));
-                cap = need + need / 8 + 256;
-            };
-            if (compact && !sl.d_over) GX_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_over), 8));
+            if (!sl.stream) GX_HIP(hipStreamCreateWithFlags(sl.stream.out(), hipStreamNonBlocking));
+            hipStream_t stream = sl.stream.get();
+            if (compact && !sl.over) GX_HIP(hipMalloc(sl.over.out(), 8));
             for (size_t c = static_cast<size_t>(w); c < n_chunks; c += static_cast<size_t>(workers)) {
                 const uint64_t a = cuts[c], e = cuts[c + 1], m = e - a;
-                const uint64_t b0 = off_at(a) * unit, nbytes = off_at(e) * unit - b0;
-                grow(sl.d_bytes, sl.cap_bytes, nbytes + 64);
-                grow(sl.d_off, sl.cap_off, (m + 1) * off_w);
+                const uint64_t b0 = off[a] * unit, nbytes = off[e] * unit - b0;
+                uint8_t* place = static_cast<uint8_t*>(sl.bytes.get(nbytes + 64)) + 16;  // (a 16-byte aligned first line, room for the aligned span before it)
+                void* d_off = sl.off.get((m + 1) * off_w);
                 GxBatch b = proto;
                 b.n = m;
-                uint8_t* place = static_cast<uint8_t*>(sl.d_bytes) + 16;  // (a 16-byte aligned first line, room for the aligned span before it)
                 b.data = place - b0;
-                b.offsets = sl.d_off;
-                if (nbytes) GX_HIP(hipMemcpyAsync(place, bytes + b0, nbytes, hipMemcpyHostToDevice, sl.stream));
-                GX_HIP(hipMemcpyAsync(sl.d_off, static_cast<const uint8_t*>(offsets) + a * off_w, (m + 1) * off_w, hipMemcpyHostToDevice, sl.stream));
-                if (states) { grow(sl.d_states, sl.cap_states, m * 4); b.state_out = static_cast<int32_t*>(sl.d_states); }
+                b.offsets = d_off;
+                if (nbytes) GX_HIP(hipMemcpyAsync(place, bytes + b0, nbytes, hipMemcpyHostToDevice, stream));
+                GX_HIP(hipMemcpyAsync(d_off, static_cast<const uint8_t*>(off.p) + a * off_w, (m + 1) * off_w, hipMemcpyHostToDevice, stream));
+                if (states) b.state_out = static_cast<int32_t*>(sl.states.get(m * 4));
                 const size_t row_bytes = (1 + slots) * (proto.narrow ? 1 : 2);  // compact rows: u8 or u16 entries
                 if (compact) {
-                    grow(sl.d_res, sl.cap_res, m * row_bytes);
-                    GX_HIP(hipMemsetAsync(sl.d_over, 0, 8, sl.stream));
-                    b.packed = static_cast<uint16_t*>(sl.d_res);
-                    b.overflow = sl.d_over;
+                    b.packed = static_cast<uint16_t*>(sl.res.get(m * row_bytes));
+                    GX_HIP(hipMemsetAsync(sl.over.get(), 0, 8, stream));
+                    b.overflow = sl.over.get();
                 } else {
-                    grow(sl.d_res, sl.cap_res, m * 4);
-                    b.match_id = static_cast<int32_t*>(sl.d_res);
-                    if (!match_only) { grow(sl.d_caps, sl.cap_caps, m * slots * 4 + 16); b.caps = static_cast<int32_t*>(sl.d_caps); }
+                    b.match_id = static_cast<int32_t*>(sl.res.get(m * 4));
+                    if (!match_only) b.caps = static_cast<int32_t*>(sl.caps.get(m * slots * 4 + 16));
                 }
-                launch_batch(h, b, hint, kernel, sl.stream, uneven);
+                launch_batch(h, b, hint, kernel, stream, uneven);
                 unsigned long long over = 0;
                 if (compact) {
-                    GX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(caps) + a * row_bytes, sl.d_res, m * row_bytes, hipMemcpyDeviceToHost, sl.stream));
-                    GX_HIP(hipMemcpyAsync(&over, sl.d_over, 8, hipMemcpyDeviceToHost, sl.stream));
+                    GX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(caps) + a * row_bytes, b.packed, m * row_bytes, hipMemcpyDeviceToHost, stream));
+                    GX_HIP(hipMemcpyAsync(&over, sl.over.get(), 8, hipMemcpyDeviceToHost, stream));
                 } else {
-                    GX_HIP(hipMemcpyAsync(match_id + a, sl.d_res, m * 4, hipMemcpyDeviceToHost, sl.stream));
-                    if (!match_only && slots) GX_HIP(hipMemcpyAsync(caps + a * slots, sl.d_caps, m * slots * 4, hipMemcpyDeviceToHost, sl.stream));
+                    GX_HIP(hipMemcpyAsync(match_id + a, b.match_id, m * 4, hipMemcpyDeviceToHost, stream));
+                    if (!match_only && slots) GX_HIP(hipMemcpyAsync(caps + a * slots, b.caps, m * slots * 4, hipMemcpyDeviceToHost, stream));
                 }
-                if (states) GX_HIP(hipMemcpyAsync(states + a, sl.d_states, m * 4, hipMemcpyDeviceToHost, sl.stream));
-                GX_HIP(hipStreamSynchronize(sl.stream));  // this worker's buffers are free again; the other workers keep the bus busy
+                if (states) GX_HIP(hipMemcpyAsync(states + a, b.state_out, m * 4, hipMemcpyDeviceToHost, stream));
+                GX_HIP(hipStreamSynchronize(stream));  // this worker's buffers are free again; the other workers keep the bus busy
                 over_sum += over;
             }
-        } catch (GxError& e) {
-            std::lock_guard<std::mutex> g(err_mu);
-            if (err_code == GX_OK) { err_code = e.code; err_msg = e.what(); }
-        } catch (std::bad_alloc&) {
-            std::lock_guard<std::mutex> g(err_mu);
-            if (err_code == GX_OK) { err_code = GX_E_NOMEM; err_msg = "out of memory"; }
-        }
+            return GX_OK;
+        });
+        if (rc == GX_OK) return;
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_code == GX_OK) { err_code = rc; err_msg = g_last_error; }
     };
     if (workers == 1) work(0);
     else {
@@ -1170,18 +1146,16 @@ static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* byt
 
 // Do the lines of a batch differ much in length?  Lines run in lock step in groups of 64, a group takes as long as its longest
 // line: over a sample of up to 64 groups spread over the batch, (sum of 64 x longest line) / (sum of lengths) > 1.25.
-// offsets: n + 1 offsets in HOST memory.
-static bool lines_are_uneven(const void* offsets, uint64_t n, bool off64) {
-    if (n < 128) return false;
-    auto at = [&](uint64_t i) -> uint64_t { return off64 ? static_cast<const uint64_t*>(offsets)[i] : static_cast<const uint32_t*>(offsets)[i]; };
-    const uint64_t groups = n / 64, sample = std::min<uint64_t>(groups, 64), stride = groups / sample;
+static bool lines_are_uneven(const HostOffsets& off) {
+    if (off.n < 128) return false;
+    const uint64_t groups = off.n / 64, sample = std::min<uint64_t>(groups, 64), stride = groups / sample;
     uint64_t lock_step = 0, bytes = 0;
     for (uint64_t g = 0; g < sample; ++g) {
         const uint64_t i0 = g * stride * 64;
         uint64_t longest = 0;
-        for (uint64_t i = i0; i < i0 + 64; ++i) longest = std::max(longest, at(i + 1) - at(i));
+        for (uint64_t i = i0; i < i0 + 64; ++i) longest = std::max(longest, off[i + 1] - off[i]);
         lock_step += 64 * longest;
-        bytes += at(i0 + 64) - at(i0);
+        bytes += off[i0 + 64] - off[i0];
     }
     return bytes > 0 && lock_step * 4 > bytes * 5;
 }
@@ -1190,19 +1164,18 @@ static bool lines_are_uneven(const void* offsets, uint64_t n, bool off64) {
 // per-line generic kernel then, which is the one that keeps it)
 static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* offsets, uint64_t n, int32_t* match_id, int32_t* caps,
                               int32_t* states, const gx_batch_opts* opts) {
-    if (!h || !offsets) return fail(GX_E_ARG, "gx_extract_batch: bad argument");
-    if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    if (o.kernel > GX_KERNEL_HOP_SLICES) return fail(GX_E_ARG, "gx_batch_opts.kernel: unknown kernel");
-    const bool match_only = o.match_only || states || !h->T.has_capture;
-    const bool compact = o.compact_results && !match_only;  // rows of u16[1 + slots] (2: u8[1 + slots]) through `caps`
-    if (o.compact_results > 2) return fail(GX_E_ARG, "gx_batch_opts.compact_results: 0, 1 (u16 rows) or 2 (u8 rows)");
-    if (compact && o.compact_results == 2 && h->T.n_rules > 126)
-        return fail(GX_E_ARG, "gx_batch_opts.compact_results = 2: u8 rows hold match ids -128 .. 127 (at most 126 extractions)");
-    if (!compact && !match_id) return fail(GX_E_ARG, "gx_extract_batch: match_id is NULL");
-    if (!match_only && !caps && n > 0 && (compact || h->T.max_groups > 0)) return fail(GX_E_ARG, "gx_extract_batch: caps is NULL");
-    try {
+    return guarded([&]() -> int {
+        if (!h || !offsets) return fail(GX_E_ARG, "gx_extract_batch: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const gx_batch_opts o = read_opts(opts);
+        if (o.kernel > GX_KERNEL_HOP_SLICES) return fail(GX_E_ARG, "gx_batch_opts.kernel: unknown kernel");
+        const bool match_only = o.match_only || states || !h->T.has_capture;
+        const bool compact = o.compact_results && !match_only;  // rows of u16[1 + slots] (2: u8[1 + slots]) through `caps`
+        if (o.compact_results > 2) return fail(GX_E_ARG, "gx_batch_opts.compact_results: 0, 1 (u16 rows) or 2 (u8 rows)");
+        if (compact && o.compact_results == 2 && h->T.n_rules > 126)
+            return fail(GX_E_ARG, "gx_batch_opts.compact_results = 2: u8 rows hold match ids -128 .. 127 (at most 126 extractions)");
+        if (!compact && !match_id) return fail(GX_E_ARG, "gx_extract_batch: match_id is NULL");
+        if (!match_only && !caps && n > 0 && (compact || h->T.max_groups > 0)) return fail(GX_E_ARG, "gx_extract_batch: caps is NULL");
         GX_HIP(hipSetDevice(h->device));
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
         GxBatch b{};
@@ -1212,7 +1185,6 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
         b.match_only = match_only ? 1 : 0;
         b.strip_eol = o.strip_eol ? 1 : 0;
         b.narrow = (compact && o.compact_results == 2) ? 1 : 0;
-        const size_t off_w = o.offsets64 ? 8 : 4;
         if (o.device_pointers) {
             b.data = bytes; b.offsets = offsets;
             b.state_out = states;
@@ -1226,47 +1198,21 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
             uint32_t hint = o.line_bytes_hint;
             bool uneven = o.uneven_lines == 2;
             if (hint == 0 && n && o.no_sync) {
-                // no hint and no synchronisation allowed: what the previous such batch measured (200 until one has), and
-                // a probe of this batch for the next call
-                std::lock_guard<std::mutex> lock(h->hint_mu);
-                if (!h->hint_probe) {
-                    GX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->hint_probe), 16, hipHostMallocDefault));
-                    GX_HIP(hipEventCreateWithFlags(&h->hint_event, hipEventDisableTiming));
-                }
-                if (h->hint_pending && hipEventQuery(h->hint_event) == hipSuccess) {
-                    const uint64_t first = h->hint_off64 ? h->hint_probe[0] : (h->hint_probe[0] & 0xFFFFFFFFull);
-                    const uint64_t last = h->hint_off64 ? h->hint_probe[1] : (h->hint_probe[1] & 0xFFFFFFFFull);
-                    if (h->hint_n && last >= first)
-                        h->learned_hint = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((last - first + h->hint_n - 1) / h->hint_n, 4096)));
-                    h->hint_pending = false;
-                }
-                hint = h->learned_hint;
-                if (!h->hint_pending) {
-                    h->hint_probe[0] = h->hint_probe[1] = 0;
-                    GX_HIP(hipMemcpyAsync(&h->hint_probe[0], offsets, off_w, hipMemcpyDeviceToHost, stream));
-                    GX_HIP(hipMemcpyAsync(&h->hint_probe[1], static_cast<const uint8_t*>(offsets) + n * off_w, off_w, hipMemcpyDeviceToHost, stream));
-                    GX_HIP(hipEventRecord(h->hint_event, stream));
-                    h->hint_pending = true;
-                    h->hint_n = n;
-                    h->hint_off64 = o.offsets64 != 0;
-                }
-            }
-            if (hint == 0 && n && !o.no_sync) {
+                hint = h->hint.next(offsets, n, o.offsets64 != 0, stream);
+            } else if (hint == 0 && n) {
                 // no hint: the mean line length, from the two ends of the offsets array (a small synchronous read;
                 // asynchronous callers pass line_bytes_hint themselves)
-                uint64_t first = 0, last = 0;
-                GX_HIP(hipMemcpyAsync(&first, offsets, off_w, hipMemcpyDeviceToHost, stream));
-                GX_HIP(hipMemcpyAsync(&last, static_cast<const uint8_t*>(offsets) + n * off_w, off_w, hipMemcpyDeviceToHost, stream));
-                GX_HIP(hipStreamSynchronize(stream));
+                const auto [first, last] = device_offset_ends(offsets, n, o.offsets64 != 0, stream);
                 hint = static_cast<uint32_t>(std::min<uint64_t>((last - first + n - 1) / n, 4096));
                 if (hint == 0) hint = 1;
                 if (o.uneven_lines == 0 && n >= 128) {
                     // ... and whether the lines differ much in length: the first 4096 of them
                     const uint64_t m = std::min<uint64_t>(n, 4096);
+                    const size_t off_w = o.offsets64 ? 8 : 4;
                     std::vector<uint8_t> sample((m + 1) * off_w);
                     GX_HIP(hipMemcpyAsync(sample.data(), offsets, sample.size(), hipMemcpyDeviceToHost, stream));
                     GX_HIP(hipStreamSynchronize(stream));
-                    uneven = lines_are_uneven(sample.data(), m, o.offsets64 != 0);
+                    uneven = lines_are_uneven(HostOffsets{sample.data(), o.offsets64 != 0, m});
                 }
             }
             b.max_line_bytes = o.max_line_bytes;
@@ -1275,14 +1221,12 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
             launch_batch(h, b, hint, o.kernel, stream, uneven, &done);
             if (!o.no_sync) {
                 GX_HIP(hipStreamSynchronize(stream));
-                if (done.promised && __atomic_load_n(&h->h_broken[done.slot], __ATOMIC_RELAXED) == done.seq) {
+                if (done.promised && h->slots.word(done.slot) == done.seq) {
                     // the promise did not hold: the lines the batch kernel left, now (and the word is clean for the stream's next launch)
                     {
                         std::lock_guard<std::mutex> lock(h->slot_mu);
-                        if (h->promise_seq[done.slot] == done.seq) h->promise_seq[done.slot] = 0;
-                        h->broken_seen[done.slot] = done.seq;   // (seen, and put right below)
+                        h->slots.mark_seen(done.slot, done.seq);
                     }
-                    h->promises_broken.fetch_add(1);
                     b.seq = done.seq;
                     b.oversize_flag = h->d_broken + done.slot;
                     PikeGate pike_gate(h, stream);
@@ -1294,18 +1238,16 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
         }
         // host pointers: the chunked pipeline (gx_handle::host_slot)
         std::lock_guard<std::mutex> lock(h->mu);
-        uint64_t total = 0;  // code units in the batch (offsets need not start at 0: a shard of a larger CSR buffer)
-        if (n) total = o.offsets64 ? static_cast<const uint64_t*>(offsets)[n] - static_cast<const uint64_t*>(offsets)[0]
-                                   : static_cast<const uint32_t*>(offsets)[n] - static_cast<const uint32_t*>(offsets)[0];
+        const HostOffsets off{offsets, o.offsets64 != 0, n};
+        const uint64_t total = n ? off[n] - off[0] : 0;  // code units in the batch (offsets need not start at 0: a shard of a larger CSR buffer)
         uint32_t hint = o.line_bytes_hint;
         if (hint == 0 && n) hint = static_cast<uint32_t>(std::min<uint64_t>((total + n - 1) / n, 1u << 20));
         uint64_t over_total = 0;
-        const bool uneven = o.uneven_lines == 2 || (o.uneven_lines == 0 && lines_are_uneven(offsets, n, o.offsets64 != 0));
-        host_pipeline(h, b, bytes, offsets, n, total, match_id, caps, states, compact, match_only, hint, o.kernel, uneven, &over_total);
+        const bool uneven = o.uneven_lines == 2 || (o.uneven_lines == 0 && lines_are_uneven(off));
+        host_pipeline(h, b, bytes, off, total, match_id, caps, states, compact, match_only, hint, o.kernel, uneven, &over_total);
         if (compact && o.overflow) *static_cast<uint64_t*>(o.overflow) += over_total;
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
+    });
 }
 
 int gx_extract_batch(gx_handle* h, const uint8_t* bytes, const void* offsets, uint64_t n, int32_t* match_id, int32_t* caps,
@@ -1347,116 +1289,110 @@ int gx_host_unregister(void* p) {
 int gx_extract_batch_multi(gx_handle* const* handles, int32_t n_handles, const uint8_t* bytes, const void* offsets, uint64_t n,
                            int32_t* match_id, int32_t* caps, const gx_batch_opts* opts) {
     if (!handles || n_handles <= 0 || !offsets) return fail(GX_E_ARG, "gx_extract_batch_multi: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    if (o.device_pointers) return fail(GX_E_ARG, "gx_extract_batch_multi: host buffers only (device buffers belong to one device: use gx_extract_batch per handle)");
-    for (int32_t k = 0; k < n_handles; ++k) {
-        if (!handles[k] || !handles[k]->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi: NULL or host-only handle");
-        if (handles[k]->T.max_groups != handles[0]->T.max_groups || handles[k]->T.n_rules != handles[0]->T.n_rules)
-            return fail(GX_E_ARG, "gx_extract_batch_multi: the handles were not built from the same definition");
-    }
-    const size_t off_w = o.offsets64 ? 8 : 4;
-    auto off_at = [&](uint64_t i) -> uint64_t {
-        return o.offsets64 ? static_cast<const uint64_t*>(offsets)[i] : static_cast<const uint32_t*>(offsets)[i];
-    };
-    // shard boundaries by bytes
-    std::vector<uint64_t> cuts(static_cast<size_t>(n_handles) + 1, n);
-    cuts[0] = 0;
-    const uint64_t base = n ? off_at(0) : 0, total = n ? off_at(n) - base : 0;
-    for (int32_t k = 1; k < n_handles; ++k) {
-        const uint64_t want = base + total / static_cast<uint64_t>(n_handles) * static_cast<uint64_t>(k);
-        uint64_t lo = cuts[k - 1], hi = n;
-        while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (off_at(mid) >= want) hi = mid; else lo = mid + 1; }
-        cuts[k] = lo;
-    }
-    const bool compact = o.compact_results && !(o.match_only || !handles[0]->T.has_capture);
-    const size_t slots = 2 * static_cast<size_t>(handles[0]->T.max_groups);
-    std::vector<int> rc(static_cast<size_t>(n_handles), GX_OK);
-    std::vector<std::string> msg(static_cast<size_t>(n_handles));
-    std::vector<uint64_t> over(static_cast<size_t>(n_handles), 0);
-    std::vector<std::thread> pool;
-    for (int32_t k = 0; k < n_handles; ++k) {
-        pool.emplace_back([&, k]() {
-            const uint64_t a = cuts[k], m = cuts[k + 1] - cuts[k];
-            if (m == 0) return;
-            gx_batch_opts ok = o;
-            ok.struct_size = sizeof(gx_batch_opts);
-            ok.stream = nullptr;
-            ok.overflow = compact ? &over[k] : nullptr;
-            int32_t* mid_k = match_id ? match_id + a : nullptr;
-            const size_t row_bytes = (1 + slots) * (o.compact_results == 2 ? 1 : 2);
-            int32_t* caps_k = !caps ? nullptr : compact ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(caps) + a * row_bytes) : caps + a * slots;
-            rc[k] = gx_extract_batch(handles[k], bytes, static_cast<const uint8_t*>(offsets) + a * off_w, m, mid_k, caps_k, &ok);
-            if (rc[k] != GX_OK) msg[k] = gx_last_error();
-        });
-    }
-    for (auto& t : pool) t.join();
-    for (int32_t k = 0; k < n_handles; ++k) if (rc[k] != GX_OK) return fail(rc[k], msg[k]);
-    if (compact && o.overflow) for (uint64_t v : over) *static_cast<uint64_t*>(o.overflow) += v;
-    return GX_OK;
+    return guarded([&]() -> int {
+        const gx_batch_opts o = read_opts(opts);
+        if (o.device_pointers) return fail(GX_E_ARG, "gx_extract_batch_multi: host buffers only (device buffers belong to one device: use gx_extract_batch per handle)");
+        for (int32_t k = 0; k < n_handles; ++k) {
+            if (!handles[k] || !handles[k]->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi: NULL or host-only handle");
+            if (handles[k]->T.max_groups != handles[0]->T.max_groups || handles[k]->T.n_rules != handles[0]->T.n_rules)
+                return fail(GX_E_ARG, "gx_extract_batch_multi: the handles were not built from the same definition");
+        }
+        const size_t off_w = o.offsets64 ? 8 : 4;
+        const HostOffsets off{offsets, o.offsets64 != 0, n};
+        // shard boundaries by bytes
+        std::vector<uint64_t> cuts(static_cast<size_t>(n_handles) + 1, n);
+        cuts[0] = 0;
+        const uint64_t base = n ? off[0] : 0, total = n ? off[n] - base : 0;
+        for (int32_t k = 1; k < n_handles; ++k)
+            cuts[k] = off.lines_at_or_after(base + total / static_cast<uint64_t>(n_handles) * static_cast<uint64_t>(k), cuts[k - 1]);
+        const bool compact = o.compact_results && !(o.match_only || !handles[0]->T.has_capture);
+        const size_t slots = 2 * static_cast<size_t>(handles[0]->T.max_groups);
+        std::vector<int> rc(static_cast<size_t>(n_handles), GX_OK);
+        std::vector<std::string> msg(static_cast<size_t>(n_handles));
+        std::vector<uint64_t> over(static_cast<size_t>(n_handles), 0);
+        std::vector<std::thread> pool;
+        for (int32_t k = 0; k < n_handles; ++k) {
+            pool.emplace_back([&, k]() {
+                const uint64_t a = cuts[k], m = cuts[k + 1] - cuts[k];
+                if (m == 0) return;
+                gx_batch_opts ok = o;
+                ok.struct_size = sizeof(gx_batch_opts);
+                ok.stream = nullptr;
+                ok.overflow = compact ? &over[k] : nullptr;
+                int32_t* mid_k = match_id ? match_id + a : nullptr;
+                const size_t row_bytes = (1 + slots) * (o.compact_results == 2 ? 1 : 2);
+                int32_t* caps_k = !caps ? nullptr : compact ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(caps) + a * row_bytes) : caps + a * slots;
+                rc[k] = gx_extract_batch(handles[k], bytes, static_cast<const uint8_t*>(offsets) + a * off_w, m, mid_k, caps_k, &ok);
+                if (rc[k] != GX_OK) msg[k] = gx_last_error();
+            });
+        }
+        for (auto& t : pool) t.join();
+        for (int32_t k = 0; k < n_handles; ++k) if (rc[k] != GX_OK) return fail(rc[k], msg[k]);
+        if (compact && o.overflow) for (uint64_t v : over) *static_cast<uint64_t*>(o.overflow) += v;
+        return GX_OK;
+    });
 }
 
 int gx_extract_batch_multi_device(const gx_device_shard* shards, int32_t n_shards, const gx_batch_opts* opts) {
     if (!shards || n_shards <= 0) return fail(GX_E_ARG, "gx_extract_batch_multi_device: bad argument");
-    gx_batch_opts o{};
-    if (!read_opts(opts, &o)) return fail(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
-    for (int32_t k = 0; k < n_shards; ++k)
-        if (!shards[k].handle || !shards[k].handle->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi_device: NULL or host-only handle");
-    int prev_device = 0;
-    (void)hipGetDevice(&prev_device);
-    int first_rc = GX_OK;
-    std::string first_msg;
-    std::vector<hipStream_t> used(static_cast<size_t>(n_shards), nullptr);
-    // enqueue everything first (asynchronous launches from this one thread), wait afterwards
-    for (int32_t k = 0; k < n_shards; ++k) {
-        const gx_device_shard& sh = shards[k];
-        gx_handle* h = sh.handle;
-        hipStream_t stream = static_cast<hipStream_t>(sh.stream);
-        if (!stream) {
-            std::lock_guard<std::mutex> lock(h->slot_mu);
-            if (!h->multi_stream) {
-                if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->multi_stream, hipStreamNonBlocking) != hipSuccess) {
-                    if (first_rc == GX_OK) { first_rc = GX_E_DEVICE; first_msg = "gx_extract_batch_multi_device: no stream on the shard's device"; }
+    return guarded([&]() -> int {
+        const gx_batch_opts o = read_opts(opts);
+        for (int32_t k = 0; k < n_shards; ++k)
+            if (!shards[k].handle || !shards[k].handle->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi_device: NULL or host-only handle");
+        DeviceScope scope;
+        int first_rc = GX_OK;
+        std::string first_msg;
+        std::vector<hipStream_t> used(static_cast<size_t>(n_shards), nullptr);
+        // enqueue everything first (asynchronous launches from this one thread), wait afterwards
+        for (int32_t k = 0; k < n_shards; ++k) {
+            const gx_device_shard& sh = shards[k];
+            gx_handle* h = sh.handle;
+            hipStream_t stream = static_cast<hipStream_t>(sh.stream);
+            if (!stream) {
+                std::lock_guard<std::mutex> lock(h->slot_mu);
+                if (!h->multi_stream) {
+                    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(h->multi_stream.out(), hipStreamNonBlocking) != hipSuccess) {
+                        if (first_rc == GX_OK) { first_rc = GX_E_DEVICE; first_msg = "gx_extract_batch_multi_device: no stream on the shard's device"; }
+                        continue;
+                    }
+                }
+                stream = h->multi_stream.get();
+            }
+            used[k] = stream;
+            gx_batch_opts ok = o;
+            ok.struct_size = sizeof(gx_batch_opts);
+            ok.device_pointers = 1;
+            ok.no_sync = 1;
+            ok.stream = stream;
+            ok.overflow = sh.overflow;
+            const int rc = sh.n ? gx_extract_batch(h, sh.bytes, sh.offsets, sh.n, sh.match_id, sh.caps, &ok) : GX_OK;
+            if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
+        }
+        if (!o.no_sync) {
+            for (int32_t k = 0; k < n_shards; ++k) {
+                if (!used[k]) continue;
+                if (hipSetDevice(shards[k].handle->device) != hipSuccess || hipStreamSynchronize(used[k]) != hipSuccess) {
+                    if (first_rc == GX_OK) { first_rc = GX_E_DEVICE; first_msg = "gx_extract_batch_multi_device: a shard's stream failed"; }
                     continue;
                 }
-            }
-            stream = h->multi_stream;
-        }
-        used[k] = stream;
-        gx_batch_opts ok = o;
-        ok.struct_size = sizeof(gx_batch_opts);
-        ok.device_pointers = 1;
-        ok.no_sync = 1;
-        ok.stream = stream;
-        ok.overflow = sh.overflow;
-        const int rc = sh.n ? gx_extract_batch(h, sh.bytes, sh.offsets, sh.n, sh.match_id, sh.caps, &ok) : GX_OK;
-        if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
-    }
-    if (!o.no_sync) {
-        for (int32_t k = 0; k < n_shards; ++k) {
-            if (!used[k]) continue;
-            if (hipSetDevice(shards[k].handle->device) != hipSuccess || hipStreamSynchronize(used[k]) != hipSuccess) {
-                if (first_rc == GX_OK) { first_rc = GX_E_DEVICE; first_msg = "gx_extract_batch_multi_device: a shard's stream failed"; }
-                continue;
-            }
-            // a shard whose max_line_bytes promise did not hold (its kernel left the longer lines' rows unwritten): the shard again,
-            // without the promise -- this call waits for its batches, so its results are right when it returns
-            if (o.max_line_bytes != 0 && shards[k].n && promise_broken_since(shards[k].handle, used[k])) {
-                gx_batch_opts ok = o;
-                ok.struct_size = sizeof(gx_batch_opts);
-                ok.device_pointers = 1;
-                ok.no_sync = 0;
-                ok.max_line_bytes = 0;
-                ok.stream = used[k];
-                ok.overflow = nullptr;   // (the first run has counted)
-                const int rc = gx_extract_batch(shards[k].handle, shards[k].bytes, shards[k].offsets, shards[k].n, shards[k].match_id, shards[k].caps, &ok);
-                if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
+                // a shard whose max_line_bytes promise did not hold (its kernel left the longer lines' rows unwritten): the shard again,
+                // without the promise -- this call waits for its batches, so its results are right when it returns
+                if (o.max_line_bytes != 0 && shards[k].n && promise_broken_since(shards[k].handle, used[k])) {
+                    gx_batch_opts ok = o;
+                    ok.struct_size = sizeof(gx_batch_opts);
+                    ok.device_pointers = 1;
+                    ok.no_sync = 0;
+                    ok.max_line_bytes = 0;
+                    ok.stream = used[k];
+                    ok.overflow = nullptr;   // (the first run has counted)
+                    const int rc = gx_extract_batch(shards[k].handle, shards[k].bytes, shards[k].offsets, shards[k].n, shards[k].match_id, shards[k].caps, &ok);
+                    if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
+                }
             }
         }
-    }
-    (void)hipSetDevice(prev_device);
-    if (first_rc != GX_OK) return fail(first_rc, first_msg);
-    return GX_OK;
+        if (first_rc != GX_OK) return fail(first_rc, first_msg);
+        return GX_OK;
+    });
 }
 
 // ---- one process, all GPUs of a node: the tables on every device, the rows back on one (north_star: "broadcast of the DFA tables
@@ -1470,8 +1406,7 @@ int gx_create_on_devices(const void* blob, size_t size, const int32_t* devices, 
         handles[k] = nullptr;
         if (devices[k] < 0 || devices[k] >= count) return fail(GX_E_ARG, "gx_create_on_devices: no such device");
     }
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    DeviceScope scope;
     // the first handle from the blob (host work + upload over the bus), the others beside it: their host-side tables in threads of
     // their own, their device images copied from the first handle's device
     int rc = GX_OK;
@@ -1502,7 +1437,6 @@ int gx_create_on_devices(const void* blob, size_t size, const int32_t* devices, 
         for (int32_t k = 1; k < n_devices && rc == GX_OK; ++k)
             if (rcs[k] != GX_OK) { rc = rcs[k]; msg = msgs[k]; }
     }
-    (void)hipSetDevice(prev);
     if (rc != GX_OK) {
         for (int32_t k = 0; k < n_devices; ++k) { if (handles[k]) gx_destroy(handles[k]); handles[k] = nullptr; }
         return fail(rc, msg);
@@ -1514,8 +1448,7 @@ int gx_gather_rows(const gx_rows_shard* shards, int32_t n_shards, uint32_t row_b
     if (!shards || n_shards <= 0 || row_bytes == 0 || !dst_rows) return fail(GX_E_ARG, "gx_gather_rows: bad argument");
     for (int32_t k = 0; k < n_shards; ++k)
         if (!shards[k].handle || !shards[k].handle->on_device || (shards[k].n && !shards[k].rows)) return fail(GX_E_ARG, "gx_gather_rows: NULL or host-only handle, or no rows");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    DeviceScope scope;
     int rc = GX_OK;
     std::string msg;
     auto bad = [&](const char* what) { if (rc == GX_OK) { rc = GX_E_DEVICE; msg = what; } };
@@ -1529,47 +1462,44 @@ int gx_gather_rows(const gx_rows_shard* shards, int32_t n_shards, uint32_t row_b
         if (hipSetDevice(h->device) != hipSuccess) { bad("gx_gather_rows: hipSetDevice failed"); break; }
         std::lock_guard<std::mutex> lock(h->slot_mu);
         if (!h->gather_stream) {
-            if (hipStreamCreateWithFlags(&h->gather_stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&h->gather_event, hipEventDisableTiming) != hipSuccess) { bad("gx_gather_rows: no stream on the shard's device"); break; }
+            if (hipStreamCreateWithFlags(h->gather_stream.out(), hipStreamNonBlocking) != hipSuccess ||
+                hipEventCreateWithFlags(h->gather_event.out(), hipEventDisableTiming) != hipSuccess) { bad("gx_gather_rows: no stream on the shard's device"); break; }
             int can = 0;   // the shard's device writes into the root's memory itself: one link per peer, all of them at once
             if (h->device != dst_device && hipDeviceCanAccessPeer(&can, h->device, dst_device) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(dst_device, 0);
             (void)hipGetLastError();
         }
         // behind the shard's kernel (the stream it was enqueued on: the caller's, or the one gx_extract_batch_multi_device used) ...
         hipStream_t ks = static_cast<hipStream_t>(shards[k].stream);
-        if (!ks) ks = h->multi_stream;
+        if (!ks) ks = h->multi_stream.get();
         if (ks) {
-            if (hipEventRecord(h->gather_event, ks) != hipSuccess || hipStreamWaitEvent(h->gather_stream, h->gather_event, 0) != hipSuccess) { bad("gx_gather_rows: event"); break; }
+            if (hipEventRecord(h->gather_event.get(), ks) != hipSuccess || hipStreamWaitEvent(h->gather_stream.get(), h->gather_event.get(), 0) != hipSuccess) { bad("gx_gather_rows: event"); break; }
         }
         // ... on the copy stream of the shard's own device: the kernels of the next batch go on beside it
-        const hipError_t e = h->device == dst_device ? hipMemcpyAsync(dst, shards[k].rows, bytes, hipMemcpyDeviceToDevice, h->gather_stream)
-                                                     : hipMemcpyPeerAsync(dst, dst_device, shards[k].rows, h->device, bytes, h->gather_stream);
+        const hipError_t e = h->device == dst_device ? hipMemcpyAsync(dst, shards[k].rows, bytes, hipMemcpyDeviceToDevice, h->gather_stream.get())
+                                                     : hipMemcpyPeerAsync(dst, dst_device, shards[k].rows, h->device, bytes, h->gather_stream.get());
         if (e != hipSuccess) bad("gx_gather_rows: the copy between the devices failed");
     }
     if (rc == GX_OK && !no_sync) {
         for (int32_t k = 0; k < n_shards; ++k) {
             gx_handle* h = shards[k].handle;
             if (!h->gather_stream) continue;
-            if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->gather_stream) != hipSuccess) bad("gx_gather_rows: a copy stream failed");
+            if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->gather_stream.get()) != hipSuccess) bad("gx_gather_rows: a copy stream failed");
         }
     }
-    (void)hipSetDevice(prev);
     if (rc != GX_OK) return fail(rc, msg);
     return GX_OK;
 }
 
 int gx_gather_wait(gx_handle* const* handles, int32_t n_handles) {
     if (!handles || n_handles <= 0) return fail(GX_E_ARG, "gx_gather_wait: bad argument");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    DeviceScope scope;
     int rc = GX_OK;
     for (int32_t k = 0; k < n_handles; ++k) {
         gx_handle* h = handles[k];
         if (!h || !h->on_device) { rc = GX_E_ARG; continue; }
         if (!h->gather_stream) continue;
-        if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->gather_stream) != hipSuccess) rc = GX_E_DEVICE;
+        if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->gather_stream.get()) != hipSuccess) rc = GX_E_DEVICE;
     }
-    (void)hipSetDevice(prev);
     if (rc != GX_OK) return fail(rc, "gx_gather_wait: a handle without a device, or a copy stream that failed");
     return GX_OK;
 }
@@ -1588,24 +1518,23 @@ int gx_state_accepts(const gx_handle* h, int32_t state, int32_t* indexes, int32_
 static int one_line(gx_handle* h, const uint16_t* s, int32_t len, int32_t* match_id, int32_t* caps, int32_t* state, int mode) {
     if (!h || len < 0 || (len && !s)) return fail(GX_E_ARG, "bad argument");
     if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-    try {
+    return guarded([&]() -> int {
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         const size_t out_words = 2 + slots;
         const size_t in_bytes = 8 + ((static_cast<size_t>(len) * 2 + 7) & ~size_t(7));  // offsets + code units: one copy in
         const size_t need = in_bytes + out_words * 4 + 16;
-        if (need > h->one_cap) {
-            if (h->one_dev) (void)hipFree(h->one_dev);
-            if (h->one_host) (void)hipHostFree(h->one_host);
-            h->one_dev = nullptr; h->one_host = nullptr; h->one_cap = 0;
+        gx_handle::OneScratch& one = h->one;
+        if (need > one.cap) {
+            one = {};
             const size_t cap = std::max<size_t>(need * 2, 4096);
-            GX_HIP(hipMalloc(&h->one_dev, cap));
-            GX_HIP(hipHostMalloc(&h->one_host, cap, hipHostMallocDefault));
-            h->one_cap = cap;
+            GX_HIP(hipMalloc(one.dev.out(), cap));
+            GX_HIP(hipHostMalloc(one.host.out(), cap, hipHostMallocDefault));
+            one.cap = cap;
         }
-        uint8_t* hb = static_cast<uint8_t*>(h->one_host);
-        uint8_t* db = static_cast<uint8_t*>(h->one_dev);
+        uint8_t* hb = one.host.get();
+        uint8_t* db = one.dev.get();
         uint32_t* offs = reinterpret_cast<uint32_t*>(hb);
         offs[0] = 0; offs[1] = static_cast<uint32_t>(len);
         if (len) memcpy(hb + 8, s, static_cast<size_t>(len) * 2);
@@ -1615,9 +1544,9 @@ static int one_line(gx_handle* h, const uint16_t* s, int32_t len, int32_t* match
             // the resident wave (gx_service.hip): the line into the mailbox -- every cache line's text before its tag, the first cache
             // line, whose tag is what the wave polls, last -- and a spin on the answer's sequence number
             gx_handle::Service& sv = h->svc;
-            uint32_t* mb = sv.host;
-            int32_t* ans = reinterpret_cast<int32_t*>(sv.host + 17 * 16);
-            uint32_t* state = sv.host + 17 * 16 + 80;
+            uint32_t* mb = sv.host.get();
+            int32_t* ans = reinterpret_cast<int32_t*>(mb + 17 * 16);
+            uint32_t* state = mb + 17 * 16 + 80;
             const uint32_t seq = ++sv.seq ? sv.seq : ++sv.seq;   // (never 0... the wave compares for inequality only, but keep it tidy)
             const uint32_t ulen = static_cast<uint32_t>(len);
             for (uint32_t cl = 1; 56u + 60u * (cl - 1u) < ulen; ++cl) {
@@ -1635,8 +1564,8 @@ static int one_line(gx_handle* h, const uint16_t* s, int32_t len, int32_t* match
             auto start_wave = [&]() {
                 __atomic_store_n(state, 1u, __ATOMIC_RELEASE);
                 // the wave starts with the PREVIOUS sequence number as the last one it has seen: the request that is waiting is new to it
-                GX_HIP(launch_one_service(sv.mode, sv.L, static_cast<const uint8_t*>(h->d_img[IMG_DENSE]), sv.dev, reinterpret_cast<int32_t*>(sv.dev + 17 * 16),
-                                          sv.dev + 17 * 16 + 80, seq - 1u, h->T.max_groups, 30000ull, 2000000ull, sv.stream));
+                GX_HIP(launch_one_service(sv.mode, sv.L, static_cast<const uint8_t*>(h->d_img[IMG_DENSE].get()), sv.dev, reinterpret_cast<int32_t*>(sv.dev + 17 * 16),
+                                          sv.dev + 17 * 16 + 80, seq - 1u, h->T.max_groups, 30000ull, 2000000ull, sv.stream.get()));
                 sv.started = true;
                 ++sv.launches;
             };
@@ -1644,7 +1573,7 @@ static int one_line(gx_handle* h, const uint16_t* s, int32_t len, int32_t* match
             const uint32_t* ans_seq = reinterpret_cast<const uint32_t*>(ans) + 1 + 2 * h->T.max_groups;
             uint64_t spins = 0;
             while (__atomic_load_n(ans_seq, __ATOMIC_ACQUIRE) != seq) {
-                if ((++spins & 63u) == 0 && __atomic_load_n(state, __ATOMIC_ACQUIRE) == 2u && hipStreamQuery(sv.stream) == hipSuccess) {
+                if ((++spins & 63u) == 0 && __atomic_load_n(state, __ATOMIC_ACQUIRE) == 2u && hipStreamQuery(sv.stream.get()) == hipSuccess) {
                     // the wave has left (idle, or its time was up) -- without this request's answer: a fresh one
                     if (__atomic_load_n(ans_seq, __ATOMIC_ACQUIRE) == seq) break;
                     start_wave();
@@ -1655,59 +1584,45 @@ static int one_line(gx_handle* h, const uint16_t* s, int32_t len, int32_t* match
             if (caps) for (size_t t = 0; t < slots; ++t) caps[t] = h->T.has_capture ? ans[1 + t] : -1;
             return GX_OK;
         }
+        // the result words, in the pinned buffer after the line: match id, state, captures
+        int32_t* out = reinterpret_cast<int32_t*>(hb + in_bytes);
+        GxBatch b{};
+        b.n = 1;
         if (latin1) {
             // Gorp.extract(String) on a Latin-1 line -- nearly every call: the line's BYTES go through the batch kernels as a batch of
             // one (tables in LDS, the line staged there too: a step costs an LDS round trip, not two trips to L2 as in the per-line
             // kernel), straight out of the pinned buffer and back into it; the host knows the line fits: no follow-up launch
             uint8_t* bytes = hb + 8;
             for (int32_t q = 0; q < len; ++q) bytes[q] = static_cast<uint8_t>(s[q]);   // (in place of the units copied above)
-            GxBatch b{};
-            b.data = bytes; b.offsets = hb; b.n = 1; b.wide = 0; b.offsets64 = 0;
+            b.data = bytes; b.offsets = hb;
             b.match_only = h->T.has_capture ? 0 : 1;
-            int32_t* out = reinterpret_cast<int32_t*>(hb + in_bytes);
             b.match_id = out; b.caps = h->T.has_capture ? out + 2 : nullptr;
             b.no_followup = 1;
             launch_batch(h, b, static_cast<uint32_t>(len), GX_KERNEL_AUTO, nullptr);
-            GX_HIP(hipStreamSynchronize(nullptr));
-            if (match_id) *match_id = out[0];
-            if (caps) for (size_t t = 0; t < slots; ++t) caps[t] = h->T.has_capture ? out[2 + t] : -1;
-            return GX_OK;
-        }
-        if (len <= 16384) {
-            // the short way: the kernel reads the units out of the pinned buffer and writes the result words into it (no copy commands)
-            GxBatch b{};
-            b.n = 1; b.wide = 1;
+        } else {
+            b.wide = 1;
             b.match_only = mode < 0 ? mode : ((mode == 1 || !h->T.has_capture) ? 1 : 0);
-            int32_t* out = reinterpret_cast<int32_t*>(hb + in_bytes);
-            b.match_id = out; b.state_out = out + 1; b.caps = b.match_only == 1 ? nullptr : out + 2;
             PikeGate pike_gate(h, nullptr);
-            GX_HIP(launch_extract_one(h->dev, reinterpret_cast<const uint16_t*>(hb + 8), static_cast<uint32_t>(len), b, nullptr));
-            GX_HIP(hipStreamSynchronize(nullptr));
-            const int32_t* host = out;
-            if (match_id) *match_id = host[0];
-            if (state) *state = host[1];
-            if (caps) for (size_t t = 0; t < slots; ++t) caps[t] = b.match_only == 1 ? -1 : host[2 + t];
-            return GX_OK;
+            if (len <= 16384) {
+                // the short way: the kernel reads the units out of the pinned buffer and writes the result words into it (no copy commands)
+                b.match_id = out; b.state_out = out + 1; b.caps = b.match_only == 1 ? nullptr : out + 2;
+                GX_HIP(launch_extract_one(h->dev, reinterpret_cast<const uint16_t*>(hb + 8), static_cast<uint32_t>(len), b, nullptr));
+            } else {
+                // (the results area is not initialised: the kernel writes every word that is read back)
+                GX_HIP(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, nullptr));
+                int32_t* dout = reinterpret_cast<int32_t*>(db + in_bytes);
+                b.data = db + 8; b.offsets = db;
+                b.match_id = dout; b.state_out = dout + 1; b.caps = b.match_only == 1 ? nullptr : dout + 2;
+                GX_HIP(launch_extract_generic(h->dev, b, nullptr));
+                GX_HIP(hipMemcpyAsync(out, dout, (b.match_only == 1 ? 2 : out_words) * 4, hipMemcpyDeviceToHost, nullptr));
+            }
         }
-        // (the results area is not initialised: the kernel writes every word that is read back)
-        GX_HIP(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, nullptr));
-        GxBatch b{};
-        b.data = db + 8; b.offsets = db; b.n = 1; b.wide = 1; b.offsets64 = 0;
-        b.match_only = mode < 0 ? mode : ((mode == 1 || !h->T.has_capture) ? 1 : 0);
-        int32_t* out = reinterpret_cast<int32_t*>(db + in_bytes);
-        b.match_id = out; b.state_out = out + 1; b.caps = b.match_only == 1 ? nullptr : out + 2;
-        PikeGate pike_gate(h, nullptr);
-        GX_HIP(launch_extract_generic(h->dev, b, nullptr));
-        const size_t back = (b.match_only == 1 ? 2 : out_words) * 4;
-        GX_HIP(hipMemcpyAsync(hb + in_bytes, db + in_bytes, back, hipMemcpyDeviceToHost, nullptr));
         GX_HIP(hipStreamSynchronize(nullptr));
-        const int32_t* host = reinterpret_cast<const int32_t*>(hb + in_bytes);
-        if (match_id) *match_id = host[0];
-        if (state) *state = host[1];
-        if (caps) for (size_t t = 0; t < slots; ++t) caps[t] = b.match_only == 1 ? -1 : host[2 + t];
+        if (match_id) *match_id = out[0];
+        if (state) *state = out[1];
+        if (caps) for (size_t t = 0; t < slots; ++t) caps[t] = b.match_only == 1 ? -1 : out[2 + t];
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
+    });
 }
 
 int gx_capture_one_utf16(gx_handle* h, int32_t k, const uint16_t* s, int32_t len, int32_t* matched, int32_t* caps) {
@@ -1747,23 +1662,20 @@ static int string_result(const ustr& r, char* out, size_t cap, size_t* out_len) 
 
 int gx_quote_literal_as_regexp(const char* text, char* out, size_t cap, size_t* out_len) {
     if (!text) return fail(GX_E_ARG, "null text");
-    try { return string_result(quote_literal_as_regexp(utf8_to_u16(text)), out, cap, out_len); }
-    catch (GxError& e) { return fail(e.code, e.what()); }
+    return guarded([&]() -> int { return string_result(quote_literal_as_regexp(utf8_to_u16(text)), out, cap, out_len); });
 }
 int gx_massage_regexp_for_automaton(const char* pattern, char* out, size_t cap, size_t* out_len) {
     if (!pattern) return fail(GX_E_ARG, "null pattern");
-    try { return string_result(massage_regexp_for_automaton(utf8_to_u16(pattern)), out, cap, out_len); }
-    catch (GxError& e) { return fail(e.code, e.what()); }
+    return guarded([&]() -> int { return string_result(massage_regexp_for_automaton(utf8_to_u16(pattern)), out, cap, out_len); });
 }
 int gx_massage_regexp_for_jdk(const char* pattern, char* out, size_t cap, size_t* out_len) {
     if (!pattern) return fail(GX_E_ARG, "null pattern");
-    try { return string_result(massage_regexp_for_jdk(utf8_to_u16(pattern)), out, cap, out_len); }
-    catch (GxError& e) { return fail(e.code, e.what()); }
+    return guarded([&]() -> int { return string_result(massage_regexp_for_jdk(utf8_to_u16(pattern)), out, cap, out_len); });
 }
 
 int gx_create_from_definition(const char* definition_text, const char* source_ref, uint32_t flags, gx_handle** out) {
     if (!definition_text || !out) return fail(GX_E_ARG, "gx_create_from_definition: bad argument");
-    try {
+    return guarded([&]() -> int {
         std::vector<dsl::Extraction> xs = dsl::read_definition(definition_text, source_ref ? source_ref : "<input string>");
         std::vector<ustr> a, j;
         for (auto& x : xs) {
@@ -1782,9 +1694,7 @@ int gx_create_from_definition(const char* definition_text, const char* source_re
         }
         h->meta = xs;
         return finish_create(h, flags, out);
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 const char* gx_extraction_name(const gx_handle* h, int32_t k) {
@@ -1828,15 +1738,13 @@ const char* gx_extraction_append_value_json(const gx_handle* h, int32_t k, int32
 int gx_definition_to_json(const char* definition_text, const char* source_ref, const char* stage, char* out, size_t cap,
                           size_t* out_len) {
     if (!definition_text || !stage) return fail(GX_E_ARG, "gx_definition_to_json: bad argument");
-    try {
+    return guarded([&]() -> int {
         std::string js = dsl::dump_json(definition_text, source_ref ? source_ref : "<input string>", stage);
         if (out_len) *out_len = js.size();
         if (!out || cap < js.size() + 1) return fail(GX_E_ARG, "output buffer too small");
         memcpy(out, js.c_str(), js.size() + 1);
         return GX_OK;
-    } catch (GxError& e) { return fail(e.code, e.what()); }
-    catch (std::bad_alloc&) { return fail(GX_E_NOMEM, "out of memory"); }
-    catch (std::exception& e) { return fail(GX_E_ARG, e.what()); }
+    });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // ASan/UBSan driver for the host-side compiler (no HIP): definitions -> regex strings -> tables -> blob -> tables; table images
-// and the kernel a batch gets (gx_images.hpp).
+// and the kernel a batch gets (gx_images.hpp); the launch slots' bookkeeping (gx_slots.hpp).
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -12,6 +12,7 @@
 #include "gx_dsl.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
+#include "gx_slots.hpp"
 using namespace gx;
 
 // ---- the hop tier's tables (gx_hop.hpp) walked on the host exactly as gx_hop_dev.hpp walks them, against the dense fused
@@ -258,8 +259,47 @@ std::string pinned_plans(const Tables& T, uint32_t flags) {
     }
     return out;
 }
+
+// The launch slots' bookkeeping over stream keys, as gx_api.cpp drives it.  Returns what went wrong (empty: nothing).
+std::string check_launch_slots() {
+    LaunchSlots S;
+    uint32_t broken[LaunchSlots::N] = {};
+    S.broken = broken;
+    int keys[40];
+    // repeat calls from one key: the same slot, a new sequence number each time
+    const LaunchSlots::Use a = S.take(&keys[0]), b = S.take(&keys[0]);
+    if (a.slot != 0 || b.slot != 0 || a.shared || a.wait_shared || b.seq == a.seq || S.slot_of(&keys[0]) != 0) return "repeat calls from one key";
+    // 31 distinct keys take slots 0-30; the keys after them share slot 31, each user after the first waiting for the one before
+    for (int k = 1; k < 31; ++k)
+        if (S.take(&keys[k]).slot != k) return "key " + std::to_string(k) + " did not take slot " + std::to_string(k);
+    for (int k = 31; k < 40; ++k) {
+        const LaunchSlots::Use u = S.take(&keys[k]);
+        if (u.slot != LaunchSlots::N - 1 || !u.shared || u.wait_shared != (k > 31)) return "key " + std::to_string(k) + " did not share the last slot";
+    }
+    if (S.slot_of(&keys[30]) != 30 || S.slot_of(&keys[35]) != LaunchSlots::N - 1 || S.take(&keys[7]).slot != 7) return "slot_of";
+    // a changed broken word is reported once and counted once, then reads as seen
+    if (S.consume_broken(3)) return "an unchanged word reported";
+    broken[3] = 7;
+    if (!S.consume_broken(3) || S.consume_broken(3) || S.promises_broken.load() != 1) return "a changed word not reported exactly once";
+    // the synchronous fix-up marks its own sequence number seen: that word is not reported again
+    broken[5] = 9;
+    S.mark_seen(5, 9);
+    if (S.consume_broken(5) || S.promises_broken.load() != 2) return "a word marked seen reported";
+    // sequence numbers skip 0 when they wrap
+    S.next_seq = 0xFFFFFFFFu;
+    if (S.take(&keys[0]).seq != 0xFFFFFFFFu || S.take(&keys[0]).seq != 1) return "sequence numbers through 0";
+    // the default stream (a null key) owns a slot like any other; a handle without pinned words reports nothing
+    LaunchSlots T;
+    if (T.take(nullptr).slot != 0 || T.take(&keys[0]).slot != 1 || T.take(nullptr).slot != 0 || T.consume_broken(0)) return "null key";
+    return "";
+}
 }  // namespace
 int main(int argc, char** argv) {
+    const std::string slots_wrong = check_launch_slots();
+    if (!slots_wrong.empty()) {
+        printf("launch slots: %s\n", slots_wrong.c_str());
+        return 1;
+    }
     int ok = 0, bad = 0, mutated_ok = 0, mutated_bad = 0;
     size_t hop_lines = 0, hop_defs = 0, plans = 0;
     for (int a = 1; a < argc; ++a) {
