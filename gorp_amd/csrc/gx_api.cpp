@@ -1106,9 +1106,9 @@ static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* byt
                 if (nbytes) GX_HIP(hipMemcpyAsync(place, bytes + b0, nbytes, hipMemcpyHostToDevice, stream));
                 GX_HIP(hipMemcpyAsync(d_off, static_cast<const uint8_t*>(off.p) + a * off_w, (m + 1) * off_w, hipMemcpyHostToDevice, stream));
                 if (states) b.state_out = static_cast<int32_t*>(sl.states.get(m * 4));
-                const size_t row_bytes = (1 + slots) * (proto.narrow ? 1 : 2);  // compact rows: u8 or u16 entries
+                const size_t rb = row_bytes(row_format(true, proto.narrow != 0), static_cast<uint32_t>(slots));
                 if (compact) {
-                    b.packed = static_cast<uint16_t*>(sl.res.get(m * row_bytes));
+                    b.packed = static_cast<uint16_t*>(sl.res.get(m * rb));
                     GX_HIP(hipMemsetAsync(sl.over.get(), 0, 8, stream));
                     b.overflow = sl.over.get();
                 } else {
@@ -1118,7 +1118,7 @@ static void host_pipeline(gx_handle* h, const GxBatch& proto, const uint8_t* byt
                 launch_batch(h, b, hint, kernel, stream, uneven);
                 unsigned long long over = 0;
                 if (compact) {
-                    GX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(caps) + a * row_bytes, b.packed, m * row_bytes, hipMemcpyDeviceToHost, stream));
+                    GX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(caps) + a * rb, b.packed, m * rb, hipMemcpyDeviceToHost, stream));
                     GX_HIP(hipMemcpyAsync(&over, sl.over.get(), 8, hipMemcpyDeviceToHost, stream));
                 } else {
                     GX_HIP(hipMemcpyAsync(match_id + a, b.match_id, m * 4, hipMemcpyDeviceToHost, stream));
@@ -1320,8 +1320,8 @@ int gx_extract_batch_multi(gx_handle* const* handles, int32_t n_handles, const u
                 ok.stream = nullptr;
                 ok.overflow = compact ? &over[k] : nullptr;
                 int32_t* mid_k = match_id ? match_id + a : nullptr;
-                const size_t row_bytes = (1 + slots) * (o.compact_results == 2 ? 1 : 2);
-                int32_t* caps_k = !caps ? nullptr : compact ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(caps) + a * row_bytes) : caps + a * slots;
+                const size_t rb = row_bytes(row_format(true, o.compact_results == 2), static_cast<uint32_t>(slots));
+                int32_t* caps_k = !caps ? nullptr : compact ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(caps) + a * rb) : caps + a * slots;
                 rc[k] = gx_extract_batch(handles[k], bytes, static_cast<const uint8_t*>(offsets) + a * off_w, m, mid_k, caps_k, &ok);
                 if (rc[k] != GX_OK) msg[k] = gx_last_error();
             });

@@ -249,7 +249,7 @@ bool build_hop_image(const Tables& T, bool match_automaton, uint32_t hot_budget_
     out.n_hot = std::min<uint32_t>(out.n_reachable_hot, hot_budget_bytes / HOP_REC_BYTES);
     if (out.n_hot == 0) out.n_hot = 1;
 
-    // final records, as gx_walk.hpp's line_result reads them (the layout build_tile_image gives the other tiers):
+    // final records, as gx_rows.hpp's line_result reads them (the layout build_tile_image gives the other tiers):
     // u16 [begin tag, end tag] x max_groups padded to four groups, then the extraction; record 0 = nothing set
     // Round 5: EVERY tag names a column of the wave's register block -- a register's, "the line's length" (which the lane writes there
     // before it reads its result) or "unset" -- so a group's two values are two reads and one test on the tag (the selects on "tag 0:

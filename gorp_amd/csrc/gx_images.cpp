@@ -344,7 +344,7 @@ bool build_tile_image(TileImages& I, const Tables& T, uint32_t flags, int tier, 
     L.simple_ops = simple ? 1u : 0u;
     // Final records, one per distinct (final tag list, extraction): u16 [begin tag, end tag] x max_groups padded to a
     // multiple of four groups (16 bytes), then the extraction and padding to the next 16 bytes; the tags as
-    // line_result (gx_walk.hpp) wants them: 0 = unset, 1 = the line length, else the byte offset of the register's
+    // line_result (gx_rows.hpp) wants them: 0 = unset, 1 = the line length, else the byte offset of the register's
     // column from the dummy column.  Record 0 = "no groups" for the lines that match nothing.  A row's info word is
     // the byte offset of its record.
     const size_t tag_slots = 8 * static_cast<size_t>((T.max_groups + 3) / 4), rec_len = tag_slots + 8;
@@ -560,7 +560,7 @@ bool plan_lanes_launch(const TileImages& I, GxLds* out, bool mo, bool compact, b
     GxLds L = I.dense[I.dense_of(mo)].L;
     if (!mo && I.has_capture && L.u_start == 0xFFFFFFFFu) return false;  // walks the fused automaton
     const uint32_t slots = 2u * static_cast<uint32_t>(I.max_groups);
-    const uint32_t rows = mo || !compact ? 0u : 64u * (2u + 2u * slots);  // (dense rows are stored lane by lane)
+    const uint32_t rows = mo || !compact ? 0u : 64u * row_bytes(ROWS_U16, slots);  // (u16 or u8 rows; dense rows are stored lane by lane)
     L.stage_bytes = L.regs_wave_bytes;                       // (the register block)
     L.regs_wave_bytes = (L.regs_wave_bytes + rows + 16u + 15u) & ~15u;
     // length-sorted tiles (uneven lines, tables in global memory): a chunk's line order, 2 bytes per line, + two 64-entry tables
@@ -822,8 +822,8 @@ BatchPlan plan_batch(const TileImages& I, const BatchShape& s, int num_cus) {
             p.L = S;
             return plan(GX_KERNEL_SLICES, dense, global, 0, 0, 0);
         }
-        // (the lines the lane kernel leaves: longer than its 16-bit positions -- with compact rows, than the 65 534 they can hold)
-        return pieces(GX_KERNEL_LANES, dense, global, s.packed ? 65534u : 65535u);
+        // (the lines the lane kernel leaves: longer than its 16-bit positions -- with compact rows, than the largest offset u16 rows hold)
+        return pieces(GX_KERNEL_LANES, dense, global, s.packed ? static_cast<uint32_t>(row_max_offset(ROWS_U16)) : 65535u);
     }
     if ((!want_states || image_tier <= 1u) && plan_tile_launch(I, hint, &p.L, mo)) return tiles(GX_KERNEL_TILES, dense, global);
     return p;

@@ -1222,8 +1222,8 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_write(const uint32_t* __r
 }  // namespace
 
 // ---- compact result rows for transport (the gather payload) ----
-// row = [match id as int16][2 * Gmax offsets as uint16, 0xFFFF = unset]: 2 + 4 * Gmax bytes per line instead of
-// 4 + 8 * Gmax.  Offsets above 65534 do not fit: such lines are counted and the caller sends the batch wide.
+// dense results <-> u16 rows (gx_layout.hpp: ROWS_U16), 2 + 4 * Gmax bytes per line instead of 4 + 8 * Gmax.  Offsets that do not
+// fit are stored clipped; every thread that clipped one counts once, and the caller then sends the batch wide.
 namespace {
 __global__ void __launch_bounds__(256) k_pack_results(const int32_t* __restrict__ match_id, const int32_t* __restrict__ caps, uint64_t n, int slots,
                                                      uint16_t* __restrict__ packed, unsigned long long* __restrict__ n_overflow) {
@@ -1234,17 +1234,17 @@ __global__ void __launch_bounds__(256) k_pack_results(const int32_t* __restrict_
     for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
         const uint64_t line = t / width;
         const uint32_t col = static_cast<uint32_t>(t - line * width);
-        int32_t v;
-        if (col == 0) v = match_id[line];
-        else {
-            v = caps[line * static_cast<uint64_t>(slots) + (col - 1)];
-            if (v > 65534) { over = 1; v = 65534; }
-        }
-        packed[t] = static_cast<uint16_t>(v);  // -1 -> 0xFFFF; match ids are >= -32768 (at most 32767 extractions)
+        RowUnit u{0u, 0u};
+        if (col == 0) u.unit = encode_id(ROWS_U16, match_id[line]);
+        else u = encode_offset(ROWS_U16, caps[line * static_cast<uint64_t>(slots) + (col - 1)]);
+        over |= u.clipped;
+        packed[t] = static_cast<uint16_t>(u.unit);
     }
     if (over) atomicAdd(n_overflow, 1ull);
 }
-__global__ void __launch_bounds__(256) k_unpack_results(const uint16_t* __restrict__ packed, uint64_t n, int slots, int32_t* __restrict__ match_id,
+// the other way, from u16 or u8 rows (F)
+template <RowFormat F, typename UNIT>
+__global__ void __launch_bounds__(256) k_unpack_results(const UNIT* __restrict__ rows, uint64_t n, int slots, int32_t* __restrict__ match_id,
                                                        int32_t* __restrict__ caps) {
     const uint64_t width = static_cast<uint64_t>(slots) + 1;
     const uint64_t total = n * width;
@@ -1252,23 +1252,9 @@ __global__ void __launch_bounds__(256) k_unpack_results(const uint16_t* __restri
     for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
         const uint64_t line = t / width;
         const uint32_t col = static_cast<uint32_t>(t - line * width);
-        const uint16_t v = packed[t];
-        if (col == 0) match_id[line] = static_cast<int16_t>(v);
-        else caps[line * static_cast<uint64_t>(slots) + (col - 1)] = v == 0xFFFFu ? -1 : static_cast<int32_t>(v);
-    }
-}
-// the same from u8 rows (gx_batch_opts.compact_results = 2: int8 id, offsets with 0xFF = unset)
-__global__ void __launch_bounds__(256) k_unpack_results8(const uint8_t* __restrict__ rows, uint64_t n, int slots, int32_t* __restrict__ match_id,
-                                                        int32_t* __restrict__ caps) {
-    const uint64_t width = static_cast<uint64_t>(slots) + 1;
-    const uint64_t total = n * width;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const uint64_t line = t / width;
-        const uint32_t col = static_cast<uint32_t>(t - line * width);
-        const uint8_t v = rows[t];
-        if (col == 0) match_id[line] = static_cast<int8_t>(v);
-        else caps[line * static_cast<uint64_t>(slots) + (col - 1)] = v == 0xFFu ? -1 : static_cast<int32_t>(v);
+        const uint32_t v = rows[t];
+        if (col == 0) match_id[line] = decode_id(F, v);
+        else caps[line * static_cast<uint64_t>(slots) + (col - 1)] = decode_offset(F, v);
     }
 }
 }  // namespace
@@ -1277,7 +1263,7 @@ hipError_t launch_unpack_results8(const uint8_t* rows, uint64_t n, int slots, in
     if (n == 0) return hipSuccess;
     uint64_t blocks = (n * (static_cast<uint64_t>(slots) + 1) + 255) / 256;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
-    hipLaunchKernelGGL(k_unpack_results8, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, rows, n, slots, match_id, caps);
+    hipLaunchKernelGGL((k_unpack_results<ROWS_U8, uint8_t>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, rows, n, slots, match_id, caps);
     return hipGetLastError();
 }
 hipError_t launch_pack_results(const int32_t* match_id, const int32_t* caps, uint64_t n, int slots, uint16_t* packed,
@@ -1293,7 +1279,7 @@ hipError_t launch_unpack_results(const uint16_t* packed, uint64_t n, int slots, 
     if (n == 0) return hipSuccess;
     uint64_t blocks = (n * (static_cast<uint64_t>(slots) + 1) + 255) / 256;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
-    hipLaunchKernelGGL(k_unpack_results, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, packed, n, slots, match_id, caps);
+    hipLaunchKernelGGL((k_unpack_results<ROWS_U16, uint16_t>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, packed, n, slots, match_id, caps);
     return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@
 //   hot loop #2  JDKRegexpCookedExtraction.match/_constructMatch
 //                                       core/jdkre/JDKRegexpCookedExtraction.java:36-59
 //   driver       Gorp.extract           core/Gorp.java:159-186
-#include "gx_walk.hpp"
+#include "gx_rows.hpp"
 #include "gx_hop_dev.hpp"
 
 namespace gx {
@@ -27,250 +27,6 @@ __device__ __forceinline__ int class_of(const GxDev& T, CH ch) {
         if (T.hi_lo[mid] <= c) lo = mid; else hi = mid;
     }
     return T.hi_cls[lo];
-}
-
-// Where one line's result goes: dense (match_id[n] + caps[n][slots], int32) or compact rows
-// (u16[1 + slots] per line: int16 id, then offsets with 0xFFFF = unset; an offset above 65534 is stored as 65534
-// and counted in *overflow, and the caller then takes that batch in the dense format).
-struct LineOut {
-    int32_t* match_id;
-    int32_t* caps;
-    uint16_t* packed;
-    unsigned long long* overflow;
-    int slots;
-    int narrow;  // `packed` holds u8 rows (int8 id, offsets with 0xFF = unset, above 254: stored as 254 and counted)
-    __device__ __forceinline__ void id(uint64_t i, int32_t k) const {
-        if (packed && narrow) reinterpret_cast<uint8_t*>(packed)[i * static_cast<uint64_t>(1 + slots)] = static_cast<uint8_t>(k);
-        else if (packed) packed[i * static_cast<uint64_t>(1 + slots)] = static_cast<uint16_t>(k);
-        else match_id[i] = k;
-    }
-    __device__ __forceinline__ void cap(uint64_t i, int t, int32_t v) const {
-        if (packed && narrow) {
-            uint8_t w = 0xFFu;
-            if (v >= 0) {
-                if (v > 254) { v = 254; if (overflow) atomicAdd(overflow, 1ull); }
-                w = static_cast<uint8_t>(v);
-            }
-            reinterpret_cast<uint8_t*>(packed)[i * static_cast<uint64_t>(1 + slots) + 1 + t] = w;
-        } else if (packed) {
-            uint16_t w = 0xFFFFu;
-            if (v >= 0) {
-                if (v > 65534) { v = 65534; if (overflow) atomicAdd(overflow, 1ull); }
-                w = static_cast<uint16_t>(v);
-            }
-            packed[i * static_cast<uint64_t>(1 + slots) + 1 + t] = w;
-        } else caps[i * static_cast<uint64_t>(slots) + t] = v;
-    }
-};
-
-// A line's whole result row from its lane in as few stores as the format allows (the slice kernels: a lane holds a line of its
-// own, its row goes where no neighbour's does -- 1 + 2 G scattered stores of two bytes each were a sixth of the hop slice kernel on
-// BASELINE configs[4]).  Four groups at a time, as the final records hold their tags: dense results leave as two 16-byte stores,
-// u16 rows as one (the row's first halfword is the id, so a word is one group's end and the next group's begin: `carry`), u8 rows
-// as one of 8 bytes; global memory takes them at any alignment.  Returns nothing: the id is the row's (or match_id's) to keep.
-struct __attribute__((packed)) UnalignedU32x4 { u32x4 v; };
-struct __attribute__((packed)) UnalignedU32x2 { u32x2 v; };
-struct __attribute__((packed)) UnalignedU32 { uint32_t v; };
-struct __attribute__((packed)) UnalignedU16 { uint16_t v; };
-
-template <int TIER>
-__device__ __forceinline__ void write_row(const LineOut& out, uint64_t i, int32_t info, uint32_t fin_lds, const uint8_t* fin_g, uint32_t regs,
-                                          uint32_t len, int G, uint32_t hop_unset = 0u) {
-    const uint32_t rec = info >= 0 ? static_cast<uint32_t>(info) : 0u;
-    const uint32_t dummy_col = regs - 128u;
-    const uint32_t id_at = rec + 16u * static_cast<uint32_t>((G + 3) >> 2);
-    const bool FIN_GLOBAL = TIER == TIER_L2 || TIER == TIER_RECG || (TIER == TIER_HOP && fin_g != nullptr);
-    uint32_t idw;
-    if (FIN_GLOBAL) idw = *reinterpret_cast<const uint16_t*>(fin_g + id_at);
-    else idw = lds_ld<uint16_t>(fin_lds + id_at);
-    const int32_t mid = info >= 0 ? static_cast<int32_t>(static_cast<int16_t>(idw)) : info;
-    const uint32_t unit = out.packed ? (out.narrow ? 1u : 2u) : 4u;
-    uint8_t* row = out.packed ? reinterpret_cast<uint8_t*>(out.packed) + i * static_cast<uint64_t>(1 + out.slots) * unit
-                              : reinterpret_cast<uint8_t*>(out.caps + i * static_cast<uint64_t>(out.slots));
-    if (!out.packed) out.match_id[i] = mid;
-    uint32_t carry = static_cast<uint32_t>(mid) & (out.narrow ? 0xFFu : 0xFFFFu);
-    uint32_t clipped = 0u;
-    for (int g0 = 0; g0 < G; g0 += 4) {
-        u32x4 t;
-        if (FIN_GLOBAL) t = *reinterpret_cast<const u32x4*>(fin_g + rec + 4u * g0);
-        else t = lds_ld<u32x4>(fin_lds + rec + 4u * g0);
-        const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
-        uint32_t vb[4], ve[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            vb[q] = lds_ld<uint16_t>(dummy_col + (tw[q] & (TIER == TIER_HOP ? 0xFFFFu : 0xFF80u)));
-            ve[q] = lds_ld<uint16_t>(dummy_col + (TIER == TIER_HOP ? tw[q] >> 16 : (tw[q] >> 16) & 0xFF80u));
-        }
-        int32_t pb[4], pe[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t tb = tw[q] & 0xFFFFu, te = tw[q] >> 16;
-            if (TIER == TIER_HOP) {   // (tags name columns, "the length" and "unset" among them: gx_hop.cpp)
-                const bool unset = tb == hop_unset || info < 0;
-                pb[q] = unset ? -1 : static_cast<int32_t>(vb[q]);
-                pe[q] = unset ? -1 : static_cast<int32_t>(ve[q]);
-            } else {
-                pb[q] = tb == 1u ? static_cast<int32_t>(len) : static_cast<int32_t>(vb[q]);
-                pe[q] = te == 1u ? static_cast<int32_t>(len) : static_cast<int32_t>(ve[q]);
-                if (tb == 0u || te == 0u || info < 0) { pb[q] = -1; pe[q] = -1; }
-            }
-        }
-        const int cnt = G - g0 < 4 ? G - g0 : 4;
-        if (!out.packed) {
-            uint8_t* dst = row + 8u * g0;
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x4*>(dst)->v = u32x4{static_cast<uint32_t>(pb[0]), static_cast<uint32_t>(pe[0]), static_cast<uint32_t>(pb[1]), static_cast<uint32_t>(pe[1])};
-                reinterpret_cast<UnalignedU32x4*>(dst + 16)->v = u32x4{static_cast<uint32_t>(pb[2]), static_cast<uint32_t>(pe[2]), static_cast<uint32_t>(pb[3]), static_cast<uint32_t>(pe[3])};
-            } else {
-                for (int q = 0; q < cnt; ++q) reinterpret_cast<UnalignedU32x2*>(dst + 8 * q)->v = u32x2{static_cast<uint32_t>(pb[q]), static_cast<uint32_t>(pe[q])};
-            }
-        } else if (!out.narrow) {
-            uint32_t hb[4], he[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                clipped += (pb[q] > 65534 ? 1u : 0u) + (pe[q] > 65534 ? 1u : 0u);
-                hb[q] = pb[q] < 0 ? 0xFFFFu : static_cast<uint32_t>(min(pb[q], 65534));
-                he[q] = pe[q] < 0 ? 0xFFFFu : static_cast<uint32_t>(min(pe[q], 65534));
-            }
-            uint8_t* dst = row + 4u * g0;   // (the halfword before group g0's begin: the id, or the end of the group before)
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x4*>(dst)->v = u32x4{carry | hb[0] << 16, he[0] | hb[1] << 16, he[1] | hb[2] << 16, he[2] | hb[3] << 16};
-                carry = he[3];
-            } else {
-                for (int q = 0; q < cnt; ++q) {
-                    reinterpret_cast<UnalignedU32*>(dst + 4 * q)->v = carry | hb[q] << 16;
-                    carry = he[q];
-                }
-            }
-        } else {
-            uint32_t hb[4], he[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                clipped += (pb[q] > 254 ? 1u : 0u) + (pe[q] > 254 ? 1u : 0u);
-                hb[q] = pb[q] < 0 ? 0xFFu : static_cast<uint32_t>(min(pb[q], 254));
-                he[q] = pe[q] < 0 ? 0xFFu : static_cast<uint32_t>(min(pe[q], 254));
-            }
-            uint8_t* dst = row + 2u * g0;
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x2*>(dst)->v = u32x2{carry | hb[0] << 8 | he[0] << 16 | hb[1] << 24, he[1] | hb[2] << 8 | he[2] << 16 | hb[3] << 24};
-                carry = he[3];
-            } else {
-                for (int q = 0; q < cnt; ++q) {
-                    reinterpret_cast<UnalignedU16*>(dst + 2 * q)->v = static_cast<uint16_t>(carry | hb[q] << 8);
-                    carry = he[q];
-                }
-            }
-        }
-    }
-    if (out.packed) {
-        // the row's last unit; slots beyond the definition's groups do not exist (slots == 2 * max_groups == 2 G)
-        if (out.narrow) row[2 * G] = static_cast<uint8_t>(carry);
-        else reinterpret_cast<UnalignedU16*>(row + 4 * G)->v = static_cast<uint16_t>(carry);
-        if (clipped && out.overflow) atomicAdd(out.overflow, static_cast<unsigned long long>(clipped));
-    }
-}
-
-// The same from the final record OF THE STATE (gx_hop.cpp: fin_state_off): `recp` = its tags (u16 begin, end per group, padded to
-// four groups) and behind them the extraction's index, or -1 / -2-k for a state that accepts nothing.  Everything the row needs
-// from global memory is one cache line, read at once (the first twelve groups' tags and the index before anything waits).
-// (the first twelve groups' tags and the index of a final record, as a lane asks for them when its line is over: FinAhead)
-struct FinAhead {
-    u32x4 t0 = {0u, 0u, 0u, 0u}, t1 = {0u, 0u, 0u, 0u}, t2 = {0u, 0u, 0u, 0u};
-    uint32_t id = 0u;
-    __device__ __forceinline__ void load(const uint8_t* __restrict__ recp, int G) {
-        const int nblk = (G + 3) >> 2;
-        t0 = *reinterpret_cast<const u32x4*>(recp);
-        t1 = *reinterpret_cast<const u32x4*>(recp + (nblk > 1 ? 16 : 0));
-        t2 = *reinterpret_cast<const u32x4*>(recp + (nblk > 2 ? 32 : 0));
-        id = *reinterpret_cast<const uint16_t*>(recp + 16 * nblk);
-    }
-};
-__device__ __forceinline__ void write_row_rec(const LineOut& out, uint64_t i, const uint8_t* __restrict__ recp, const FinAhead& F, uint32_t regs, uint32_t len, int G,
-                                              uint32_t hop_unset) {
-    const uint32_t dummy_col = regs - 128u;
-    const u32x4 pre[3] = {F.t0, F.t1, F.t2};
-    const int32_t mid = static_cast<int16_t>(F.id);
-    const uint32_t unit = out.packed ? (out.narrow ? 1u : 2u) : 4u;
-    uint8_t* row = out.packed ? reinterpret_cast<uint8_t*>(out.packed) + i * static_cast<uint64_t>(1 + out.slots) * unit
-                              : reinterpret_cast<uint8_t*>(out.caps + i * static_cast<uint64_t>(out.slots));
-    if (!out.packed) out.match_id[i] = mid;
-    uint32_t carry = static_cast<uint32_t>(mid) & (out.narrow ? 0xFFu : 0xFFFFu);
-    uint32_t clipped = 0u;
-    const bool may_clip = __builtin_amdgcn_ballot_w64(len > 65534u) != 0ull;   // (wave-uniform: of the lanes that are here)
-    for (int g0 = 0; g0 < G; g0 += 4) {
-        u32x4 t = g0 == 0 ? pre[0] : g0 == 4 ? pre[1] : pre[2];
-        if (g0 >= 12) t = *reinterpret_cast<const u32x4*>(recp + 4 * g0);
-        const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
-        uint32_t vb[4], ve[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            vb[q] = lds_ld<uint16_t>(dummy_col + (tw[q] & 0xFFFFu));
-            ve[q] = lds_ld<uint16_t>(dummy_col + (tw[q] >> 16));
-        }
-        int32_t pb[4], pe[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool unset = (tw[q] & 0xFFFFu) == hop_unset;   // (a state that accepts nothing has every tag unset)
-            pb[q] = unset ? -1 : static_cast<int32_t>(vb[q]);
-            pe[q] = unset ? -1 : static_cast<int32_t>(ve[q]);
-        }
-        const int cnt = G - g0 < 4 ? G - g0 : 4;
-        if (!out.packed) {
-            uint8_t* dst = row + 8u * g0;
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x4*>(dst)->v = u32x4{static_cast<uint32_t>(pb[0]), static_cast<uint32_t>(pe[0]), static_cast<uint32_t>(pb[1]), static_cast<uint32_t>(pe[1])};
-                reinterpret_cast<UnalignedU32x4*>(dst + 16)->v = u32x4{static_cast<uint32_t>(pb[2]), static_cast<uint32_t>(pe[2]), static_cast<uint32_t>(pb[3]), static_cast<uint32_t>(pe[3])};
-            } else {
-                for (int q = 0; q < cnt; ++q) reinterpret_cast<UnalignedU32x2*>(dst + 8 * q)->v = u32x2{static_cast<uint32_t>(pb[q]), static_cast<uint32_t>(pe[q])};
-            }
-        } else if (!out.narrow) {
-            uint32_t hb[4], he[4];
-            if (!may_clip) {   // (no line of this service reaches the 65 535th byte: -1 is 0xFFFF, everything else fits; config 5: 1 %)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { hb[q] = static_cast<uint32_t>(pb[q]) & 0xFFFFu; he[q] = static_cast<uint32_t>(pe[q]) & 0xFFFFu; }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    clipped += (pb[q] > 65534 ? 1u : 0u) + (pe[q] > 65534 ? 1u : 0u);
-                    hb[q] = pb[q] < 0 ? 0xFFFFu : static_cast<uint32_t>(min(pb[q], 65534));
-                    he[q] = pe[q] < 0 ? 0xFFFFu : static_cast<uint32_t>(min(pe[q], 65534));
-                }
-            }
-            uint8_t* dst = row + 4u * g0;   // (the halfword before group g0's begin: the id, or the end of the group before)
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x4*>(dst)->v = u32x4{carry | hb[0] << 16, he[0] | hb[1] << 16, he[1] | hb[2] << 16, he[2] | hb[3] << 16};
-                carry = he[3];
-            } else {
-                for (int q = 0; q < cnt; ++q) {
-                    reinterpret_cast<UnalignedU32*>(dst + 4 * q)->v = carry | hb[q] << 16;
-                    carry = he[q];
-                }
-            }
-        } else {
-            uint32_t hb[4], he[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                clipped += (pb[q] > 254 ? 1u : 0u) + (pe[q] > 254 ? 1u : 0u);
-                hb[q] = pb[q] < 0 ? 0xFFu : static_cast<uint32_t>(min(pb[q], 254));
-                he[q] = pe[q] < 0 ? 0xFFu : static_cast<uint32_t>(min(pe[q], 254));
-            }
-            uint8_t* dst = row + 2u * g0;
-            if (cnt == 4) {
-                reinterpret_cast<UnalignedU32x2*>(dst)->v = u32x2{carry | hb[0] << 8 | he[0] << 16 | hb[1] << 24, he[1] | hb[2] << 8 | he[2] << 16 | hb[3] << 24};
-                carry = he[3];
-            } else {
-                for (int q = 0; q < cnt; ++q) {
-                    reinterpret_cast<UnalignedU16*>(dst + 2 * q)->v = static_cast<uint16_t>(carry | hb[q] << 8);
-                    carry = he[q];
-                }
-            }
-        }
-    }
-    if (out.packed) {
-        if (out.narrow) row[2 * G] = static_cast<uint8_t>(carry);
-        else reinterpret_cast<UnalignedU16*>(row + 4 * G)->v = static_cast<uint16_t>(carry);
-        if (clipped && out.overflow) atomicAdd(out.overflow, static_cast<unsigned long long>(clipped));
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -357,7 +113,7 @@ __device__ bool pike_capture(const GxDev& T, int k, const CH* __restrict__ s, in
 // that has such extractions within GxDev::pike_blocks workgroups)
 template <typename CH, typename MS>
 __device__ void extract_line_global(const GxDev& T, const MS* __restrict__ m_next, const CH* __restrict__ s, int64_t len,
-                                    uint64_t i, const LineOut& out, int32_t* __restrict__ state_out, int match_only, uint32_t pike_slot = 0xFFFFFFFFu) {
+                                    uint64_t i, const RowOut& out, int32_t* __restrict__ state_out, int match_only, uint32_t pike_slot = 0xFFFFFFFFu) {
     const int ncls = T.ncls;
     const int slots = out.slots;
     // match_only < 0: CookedExtraction.match(String) alone (core/jdkre/JDKRegexpCookedExtraction.java:36-39) for
@@ -450,7 +206,7 @@ __device__ __forceinline__ int64_t trim_eol(const CH* __restrict__ s, int64_t le
 // do not fit LDS, UTF-16 input and 32-bit match states.
 template <typename CH, typename OFF, typename MS>
 __global__ void __launch_bounds__(256)
-k_extract_generic(GxDev T, const CH* __restrict__ data, const OFF* __restrict__ off, uint64_t n, LineOut out,
+k_extract_generic(GxDev T, const CH* __restrict__ data, const OFF* __restrict__ off, uint64_t n, RowOut out,
                   int32_t* __restrict__ state_out, int match_only, const MS* __restrict__ m_next, int strip_eol) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -506,7 +262,7 @@ k_narrow_units(const uint16_t* __restrict__ units, const OFF* __restrict__ off, 
 template <typename OFF, typename MS>
 __global__ void __launch_bounds__(256)
 k_extract_flagged(GxDev T, const uint16_t* __restrict__ units, const OFF* __restrict__ off, uint64_t n, const uint8_t* __restrict__ flags,
-                  LineOut out, int match_only, const MS* __restrict__ m_next, int strip_eol, const uint32_t* __restrict__ any_word, uint32_t seq) {
+                  RowOut out, int match_only, const MS* __restrict__ m_next, int strip_eol, const uint32_t* __restrict__ any_word, uint32_t seq) {
     if (any_word && __hip_atomic_load(any_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq) return;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -526,7 +282,7 @@ k_extract_flagged(GxDev T, const uint16_t* __restrict__ units, const OFF* __rest
 // already answered (it would be counted twice in *overflow).
 template <typename OFF, typename CH>
 __global__ void __launch_bounds__(256)
-k_extract_oversize(GxDev T, const CH* __restrict__ data, const OFF* __restrict__ off, uint64_t n, LineOut out, int match_only,
+k_extract_oversize(GxDev T, const CH* __restrict__ data, const OFF* __restrict__ off, uint64_t n, RowOut out, int match_only,
                    int strip_eol, const uint32_t* __restrict__ flag, uint32_t seq, uint32_t limit, int by_length, int32_t* __restrict__ state_out) {
     if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != seq) return;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
@@ -548,17 +304,6 @@ k_extract_oversize(GxDev T, const CH* __restrict__ data, const OFF* __restrict__
     }
 }
 
-LineOut line_out(const GxDev& dev, const GxBatch& b) {
-    LineOut o;
-    o.match_id = b.match_id;
-    o.caps = b.caps;
-    o.packed = b.packed;
-    o.overflow = b.overflow;
-    o.narrow = b.narrow;
-    o.slots = 2 * dev.max_groups;
-    return o;
-}
-
 template <typename CH, typename OFF>
 hipError_t launch_generic_t(const GxDev& dev, const GxBatch& b, hipStream_t stream) {
     if (b.n == 0) return hipSuccess;
@@ -569,11 +314,11 @@ hipError_t launch_generic_t(const GxDev& dev, const GxBatch& b, hipStream_t stre
     dim3 grid(static_cast<unsigned>(blocks));
     if (dev.m_next16)
         hipLaunchKernelGGL((k_extract_generic<CH, OFF, uint16_t>), grid, dim3(block), 0, stream, dev,
-                           static_cast<const CH*>(b.data), static_cast<const OFF*>(b.offsets), b.n, line_out(dev, b),
+                           static_cast<const CH*>(b.data), static_cast<const OFF*>(b.offsets), b.n, row_out(dev, b),
                            b.state_out, b.match_only, dev.m_next16, b.strip_eol);
     else
         hipLaunchKernelGGL((k_extract_generic<CH, OFF, uint32_t>), grid, dim3(block), 0, stream, dev,
-                           static_cast<const CH*>(b.data), static_cast<const OFF*>(b.offsets), b.n, line_out(dev, b),
+                           static_cast<const CH*>(b.data), static_cast<const OFF*>(b.offsets), b.n, row_out(dev, b),
                            b.state_out, b.match_only, dev.m_next32, b.strip_eol);
     return hipGetLastError();
 }
@@ -585,7 +330,7 @@ hipError_t launch_generic_t(const GxDev& dev, const GxBatch& b, hipStream_t stre
 constexpr uint32_t ONE_LINE_MAX_UNITS = 16384;   // 32 KB of LDS; longer lines take the batch path's kernel on a device copy
 template <typename MS>
 __global__ void __launch_bounds__(64)
-k_extract_one(GxDev T, const uint16_t* __restrict__ units, uint32_t len, LineOut out, int32_t* __restrict__ state_out, int match_only,
+k_extract_one(GxDev T, const uint16_t* __restrict__ units, uint32_t len, RowOut out, int32_t* __restrict__ state_out, int match_only,
               const MS* __restrict__ m_next) {
     __shared__ uint16_t line[ONE_LINE_MAX_UNITS];
     const uint32_t pairs = (len + 1u) >> 1;   // (the buffer is padded to a multiple of 8 bytes)
@@ -611,7 +356,7 @@ constexpr uint32_t SLICE_BYTES = 64, SLICE_ROW = 80;
 template <typename OFF, int TIER>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4)))
 k_extract_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, const uint8_t* __restrict__ at_global,
-                 const uint8_t* __restrict__ data, const OFF* __restrict__ off, uint64_t n, LineOut out, int match_only, int strip_eol) {
+                 const uint8_t* __restrict__ data, const OFF* __restrict__ off, uint64_t n, RowOut out, int match_only, int strip_eol) {
     {
         extern __shared__ __attribute__((aligned(16))) uint8_t gx_smem[];
         const uint4* src = reinterpret_cast<const uint4*>(lds_image);
@@ -662,7 +407,7 @@ k_extract_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, const 
         if (done) {
             const int32_t info = state_info<TIER>(W, row);
             if (!want_caps) out.id(i, info);
-            else write_row<TIER>(out, i, info, L.fin_tags, fin_g, regs, len, T.max_groups);
+            else store_row<TIER>(out, i, info, fin_rec<TIER>(info, L.fin_tags, fin_g), regs, len, T.max_groups);
             has_line = false;
         }
         // ---- free lanes take the next lines of the range, in lane order ----
@@ -771,7 +516,7 @@ hipError_t launch_slices_t(const GxDev& dev, const GxLds& lds, const uint8_t* ld
     hipError_t e = allow_full_lds(&k_extract_slices<OFF, TIER>);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_extract_slices<OFF, TIER>), grid, block, lds.total_bytes, stream, dev, lds, lds_image, at_global,
-                       static_cast<const uint8_t*>(b.data), static_cast<const OFF*>(b.offsets), b.n, line_out(dev, b), b.match_only, b.strip_eol);
+                       static_cast<const uint8_t*>(b.data), static_cast<const OFF*>(b.offsets), b.n, row_out(dev, b), b.match_only, b.strip_eol);
     return hipGetLastError();
 }
 
@@ -859,7 +604,7 @@ __device__ __forceinline__ bool chunk_in_run(const u32x4& v, uint32_t runinfo) {
 template <typename OFF, bool WIDE>
 __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(1, 3)))   // (12 waves at most: plan_hop_slice_launch)
 k_extract_hop_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, const uint8_t* __restrict__ at_global,
-                     const uint8_t* __restrict__ data, const OFF* __restrict__ off, uint64_t n, LineOut out, int match_only, int strip_eol,
+                     const uint8_t* __restrict__ data, const OFF* __restrict__ off, uint64_t n, RowOut out, int match_only, int strip_eol,
                      uint32_t* __restrict__ oversize_flag, uint32_t seq, unsigned long long* __restrict__ stamps,
                      uint32_t* __restrict__ pool_ctr, uint32_t pool_base, uint64_t n_static,
                      uint8_t* __restrict__ wide_flags, uint32_t* __restrict__ wide_any) {
@@ -946,14 +691,14 @@ k_extract_hop_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, co
                 // the walk; a line that ended where it began is read now)
                 const uint8_t* recp = at_global + L.fin_state_off + static_cast<uint64_t>(row) * L.fin_state_rec;
                 if (!fin_here) F.load(recp, T.max_groups);
-                write_row_rec(out, i, recp, F, regs, len, T.max_groups, L.fin_unset);
+                store_row<TIER_HOP>(out, i, 0, F.at(recp), regs, len, T.max_groups, L.fin_unset);
                 fin_here = false;
             } else {
                 const int32_t hot_info = static_cast<int16_t>(lds_ld<uint16_t>(L.acc_tab + 2u * min(row, H.n_hot - 1u)));
                 int32_t info = hot_info >= 0 && !match_only ? hot_info * 16 : hot_info;
                 if (row >= H.n_hot) info = *reinterpret_cast<const int32_t*>(H.rows + (static_cast<uint64_t>(row) * H.row_bytes + H.info_off));
                 if (match_only) out.id(i, info);
-                else write_row<TIER_HOP>(out, i, info, fin_lds, fin_g, regs, len, T.max_groups, L.fin_unset);
+                else store_row<TIER_HOP>(out, i, info, fin_rec<TIER_HOP>(info, fin_lds, fin_g), regs, len, T.max_groups, L.fin_unset);
             }
             if (WIDE) {   // (a flagged line's result is the per-line walk's to write again)
                 wide_flags[i] = line_wide ? 1 : 0;
@@ -1285,7 +1030,7 @@ hipError_t launch_extract_hop_slices(const GxDev& dev, const GxLds& lds, const u
     auto go = [&](auto kernel, auto offsets) -> hipError_t {
         hipError_t e = allow_full_lds(kernel);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, grid, block, lds.total_bytes, stream, dev, lds, lds_image, at_global, static_cast<const uint8_t*>(b.data), offsets, b.n, line_out(dev, b),
+        hipLaunchKernelGGL(kernel, grid, block, lds.total_bytes, stream, dev, lds, lds_image, at_global, static_cast<const uint8_t*>(b.data), offsets, b.n, row_out(dev, b),
                            (b.match_only != 0 || !dev.has_capture) ? 1 : 0, b.strip_eol, b.oversize_flag, b.seq, stamps, b.chunk_ctr, b.chunk_base, n_static,
                            b.wide_flags, b.wide_any);
         return hipGetLastError();
@@ -1314,7 +1059,7 @@ hipError_t launch_extract_flagged(const GxDev& dev, const GxBatch& b, const uint
     if (b.n == 0) return hipSuccess;
     const dim3 grid(dev.pike_off ? dev.pike_blocks : 256u * 4u), block(256);
     const uint16_t* units = static_cast<const uint16_t*>(b.data);
-#define GX_FLAGGED(OFF, MS, NEXT) hipLaunchKernelGGL((k_extract_flagged<OFF, MS>), grid, block, 0, stream, dev, units, static_cast<const OFF*>(b.offsets), b.n, flags, line_out(dev, b), b.match_only, NEXT, b.strip_eol, any_word, b.seq)
+#define GX_FLAGGED(OFF, MS, NEXT) hipLaunchKernelGGL((k_extract_flagged<OFF, MS>), grid, block, 0, stream, dev, units, static_cast<const OFF*>(b.offsets), b.n, flags, row_out(dev, b), b.match_only, NEXT, b.strip_eol, any_word, b.seq)
     if (b.offsets64) { if (dev.m_next16) GX_FLAGGED(uint64_t, uint16_t, dev.m_next16); else GX_FLAGGED(uint64_t, uint32_t, dev.m_next32); }
     else { if (dev.m_next16) GX_FLAGGED(uint32_t, uint16_t, dev.m_next16); else GX_FLAGGED(uint32_t, uint32_t, dev.m_next32); }
 #undef GX_FLAGGED
@@ -1324,9 +1069,9 @@ hipError_t launch_extract_flagged(const GxDev& dev, const GxBatch& b, const uint
 hipError_t launch_extract_one(const GxDev& dev, const uint16_t* units, uint32_t len, const GxBatch& b, hipStream_t stream) {
     if (len > ONE_LINE_MAX_UNITS) return hipErrorInvalidValue;
     if (dev.m_next16)
-        hipLaunchKernelGGL((k_extract_one<uint16_t>), dim3(1), dim3(64), 0, stream, dev, units, len, line_out(dev, b), b.state_out, b.match_only, dev.m_next16);
+        hipLaunchKernelGGL((k_extract_one<uint16_t>), dim3(1), dim3(64), 0, stream, dev, units, len, row_out(dev, b), b.state_out, b.match_only, dev.m_next16);
     else
-        hipLaunchKernelGGL((k_extract_one<uint32_t>), dim3(1), dim3(64), 0, stream, dev, units, len, line_out(dev, b), b.state_out, b.match_only, dev.m_next32);
+        hipLaunchKernelGGL((k_extract_one<uint32_t>), dim3(1), dim3(64), 0, stream, dev, units, len, row_out(dev, b), b.state_out, b.match_only, dev.m_next32);
     return hipGetLastError();
 }
 
@@ -1342,7 +1087,7 @@ hipError_t launch_extract_oversize(const GxDev& dev, const GxBatch& b, uint32_t 
     // a small grid: without the flag every wave leaves at once; with it, the lines in question are few and long
     const dim3 grid(dev.pike_off ? dev.pike_blocks : 256u), block(256);
 #define GX_OVERSIZE(OFF, CH) hipLaunchKernelGGL((k_extract_oversize<OFF, CH>), grid, block, 0, stream, dev, static_cast<const CH*>(b.data), \
-                           static_cast<const OFF*>(b.offsets), b.n, line_out(dev, b), b.match_only, b.strip_eol, b.oversize_flag, b.seq, limit, by_length, b.state_out)
+                           static_cast<const OFF*>(b.offsets), b.n, row_out(dev, b), b.match_only, b.strip_eol, b.oversize_flag, b.seq, limit, by_length, b.state_out)
     if (b.wide) { if (b.offsets64) GX_OVERSIZE(uint64_t, uint16_t); else GX_OVERSIZE(uint32_t, uint16_t); }
     else { if (b.offsets64) GX_OVERSIZE(uint64_t, uint8_t); else GX_OVERSIZE(uint32_t, uint8_t); }
 #undef GX_OVERSIZE

@@ -16,7 +16,7 @@
 // SORTED: a lane does not need its tile's lines to be neighbours in memory, so for uneven lines a workgroup orders the
 // lines of a chunk by length first and forms its tiles from lines of similar length (a tile takes as long as its longest
 // line); chunks are handed out by a counter in global memory.
-#include "gx_walk.hpp"
+#include "gx_rows.hpp"
 
 namespace gx {
 
@@ -28,11 +28,7 @@ struct LanesIO {
     const uint8_t* data;
     const void* off;
     uint64_t n;
-    int32_t* match_id;
-    int32_t* caps;
-    uint16_t* packed;
-    unsigned long long* overflow;
-    int32_t narrow;              // compact rows as u8 (gx_device.hpp: GxBatch::narrow)
+    RowOut rows;                 // where the results go (gx_rows.hpp)
     uint32_t* oversize_flag;
     uint32_t seq;
     int32_t max_groups;
@@ -168,10 +164,9 @@ k_extract_lanes(GxLds L, LanesIO io) {
                 if (len64 > 0 && data[o0 + len64 - 1] == 0x0Du) --len64;
             }
             // positions are 16-bit in the register block: a longer line is left to the follow-up launch of the per-line kernel.
-            // Compact rows keep 0xFFFF for "unset" and promise that an offset above 65 534 is stored as 65 534 and counted
-            // (include/gorp_hip.h): a line of exactly 65 535 bytes can have such an offset, so it goes the same way (the
-            // per-line kernel writes through LineOut, which clamps and counts).
-            const bool oversize = valid && len64 > (PACKED ? 65534u : 65535u);
+            // With compact rows, so is a line longer than u16 rows can hold an offset of (a line of exactly 65 535 bytes can have
+            // such an offset): the per-line kernel clips and counts it, and the rows here never clip.
+            const bool oversize = valid && len64 > (PACKED ? static_cast<uint32_t>(row_max_offset(ROWS_U16)) : 65535u);
             if (oversize) __hip_atomic_store(io.oversize_flag, io.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             const uint32_t len = oversize ? 0u : static_cast<uint32_t>(len64);
             const uint8_t* line = data + o0;
@@ -235,69 +230,16 @@ k_extract_lanes(GxLds L, LanesIO io) {
             // ---- results ----
             const int32_t info = state_info<TIER>(W, row);
             if (!CAPTURE) {
-                if (valid && !oversize) io.match_id[i] = info;
+                if (valid && !oversize) io.rows.match_id[i] = info;
             } else {
+                // (dense rows leave lane by lane: the plan gives the wave's row area no room for them.  Taking them through it 32 lines
+                // at a time, as contiguous 16-byte stores, was measured: no faster, 1.558 against 1.551 ms on config 3)
+                auto result = [&](auto emit) { return line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, emit); };
                 const bool full_tile = contiguous && __all(valid) && !__any(oversize);
-                const uint64_t i0 = i - lane;
-                if (PACKED) {
-                    // u16 rows, or -- io.narrow, wave-uniform -- u8 rows (an offset above 254 stored as 254 and counted)
-                    const bool narrow = io.narrow != 0;
-                    const uint32_t row_b = narrow ? 1u + slots : 2u + 2u * slots;
-                    const bool rows_aligned = (reinterpret_cast<uintptr_t>(io.packed) & 15u) == 0u;  // (16-byte stores below)
-                    uint8_t* rows8 = reinterpret_cast<uint8_t*>(io.packed);
-                    uint32_t clamped = 0;
-                    if (full_tile && rows_aligned) {
-                        // the tile's 64 rows are one contiguous block of the output: through the wave's row area, then 1 KiB of
-                        // consecutive bytes per store instruction
-                        const uint32_t my_out = out_area + lane * row_b;
-                        if (narrow) {
-                            const int32_t result = line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                                clamped += (pb > 254 ? 1u : 0u) + (pe > 254 ? 1u : 0u);
-                                lds_st<uint8_t>(my_out + 1u + 2u * g, static_cast<uint8_t>(pb > 254 ? 254 : pb));
-                                lds_st<uint8_t>(my_out + 2u + 2u * g, static_cast<uint8_t>(pe > 254 ? 254 : pe));
-                            });
-                            lds_st<uint8_t>(my_out, static_cast<uint8_t>(result));
-                        } else {
-                            const int32_t result = line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                                lds_st<uint16_t>(my_out + 2u + 4u * g, static_cast<uint16_t>(pb));
-                                lds_st<uint16_t>(my_out + 4u + 4u * g, static_cast<uint16_t>(pe));
-                            });
-                            lds_st<uint16_t>(my_out, static_cast<uint16_t>(result));
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        uint8_t* out = rows8 + i0 * static_cast<uint64_t>(row_b);
-                        for (uint32_t c = lane; c < 4u * row_b; c += 64u)
-                            *reinterpret_cast<u32x4*>(out + (c << 4)) = lds_ld<u32x4>(out_area + (c << 4));
-                    } else if (valid && !oversize) {
-                        if (narrow) {
-                            uint8_t* rp = rows8 + i * static_cast<uint64_t>(row_b);
-                            const int32_t result = line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                                clamped += (pb > 254 ? 1u : 0u) + (pe > 254 ? 1u : 0u);
-                                rp[1 + 2 * g] = static_cast<uint8_t>(pb > 254 ? 254 : pb);
-                                rp[2 + 2 * g] = static_cast<uint8_t>(pe > 254 ? 254 : pe);
-                            });
-                            rp[0] = static_cast<uint8_t>(result);
-                        } else {
-                            uint16_t* rp = io.packed + i * static_cast<uint64_t>(1u + slots);
-                            const int32_t result = line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                                rp[1 + 2 * g] = static_cast<uint16_t>(pb);
-                                rp[2 + 2 * g] = static_cast<uint16_t>(pe);
-                            });
-                            rp[0] = static_cast<uint16_t>(result);
-                        }
-                    }
-                    if (narrow && clamped && io.overflow) atomicAdd(io.overflow, static_cast<unsigned long long>(clamped));
-                } else {
-                    // dense int32 rows: every lane stores its own (8 bytes per group).  Taking them through the wave's row area 32
-                    // lines at a time, as contiguous 16-byte stores, was measured: no faster (1.558 against 1.551 ms on config 3)
-                    if (valid && !oversize) {
-                        int32_t* cp = io.caps + i * static_cast<uint64_t>(slots);
-                        io.match_id[i] = line_result<TIER>(info, L.fin_tags, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            *reinterpret_cast<u32x2*>(cp + 2 * g) = u32x2{static_cast<uint32_t>(pb), static_cast<uint32_t>(pe)};
-                        });
-                    }
-                }
+                const uint32_t area_bytes = L.regs_wave_bytes - L.stage_bytes;
+                if (!PACKED) store_tile<ROWS_DENSE, false>(io.rows, slots, i, lane, valid && !oversize, false, out_area, area_bytes, len, result);
+                else if (io.rows.format == ROWS_U8) store_tile<ROWS_U8, true>(io.rows, slots, i, lane, valid && !oversize, full_tile, out_area, area_bytes, len, result);
+                else store_tile<ROWS_U16, false>(io.rows, slots, i, lane, valid && !oversize, full_tile, out_area, area_bytes, len, result);
             }
             // the wave's LDS area is reused by the next tile
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -375,11 +317,7 @@ hipError_t launch_extract_lanes(const GxDev& dev, const GxLds& lds, const uint8_
     io.data = static_cast<const uint8_t*>(b.data);
     io.off = b.offsets;
     io.n = b.n;
-    io.match_id = b.match_id;
-    io.caps = b.caps;
-    io.packed = b.packed;
-    io.overflow = b.overflow;
-    io.narrow = b.narrow;
+    io.rows = row_out(dev, b);
     io.oversize_flag = b.oversize_flag;
     io.seq = b.seq;
     io.max_groups = dev.max_groups;

@@ -34,7 +34,7 @@ struct GxLds {
     uint32_t u_dead;      // row of its dead state
     uint32_t ops_off;     // u32[n_oplists + 1]
     uint32_t ops;         // u16 pairs
-    uint32_t fin_tags;    // final records (gx_walk.hpp: line_result): LDS address, or byte offset in the global row image (L2 tier)
+    uint32_t fin_tags;    // final records (gx_rows.hpp: line_result): LDS address, or byte offset in the global row image (L2 tier)
     uint32_t table_bytes; // size of the image, multiple of 16
     uint32_t simple_ops;  // 1: every capture program is one "register := position"; the program field is then
                           // (register + 1) * 128 = byte offset of the register's column in the wave's register
@@ -75,5 +75,28 @@ constexpr uint32_t GX_BITMAP_WAVE_BYTES = 144;  // 16 x u64 (1024 chunks = 16 KB
 #define GX_HOP_SLICE_BYTES 128u   // (a power of two times 16, at most 1024: one piece is loaded by 64 / (bytes / 16) ... lanes per line)
 #endif
 constexpr uint32_t GX_SERVICE_MAX_BYTES = 56u + 16u * 60u;   // the longest line a request of the resident service holds (1 016 bytes)
+
+// The three formats a batch's results leave a kernel in (gx_batch_opts.compact_results, include/gorp_hip.h).  A line's result is its
+// match id and slots = 2 * max_groups offsets (begin, end per group; -1: no match / unset):
+//   ROWS_DENSE  int32 match_id[n] and int32 caps[n][slots];
+//   ROWS_U16    u16[1 + slots] per line: int16 id, offsets with 0xFFFF = unset, an offset above 65 534 stored as 65 534 and counted;
+//   ROWS_U8     u8[1 + slots] per line: int8 id, offsets with 0xFF = unset, an offset above 254 stored as 254 and counted.
+// Everything about a format is here, once: kernels (gx_rows.hpp), host code and tests use these functions.
+enum RowFormat : uint32_t { ROWS_DENSE = 0, ROWS_U16 = 1, ROWS_U8 = 2 };
+constexpr RowFormat row_format(bool compact, bool narrow) { return !compact ? ROWS_DENSE : narrow ? ROWS_U8 : ROWS_U16; }
+constexpr uint32_t row_unit_bytes(RowFormat f) { return f == ROWS_U8 ? 1u : f == ROWS_U16 ? 2u : 4u; }
+constexpr uint32_t row_bytes(RowFormat f, uint32_t slots) { return row_unit_bytes(f) + row_unit_bytes(f) * slots; }   // (dense: id + caps of a line)
+constexpr uint32_t row_unset(RowFormat f) { return f == ROWS_U8 ? 0xFFu : f == ROWS_U16 ? 0xFFFFu : 0xFFFFFFFFu; }   // also the unit mask
+constexpr int32_t row_max_offset(RowFormat f) { return f == ROWS_U8 ? 254 : f == ROWS_U16 ? 65534 : 0x7FFFFFFF; }
+struct RowUnit { uint32_t unit, clipped; };   // an offset as stored, and 1 when it was above row_max_offset (stored as that)
+constexpr RowUnit encode_offset(RowFormat f, int32_t v) {
+    return v < 0 ? RowUnit{row_unset(f), 0u}
+                 : v > row_max_offset(f) ? RowUnit{static_cast<uint32_t>(row_max_offset(f)), 1u} : RowUnit{static_cast<uint32_t>(v), 0u};
+}
+constexpr int32_t decode_offset(RowFormat f, uint32_t unit) { return unit == row_unset(f) ? -1 : static_cast<int32_t>(unit); }
+constexpr uint32_t encode_id(RowFormat f, int32_t id) { return static_cast<uint32_t>(id) & row_unset(f); }   // (at most 32 767 / 127 extractions)
+constexpr int32_t decode_id(RowFormat f, uint32_t unit) {
+    return f == ROWS_U8 ? static_cast<int8_t>(unit) : f == ROWS_U16 ? static_cast<int16_t>(unit) : static_cast<int32_t>(unit);
+}
 
 }  // namespace gx

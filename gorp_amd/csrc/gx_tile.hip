@@ -34,11 +34,7 @@ hipError_t launch_extract_tile(const GxDev& dev, const GxLds& lds, const uint8_t
     io.data = static_cast<const uint8_t*>(b.data);
     io.off = b.offsets;
     io.n = b.n;
-    io.match_id = b.match_id;
-    io.caps = b.caps;
-    io.packed = b.packed;
-    io.overflow = b.overflow;
-    io.narrow = b.narrow;
+    io.rows = row_out(dev, b);
     io.oversize_flag = b.oversize_flag;
     io.seq = b.seq;
     io.steal = b.steal;

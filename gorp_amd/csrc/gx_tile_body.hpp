@@ -24,7 +24,7 @@
 //  Exactness never depends on either: a set bit / passed test is a fact about bytes on which the state provably
 //  stays put; everything else takes the exact steps.
 #pragma once
-#include "gx_walk.hpp"
+#include "gx_rows.hpp"
 #include "gx_hop_dev.hpp"
 
 namespace gx {
@@ -38,11 +38,7 @@ struct TileIO {
     const uint8_t* data;
     const void* off;
     uint64_t n;
-    int32_t* match_id;
-    int32_t* caps;
-    uint16_t* packed;            // compact rows instead of match_id / caps
-    unsigned long long* overflow;
-    int32_t narrow;              // ... as u8 rows (gx_device.hpp: GxBatch::narrow)
+    RowOut rows;                 // where the results go (gx_rows.hpp)
     uint32_t* oversize_flag;
     uint32_t seq;
     int32_t max_groups;
@@ -548,12 +544,12 @@ k_extract_tile(GxLds L, TileIO io) {
             if (wave_any(mrow >= H.n_hot)) {
                 if (mrow >= H.n_hot) first = *reinterpret_cast<const int32_t*>(H.rows + (static_cast<uint64_t>(mrow) * H.row_bytes + H.info_off));
             }
-            if (valid) io.match_id[i] = first;
+            if (valid) io.rows.match_id[i] = first;
             GX_STAMP(2);
         } else if (MODE == 0) {
             // ---- hot loop #1 alone: PolyMatcher.match ----
             const uint32_t mrow = walk<TIER, false, false>(Wm, stage, bitmap, use_map, L.m_start, start, end, true, L.m_dead, regs);
-            if (valid) io.match_id[i] = state_info<TIER>(Wm, mrow);
+            if (valid) io.rows.match_id[i] = state_info<TIER>(Wm, mrow);
             if ((TIER == TIER_LDS || TIER == TIER_L2) && io.state_out && valid)   // (a row IS a state of the match automaton: gx_state_accepts reads the rest)
                 io.state_out[i] = mrow == L.m_dead ? -1 : static_cast<int32_t>(TIER == TIER_LDS ? (mrow - L.m_start) / L.row_bytes : mrow - L.m_start);
             GX_STAMP(2);
@@ -593,100 +589,17 @@ k_extract_tile(GxLds L, TileIO io) {
             if (HOP) lds_st<uint16_t>(regs - 128u, static_cast<uint16_t>(len));   // (the dummy column, free now: the tag "the line's length" names it -- gx_hop.cpp)
             const uint8_t* fin_g = GT && !(HOP && L.at != 0u) ? io.at_global + L.fin_tags : nullptr;
             const uint32_t fin_lds = HOP ? L.at : L.fin_tags;
-            // The tile's 64 result rows are one contiguous block of the output.  Transpose them through the staging
-            // area (free now: every lane has finished its walk) so that each store instruction writes 1 KiB of
-            // consecutive bytes, instead of every lane writing pieces of its own row.
+            // the tile's rows through the staging area (free now: every lane has finished its walk).  A staged line is shorter than
+            // 65 535 bytes, so u16 rows never clip here.
+            auto result = [&](auto emit) { return line_result<TIER>(info, fin_lds, fin_g, regs, len, G, emit, L.fin_unset); };
             const bool full_tile = cur.a == 0u && cur.b == 64u;
-            if (PACKED) {
-                // u16 rows (int16 id + u16 offsets), or -- io.narrow, wave-uniform -- u8 rows (int8 id + u8 offsets, an offset
-                // above 254 stored as 254 and counted).  A staged line is shorter than 65 535 bytes, so u16 rows never clamp here.
-                constexpr bool narrow = PACKED == 2;
-                const uint32_t row_b = narrow ? 1u + slots : 2u + 2u * slots;
-                uint8_t* out_rows = reinterpret_cast<uint8_t*>(io.packed) + (cur.i - lane) * static_cast<uint64_t>(row_b);
-                const bool rows_aligned = (reinterpret_cast<uintptr_t>(io.packed) & 15u) == 0u;  // (64 rows are a multiple of 16 bytes)
-                uint32_t clamped = 0;
-                if (full_tile && rows_aligned && 64u * row_b + 16u <= L.stage_bytes) {
-                    const uint32_t my_row = stage + lane * row_b;
-                    int32_t result;
-                    if (narrow && !__any(len > 254u)) {
-                        // (no offset of this tile's lines is above 254: nothing to clip or to count)
-                        result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            lds_st<uint8_t>(my_row + 1u + 2u * g, static_cast<uint8_t>(pb));
-                            lds_st<uint8_t>(my_row + 2u + 2u * g, static_cast<uint8_t>(pe));
-                        }, L.fin_unset);
-                        lds_st<uint8_t>(my_row, static_cast<uint8_t>(result));
-                    } else if (narrow) {
-                        result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            clamped += (pb > 254 ? 1u : 0u) + (pe > 254 ? 1u : 0u);
-                            lds_st<uint8_t>(my_row + 1u + 2u * g, static_cast<uint8_t>(pb > 254 ? 254 : pb));
-                            lds_st<uint8_t>(my_row + 2u + 2u * g, static_cast<uint8_t>(pe > 254 ? 254 : pe));
-                        }, L.fin_unset);
-                        lds_st<uint8_t>(my_row, static_cast<uint8_t>(result));
-                    } else {
-                        result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            lds_st<uint16_t>(my_row + 2u + 4u * g, static_cast<uint16_t>(pb));
-                            lds_st<uint16_t>(my_row + 4u + 4u * g, static_cast<uint16_t>(pe));
-                        }, L.fin_unset);
-                        lds_st<uint16_t>(my_row, static_cast<uint16_t>(result));
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    for (uint32_t c = lane; c < 4u * row_b; c += 64u) {  // 64 * row_b / 16 chunks
 #ifdef GX_DEV
-                        if (io.dev_flags & 2u) { __builtin_nontemporal_store(lds_ld<u32x4>(stage + (c << 4)), reinterpret_cast<u32x4*>(out_rows + (c << 4))); continue; }
-                        if ((io.dev_flags & 4u) && c != 0u) continue;  // experiment: (almost) no result stores
+            const uint32_t dev_flags = io.dev_flags;
+#else
+            const uint32_t dev_flags = 0u;
 #endif
-                        *reinterpret_cast<u32x4*>(out_rows + (c << 4)) = lds_ld<u32x4>(stage + (c << 4));
-                    }
-                } else if (valid) {
-                    if (narrow) {
-                        uint8_t* rp = reinterpret_cast<uint8_t*>(io.packed) + i * static_cast<uint64_t>(row_b);
-                        const int32_t result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            clamped += (pb > 254 ? 1u : 0u) + (pe > 254 ? 1u : 0u);
-                            rp[1 + 2 * g] = static_cast<uint8_t>(pb > 254 ? 254 : pb);
-                            rp[2 + 2 * g] = static_cast<uint8_t>(pe > 254 ? 254 : pe);
-                        }, L.fin_unset);
-                        rp[0] = static_cast<uint8_t>(result);
-                    } else {
-                        uint16_t* rp = io.packed + i * static_cast<uint64_t>(1u + slots);
-                        const int32_t result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                            rp[1 + 2 * g] = static_cast<uint16_t>(pb);
-                            rp[2 + 2 * g] = static_cast<uint16_t>(pe);
-                        }, L.fin_unset);
-                        rp[0] = static_cast<uint16_t>(result);
-                    }
-                }
-                if (narrow && io.overflow && __any(clamped != 0u)) {   // (one atomic per wave: this file is built without the compiler's atomic optimizer)
-                    uint32_t sum = clamped;
-#pragma unroll
-                    for (int d = 32; d >= 1; d >>= 1) sum += static_cast<uint32_t>(__shfl_xor(static_cast<int>(sum), d));
-                    if (lane == 0) atomicAdd(io.overflow, static_cast<unsigned long long>(sum));
-                }
-            } else {
-                const uint32_t row_b = slots * 4u;
-                const bool caps_aligned = ((reinterpret_cast<uintptr_t>(io.caps) | reinterpret_cast<uintptr_t>(io.match_id)) & 15u) == 0u;
-                if (full_tile && caps_aligned && 64u * row_b + 256u <= L.stage_bytes) {
-                    const uint32_t my_row = stage + lane * row_b;
-                    const int32_t result = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                        lds_st<u32x2>(my_row + 8u * g, u32x2{static_cast<uint32_t>(pb), static_cast<uint32_t>(pe)});
-                    }, L.fin_unset);
-                    const uint32_t ids = stage + 64u * row_b;  // the tile's 64 match ids = 256 bytes
-                    lds_st<uint32_t>(ids + 4u * lane, static_cast<uint32_t>(result));
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    uint8_t* out = reinterpret_cast<uint8_t*>(io.caps + (cur.i - lane) * static_cast<uint64_t>(slots));
-                    for (uint32_t c = lane; c < 4u * row_b; c += 64u)  // 64 * row_b / 16 chunks
-                        *reinterpret_cast<u32x4*>(out + (c << 4)) = lds_ld<u32x4>(stage + (c << 4));  // (nontemporal: measured slower)
-                    if (lane < 16u)
-                        *reinterpret_cast<u32x4*>(io.match_id + (cur.i - lane) + 4u * lane) = lds_ld<u32x4>(ids + 16u * lane);
-                } else if (valid) {
-                    int32_t* cp = io.caps + i * static_cast<uint64_t>(slots);
-                    io.match_id[i] = line_result<TIER>(info, fin_lds, fin_g, regs, len, G, [&](int g, int32_t pb, int32_t pe) {
-                        cp[2 * g] = pb;
-                        cp[2 * g + 1] = pe;
-                    }, L.fin_unset);
-                }
-            }
+            constexpr RowFormat FMT = PACKED == 2 ? ROWS_U8 : PACKED == 1 ? ROWS_U16 : ROWS_DENSE;
+            store_tile<FMT, FMT == ROWS_U8>(io.rows, slots, i, lane, valid, full_tile, stage, L.stage_bytes, len, result, dev_flags);
         }
         if (WIDE) {
             // the per-line walk on the code units takes the flagged lines again (gx_kernels.hip: k_extract_flagged); a line left to
@@ -735,8 +648,8 @@ hipError_t launch_tile_p(const GxLds& lds, const TileIO& io, dim3 grid, dim3 blo
 }
 template <typename OFF, int KCH, int TIER, int MODE, bool WIDE = false>
 hipError_t launch_tile_t(const GxLds& lds, const TileIO& io, dim3 grid, dim3 block, hipStream_t stream) {
-    if (MODE != 0 && io.packed && io.narrow) return launch_tile_p<OFF, KCH, TIER, MODE, MODE != 0 ? 2 : 0, WIDE>(lds, io, grid, block, stream);
-    if (MODE != 0 && io.packed) return launch_tile_p<OFF, KCH, TIER, MODE, MODE != 0 ? 1 : 0, WIDE>(lds, io, grid, block, stream);
+    if (MODE != 0 && io.rows.format == ROWS_U8) return launch_tile_p<OFF, KCH, TIER, MODE, MODE != 0 ? 2 : 0, WIDE>(lds, io, grid, block, stream);
+    if (MODE != 0 && io.rows.format == ROWS_U16) return launch_tile_p<OFF, KCH, TIER, MODE, MODE != 0 ? 1 : 0, WIDE>(lds, io, grid, block, stream);
     return launch_tile_p<OFF, KCH, TIER, MODE, 0, WIDE>(lds, io, grid, block, stream);
 }
 // UTF-16 batches: the one variant with 13 staged chunks per lane (lds.stage_bytes <= 13 KB, at most 8 waves: plan_tile_layout)

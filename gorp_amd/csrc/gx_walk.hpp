@@ -314,59 +314,4 @@ __device__ __forceinline__ uint32_t steps16(const uint4& win, uint32_t mask, con
     return row;
 }
 
-// The result of one line, from the info word of the state its walk ended in.  info < 0: -1 (null) or -2-k
-// (ExtractionException), no groups.  info >= 0: byte offset of a final record in the record array (LDS address
-// fin_lds, or global pointer fin_g in the L2 tier; 16-byte aligned): u16 [begin tag, end tag] x max_groups, padded to a
-// multiple of four groups, then the extraction id; a tag being
-// 0 = unset, 1 = the line length, else the byte offset of a register column from the wave's dummy column.  Record 0
-// has every tag unset and serves the lines without a match, so the loads below are unconditional and independent:
-// all tags, then all registers, then the selects -- two LDS round trips per four groups instead of two per group.
-// (Round 5: the first twelve groups' tags, then all their registers, then the rows -- two trips for config 3's ten groups instead of six:
-// 0.778 against 0.755 ms, one device; the 36 values it holds at once cost more than the trips.  Not kept.)
-// emit(g, begin, end) is called for g = 0 .. G-1 with (-1, -1) for an unset group; returns the match id.
-// TIER_HOP (round 5): every tag names a column -- a register's, "the length" or "unset" (hop_unset: its offset; the lane has filled
-// both in) -- and a group with one end unset has both unset: two reads and one test per group, no selects on tag values.
-template <int TIER, typename EMIT>
-__device__ __forceinline__ int32_t line_result(int32_t info, uint32_t fin_lds, const uint8_t* fin_g, uint32_t regs, uint32_t len, int G,
-                                               EMIT emit, uint32_t hop_unset = 0u) {
-    const uint32_t rec = info >= 0 ? static_cast<uint32_t>(info) : 0u;
-    const uint32_t dummy_col = regs - 128u;
-    const uint32_t id_at = rec + 16u * static_cast<uint32_t>((G + 3) >> 2);
-    uint32_t id;
-    // (TIER_HOP keeps small final records in LDS: fin_g == nullptr says so -- wave-uniform)
-    const bool FIN_GLOBAL = TIER == TIER_L2 || TIER == TIER_RECG || (TIER == TIER_HOP && fin_g != nullptr);
-    if (FIN_GLOBAL) id = *reinterpret_cast<const uint16_t*>(fin_g + id_at);
-    else id = lds_ld<uint16_t>(fin_lds + id_at);
-    for (int g0 = 0; g0 < G; g0 += 4) {
-        u32x4 t;
-        if (FIN_GLOBAL) t = *reinterpret_cast<const u32x4*>(fin_g + rec + 4u * g0);
-        else t = lds_ld<u32x4>(fin_lds + rec + 4u * g0);
-        const uint32_t tw[4] = {t.x, t.y, t.z, t.w};  // one dword = (begin tag, end tag) of one group
-        uint32_t vb[4], ve[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            vb[q] = lds_ld<uint16_t>(dummy_col + (tw[q] & (TIER == TIER_HOP ? 0xFFFFu : 0xFF80u)));
-            ve[q] = lds_ld<uint16_t>(dummy_col + (TIER == TIER_HOP ? tw[q] >> 16 : (tw[q] >> 16) & 0xFF80u));
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (g0 + q < G) {
-                const uint32_t tb = tw[q] & 0xFFFFu, te = tw[q] >> 16;
-                int32_t pb, pe;
-                if (TIER == TIER_HOP) {
-                    const bool unset = tb == hop_unset;
-                    pb = unset ? -1 : static_cast<int32_t>(vb[q]);
-                    pe = unset ? -1 : static_cast<int32_t>(ve[q]);
-                } else {
-                    pb = tb == 1u ? static_cast<int32_t>(len) : static_cast<int32_t>(vb[q]);
-                    pe = te == 1u ? static_cast<int32_t>(len) : static_cast<int32_t>(ve[q]);
-                    if (tb == 0u || te == 0u) { pb = -1; pe = -1; }
-                }
-                emit(g0 + q, pb, pe);
-            }
-        }
-    }
-    return info >= 0 ? static_cast<int32_t>(static_cast<int16_t>(id)) : info;
-}
-
 }  // namespace gx

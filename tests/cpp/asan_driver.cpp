@@ -12,6 +12,7 @@
 #include "gx_dsl.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
+#include "gx_layout.hpp"
 #include "gx_slots.hpp"
 using namespace gx;
 
@@ -293,8 +294,37 @@ std::string check_launch_slots() {
     if (T.take(nullptr).slot != 0 || T.take(&keys[0]).slot != 1 || T.take(nullptr).slot != 0 || T.consume_broken(0)) return "null key";
     return "";
 }
+// The result-row formats (gx_layout.hpp): sizes as bench.py prints them, and encode / decode at the edges of every format.
+std::string check_row_formats() {
+    for (uint32_t g = 0; g <= 64; ++g) {
+        if (row_bytes(ROWS_U8, 2 * g) != 1 + 2 * g || row_bytes(ROWS_U16, 2 * g) != 2 + 4 * g || row_bytes(ROWS_DENSE, 2 * g) != 4 + 8 * g)
+            return "row_bytes";
+    }
+    const RowFormat fmts[3] = {ROWS_DENSE, ROWS_U16, ROWS_U8};
+    for (RowFormat f : fmts) {
+        for (int32_t v : {-1, 0, 253, 254, 255, 65533, 65534, 65535, 65536}) {
+            const RowUnit u = encode_offset(f, v);
+            const int32_t lim = row_max_offset(f);
+            const int32_t want = v < 0 ? -1 : v > lim ? lim : v;
+            if (u.unit > row_unset(f) || decode_offset(f, u.unit) != want || u.clipped != (v > lim ? 1u : 0u)) return "encode / decode of an offset";
+            if (v >= 0 && u.unit == row_unset(f)) return "an offset stored as unset";
+        }
+        for (int32_t id : {-2 - 126, -2, -1, 0, 1, 126}) {
+            if (decode_id(f, encode_id(f, id)) != id) return "encode / decode of a match id";
+        }
+    }
+    if (row_unset(ROWS_U8) != 0xFFu || row_unset(ROWS_U16) != 0xFFFFu || row_max_offset(ROWS_U8) != 254 || row_max_offset(ROWS_U16) != 65534)
+        return "the formats' limits";
+    if (row_format(false, true) != ROWS_DENSE || row_format(true, false) != ROWS_U16 || row_format(true, true) != ROWS_U8) return "row_format";
+    return "";
+}
 }  // namespace
 int main(int argc, char** argv) {
+    const std::string rows_wrong = check_row_formats();
+    if (!rows_wrong.empty()) {
+        printf("row formats: %s\n", rows_wrong.c_str());
+        return 1;
+    }
     const std::string slots_wrong = check_launch_slots();
     if (!slots_wrong.empty()) {
         printf("launch slots: %s\n", slots_wrong.c_str());

@@ -872,6 +872,45 @@ def test_compact_rows_at_the_16_bit_boundary(kernel):
     assert np.array_equal(um, omid) and np.array_equal(uc, np.where(big, 65534, ocaps))
 
 
+_BOUNDARY_KERNELS = [("readme", k) for k in (N.GX_KERNEL_TILES, N.GX_KERNEL_LANES, N.GX_KERNEL_SLICES, N.GX_KERNEL_PER_LINE)] + \
+                    [("syslog", k) for k in (N.GX_KERNEL_HOPS, N.GX_KERNEL_HOP_SLICES)]
+
+
+@pytest.mark.parametrize("compact,limit", [(1, 65534), (2, 254)])
+@pytest.mark.parametrize("definition,kernel", _BOUNDARY_KERNELS)
+def test_compact_rows_at_every_kernels_boundary(definition, kernel, compact, limit):
+    """Captures that end just below, at and above the largest offset u16 rows (65 534) and u8 rows (254) hold, through every
+    kernel -- the hop kernels on the 64-extraction syslog definition, where the hop tier is built: every kernel stores the
+    limit and counts it."""
+    ends = range(limit - 1, limit + 4) if compact == 1 else range(limit - 1, limit + 3)
+    if definition == "readme":
+        spec = W.readme3_definition()
+        head = "[1]: GET 5ms /"
+        lines = [head + "x" * (n - len(head)) for n in ends] + ["[2]: PUT 1ms /y"] * 70
+        data, offsets = lines_to_csr(lines)
+    else:
+        spec, meta = W.syslog_definition(64, seed=3)
+        parts = [W.syslog_lines(meta, 1, seed=70 + k, line_bytes=n, corrupt_frac=0.0) for k, n in enumerate(ends)]
+        parts.append(W.syslog_lines(meta, 70, seed=7, line_bytes=120, corrupt_frac=0.0))
+        data = np.concatenate([p[0] for p in parts])
+        lens = np.concatenate([np.diff(p[1].astype(np.int64)) for p in parts])
+        offsets = np.zeros(len(lens) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum(lens)
+    gorp, orc = Gorp.construct(spec), oracle_for(spec)
+    if definition == "syslog":
+        assert gorp.stat(14) > 0 and gorp.stat(19) > 0   # (the hop tier is built, and the hop slice kernel has a layout)
+    omid, ocaps = orc.extract_batch(data, offsets)
+    assert ocaps[:len(ends)].max(axis=1).tolist() == list(ends) and (omid[:len(ends)] >= 0).all()
+    # (the hop tile kernel stages lines of the hinted length; the long ones go to the per-line kernel behind it, as with TILES)
+    hint = 120 if kernel == N.GX_KERNEL_HOPS else 0
+    rows, over = gorp.extract_batch(data, offsets, compact=compact, kernel=kernel, line_bytes_hint=hint)
+    assert gorp.stat(25) == kernel   # (the kernel asked for is the one that ran: no silent fall-back to another)
+    cm, cc = G.unpack_rows(rows)
+    big = ocaps > limit
+    assert big.any() and over == int(big.sum())
+    assert np.array_equal(cm, omid) and np.array_equal(cc, np.where(big, limit, ocaps))
+
+
 def test_cooked_extraction_match_is_the_capture_regexp_alone(golden):
     """CookedExtraction.match(String) (the product of the ExtractionCooker seam): extraction k's regexp alone, against
     java.util.regex restated (oracle.jdk_matches) -- including lines the combined matcher would give to another
