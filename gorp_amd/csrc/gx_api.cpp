@@ -214,9 +214,9 @@ struct gx_handle {
     // the launch slots (gx_slots.hpp): their bookkeeping, under slot_mu, and their device resources
     LaunchSlots slots;
     std::mutex slot_mu;
-    DevMem<uint32_t> d_slots;   // [N] oversize flags, then [N] chunk counters of the lane kernel, then [N] "a line of this UTF-16
-                                // batch holds a unit above 0xFF" words
-    PinnedMem<uint32_t> h_broken;   // [N] the words of batches that promised their longest line (LaunchSlots::broken), mapped
+    DevMem<uint32_t> d_slots;   // [N] oversize flags, [N] counts behind them (announce_left_line; nobody reads these), then [N] chunk
+                                // counters of the lane kernel, then [N] "a line of this UTF-16 batch holds a unit above 0xFF" words
+    PinnedMem<uint32_t> h_broken;   // [N] the words of batches that promised their longest line, [N] counts (LaunchSlots::broken), mapped
     uint32_t* d_broken = nullptr;   // the device's address of the same words
     DevMem<uint32_t> d_steal[LaunchSlots::N];   // per slot, at its first tile launch: [2][GX_STEAL_MAX * GX_STEAL_STRIDE], the tile kernel's workgroup counters (GxBatch::steal)
     Event shared_event;   // the shared slot's "previous user is done"
@@ -245,6 +245,7 @@ struct gx_handle {
     Event gather_event;     // ... "the shard's kernel is done", recorded on the kernel's stream
     size_t peer_image_bytes = 0;          // table bytes that came from another device's copy (gx_create_on_devices; gx_stat(h, 30))
     std::atomic<int> last_kernel{0};      // GX_KERNEL_* of the most recent batch launch (gx_stat(h, 25))
+    std::atomic<uint32_t> last_fits{0}, last_limit{0};   // ... and its BatchPlan::fits and ::limit (gx_stat(h, 31) and (h, 32); 0: a kernel that leaves no line)
     // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls.  Used under
     // `mu` only, and every call that uses it ends with a stream synchronisation.
     GrowBuf scratch[8];
@@ -379,13 +380,15 @@ void upload(gx_handle* h) {
         put_image(h, h->d_img[id].get(), v->data(), v->size(), g_peer_src ? g_peer_src->d_img[id].get() : nullptr);
     }
     if (I.tile_ok || I.hop[0].ok || I.hop[1].ok) {
-        GX_HIP(hipMalloc(h->d_slots.out(), 3 * LaunchSlots::N * sizeof(uint32_t)));
-        GX_HIP(hipMemset(h->d_slots.get(), 0, 3 * LaunchSlots::N * sizeof(uint32_t)));
+        static_assert(GX_SLOT_WORDS == LaunchSlots::N, "announce_left_line counts GX_SLOT_WORDS behind a slot's flag word");
+        GX_HIP(hipMalloc(h->d_slots.out(), 4 * LaunchSlots::N * sizeof(uint32_t)));
+        GX_HIP(hipMemset(h->d_slots.get(), 0, 4 * LaunchSlots::N * sizeof(uint32_t)));
         GX_HIP(hipEventCreateWithFlags(h->shared_event.out(), hipEventDisableTiming));
 
-        GX_HIP(hipHostMalloc(h->h_broken.out(), LaunchSlots::N * sizeof(uint32_t), hipHostMallocMapped));
-        for (int q = 0; q < LaunchSlots::N; ++q) h->h_broken.get()[q] = 0;
+        GX_HIP(hipHostMalloc(h->h_broken.out(), 2 * LaunchSlots::N * sizeof(uint32_t), hipHostMallocMapped));
+        for (int q = 0; q < 2 * LaunchSlots::N; ++q) h->h_broken.get()[q] = 0;
         h->slots.broken = h->h_broken.get();
+        h->slots.broken_count = h->h_broken.get() + LaunchSlots::N;
         GX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_broken), h->h_broken.get(), 0));
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->num_cus = cus;
@@ -420,8 +423,8 @@ LaunchSlots::Use take_slot(gx_handle* h, GxBatch& b, hipStream_t stream) {
     const LaunchSlots::Use u = h->slots.take(stream);
     b.seq = u.seq;
     if (u.wait_shared) GX_HIP(hipStreamWaitEvent(stream, h->shared_event.get(), 0));
-    // a batch of this stream that promised its longest line, ran without a follow-up launch and met a longer line after all
-    // (no_sync batches: nobody has looked yet)
+    // batches of this stream that promised their longest line, ran without a follow-up launch and met a longer line after all
+    // (no_sync batches: nobody has looked yet; one that is still queued shows to a later call)
     if (h->slots.consume_broken(u.slot))
         throw GxError(GX_E_ARG, "an earlier no_sync batch on this stream held a line longer than its gx_batch_opts.max_line_bytes: that line was not "
                                 "processed (its result row is unwritten); this batch was not launched");
@@ -450,11 +453,12 @@ bool plan_followup(gx_handle* h, GxBatch& b, const LaunchSlots::Use& u, uint32_t
     }
     return true;
 }
-// Has a batch of this stream broken its promise since anybody looked?  (For the calls that wait for their batches themselves:
-// the word is final once the stream is idle.)  Marks it seen.
+// Has any batch of this stream's slot -- the caller's own or one before it -- broken its promise since the host last accounted for
+// the slot?  Accounts for all of them.  (For a call that waits for its batch itself and has no way to make good: the count is final
+// once the stream is idle.  A call that can make good asks LaunchSlots::finished, which tells its own break from an earlier one.)
 bool promise_broken_since(gx_handle* h, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(h->slot_mu);
-    return h->slots.consume_broken(h->slots.slot_of(stream));
+    return h->slots.consume_broken(h->slots.slot_of(stream)) != 0;
 }
 void done_slot(gx_handle* h, const LaunchSlots::Use& u, hipStream_t stream) {
     if (u.shared) GX_HIP(hipEventRecord(h->shared_event.get(), stream));
@@ -542,6 +546,7 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
     const uint8_t* at_global = p.global >= 0 ? static_cast<const uint8_t*>(h->d_img[p.global].get()) : nullptr;
     if (p.kernel == GX_KERNEL_PER_LINE || p.kernel == GX_KERNEL_SLICES) {   // (no slot: these take every line themselves)
         h->last_kernel = p.kernel;
+        h->last_fits = 0, h->last_limit = 0;
         if (p.kernel == GX_KERNEL_SLICES) GX_HIP(launch_extract_slices(h->dev, p.L, image, at_global, h->num_cus, b, stream));
         else GX_HIP(launch_extract_generic(h->dev, b, stream));
         return;
@@ -560,12 +565,12 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         if (launched) { launched->limit = p.limit; launched->by_length = p.by_length; }
         if (b.wide) {
             b.wide_flags = static_cast<uint8_t*>(flags->p);
-            b.wide_any = h->d_slots.get() + 2 * LaunchSlots::N + u.slot;
+            b.wide_any = h->d_slots.get() + 3 * LaunchSlots::N + u.slot;
         }
         // (the pool of chunks the launch's waves share: the slot's chunk counter -- the hop slice kernel, the lane kernel's sorted tiles)
         const bool chunks = p.kernel == GX_KERNEL_HOP_SLICES || (p.kernel == GX_KERNEL_LANES && p.L.sort_chunk);
         if (chunks) {
-            b.chunk_ctr = h->d_slots.get() + LaunchSlots::N + u.slot;
+            b.chunk_ctr = h->d_slots.get() + 2 * LaunchSlots::N + u.slot;
             b.chunk_base = h->slots.chunk_tickets[u.slot];
         }
         unsigned long long* stamps = nullptr;
@@ -573,6 +578,7 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         if (!b.wide) stamps = h->dev_stamps;
 #endif
         h->last_kernel = p.kernel;
+        h->last_fits = p.fits, h->last_limit = p.limit;
         if (p.kernel == GX_KERNEL_TILES || p.kernel == GX_KERNEL_HOPS) {
             e = launch_extract_tile(h->dev, p.L, image, at_global, h->num_cus, b, stream, stamps);
             if (e == hipSuccess) h->slots.steal_parity[u.slot] ^= 1u;
@@ -588,6 +594,40 @@ void launch_batch(gx_handle* h, GxBatch b, uint32_t line_bytes_hint, uint32_t ke
         if (e == hipSuccess) done_slot(h, u, stream);
     }
     GX_HIP(e);
+}
+
+// A batch on device buffers as the call that enqueued it leaves it for the call that waits for it.
+struct DeviceBatch {
+    GxBatch b{};
+    Launched done;
+    hipStream_t stream = nullptr;
+    bool enqueued = false;
+};
+
+// Waits for the batch, makes good for its own broken max_line_bytes promise (the follow-up launch it went without, now: the lines the
+// batch kernel left and nothing else, so *overflow counts every line once), and reports a promise that a batch BEFORE it on the
+// stream broke -- one that nobody waited for: its rows stay unwritten (LaunchSlots::finished tells the two apart).
+void finish_device_batch(gx_handle* h, DeviceBatch& d) {
+    GX_HIP(hipStreamSynchronize(d.stream));
+    LaunchSlots::Verdict v;
+    {
+        std::lock_guard<std::mutex> lock(h->slot_mu);
+        // (a launch of a kernel that leaves no line has no slot: the one its stream owns, for what came before it -- a stream that
+        // owns none has had no launch that could break a promise, and the shared slot's reports are not this call's to take)
+        const int slot = d.done.slot >= 0 ? d.done.slot : h->slots.slot_of(d.stream);
+        if (d.done.slot >= 0 || slot != LaunchSlots::N - 1) v = h->slots.finished(slot, d.done.seq, d.done.slot >= 0 && d.done.promised);
+        else v = LaunchSlots::Verdict{false, false};
+    }
+    if (v.mine) {
+        d.b.seq = d.done.seq;
+        d.b.oversize_flag = h->d_broken + d.done.slot;   // (it holds d.done.seq: the follow-up's waves stay)
+        PikeGate pike_gate(h, d.stream);
+        GX_HIP(launch_extract_oversize(h->dev, d.b, d.done.limit, d.done.by_length, d.stream));
+        GX_HIP(hipStreamSynchronize(d.stream));
+    }
+    if (v.earlier)
+        throw GxError(GX_E_ARG, "an earlier no_sync batch on this stream held a line longer than its gx_batch_opts.max_line_bytes: that line was not "
+                                "processed (its result row is unwritten); this batch itself is complete");
 }
 
 int finish_create(std::unique_ptr<gx_handle>& h, uint32_t flags, gx_handle** out) {
@@ -724,6 +764,8 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     case 24: return static_cast<int64_t>(h->slots.promises_broken.load());
     case 30: return static_cast<int64_t>(h->peer_image_bytes);   // table bytes copied from another handle's device (gx_create_on_devices)
     case 25: return h->last_kernel.load();
+    case 31: return h->last_fits.load();
+    case 32: return h->last_limit.load();
     case 26: return I.hop_reason;
     case 28: return static_cast<int64_t>(h->svc.enabled ? h->svc.launches : -1);
     case 27: { int64_t c = 0; for (auto& r : h->T.rules) c += r.pike ? 1 : 0; return c; }
@@ -1163,7 +1205,7 @@ static bool lines_are_uneven(const HostOffsets& off) {
 // gx_extract_batch, and gx_match_batch when `states` is given (final product-DFA state per line, -1 = dead: the
 // per-line generic kernel then, which is the one that keeps it)
 static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* offsets, uint64_t n, int32_t* match_id, int32_t* caps,
-                              int32_t* states, const gx_batch_opts* opts) {
+                              int32_t* states, const gx_batch_opts* opts, DeviceBatch* keep = nullptr) {
     return guarded([&]() -> int {
         if (!h || !offsets) return fail(GX_E_ARG, "gx_extract_batch: bad argument");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
@@ -1217,23 +1259,13 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
             }
             b.max_line_bytes = o.max_line_bytes;
             b.caller_no_sync = o.no_sync ? 1u : 0u;
-            Launched done;
-            launch_batch(h, b, hint, o.kernel, stream, uneven, &done);
-            if (!o.no_sync) {
-                GX_HIP(hipStreamSynchronize(stream));
-                if (done.promised && h->slots.word(done.slot) == done.seq) {
-                    // the promise did not hold: the lines the batch kernel left, now (and the word is clean for the stream's next launch)
-                    {
-                        std::lock_guard<std::mutex> lock(h->slot_mu);
-                        h->slots.mark_seen(done.slot, done.seq);
-                    }
-                    b.seq = done.seq;
-                    b.oversize_flag = h->d_broken + done.slot;
-                    PikeGate pike_gate(h, stream);
-                    GX_HIP(launch_extract_oversize(h->dev, b, done.limit, done.by_length, stream));
-                    GX_HIP(hipStreamSynchronize(stream));
-                }
-            }
+            DeviceBatch d;
+            d.stream = stream;
+            launch_batch(h, b, hint, o.kernel, stream, uneven, &d.done);
+            d.b = b;
+            d.enqueued = true;
+            if (keep) *keep = d;   // (gx_extract_batch_multi_device waits for its shards itself)
+            if (!o.no_sync) finish_device_batch(h, d);
             return GX_OK;
         }
         // host pointers: the chunked pipeline (gx_handle::host_slot)
@@ -1343,6 +1375,7 @@ int gx_extract_batch_multi_device(const gx_device_shard* shards, int32_t n_shard
         int first_rc = GX_OK;
         std::string first_msg;
         std::vector<hipStream_t> used(static_cast<size_t>(n_shards), nullptr);
+        std::vector<DeviceBatch> batches(static_cast<size_t>(n_shards));
         // enqueue everything first (asynchronous launches from this one thread), wait afterwards
         for (int32_t k = 0; k < n_shards; ++k) {
             const gx_device_shard& sh = shards[k];
@@ -1365,7 +1398,7 @@ int gx_extract_batch_multi_device(const gx_device_shard* shards, int32_t n_shard
             ok.no_sync = 1;
             ok.stream = stream;
             ok.overflow = sh.overflow;
-            const int rc = sh.n ? gx_extract_batch(h, sh.bytes, sh.offsets, sh.n, sh.match_id, sh.caps, &ok) : GX_OK;
+            const int rc = sh.n ? extract_batch_impl(h, sh.bytes, sh.offsets, sh.n, sh.match_id, sh.caps, nullptr, &ok, &batches[k]) : GX_OK;
             if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
         }
         if (!o.no_sync) {
@@ -1375,19 +1408,12 @@ int gx_extract_batch_multi_device(const gx_device_shard* shards, int32_t n_shard
                     if (first_rc == GX_OK) { first_rc = GX_E_DEVICE; first_msg = "gx_extract_batch_multi_device: a shard's stream failed"; }
                     continue;
                 }
-                // a shard whose max_line_bytes promise did not hold (its kernel left the longer lines' rows unwritten): the shard again,
-                // without the promise -- this call waits for its batches, so its results are right when it returns
-                if (o.max_line_bytes != 0 && shards[k].n && promise_broken_since(shards[k].handle, used[k])) {
-                    gx_batch_opts ok = o;
-                    ok.struct_size = sizeof(gx_batch_opts);
-                    ok.device_pointers = 1;
-                    ok.no_sync = 0;
-                    ok.max_line_bytes = 0;
-                    ok.stream = used[k];
-                    ok.overflow = nullptr;   // (the first run has counted)
-                    const int rc = gx_extract_batch(shards[k].handle, shards[k].bytes, shards[k].offsets, shards[k].n, shards[k].match_id, shards[k].caps, &ok);
-                    if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
-                }
+                // this call waits for its batches, so a shard whose max_line_bytes promise did not hold (its kernel left the longer lines'
+                // rows unwritten) is made good before it returns, as a synchronous gx_extract_batch is: the lines that were left, and
+                // only they, so that the shard's *overflow counts every line once
+                if (!batches[k].enqueued) continue;
+                const int rc = guarded([&]() -> int { finish_device_batch(shards[k].handle, batches[k]); return GX_OK; });
+                if (rc != GX_OK && first_rc == GX_OK) { first_rc = rc; first_msg = gx_last_error(); }
             }
         }
         if (first_rc != GX_OK) return fail(first_rc, first_msg);

@@ -66,7 +66,8 @@ struct GxBatch {
     // 0xFF = unset, an offset above 254 stored as 254 and counted in *overflow
     int32_t narrow;
     // lines the tile kernel cannot stage (longer than its staging area) are left to a follow-up launch of the
-    // per-line kernel: the tile kernel stores `seq` into *oversize_flag when it meets one
+    // per-line kernel: the tile kernel puts `seq` into *oversize_flag when it meets one (announce_left_line below); the word
+    // GX_SLOT_WORDS behind it counts the launches that did
     uint32_t* oversize_flag;
     uint32_t seq;
     // lane kernel, length-sorted mode: the launch's chunk counter (never reset: chunk = ticket - chunk_base; a launch draws
@@ -75,7 +76,8 @@ struct GxBatch {
     uint32_t chunk_base;
     // the host knows that no line of the batch is beyond what the chosen kernel stages (the one-line calls: the host has the line;
     // batches: the caller's promise, gx_batch_opts.max_line_bytes): no follow-up launch of the per-line kernel behind the batch
-    // kernel.  oversize_flag then points to a word in pinned HOST memory: a kernel that meets such a line after all says so there.
+    // kernel.  oversize_flag then points to a word in pinned HOST memory: a kernel that meets such a line after all says so there,
+    // and the host tells this launch's break from an earlier one's by the count behind the word (gx_slots.hpp).
     uint32_t no_followup;
     uint32_t max_line_bytes;   // the promise itself (0: none)
     uint32_t caller_no_sync;   // host side only: the caller asked for no synchronisation (gx_batch_opts.no_sync): a path that needs one refuses
@@ -88,6 +90,20 @@ struct GxBatch {
     uint8_t* wide_flags;
     uint32_t* wide_any;
 };
+
+// A handle's flag words come in blocks of GX_SLOT_WORDS (= LaunchSlots::N, one word per launch slot): a slot's flag word, and
+// GX_SLOT_WORDS words behind it the count of the slot's launches that have left a line.
+constexpr uint32_t GX_SLOT_WORDS = 32;
+
+#ifdef __HIPCC__
+// A batch kernel leaves a line to the follow-up launch (or, under a max_line_bytes promise, to nobody): `seq` into the launch's
+// flag word, and one more launch in the slot's count if this is the launch's first such line -- the launches of a slot run one
+// after the other, so the word holds another number until then.  System scope: the words may be in pinned host memory.
+__device__ inline void announce_left_line(uint32_t* flag, uint32_t seq) {
+    if (__hip_atomic_exchange(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != seq)
+        __hip_atomic_fetch_add(flag + GX_SLOT_WORDS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+#endif
 
 // More than 64 KiB of dynamic LDS needs the attribute, once per kernel (= per instantiation of this template) and
 // per device.

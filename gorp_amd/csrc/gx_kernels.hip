@@ -685,22 +685,25 @@ k_extract_hop_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, co
         const uint32_t idle = static_cast<uint32_t>(__popcll(__ballot(finished || !has_line)));
         const bool service = idle >= GX_HOP_SERVICE || !__any(has_line && !finished);
         if (service && finished) {
+            // (WIDE: the row of a line that holds a unit above 0xFF is the per-line walk's to write, and its clipped offsets are that
+            // walk's to count: a row stored here from the low bytes would count them a second time)
+            const bool rows_here = !(WIDE && line_wide);
             if (!match_only) lds_st<uint16_t>(regs - 128u, static_cast<uint16_t>(len));   // (the dummy column, free now: the tag "the line's length" names it)
             if (!match_only && L.fin_state_off != 0u) {
                 // (the row out of the final record of the state: one read, no info word first -- asked for when the line ended, behind
                 // the walk; a line that ended where it began is read now)
                 const uint8_t* recp = at_global + L.fin_state_off + static_cast<uint64_t>(row) * L.fin_state_rec;
                 if (!fin_here) F.load(recp, T.max_groups);
-                store_row<TIER_HOP>(out, i, 0, F.at(recp), regs, len, T.max_groups, L.fin_unset);
+                if (rows_here) store_row<TIER_HOP>(out, i, 0, F.at(recp), regs, len, T.max_groups, L.fin_unset);
                 fin_here = false;
             } else {
                 const int32_t hot_info = static_cast<int16_t>(lds_ld<uint16_t>(L.acc_tab + 2u * min(row, H.n_hot - 1u)));
                 int32_t info = hot_info >= 0 && !match_only ? hot_info * 16 : hot_info;
                 if (row >= H.n_hot) info = *reinterpret_cast<const int32_t*>(H.rows + (static_cast<uint64_t>(row) * H.row_bytes + H.info_off));
                 if (match_only) out.id(i, info);
-                else store_row<TIER_HOP>(out, i, info, fin_rec<TIER_HOP>(info, fin_lds, fin_g), regs, len, T.max_groups, L.fin_unset);
+                else if (rows_here) store_row<TIER_HOP>(out, i, info, fin_rec<TIER_HOP>(info, fin_lds, fin_g), regs, len, T.max_groups, L.fin_unset);
             }
-            if (WIDE) {   // (a flagged line's result is the per-line walk's to write again)
+            if (WIDE) {   // (a flagged line's result is the per-line walk's to write)
                 wide_flags[i] = line_wide ? 1 : 0;
                 if (line_wide) __hip_atomic_store(wide_any, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -746,7 +749,7 @@ k_extract_hop_slices(GxDev T, GxLds L, const uint8_t* __restrict__ lds_image, co
                 if (len64 > 65535) {
                     // positions are 16-bit in the register block: such a line is left to the follow-up launch of the per-line
                     // kernel (not walked here: its 96 capture registers would give every lane of this kernel a scratch frame)
-                    __hip_atomic_store(oversize_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    announce_left_line(oversize_flag, seq);
                 } else {
                     has_line = true;
                     len = static_cast<uint32_t>(len64);

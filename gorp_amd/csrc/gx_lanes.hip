@@ -167,7 +167,7 @@ k_extract_lanes(GxLds L, LanesIO io) {
             // With compact rows, so is a line longer than u16 rows can hold an offset of (a line of exactly 65 535 bytes can have
             // such an offset): the per-line kernel clips and counts it, and the rows here never clip.
             const bool oversize = valid && len64 > (PACKED ? static_cast<uint32_t>(row_max_offset(ROWS_U16)) : 65535u);
-            if (oversize) __hip_atomic_store(io.oversize_flag, io.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (oversize) announce_left_line(io.oversize_flag, io.seq);
             const uint32_t len = oversize ? 0u : static_cast<uint32_t>(len64);
             const uint8_t* line = data + o0;
 

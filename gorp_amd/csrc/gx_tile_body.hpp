@@ -536,7 +536,7 @@ k_extract_tile(GxLds L, TileIO io) {
         }
         if (cur.mode == 2) {
             // one line that does not fit the staging area: the per-line kernel takes it in a follow-up launch
-            if (lane == cur.a) __hip_atomic_store(io.oversize_flag, io.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (lane == cur.a) announce_left_line(io.oversize_flag, io.seq);
         } else if (MODE == 0 && HOP) {
             // ---- hot loop #1 alone on the match automaton's hop records: a state's info word is its first accepting extraction ----
             const uint32_t mrow = walk_hop<false>(H, L.rec_indexed >= L.sort_chunk, stage, L.m_start, start, end, true, L.m_dead, regs, hop_second);
@@ -585,6 +585,9 @@ k_extract_tile(GxLds L, TileIO io) {
                 }
             }
             GX_STAMP(2);
+            // (WIDE: a line that holds a unit above 0xFF is answered by the per-line walk on its units (k_extract_flagged), which also
+            // counts its clipped offsets: a null row here, so that the walk of its low bytes counts nothing a second time)
+            if (WIDE && wide_line) info = -1;
             const uint32_t len = end - start;
             if (HOP) lds_st<uint16_t>(regs - 128u, static_cast<uint16_t>(len));   // (the dummy column, free now: the tag "the line's length" names it -- gx_hop.cpp)
             const uint8_t* fin_g = GT && !(HOP && L.at != 0u) ? io.at_global + L.fin_tags : nullptr;

@@ -110,8 +110,13 @@ int32_t gx_max_groups(const gx_handle* h);
  * 16 = states that well-formed lines reach, 17 = states that have a chain, 18 / 19 = waves per workgroup of the tile kernel on
  * these tables / of the hop slice kernel, 20 = branching states whose dense row is in LDS too, 22 / 23 = states / states with
  * their records in LDS of the second hop image, built from the match automaton alone for match-only batches;
- * 24 = batches so far that broke their gx_batch_opts.max_line_bytes promise; 25 = the kernel the most recent batch ran on
- * (a GX_KERNEL_* value; 0: none yet); 26 = why capture batches have no hop tables (0: they have; 1: no fused automaton or no
+ * 24 = batches that broke their gx_batch_opts.max_line_bytes promise, as far as calls have made good for them or reported them
+ * (every such batch is counted once; it never moves while all promises hold); 25 = the kernel the most recent batch ran on
+ * (a GX_KERNEL_* value; 0: none yet); 31 / 32 = for that most recent batch launch, the longest line (code units in memory,
+ * terminator included) for which a max_line_bytes promise drops the follow-up launch, and the figure the kernel's own rule about
+ * the lines it leaves is stated in -- a wave's staging area in bytes for the tile kernels (a line stays when its units + the 0..15
+ * its address adds + 48 are within it), the longest line without its terminator for the lane and hop slice kernels (0 / 0: a
+ * kernel that leaves no line; read-only, for tests that must know where that edge lies); 26 = why capture batches have no hop tables (0: they have; 1: no fused automaton or no
  * capture regexps; 2: a step with capture programs other than one "register := position" -- groups that may match the empty string
  * write two registers in one step; 3: beyond a limit of the tier; 4: not built -- the dense rows fit LDS, or the caller named another
  * tier; 5: the tables leave no room for a wave); 27 = extractions whose capture automaton would be too large ahead of time and
@@ -166,7 +171,12 @@ typedef struct gx_batch_opts {
                                   the offsets without waiting (host pointers; device pointers without no_sync and without a hint),
                                   and assumes 1 elsewhere.  Batches with a mean length above 255 bytes are taken as uneven. */
     void*    overflow;         /* with compact_results: uint64_t counter that the call ADDS to (the caller zeroes it); a device
-                                  pointer with device_pointers, else a host pointer.  NULL: not counted. */
+                                  pointer with device_pointers, else a host pointer.  NULL: not counted.  Every clipped offset
+                                  is counted once -- with one known exception: a utf16 batch that goes through the narrowed copy
+                                  of its code units (tables other than dense rows in LDS or hop tables, or a kernel named in
+                                  `kernel`) counts the clipped offsets of a line that holds a unit above 0xFF twice (the byte
+                                  kernel's pass over the low bytes, then the per-line walk that writes the row); the rows are
+                                  right. */
     uint32_t max_line_bytes;   /* gx_extract_batch with device_pointers.  The caller's PROMISE: no line of the batch -- offsets[i+1] -
                                   offsets[i], terminator included -- is longer than this many code units (0: no promise).
                                   gx_split_lines_max reports it for free; a log shipper knows its own cap.  Without it every batch
@@ -175,8 +185,17 @@ typedef struct gx_batch_opts {
                                   and hop slice kernels); with it, and when it is within what the chosen kernel takes, that launch
                                   is dropped (1-2 % of a 10 M-line batch).  A promise that does not hold is detected, never
                                   silently wrong: without no_sync the call sees it when it synchronises, runs the follow-up then and
-                                  returns the right results; with no_sync the longer line's result row is left UNWRITTEN, and the next
-                                  gx_extract_batch on the same stream fails with GX_E_ARG (gx_stat(h, 24) counts such batches). */
+                                  returns the right results (gx_extract_batch_multi_device without no_sync does the same for every
+                                  shard: rows and *overflow as if no promise had been made); with no_sync the longer line's result
+                                  row is left UNWRITTEN and its offsets uncounted, and a later call on the same stream fails with
+                                  GX_E_ARG -- the next gx_extract_batch (or shard) submitted once that batch has run, which is then
+                                  not launched, or the first call that waits for a batch of its own behind it, whose own rows are
+                                  complete all the same; at the latest the first call made after the stream has drained.  One
+                                  error stands for every batch of the stream that broke its promise since the last one; each is
+                                  counted in gx_stat(h, 24), once.  The streams beyond a handle's 31st share one flag word: a break
+                                  on one of them is reported to whichever of them calls next, and a synchronous call of one
+                                  whose word another's later launch has overwritten is not made good but reported like a
+                                  no_sync batch (by an error whose text then wrongly calls some batch complete: check rows). */
 } gx_batch_opts;
 
 enum { GX_KERNEL_AUTO = 0, GX_KERNEL_TILES = 1, GX_KERNEL_SLICES = 2, GX_KERNEL_PER_LINE = 3, GX_KERNEL_LANES = 4,

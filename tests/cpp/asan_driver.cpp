@@ -264,8 +264,9 @@ std::string pinned_plans(const Tables& T, uint32_t flags) {
 // The launch slots' bookkeeping over stream keys, as gx_api.cpp drives it.  Returns what went wrong (empty: nothing).
 std::string check_launch_slots() {
     LaunchSlots S;
-    uint32_t broken[LaunchSlots::N] = {};
+    uint32_t broken[2 * LaunchSlots::N] = {};   // a word and, N behind it, a count per slot
     S.broken = broken;
+    S.broken_count = broken + LaunchSlots::N;
     int keys[40];
     // repeat calls from one key: the same slot, a new sequence number each time
     const LaunchSlots::Use a = S.take(&keys[0]), b = S.take(&keys[0]);
@@ -278,14 +279,29 @@ std::string check_launch_slots() {
         if (u.slot != LaunchSlots::N - 1 || !u.shared || u.wait_shared != (k > 31)) return "key " + std::to_string(k) + " did not share the last slot";
     }
     if (S.slot_of(&keys[30]) != 30 || S.slot_of(&keys[35]) != LaunchSlots::N - 1 || S.take(&keys[7]).slot != 7) return "slot_of";
-    // a changed broken word is reported once and counted once, then reads as seen
-    if (S.consume_broken(3)) return "an unchanged word reported";
-    broken[3] = 7;
-    if (!S.consume_broken(3) || S.consume_broken(3) || S.promises_broken.load() != 1) return "a changed word not reported exactly once";
-    // the synchronous fix-up marks its own sequence number seen: that word is not reported again
-    broken[5] = 9;
-    S.mark_seen(5, 9);
-    if (S.consume_broken(5) || S.promises_broken.load() != 2) return "a word marked seen reported";
+    // a launch that broke its promise (its number in the word, one more in the count) is reported once and counted once
+    if (S.consume_broken(3)) return "an unchanged count reported";
+    broken[3] = 7, broken[LaunchSlots::N + 3] = 1;
+    if (S.consume_broken(3) != 1 || S.consume_broken(3) || S.promises_broken.load() != 1) return "a break not reported exactly once";
+    // the synchronous fix-up finds its own sequence number in the word: accounted for, not reported again (tests/cpp/slots_test.cpp
+    // has the orders in which an earlier launch's break meets it)
+    broken[5] = 9, broken[LaunchSlots::N + 5] = 1;
+    const LaunchSlots::Verdict v = S.finished(5, 9, true);
+    if (!v.mine || v.earlier || S.consume_broken(5) || S.promises_broken.load() != 2) return "a launch's own break";
+    // words without counts: a changed word is reported once and counted once, then reads as seen; the synchronous fix-up marks its
+    // own sequence number seen, and that word is not reported again
+    LaunchSlots W;
+    uint32_t words[LaunchSlots::N] = {};
+    W.broken = words;
+    if (W.consume_broken(3)) return "an unchanged word reported";
+    words[3] = 7;
+    if (!W.consume_broken(3) || W.consume_broken(3) || W.promises_broken.load() != 1) return "a changed word not reported exactly once";
+    words[5] = 9;
+    W.mark_seen(5, 9);
+    if (W.consume_broken(5) || W.promises_broken.load() != 2) return "a word marked seen reported";
+    words[6] = 4;
+    const LaunchSlots::Verdict w = W.finished(6, 4, true);
+    if (!w.mine || w.earlier || W.finished(6, 4, true).mine || W.promises_broken.load() != 3) return "a launch's own break, words alone";
     // sequence numbers skip 0 when they wrap
     S.next_seq = 0xFFFFFFFFu;
     if (S.take(&keys[0]).seq != 0xFFFFFFFFu || S.take(&keys[0]).seq != 1) return "sequence numbers through 0";

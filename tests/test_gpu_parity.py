@@ -371,9 +371,10 @@ def test_table_tiers_agree_with_oracle(tier, monkeypatch):
 
 @pytest.mark.parametrize("flags", [0, N.GX_CREATE_TIER_L2, N.GX_CREATE_TIER_RECORDS])
 def test_config3_64_rules_parity(flags):
-    """BASELINE.json configs[2]: 64 extractions.  The dense rows (2.3 MB) do not fit LDS: by default the states become range
-    records that do (gx_stat 7 and 9 = 3), walked by the lane kernel; forced: dense rows in global memory / L2 under the
-    tile kernel.  The tile kernel on the records is checked as well."""
+    """BASELINE.json configs[2]: 64 extractions.  The dense rows (2.3 MB) do not fit LDS: the states become range records that do
+    (gx_stat 7 and 9 = 3) and, by default, the handle builds the hop tier beside them, whose tables capture batches take (the tile
+    kernel on hop tables; the records serve match-only batches); forced: dense rows in global memory / L2 under the tile kernel, or
+    the range records alone, walked by the lane kernel.  The tile kernel on the records is checked as well."""
     rules, meta = W.syslog_definition(64, seed=3)
     gorp, orc = Gorp.construct(rules, flags=flags), oracle_for(rules)
     assert gorp.stat(0) > 1000  # match-automaton states
