@@ -41,6 +41,7 @@ SYMBOLS = [
     "gx_match_batch", "gx_state_accepts", "gx_set_device", "gx_handle_device", "gx_extract_batch_multi",
     "gx_host_register", "gx_host_unregister", "gx_split_lines_max", "gx_extract_batch_multi_device",
     "gx_create_on_devices", "gx_gather_rows", "gx_gather_wait", "gx_release_scratch",
+    "gx_count_outcomes", "gx_select_lines", "gx_text_select",
 ]
 
 
@@ -202,6 +203,15 @@ def lib():
     L.gx_text_to_jsonl.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_to_jsonl.restype = C.c_int
+    L.gx_count_outcomes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(gx_batch_opts)]
+    L.gx_count_outcomes.restype = C.c_int
+    L.gx_select_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                  C.POINTER(gx_batch_opts)]
+    L.gx_select_lines.restype = C.c_int
+    L.gx_text_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                                 C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_select.restype = C.c_int
     L.gx_pack_results.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_pack_results.restype = C.c_int
     L.gx_unpack_results.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gx_batch_opts)]

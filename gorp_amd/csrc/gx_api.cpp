@@ -249,6 +249,11 @@ struct gx_handle {
     // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls.  Used under
     // `mu` only, and every call that uses it ends with a stream synchronisation.
     GrowBuf scratch[8];
+    // device workspace of gx_count_outcomes / gx_select_lines / gx_text_select (gx_device.hpp: SelectWs), kept between calls and used
+    // under `mu`.  A no_sync gx_select_lines leaves its copy pass reading it: the next user's stream waits for select_event first.
+    GrowBuf select_ws;
+    Event select_event;
+    bool select_pending = false;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
@@ -900,6 +905,51 @@ static const GxJsonl& jsonl_templates(gx_handle* h, const char* id_as) {
     return h->jsonl.emplace(key, std::move(ji)).first->second.dev;
 }
 
+// Steps 1 and 2 of the whole-file calls (gx_text_to_jsonl, gx_text_select), under h->mu: raw text on the device -> line offsets
+// (gx_split_lines semantics, 32-bit) -> the match-and-extract path, enqueued on `stream`.  Everything lives in the handle's scratch:
+// 2 split workspace, 3 offsets, 4 ids, 5 captures (dense rows; unset for a handle without capture regexps).  The line count is read
+// on the host: one synchronisation.  esc_bits / passthrough: launch_split_lines'.
+struct TextLines {
+    uint64_t n;
+    GxBatch b;
+    uint32_t mean_in;
+    bool no_control_bytes;   // with esc_bits: no byte of the text takes five more bytes inside a JSON string
+};
+static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, size_t slots, hipStream_t stream, uint16_t* esc_bits, int passthrough) {
+    // offsets for the guess "64 bytes or more per line"; a text with shorter lines is split a second time
+    void* ws_split = h->scratch[2].get(split_workspace_bytes(size));
+    uint64_t cap = size / 64 + 4096;
+    void* d_off2 = h->scratch[3].get((cap + 1) * 4);
+    uint64_t* d_n = nullptr;
+    uint64_t* d_max = nullptr;
+    GX_HIP(launch_split_lines(src, size, d_off2, 0, cap, nullptr, ws_split, &d_n, stream, &d_max, esc_bits, passthrough));
+    uint64_t n_and_max[3] = {0, 0, 0};   // (the line count, the longest line and the control-character word are neighbours in the workspace)
+    GX_HIP(hipMemcpyAsync(n_and_max, d_n, 24, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    TextLines t{};
+    const uint64_t n = t.n = n_and_max[0];
+    uint64_t longest = n_and_max[1];
+    t.no_control_bytes = n_and_max[2] == 0;
+    if (n > cap) {
+        d_off2 = h->scratch[3].get((n + 1) * 4);
+        GX_HIP(launch_split_lines(src, size, d_off2, 0, n, nullptr, ws_split, &d_n, stream));
+        longest = 0;   // (measured over the first `cap` lines only: no promise)
+    }
+    void* d_mid = h->scratch[4].get(n * 4 + 16);
+    void* d_caps = h->scratch[5].get(n * slots * 4 + 16);
+    GxBatch& b = t.b;
+    b.data = src; b.offsets = d_off2; b.n = n; b.match_id = static_cast<int32_t*>(d_mid);
+    b.caps = h->T.has_capture ? static_cast<int32_t*>(d_caps) : nullptr;
+    b.match_only = h->T.has_capture ? 0 : 1;
+    b.strip_eol = 1;
+    b.max_line_bytes = static_cast<uint32_t>(std::min<uint64_t>(longest, 0xFFFFFFFFull));   // (what the split pass saw: no follow-up launch)
+    t.mean_in = n ? static_cast<uint32_t>(std::min<uint64_t>((size + n - 1) / n, 1u << 20)) : 1u;
+    launch_batch(h, b, t.mean_in, GX_KERNEL_AUTO, stream);
+    if (!h->T.has_capture && n && slots) GX_HIP(hipMemsetAsync(d_caps, 0xFF, n * slots * 4, stream));
+    b.caps = static_cast<int32_t*>(d_caps);
+    return t;
+}
+
 int gx_results_to_jsonl(gx_handle* h, const uint8_t* bytes, const void* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps,
                         const char* id_as, uint8_t* out, uint64_t out_cap, uint64_t* out_size, uint64_t* line_out_offsets,
                         const gx_batch_opts* opts) {
@@ -981,40 +1031,15 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
             return fail(GX_E_ARG, "gx_text_to_jsonl: device text must be 16-byte aligned");
         }
-        // 1. lines: offsets for the guess "64 bytes or more per line"; a text with shorter lines is split a second time
-        void* ws_split = h->scratch[2].get(split_workspace_bytes(size));
-        uint64_t cap = size / 64 + 4096;
-        void* d_off2 = h->scratch[3].get((cap + 1) * 4);
-        uint64_t* d_n = nullptr;
-        uint64_t* d_max = nullptr;
+        // 1. lines, 2. the path
         // (the split pass also leaves a bit per byte that takes one more byte inside a JSON string, and says whether some byte takes five
         // more -- a control character --: without one, the sizes pass below does not read the text again)
         uint16_t* esc_bits = static_cast<uint16_t*>(h->scratch[7].get(((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
-        GX_HIP(launch_split_lines(src, size, d_off2, 0, cap, nullptr, ws_split, &d_n, stream, &d_max, esc_bits, o.utf8_passthrough ? 1 : 0));
-        uint64_t n_and_max[3] = {0, 0, 0};   // (the line count, the longest line and the control-character word are neighbours in the workspace)
-        GX_HIP(hipMemcpyAsync(n_and_max, d_n, 24, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipStreamSynchronize(stream));
-        const uint64_t n = n_and_max[0];
-        uint64_t longest = n_and_max[1];
-        const bool sizes_from_bits = n_and_max[2] == 0;
-        if (n > cap) {
-            d_off2 = h->scratch[3].get((n + 1) * 4);
-            GX_HIP(launch_split_lines(src, size, d_off2, 0, n, nullptr, ws_split, &d_n, stream));
-            longest = 0;   // (measured over the first `cap` lines only: no promise)
-        }
-        // 2. the path
-        void* d_mid = h->scratch[4].get(n * 4 + 16);
-        void* d_caps = h->scratch[5].get(n * slots * 4 + 16);
-        GxBatch b{};
-        b.data = src; b.offsets = d_off2; b.n = n; b.match_id = static_cast<int32_t*>(d_mid);
-        b.caps = h->T.has_capture ? static_cast<int32_t*>(d_caps) : nullptr;
-        b.match_only = h->T.has_capture ? 0 : 1;
-        b.strip_eol = 1;
-        b.max_line_bytes = static_cast<uint32_t>(std::min<uint64_t>(longest, 0xFFFFFFFFull));   // (what the split pass saw: no follow-up launch)
-        const uint32_t mean_in = n ? static_cast<uint32_t>(std::min<uint64_t>((size + n - 1) / n, 1u << 20)) : 1u;
-        launch_batch(h, b, mean_in, GX_KERNEL_AUTO, stream);
-        if (!h->T.has_capture && n && slots) GX_HIP(hipMemsetAsync(d_caps, 0xFF, n * slots * 4, stream));
-        b.caps = static_cast<int32_t*>(d_caps);
+        const TextLines tl = text_lines(h, src, size, slots, stream, esc_bits, o.utf8_passthrough ? 1 : 0);
+        const uint64_t n = tl.n;
+        const GxBatch& b = tl.b;
+        const uint32_t mean_in = tl.mean_in;
+        const bool sizes_from_bits = tl.no_control_bytes;
         void* d_counts = h->scratch[6].get(16);
         GX_HIP(launch_count_outcomes(b.match_id, n, static_cast<unsigned long long*>(d_counts), stream));
         // 3. the text
@@ -1040,6 +1065,184 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         const uint32_t mean_out = n ? static_cast<uint32_t>(std::min<uint64_t>((total + n - 1) / n, 1u << 20)) : 1u;
         GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, mean_out, loff, dst, ws_json, stream));
         if (!o.device_pointers && total) GX_HIP(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+        return GX_OK;
+    });
+}
+
+// The format of an id column as gx_batch_opts.compact_results names it, and the units of one of its rows.
+static RowFormat id_format(const gx_handle* h, const gx_batch_opts& o, uint32_t* row_units) {
+    if (o.compact_results > 2) throw GxError(GX_E_ARG, "gx_batch_opts.compact_results: 0, 1 or 2");
+    const RowFormat f = row_format(o.compact_results != 0, o.compact_results == 2);
+    *row_units = f == ROWS_DENSE ? 1u : 1u + 2u * static_cast<uint32_t>(h->T.max_groups);
+    return f;
+}
+
+// The flags pass and, with offsets, the two scans behind it, on the handle's workspace (under h->mu); then the host reads what
+// it must know before anything is written -- the number of kept lines and of kept code units, and whether a line was too long
+// to count -- and the histogram if the caller wants it: ONE small synchronisation of the stream, as gx_pack_results has
+// (before it the want mask goes to the device: a second small transfer per call, from pageable memory, which the runtime stages).
+// ids / offsets / want: device pointers, except want (host, uint8_t[2K + 1]; nullptr with offsets == nullptr: counts alone).
+struct Selected {
+    SelectWs w;
+    uint64_t lines = 0, units = 0;
+};
+static Selected select_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const uint8_t* want,
+                     uint64_t* counts, hipStream_t stream) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
+    if (h->select_pending) {
+        GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+        h->select_pending = false;
+    }
+    Selected s;
+    s.w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, offsets != nullptr)), n, K, offsets != nullptr);
+    if (offsets) GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
+    GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+    uint32_t status = 0;
+    if (offsets) {
+        GX_HIP(hipMemcpyAsync(&s.lines, s.w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&s.units, s.w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&status, s.w.status, 4, hipMemcpyDeviceToHost, stream));
+    }
+    if (counts) GX_HIP(hipMemcpyAsync(counts, s.w.counts, static_cast<size_t>(bins) * 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (status) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be selected");
+    return s;
+}
+
+int gx_count_outcomes(gx_handle* h, const void* ids, uint64_t n, uint64_t* counts, const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!h || !counts || (n && !ids)) return fail(GX_E_ARG, "gx_count_outcomes: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<> d_ids;
+        if (!o.device_pointers) {
+            const size_t bytes = static_cast<size_t>(n) * row_units * row_unit_bytes(fmt);
+            d_ids = dev_alloc(bytes);
+            if (bytes) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, bytes, hipMemcpyHostToDevice, stream));
+            ids = d_ids.get();
+        }
+        select_pass(h, ids, fmt, row_units, n, nullptr, false, nullptr, counts, stream);
+        return GX_OK;
+    });
+}
+
+int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const uint8_t* want,
+                    uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines,
+                    uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected, const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!h || !want || !offsets || !n_selected || !bytes_selected || (n && !ids)) return fail(GX_E_ARG, "gx_select_lines: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (n >= (1ull << 32)) return fail(GX_E_LIMIT, "gx_select_lines: line numbers are 32 bits; split batches of 4 G lines and more");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) { caps = nullptr; out_caps = nullptr; }
+        if (out_caps && slots && n && !caps) return fail(GX_E_ARG, "gx_select_lines: out_caps without caps");
+        if (!slots) out_caps = nullptr;
+        if (o.no_sync && !o.device_pointers) return fail(GX_E_ARG, "gx_select_lines: no_sync needs device pointers");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        const bool host = !o.device_pointers;
+        // host buffers are staged to the device and back; the passes are the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps, d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (host) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, "gx_select_lines: bytes is NULL");
+            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (out_caps && n) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        const Selected s = select_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, nullptr, stream);
+        *n_selected = s.lines;
+        *bytes_selected = s.units * unit;
+        if (!out_bytes && !out_index && !out_offsets && !out_ids && !out_caps) return GX_OK;   // size query
+        if ((out_index || out_offsets || out_ids || out_caps) && s.lines > cap_lines)
+            return fail(GX_E_LIMIT, "gx_select_lines: cap_lines is smaller than the selection (see *n_selected)");
+        if (out_bytes && s.units * unit > out_bytes_cap)
+            return fail(GX_E_LIMIT, "gx_select_lines: out_bytes_cap is smaller than the selected text (see *bytes_selected)");
+        SelectOut out{};
+        out.index = out_index; out.bytes = out_bytes; out.offsets = out_offsets;
+        void *dst_ids = out_ids, *dst_caps = out_caps;
+        if (host) {
+            if (out_index) { d_oindex = dev_alloc(s.lines * 4); out.index = static_cast<uint32_t*>(d_oindex.get()); }
+            if (out_bytes) { d_obytes = dev_alloc(s.units * unit); out.bytes = d_obytes.get(); }
+            if (out_offsets) { d_ooff = dev_alloc((s.lines + 1) * off_w); out.offsets = d_ooff.get(); }
+            if (out_ids) { d_oids = dev_alloc(s.lines * id_row); dst_ids = d_oids.get(); }
+            if (out_caps) { d_ocaps = dev_alloc(s.lines * slots * 4); dst_caps = d_ocaps.get(); }
+        }
+        if (out_ids) { out.col_src[0] = src_ids; out.col_dst[0] = dst_ids; out.col_width[0] = row_units; out.col_unit_bytes[0] = row_unit_bytes(fmt); }
+        if (out_caps) { out.col_src[1] = src_caps; out.col_dst[1] = dst_caps; out.col_width[1] = static_cast<uint32_t>(slots); out.col_unit_bytes[1] = 4; }
+        if (out.offsets && n == 0) GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
+        GX_HIP(launch_select_copy(out, src, src_off, o.offsets64 ? 1 : 0, o.utf16 ? 1 : 0, n, s.w, stream));
+        if (host) {
+            if (out_index && s.lines) GX_HIP(hipMemcpyAsync(out_index, out.index, s.lines * 4, hipMemcpyDeviceToHost, stream));
+            if (out_bytes && s.units) GX_HIP(hipMemcpyAsync(out_bytes, out.bytes, s.units * unit, hipMemcpyDeviceToHost, stream));
+            if (out_offsets) GX_HIP(hipMemcpyAsync(out_offsets, out.offsets, (s.lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
+            if (out_ids && s.lines) GX_HIP(hipMemcpyAsync(out_ids, dst_ids, s.lines * id_row, hipMemcpyDeviceToHost, stream));
+            if (out_caps && s.lines) GX_HIP(hipMemcpyAsync(out_caps, dst_caps, s.lines * slots * 4, hipMemcpyDeviceToHost, stream));
+        }
+        if (o.no_sync) {
+            // (the copy pass still reads the workspace: whoever uses it next waits for this)
+            if (!h->select_event) GX_HIP(hipEventCreateWithFlags(h->select_event.out(), hipEventDisableTiming));
+            GX_HIP(hipEventRecord(h->select_event.get(), stream));
+            h->select_pending = true;
+            return GX_OK;
+        }
+        GX_HIP(hipStreamSynchronize(stream));
+        return GX_OK;
+    });
+}
+
+int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap, uint64_t* out_size,
+                   uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!h || !want || !out_size || (size && !text)) return fail(GX_E_ARG, "gx_text_select: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_select: split texts of 4 GiB and more at a line boundary");
+        const gx_batch_opts o = read_opts(opts);
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text, d_out;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, "gx_text_select: device text must be 16-byte aligned");
+        }
+        // lines and the path as in gx_text_to_jsonl; then the selection's passes over the ids and offsets they left on the device
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0);
+        const Selected s = select_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, want, counts, stream);
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: gx_text_select: a line longer than the split pass reported");
+        *out_size = s.units;
+        if (n_lines) *n_lines = tl.n;
+        if (!out) return GX_OK;
+        if (s.units > out_cap) return fail(GX_E_LIMIT, "gx_text_select: out_cap is smaller than the selected text (see *out_size)");
+        SelectOut sel{};
+        sel.bytes = out;
+        if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(s.units); sel.bytes = d_out.get(); }
+        GX_HIP(launch_select_copy(sel, src, tl.b.offsets, 0, 0, tl.n, s.w, stream));
+        if (!o.device_pointers && s.units) GX_HIP(hipMemcpyAsync(out, sel.bytes, s.units, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });

@@ -201,4 +201,37 @@ hipError_t launch_unpack_results8(const uint8_t* rows, uint64_t n, int slots, in
 hipError_t launch_jsonl_write(const GxJsonl& tm, const GxBatch& b, int slots, int passthrough, uint32_t mean_in, uint32_t mean_out,
                               const uint64_t* line_out_off, uint8_t* out, void* workspace, hipStream_t stream);
 
+// Outcomes of a finished batch (gx_select.hip): the histogram over the outcome index (2K + 2 bins) and the selection of lines by
+// outcome.  The passes' device workspace, cut out of one allocation of select_workspace_bytes(n, K, select) bytes:
+struct SelectWs {
+    unsigned long long* counts;   // [2K + 2]
+    uint32_t* status;             // != 0: a line of 4 G code units or more
+    uint8_t* want;                // [2K + 1] the mask, put there by the caller of launch_select_flags
+    uint32_t* slab;               // the workgroups' histograms
+    uint64_t* block_sums;         // the scans'
+    uint64_t* idx_off;            // [n + 1] kept lines before line i; [n]: all of them
+    uint64_t* dst_off;            // [n + 1] kept code units before line i; [n]: all of them
+    uint32_t* klen;               // [n] the line's code units when it is kept, else 0
+    uint8_t* flags;               // [n] kept
+    size_t bytes;
+};
+SelectWs select_workspace(void* ws, uint64_t n, uint32_t K, bool select);   // select = false: counts, status and slab alone
+size_t select_workspace_bytes(uint64_t n, uint32_t K, bool select);
+// what the copy pass writes, each part optional (nullptr): the kept lines' numbers, their code units, their offsets (the width of the
+// input's), and up to two fixed-size columns (result rows; or match ids and dense capture rows)
+struct SelectOut {
+    uint32_t* index;
+    void* bytes;
+    void* offsets;
+    const void* col_src[2];
+    void* col_dst[2];
+    uint32_t col_width[2];        // units per line
+    uint32_t col_unit_bytes[2];   // 1, 2 or 4
+};
+// ids: int32[n] (ROWS_DENSE, row_units 1) or rows of row_units units whose first is the id.  offsets == nullptr: counts alone.
+hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64,
+                               const SelectWs& w, hipStream_t stream);
+hipError_t launch_select_copy(const SelectOut& o, const void* data, const void* offsets, int offsets64, int wide, uint64_t n, const SelectWs& w,
+                              hipStream_t stream);
+
 }  // namespace gx

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gx_device.hpp"
+#include "gx_scan.hpp"
 
 namespace gx {
 namespace {
@@ -1135,90 +1136,6 @@ __global__ void __launch_bounds__(256) k_jsonl_sizes_bits(JsonlTemplates tm, con
     }
 }
 
-// ---- exclusive scan u32[n] -> u64[n + 1] (out[n] = total): block sums, one-workgroup scan, block scans ----
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 8;
-constexpr uint64_t SCAN_BLOCK = static_cast<uint64_t>(SCAN_THREADS) * SCAN_ITEMS;
-
-__global__ void __launch_bounds__(SCAN_THREADS) k_scan_block_sums(const uint32_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ block_sums) {
-    __shared__ uint64_t wsum[SCAN_THREADS / 64];
-    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * SCAN_BLOCK;
-    uint64_t t = 0;
-#pragma unroll
-    for (int it = 0; it < SCAN_ITEMS; ++it) {
-        const uint64_t i = base + static_cast<uint64_t>(it) * SCAN_THREADS + threadIdx.x;
-        if (i < n) t += in[i];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(static_cast<unsigned long long>(t), d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t s = 0;
-        for (int w = 0; w < SCAN_THREADS / 64; ++w) s += wsum[w];
-        block_sums[blockIdx.x] = s;
-    }
-}
-
-// in place: block_sums[b] <- sum of the blocks before b; block_sums[nblocks] <- total
-__global__ void __launch_bounds__(1024) k_scan_of_sums(uint64_t* __restrict__ block_sums, uint64_t nblocks) {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += 1024) {
-        const uint64_t b = b0 + threadIdx.x;
-        const uint64_t v = b < nblocks ? block_sums[b] : 0;
-        uint64_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t o = __shfl_up(static_cast<unsigned long long>(inc), d);
-            if (lane >= static_cast<uint32_t>(d)) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint64_t wbase = 0;
-        for (uint32_t w = 0; w < wave; ++w) wbase += wsum[w];
-        const uint64_t c = carry;
-        if (b < nblocks) block_sums[b] = c + wbase + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = c + wbase + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[nblocks] = carry;
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS) k_scan_write(const uint32_t* __restrict__ in, uint64_t n, const uint64_t* __restrict__ block_sums,
-                                                             uint64_t nblocks, uint64_t* __restrict__ out) {
-    __shared__ uint64_t wsum[SCAN_THREADS / 64];
-    __shared__ uint64_t running;
-    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * SCAN_BLOCK;
-    if (threadIdx.x == 0) running = block_sums[blockIdx.x];
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = block_sums[nblocks];
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (int it = 0; it < SCAN_ITEMS; ++it) {
-        const uint64_t i = base + static_cast<uint64_t>(it) * SCAN_THREADS + threadIdx.x;
-        const uint64_t v = i < n ? in[i] : 0;
-        uint64_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t o = __shfl_up(static_cast<unsigned long long>(inc), d);
-            if (lane >= static_cast<uint32_t>(d)) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint64_t wbase = 0;
-        for (uint32_t w = 0; w < wave; ++w) wbase += wsum[w];
-        const uint64_t r0 = running;
-        if (i < n) out[i] = r0 + wbase + inc - v;
-        __syncthreads();
-        if (threadIdx.x == SCAN_THREADS - 1) running = r0 + wbase + inc;
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
 // ---- compact result rows for transport (the gather payload) ----
@@ -1329,8 +1246,7 @@ hipError_t launch_count_outcomes(const int32_t* match_id, uint64_t n, unsigned l
 // u32 split_at[n] (the split point itself) | u32 tile_flags[tiles] (1: no captured character of the tile takes an escape)
 static uint64_t jsonl_ws_sums(uint64_t n) { return (n * 4 + 15) & ~static_cast<uint64_t>(15); }
 static uint64_t jsonl_ws_split(uint64_t n) {
-    const uint64_t nblocks = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    return jsonl_ws_sums(n) + (((nblocks + 2) * 8 + 15) & ~static_cast<uint64_t>(15));
+    return jsonl_ws_sums(n) + scan_sums_bytes(n);
 }
 size_t jsonl_workspace_bytes(uint64_t n) { return static_cast<size_t>(jsonl_ws_split(n) + n * 8 + ((n + 63) >> 6) * 4 + 64); }
 
@@ -1389,7 +1305,6 @@ hipError_t launch_jsonl_tile(const JsonlTemplates& t, const JsonlTileCfg& cfg, c
 hipError_t launch_jsonl_sizes(const GxJsonl& tm, const GxBatch& b, int slots, int passthrough, uint32_t mean_in, uint64_t* line_out_off,
                               void* workspace, hipStream_t stream, const uint32_t* esc_bits) {
     if (b.n == 0) return hipMemsetAsync(line_out_off, 0, 8, stream);
-    const uint64_t nblocks = (b.n + SCAN_BLOCK - 1) / SCAN_BLOCK;
     uint32_t* sizes = static_cast<uint32_t*>(workspace);
     uint64_t* block_sums = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(workspace) + jsonl_ws_sums(b.n));
     uint32_t* split = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(workspace) + jsonl_ws_split(b.n));
@@ -1421,11 +1336,8 @@ hipError_t launch_jsonl_sizes(const GxJsonl& tm, const GxBatch& b, int slots, in
                                                          split, split_at, tile_flags, stream);
         if (e != hipSuccess) return e;
     }
-    if (nblocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(static_cast<unsigned>(nblocks)), dim3(SCAN_THREADS), 0, stream, sizes, b.n, block_sums);
-    hipLaunchKernelGGL(k_scan_of_sums, dim3(1), dim3(1024), 0, stream, block_sums, nblocks);
-    hipLaunchKernelGGL(k_scan_write, dim3(static_cast<unsigned>(nblocks)), dim3(SCAN_THREADS), 0, stream, sizes, b.n, block_sums, nblocks, line_out_off);
-    return hipGetLastError();
+    // the exclusive scan of the sizes (gx_scan.hpp)
+    return launch_exclusive_scan<uint32_t>(sizes, b.n, block_sums, line_out_off, stream);
 }
 
 // Pass 2: write the text.

@@ -598,6 +598,151 @@ class Gorp:
         o.utf16 = 1 if utf16 else 0
         _check(N.lib().gx_extract_batch(self._h.ptr, data_ptr, offsets_ptr, n, match_id_ptr, caps_ptr, C.byref(o)))
 
+    # -- outcomes of a finished batch (gx_count_outcomes / gx_select_lines / gx_text_select) --------------------------
+    @property
+    def num_extractions(self):
+        return N.lib().gx_num_extractions(self._h.ptr)
+
+    def outcome_index(self, match_id):
+        """The outcome index of a match id (include/gorp_hip.h): id in [0, K) -> id; -1 (no match) -> K; -2-k (exception of
+        extraction k) -> K + 1 + k; any other value -> 2K + 1.  Scalars or arrays."""
+        K = self.num_extractions
+        v = np.asarray(match_id, dtype=np.int64)
+        out = np.full(v.shape, 2 * K + 1, np.int64)
+        hit = (v >= 0) & (v < K)
+        out[hit] = v[hit]
+        out[v == -1] = K
+        exc = (v <= -2) & (v >= -1 - K)
+        out[exc] = K + 1 + (-2 - v[exc])
+        return int(out) if out.ndim == 0 else out
+
+    def want_mask(self, want):
+        """uint8[2K + 1] over the outcome index from a byte mask of that length, or from names: "unmatched", "exceptions" (of every
+        extraction), an extraction's name or index (its matched lines) -- one of them or a list."""
+        K = self.num_extractions
+        if isinstance(want, (bytes, bytearray, np.ndarray)):
+            mask = np.ascontiguousarray(np.frombuffer(want, dtype=np.uint8) if isinstance(want, (bytes, bytearray)) else want, dtype=np.uint8)
+            if mask.shape != (2 * K + 1,):
+                raise ValueError("want mask must have 2K + 1 = %d entries" % (2 * K + 1))
+            return mask
+        mask = np.zeros(2 * K + 1, np.uint8)
+        names = [x.getName() for x in self._extractions]
+        for w in ([want] if isinstance(want, (str, int, np.integer)) else list(want)):
+            if isinstance(w, (int, np.integer)) and not isinstance(w, bool):
+                if not 0 <= int(w) < K:
+                    raise ValueError("no extraction %d" % int(w))
+                mask[int(w)] = 1
+            elif w == "unmatched":
+                mask[K] = 1
+            elif w == "exceptions":
+                mask[K + 1:] = 1
+            elif w in names:
+                mask[names.index(w)] = 1
+            else:
+                raise ValueError("unknown outcome %r" % (w,))
+        return mask
+
+    def _ids_format(self, ids):
+        """compact_results value of an id column given as a numpy array: int32[n] -> 0, uint16 rows -> 1, uint8 rows -> 2."""
+        if ids.dtype == np.int32 and ids.ndim == 1:
+            return 0
+        if ids.dtype in (np.uint16, np.uint8) and ids.ndim == 2 and ids.shape[1] == 1 + 2 * self.max_groups:
+            return 1 if ids.dtype == np.uint16 else 2
+        raise TypeError("ids: int32[n], or result rows uint16|uint8[n, 1 + 2*max_groups]")
+
+    def count_outcomes(self, ids):
+        """gx_count_outcomes on a host array (int32 match ids, or u16 / u8 result rows): uint64[2K + 2] lines per outcome index."""
+        ids = np.ascontiguousarray(ids)
+        return self.count_outcomes_device(ids.ctypes.data if ids.size else None, len(ids), compact=self._ids_format(ids), device_pointers=False)
+
+    def count_outcomes_device(self, ids_ptr, n, compact=0, stream=None, device_pointers=True):
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        _check(N.lib().gx_count_outcomes(self._h.ptr, ids_ptr, n, counts.ctypes.data, C.byref(o)))
+        return counts
+
+    def select_lines(self, data, offsets, ids, rows=None, want="unmatched"):
+        """gx_select_lines on host buffers: the lines of the CSR batch (data uint8 or uint16 code units, offsets uint32|uint64)
+        whose outcome `want` names (want_mask), in input order.  ids: int32 match ids (rows: their dense capture rows, optional) or
+        u16 / u8 result rows.  Returns (index uint32, data, offsets) and, with dense rows given, (.., match_id, caps); with compact
+        rows as ids, (.., rows)."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        n = len(offsets) - 1
+        mask = self.want_mask(want)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = dict(offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False)
+        # one pass: no selection is larger than its input, so outputs of the input's size always do
+        total = int(offsets[n] - offsets[0]) if n else 0
+        index = np.zeros(n, np.uint32)
+        out = np.zeros(total, data.dtype)
+        out_off = np.zeros(n + 1, offsets.dtype)
+        out_ids = np.zeros(ids.shape, ids.dtype)
+        out_caps = None if caps is None else np.zeros((n, 2 * self.max_groups), np.int32)
+        # (numpy gives an empty array an address too: every output is asked for, whatever its size)
+        k, nbytes = self.select_lines_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), mask, out_index_ptr=index.ctypes.data,
+                                             out_data_ptr=out.ctypes.data, out_offsets_ptr=out_off.ctypes.data, out_ids_ptr=out_ids.ctypes.data,
+                                             out_caps_ptr=None if out_caps is None else out_caps.ctypes.data, cap_lines=n,
+                                             out_bytes_cap=total * data.itemsize, **args)
+        index, out, out_off, out_ids = index[:k], out[:nbytes // data.itemsize], out_off[:k + 1], out_ids[:k]
+        out_caps = None if out_caps is None else out_caps[:k]
+        if compact:
+            return index, out, out_off, out_ids
+        if caps is not None:
+            return index, out, out_off, out_ids, out_caps
+        return index, out, out_off
+
+    def select_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, want, out_index_ptr=None, out_data_ptr=None,
+                            out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0, offsets64=False,
+                            utf16=False, compact=0, stream=None, no_sync=False, device_pointers=True):
+        """gx_select_lines on device pointers (ints); every output optional, none at all only asks for the sizes.
+        Returns (lines selected, bytes selected).  GorpError with code GX_E_LIMIT when a capacity is too small."""
+        mask = self.want_mask(want)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        o.no_sync = 1 if no_sync else 0
+        k, nbytes = C.c_uint64(0), C.c_uint64(0)
+        _check(N.lib().gx_select_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, mask.ctypes.data, out_index_ptr, out_data_ptr,
+                                       out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, C.byref(k), C.byref(nbytes), C.byref(o)))
+        return k.value, nbytes.value
+
+    def text_select(self, text, want=("unmatched", "exceptions")):
+        """gx_text_select on a host buffer: raw log text -> the text of the lines whose outcome `want` names, terminators included.
+        Returns (selected text bytes, counts uint64[2K + 2], n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        ptr = raw.ctypes.data if raw.size else None
+        out = np.zeros(max(1, raw.size), np.uint8)   # (one pass: the selected text is no larger than the text)
+        size, counts, n_lines = self.text_select_device(ptr, raw.size, want, out.ctypes.data, raw.size, device_pointers=False)
+        return out[:size].tobytes(), counts, n_lines
+
+    def text_select_device(self, text_ptr, size, want, out_ptr, out_cap, stream=None, device_pointers=True):
+        """gx_text_select on device buffers (ints); out_ptr=None only asks for the sizes.  Returns (selected bytes, counts, n_lines)."""
+        mask = self.want_mask(want)
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        out_size, nl = C.c_uint64(0), C.c_uint64(0)
+        _check(N.lib().gx_text_select(self._h.ptr, text_ptr, size, mask.ctypes.data, out_ptr, out_cap, C.byref(out_size), counts.ctypes.data,
+                                      C.byref(nl), C.byref(o)))
+        return out_size.value, counts, nl.value
+
     def results(self, data, offsets, match_id, caps, safe=False):
         """Materialise ExtractionResult objects (or None) for a finished batch."""
         out = []

@@ -170,6 +170,55 @@ public:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         return out;
     }
+    // Outcomes of a finished batch (gx_count_outcomes / gx_select_lines / gx_text_select).  The outcome index over
+    // K = getExtractions().size(): extraction k -> k; no match -> K; exception of extraction k -> K + 1 + k; any other id -> 2K + 1.
+    // A want mask has 2K + 1 entries; want(unmatched, exceptions of every extraction, matched lines of these extractions) builds one.
+    using Want = std::vector<uint8_t>;
+    Want want(bool unmatched, bool exceptions, const std::vector<size_t>& extractions = {}) const {
+        const size_t K = extractions_.size();
+        Want w(2 * K + 1, 0);
+        w[K] = unmatched ? 1 : 0;
+        for (size_t k = 0; k < K; ++k) w[K + 1 + k] = exceptions ? 1 : 0;
+        for (size_t k : extractions) w.at(k < K ? k : w.size()) = 1;   // (std::out_of_range for an extraction that does not exist)
+        return w;
+    }
+    // lines per outcome index, 2K + 2 entries; ids in the format opts->compact_results names
+    std::vector<uint64_t> countOutcomes(const void* ids, uint64_t n, const gx_batch_opts* opts = nullptr) const {
+        std::vector<uint64_t> counts(2 * extractions_.size() + 2, 0);
+        int rc = gx_count_outcomes(h_, ids, n, counts.data(), opts);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return counts;
+    }
+    // The lines `want` names, in input order, as a new batch: their line numbers, bytes and offsets (host buffers, Latin-1, 32-bit
+    // offsets, int32 match ids; the C call takes every other layout)
+    struct Selection { std::vector<uint32_t> index; std::vector<uint8_t> bytes; std::vector<uint32_t> offsets; };
+    Selection selectLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const Want& want) const {
+        if (want.size() != 2 * extractions_.size() + 1) throw GorpError(GX_E_ARG, "selectLines: the want mask has 2K + 1 entries");
+        // one pass: no selection is larger than its input
+        const uint64_t total = offsets[n] - offsets[0];
+        uint64_t k = 0, size = 0;
+        Selection s{std::vector<uint32_t>(static_cast<size_t>(n) + 1), std::vector<uint8_t>(static_cast<size_t>(total) + 1), std::vector<uint32_t>(static_cast<size_t>(n) + 1)};
+        int rc = gx_select_lines(h_, bytes, offsets, n, match_id, nullptr, want.data(), s.index.data(), s.bytes.data(), s.offsets.data(), nullptr, nullptr, n, total,
+                                 &k, &size, nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        s.index.resize(static_cast<size_t>(k));
+        s.bytes.resize(static_cast<size_t>(size));
+        s.offsets.resize(static_cast<size_t>(k) + 1);
+        return s;
+    }
+    // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
+    // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
+    std::string textSelect(const std::string& text, const Want& want, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr) const {
+        if (want.size() != 2 * extractions_.size() + 1) throw GorpError(GX_E_ARG, "textSelect: the want mask has 2K + 1 entries");
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        uint64_t size = 0;
+        std::string out(text.size() + 1, '\0');   // (one pass: the selected text is no larger than the text)
+        int rc = gx_text_select(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), want.data(), reinterpret_cast<uint8_t*>(&out[0]), text.size(), &size,
+                                counts ? counts->data() : nullptr, nLines, nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        out.resize(static_cast<size_t>(size));
+        return out;
+    }
     int maxGroups() const { return gx_max_groups(h_); }
     gx_handle* handle() const { return h_; }
 

@@ -256,6 +256,54 @@ int gx_results_to_jsonl(gx_handle* h, const uint8_t* bytes, const void* offsets,
 int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const char* id_as, uint8_t* out, uint64_t out_cap,
                      uint64_t* out_size, uint64_t* n_lines, uint64_t* n_matched, uint64_t* n_exceptions, const gx_batch_opts* opts);
 
+/* Outcomes of a finished batch, on the device.  The reference has no counterpart: its caller sees every line's outcome in its own
+ * loop, "while ((line = readLine()) != null) { r = gorp.extract(line); ... }" (README.md:26,63-79) -- a null result is a line no
+ * extraction matched and can be kept aside, an ExtractionException is a definition bug and the line can be logged, a result goes to
+ * the sink of its extraction (the three outcomes: core/Gorp.java:159-186).  In bulk the outcomes are match ids in device memory;
+ * these calls count them and pick lines by them without a copy to the host.  They are named through the OUTCOME INDEX over
+ * K = gx_num_extractions(h):
+ *     id in [0, K)   ->  id            matched extraction id
+ *     id == -1       ->  K             no match
+ *     id == -2-k     ->  K + 1 + k     exception of extraction k (0 <= k < K)
+ *     anything else  ->  2K + 1        a row nobody wrote (a broken max_line_bytes promise): counted, never selected
+ * ids is read in the format opts->compact_results names: 0: int32_t match_id[n]; 1 / 2: the u16 / u8 result rows of
+ * 1 + 2 * gx_max_groups(h) units, whose first unit is the id.
+ *
+ * gx_count_outcomes: counts[2K + 2] (host) receives the number of lines per outcome index.  opts: device_pointers (ids on the
+ * device; else it is staged), stream, compact_results.  Synchronises the stream to deliver the counts. */
+int gx_count_outcomes(gx_handle* h, const void* ids, uint64_t n, uint64_t* counts, const gx_batch_opts* opts);
+
+/* gx_select_lines: the lines whose outcome index x has want[x] != 0 (want: uint8_t[2K + 1] on the host), in input order.  The
+ * batch is bytes / offsets / n as for gx_extract_batch (opts->offsets64, opts->utf16: two-byte code units, offsets in units), ids as
+ * above, caps the dense capture rows (compact_results 0 only, and only needed for out_caps).  Outputs, each optional (NULL):
+ *   out_index    uint32_t[cap_lines]: the kept lines' numbers in the input (n of 2^32 and more: GX_E_LIMIT);
+ *   out_bytes    out_bytes_cap bytes, and out_offsets, cap_lines + 1 entries of the input offsets' width: a new CSR batch -- every
+ *                kept line copied exactly as bytes[offsets[i] .. offsets[i+1]), terminator included if it had one; out_offsets
+ *                starts at 0, counts code units, and has *n_selected + 1 entries.  Directly an input of gx_extract_batch and
+ *                gx_results_to_jsonl;
+ *   out_ids      the kept lines' ids in the input's format: int32_t[cap_lines], or whole u16 / u8 result rows;
+ *   out_caps     compact_results 0: their dense capture rows, int32_t[cap_lines * 2 * gx_max_groups(h)].
+ * No output may overlap an input.  *n_selected and *bytes_selected (host; bytes, also with utf16) are always set;
+ * no output at all (all five NULL) only asks for them.  GX_E_LIMIT when cap_lines
+ * or out_bytes_cap is too small: the sizes are set and nothing has been written.  With opts->device_pointers every buffer except
+ * want and the two sizes is a device pointer; host buffers are staged to the device and back (there is no CPU path).  Three passes
+ * on opts->stream -- flags, scan, copy -- with ONE small synchronisation between scan and copy, where the host reads the two sizes
+ * (as gx_pack_results reads its counter; the want mask, 2K + 1 bytes, is copied to the device on every call); opts->no_sync (device pointers) then means: do not wait for the copy pass.  A line of
+ * 2^32 code units and more is refused (GX_E_LIMIT).  The device workspace stays on the handle, like gx_results_to_jsonl's. */
+int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                    const uint8_t* want, uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps,
+                    uint64_t cap_lines, uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected,
+                    const gx_batch_opts* opts);
+
+/* The whole-file form, next to gx_text_to_jsonl: raw text -> lines (gx_split_lines semantics) -> the match-and-extract path ->
+ * the selected lines' text, concatenated with their terminators.  With want marking outcome K and K+1 .. 2K these are exactly the
+ * lines gx_text_to_jsonl writes nothing for: the dead-letter file.  counts (optional, uint64_t[2K + 2], host) receives the
+ * histogram of the same pass, *n_lines (optional) the number of lines, *out_size the size of the selected text; out == NULL only
+ * asks for the sizes; GX_E_LIMIT when out_cap is too small.  opts: device_pointers (text -- 16-byte aligned -- and out on the
+ * device), stream.  Text of 4 GiB and more must be split by the caller (at a line boundary). */
+int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap,
+                   uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* Compact result rows for transport between GPUs (the gather of SURVEY.md section 8(e)): per line one int16 match id
  * followed by `slots` (= 2 * gx_max_groups) uint16 offsets, 0xFFFF = unset: 2 + 2*slots bytes instead of 4 + 4*slots.
  * Device buffers only.  *n_overflow (host) receives the number of offsets above 65534, which do not fit (they are
