@@ -41,7 +41,7 @@ SYMBOLS = [
     "gx_match_batch", "gx_state_accepts", "gx_set_device", "gx_handle_device", "gx_extract_batch_multi",
     "gx_host_register", "gx_host_unregister", "gx_split_lines_max", "gx_extract_batch_multi_device",
     "gx_create_on_devices", "gx_gather_rows", "gx_gather_wait", "gx_release_scratch",
-    "gx_count_outcomes", "gx_select_lines", "gx_text_select",
+    "gx_count_outcomes", "gx_select_lines", "gx_text_select", "gx_utf8_to_utf16",
 ]
 
 
@@ -62,6 +62,8 @@ class gx_batch_opts(C.Structure):
         ("uneven_lines", C.c_uint32),
         ("overflow", C.c_void_p),
         ("max_line_bytes", C.c_uint32),
+        ("utf8", C.c_uint32),
+        ("utf8_line_flags", C.c_void_p),
     ]
 
 
@@ -212,6 +214,9 @@ def lib():
     L.gx_text_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
                                  C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_select.restype = C.c_int
+    L.gx_utf8_to_utf16.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                   C.POINTER(gx_batch_opts)]
+    L.gx_utf8_to_utf16.restype = C.c_int
     L.gx_pack_results.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_pack_results.restype = C.c_int
     L.gx_unpack_results.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gx_batch_opts)]

@@ -245,6 +245,7 @@ struct gx_handle {
     Event gather_event;     // ... "the shard's kernel is done", recorded on the kernel's stream
     size_t peer_image_bytes = 0;          // table bytes that came from another device's copy (gx_create_on_devices; gx_stat(h, 30))
     std::atomic<int> last_kernel{0};      // GX_KERNEL_* of the most recent batch launch (gx_stat(h, 25))
+    std::atomic<uint64_t> last_utf8_lines{0}, last_utf8_units{0};   // the most recent utf8 batch: lines walked again, units made (gx_stat(h, 33) and (h, 34))
     std::atomic<uint32_t> last_fits{0}, last_limit{0};   // ... and its BatchPlan::fits and ::limit (gx_stat(h, 31) and (h, 32); 0: a kernel that leaves no line)
     // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls.  Used under
     // `mu` only, and every call that uses it ends with a stream synchronisation.
@@ -635,6 +636,52 @@ void finish_device_batch(gx_handle* h, DeviceBatch& d) {
                                 "processed (its result row is unwritten); this batch itself is complete");
 }
 
+// gx_batch_opts.utf8: the fix-up behind a byte batch whose lines are UTF-8 (gx_utf8.hip).  The byte kernels' rows are right for every
+// ASCII-only line; the lines that hold a byte >= 0x80 (line_flags: the caller's, from gx_split_lines; nullptr: a sweep finds them) are
+// transcoded to the UTF-16 code units of the String Java would see, walked again on those (k_extract_listed, the per-line walk over the list of flagged lines the count pass leaves, overwrites their rows),
+// and -- mode 1 -- their capture offsets taken back to bytes.  ONE synchronisation, where the host reads "flagged lines, their units":
+// it sizes the units' memory, and with no flagged line everything behind it is skipped.  Call when nothing else will write the rows
+// any more (behind finish_device_batch).
+void utf8_fixup(gx_handle* h, const GxBatch& b, uint32_t mode, const uint8_t* line_flags, hipStream_t stream) {
+    h->last_utf8_lines = 0;
+    h->last_utf8_units = 0;
+    if (b.n == 0) return;
+    const uint8_t* data = static_cast<const uint8_t*>(b.data);
+    PoolBuffer ws_buf(h, utf8_workspace_bytes(b.n), stream);
+    const Utf8Ws w = utf8_workspace(ws_buf.p, b.n);
+    const uint8_t* flags = line_flags;
+    if (!flags) {
+        GX_HIP(launch_utf8_flags(data, b.offsets, b.offsets64, b.n, w.flags, stream));
+        flags = w.flags;
+    }
+    GX_HIP(launch_utf8_count(data, b.offsets, b.offsets64, b.n, flags, w, stream));
+    uint64_t units = 0;
+    uint64_t lines_status[2] = {0, 0};   // (neighbours in the workspace)
+    GX_HIP(hipMemcpyAsync(&units, w.unit_off + b.n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(lines_status, w.flagged, 16, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (lines_status[1] & 0xFFFFFFFFull) throw GxError(GX_E_LIMIT, "gx_batch_opts.utf8: a line of 4 G code units or more");
+    h->last_utf8_lines = lines_status[0];
+    h->last_utf8_units = units;
+    if (lines_status[0] == 0) return;
+    const bool to_bytes = mode == 1 && !b.match_only;
+    const size_t units_bytes = (static_cast<size_t>(units) * 2 + 64 + 15) & ~static_cast<size_t>(15);
+    PoolBuffer units_buf(h, units_bytes + (to_bytes ? static_cast<size_t>(units) * 4 + 16 : 0), stream);
+    uint16_t* d_units = static_cast<uint16_t*>(units_buf.p);
+    uint32_t* d_unit_byte = to_bytes ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(units_buf.p) + units_bytes) : nullptr;
+    GX_HIP(launch_utf8_write(data, b.offsets, b.offsets64, b.n, flags, w.unit_off, d_units, d_unit_byte, stream));
+    GxBatch ub = b;   // the same lines and rows, on the units
+    ub.data = d_units;
+    ub.offsets = w.unit_off;
+    ub.offsets64 = 1;
+    ub.wide = 1;
+    {
+        PikeGate pike_gate(h, stream);
+        GX_HIP(launch_extract_listed(h->dev, ub, w.list, lines_status[0], stream));   // (a lane per flagged line: few among many fill their waves)
+    }
+    if (to_bytes) GX_HIP(launch_utf8_offsets_to_bytes(h->dev, b, flags, w.unit_off, d_unit_byte, stream));
+}
+
 int finish_create(std::unique_ptr<gx_handle>& h, uint32_t flags, gx_handle** out) {
     h->create_flags = flags;
     h->blob = pack_blob(h->T);
@@ -653,6 +700,7 @@ struct SplitScratch {
     GrowBuf ws[64];
 };
 SplitScratch& g_split_scratch = *new SplitScratch;   // (never destroyed: the HIP runtime may be gone when static destructors run)
+SplitScratch& g_utf8_scratch = *new SplitScratch;    // gx_utf8_to_utf16's, kept the same way (gx_device.hpp: Utf8Ws)
 
 // Accepts the current gx_batch_opts and every earlier, shorter layout of it (struct_size says which).
 gx_batch_opts read_opts(const gx_batch_opts* opts) {
@@ -662,6 +710,10 @@ gx_batch_opts read_opts(const gx_batch_opts* opts) {
     if (opts->struct_size < v1 || opts->struct_size > sizeof(gx_batch_opts) || (opts->struct_size & 3u))
         throw GxError(GX_E_ARG, "gx_batch_opts.struct_size mismatch");
     memcpy(&o, opts, opts->struct_size);
+    // utf8 lies in what was the tail padding of the layout that ended with max_line_bytes: a caller compiled against that layout
+    // copies those four bytes in uninitialised
+    if (opts->struct_size <= offsetof(gx_batch_opts, utf8) + sizeof(uint32_t)) { o.utf8 = 0; o.utf8_line_flags = nullptr; }
+    if (o.utf8 > 2) throw GxError(GX_E_ARG, "gx_batch_opts.utf8: 0, 1 (capture offsets in bytes) or 2 (in UTF-16 code units)");
     return o;
 }
 
@@ -680,6 +732,10 @@ int gx_release_scratch(int device) {
     if (device >= 0 && device < 64) {
         std::lock_guard<std::mutex> lock(g_split_scratch.mu[device]);
         g_split_scratch.ws[device] = {};
+    }
+    if (device >= 0 && device < 64) {
+        std::lock_guard<std::mutex> lock(g_utf8_scratch.mu[device]);
+        g_utf8_scratch.ws[device] = {};
     }
     return GX_OK;
 }
@@ -771,6 +827,8 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     case 25: return h->last_kernel.load();
     case 31: return h->last_fits.load();
     case 32: return h->last_limit.load();
+    case 33: return static_cast<int64_t>(h->last_utf8_lines.load());
+    case 34: return static_cast<int64_t>(h->last_utf8_units.load());
     case 26: return I.hop_reason;
     case 28: return static_cast<int64_t>(h->svc.enabled ? h->svc.launches : -1);
     case 27: { int64_t c = 0; for (auto& r : h->T.rules) c += r.pike ? 1 : 0; return c; }
@@ -832,6 +890,70 @@ int gx_split_lines_max(const uint8_t* bytes, uint64_t size, void* offsets, uint6
             GX_HIP(hipMemcpy(offsets, d_off.get(), (n + 1) * off_w, hipMemcpyDeviceToHost));
             if (line_flags && n) GX_HIP(hipMemcpy(line_flags, d_flags.get(), n, hipMemcpyDeviceToHost));
         }
+        return GX_OK;
+    });
+}
+
+int gx_utf8_to_utf16(const uint8_t* bytes, const void* offsets, uint64_t n, uint16_t* units, uint64_t units_cap, void* unit_offsets,
+                     uint64_t* n_units, const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!offsets || !n_units || (units && !unit_offsets)) return fail(GX_E_ARG, "gx_utf8_to_utf16: bad argument");
+        *n_units = 0;
+        const gx_batch_opts o = read_opts(opts);
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+            throw GxError(GX_E_DEVICE, "no HIP device available (libgorp_hip needs a gfx950 GPU; there is no CPU fallback)");
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4;
+        int dev = 0;
+        GX_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64) return fail(GX_E_DEVICE, "gx_utf8_to_utf16: device ordinal beyond 63");
+        std::lock_guard<std::mutex> ws_lock(g_utf8_scratch.mu[dev]);
+        const Utf8Ws w = utf8_workspace(g_utf8_scratch.ws[dev].get(utf8_workspace_bytes(n)), n);
+        const bool host = !o.device_pointers;
+        DevMem<uint8_t> d_bytes;
+        DevMem<> d_off, d_units, d_uoff;
+        const uint8_t* data = bytes;
+        const void* src_off = offsets;
+        if (host) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const uint64_t first = off[0], total = off[n] - first;
+            if (total && !bytes) return fail(GX_E_ARG, "gx_utf8_to_utf16: bytes is NULL");
+            d_bytes = dev_alloc<uint8_t>(total + 32);
+            d_off = dev_alloc((n + 1) * off_w);
+            if (total) GX_HIP(hipMemcpyAsync(d_bytes.get() + 16, bytes + first, total, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            // (line i at data + offsets[i], as in the caller's buffer; the base may lie below the allocation: made as an integer)
+            data = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_bytes.get()) + 16u - static_cast<uintptr_t>(first));
+            src_off = d_off.get();
+        }
+        // the count / scan / write passes of the utf8 fix-up with every line flagged
+        GX_HIP(launch_utf8_count(data, src_off, o.offsets64 ? 1 : 0, n, nullptr, w, stream));
+        uint64_t total_units = 0;
+        uint64_t lines_status[2] = {0, 0};
+        GX_HIP(hipMemcpyAsync(&total_units, w.unit_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(lines_status, w.flagged, 16, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+        *n_units = total_units;
+        if (lines_status[1] & 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_utf8_to_utf16: a line of 4 G code units or more");
+        if (!o.offsets64 && total_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_utf8_to_utf16: 4 G code units and more need offsets64");
+        if (!units) return GX_OK;   // size query
+        if (total_units > units_cap) return fail(GX_E_LIMIT, "gx_utf8_to_utf16: units_cap is smaller than the text (see *n_units)");
+        uint16_t* dst = units;
+        void* dst_off = unit_offsets;
+        if (host) {
+            d_units = dev_alloc(total_units * 2);
+            dst = static_cast<uint16_t*>(d_units.get());
+            if (!o.offsets64) { d_uoff = dev_alloc((n + 1) * 4); dst_off = d_uoff.get(); }
+        }
+        GX_HIP(launch_utf8_write(data, src_off, o.offsets64 ? 1 : 0, n, nullptr, w.unit_off, dst, nullptr, stream));
+        if (o.offsets64) GX_HIP(hipMemcpyAsync(unit_offsets, w.unit_off, (n + 1) * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+        else GX_HIP(launch_utf8_offsets32(w.unit_off, n, static_cast<uint32_t*>(dst_off), stream));
+        if (host) {
+            if (total_units) GX_HIP(hipMemcpyAsync(units, dst, total_units * 2, hipMemcpyDeviceToHost, stream));
+            if (!o.offsets64) GX_HIP(hipMemcpyAsync(unit_offsets, dst_off, (n + 1) * 4, hipMemcpyDeviceToHost, stream));
+        }
+        GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });
 }
@@ -915,14 +1037,22 @@ struct TextLines {
     uint32_t mean_in;
     bool no_control_bytes;   // with esc_bits: no byte of the text takes five more bytes inside a JSON string
 };
-static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, size_t slots, hipStream_t stream, uint16_t* esc_bits, int passthrough) {
+// utf8 (gx_batch_opts.utf8 = 1; not with esc_bits: the split pass's first kernel makes EITHER the escape bits or the masks of the bytes
+// >= 0x80 that the line flags come from -- launch_split_lines refuses both at once -- so a utf8 text's JSON sizes are taken from the text
+// itself, as gx_results_to_jsonl takes them): the text is UTF-8 -- the split pass leaves its line flags, and the lines that are not
+// ASCII are walked again as Strings behind the batch kernel (utf8_fixup), their capture offsets back in bytes for the passes that follow.
+static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, size_t slots, hipStream_t stream, uint16_t* esc_bits, int passthrough,
+                            bool utf8 = false) {
     // offsets for the guess "64 bytes or more per line"; a text with shorter lines is split a second time
-    void* ws_split = h->scratch[2].get(split_workspace_bytes(size));
+    void* ws_split = h->scratch[2].get(split_workspace_bytes(size, utf8));
     uint64_t cap = size / 64 + 4096;
     void* d_off2 = h->scratch[3].get((cap + 1) * 4);
     uint64_t* d_n = nullptr;
     uint64_t* d_max = nullptr;
-    GX_HIP(launch_split_lines(src, size, d_off2, 0, cap, nullptr, ws_split, &d_n, stream, &d_max, esc_bits, passthrough));
+    std::optional<PoolBuffer> line_flags;
+    if (utf8) line_flags.emplace(h, cap + 64, stream);
+    uint8_t* d_flags = utf8 ? static_cast<uint8_t*>(line_flags->p) : nullptr;
+    GX_HIP(launch_split_lines(src, size, d_off2, 0, cap, d_flags, ws_split, &d_n, stream, &d_max, esc_bits, passthrough));
     uint64_t n_and_max[3] = {0, 0, 0};   // (the line count, the longest line and the control-character word are neighbours in the workspace)
     GX_HIP(hipMemcpyAsync(n_and_max, d_n, 24, hipMemcpyDeviceToHost, stream));
     GX_HIP(hipStreamSynchronize(stream));
@@ -932,7 +1062,11 @@ static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, siz
     t.no_control_bytes = n_and_max[2] == 0;
     if (n > cap) {
         d_off2 = h->scratch[3].get((n + 1) * 4);
-        GX_HIP(launch_split_lines(src, size, d_off2, 0, n, nullptr, ws_split, &d_n, stream));
+        if (utf8) {
+            line_flags.emplace(h, n + 64, stream);
+            d_flags = static_cast<uint8_t*>(line_flags->p);
+        }
+        GX_HIP(launch_split_lines(src, size, d_off2, 0, n, d_flags, ws_split, &d_n, stream));
         longest = 0;   // (measured over the first `cap` lines only: no promise)
     }
     void* d_mid = h->scratch[4].get(n * 4 + 16);
@@ -945,6 +1079,7 @@ static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, siz
     b.max_line_bytes = static_cast<uint32_t>(std::min<uint64_t>(longest, 0xFFFFFFFFull));   // (what the split pass saw: no follow-up launch)
     t.mean_in = n ? static_cast<uint32_t>(std::min<uint64_t>((size + n - 1) / n, 1u << 20)) : 1u;
     launch_batch(h, b, t.mean_in, GX_KERNEL_AUTO, stream);
+    if (utf8) utf8_fixup(h, b, 1, d_flags, stream);
     if (!h->T.has_capture && n && slots) GX_HIP(hipMemsetAsync(d_caps, 0xFF, n * slots * 4, stream));
     b.caps = static_cast<int32_t*>(d_caps);
     return t;
@@ -1016,6 +1151,7 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_to_jsonl: split texts of 4 GiB and more at a line boundary");
         const gx_batch_opts o = read_opts(opts);
+        if (o.utf8 == 2) return fail(GX_E_ARG, "gx_text_to_jsonl: gx_batch_opts.utf8 = 1 (the text is written from its bytes)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         if (slots > 128) return fail(GX_E_LIMIT, "gx_text_to_jsonl: more than 64 capture groups per extraction");
         GX_HIP(hipSetDevice(h->device));
@@ -1034,18 +1170,20 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         // 1. lines, 2. the path
         // (the split pass also leaves a bit per byte that takes one more byte inside a JSON string, and says whether some byte takes five
         // more -- a control character --: without one, the sizes pass below does not read the text again)
-        uint16_t* esc_bits = static_cast<uint16_t*>(h->scratch[7].get(((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
-        const TextLines tl = text_lines(h, src, size, slots, stream, esc_bits, o.utf8_passthrough ? 1 : 0);
+        // (utf8: the split pass makes line flags in their place)
+        uint16_t* esc_bits = o.utf8 ? nullptr : static_cast<uint16_t*>(h->scratch[7].get(((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
+        const int passthrough = (o.utf8_passthrough || o.utf8) ? 1 : 0;   // (utf8 implies it)
+        const TextLines tl = text_lines(h, src, size, slots, stream, esc_bits, passthrough, o.utf8 != 0);
         const uint64_t n = tl.n;
         const GxBatch& b = tl.b;
         const uint32_t mean_in = tl.mean_in;
-        const bool sizes_from_bits = tl.no_control_bytes;
+        const bool sizes_from_bits = !o.utf8 && tl.no_control_bytes;   // (utf8: the split pass made line flags, not escape bits)
         void* d_counts = h->scratch[6].get(16);
         GX_HIP(launch_count_outcomes(b.match_id, n, static_cast<unsigned long long*>(d_counts), stream));
         // 3. the text
         void* ws_json = h->scratch[0].get(jsonl_workspace_bytes(n));
         uint64_t* loff = static_cast<uint64_t*>(h->scratch[1].get((n + 1) * 8));
-        GX_HIP(launch_jsonl_sizes(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, loff, ws_json, stream,
+        GX_HIP(launch_jsonl_sizes(tm, b, static_cast<int>(slots), passthrough, mean_in, loff, ws_json, stream,
                                   sizes_from_bits ? reinterpret_cast<const uint32_t*>(esc_bits) : nullptr));
         uint64_t total = 0;
         unsigned long long counts[2] = {0, 0};
@@ -1063,7 +1201,7 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         uint8_t* dst = out;
         if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(total); dst = d_out.get(); }
         const uint32_t mean_out = n ? static_cast<uint32_t>(std::min<uint64_t>((total + n - 1) / n, 1u << 20)) : 1u;
-        GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), o.utf8_passthrough ? 1 : 0, mean_in, mean_out, loff, dst, ws_json, stream));
+        GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), passthrough, mean_in, mean_out, loff, dst, ws_json, stream));
         if (!o.device_pointers && total) GX_HIP(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
@@ -1231,7 +1369,8 @@ int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8
             return fail(GX_E_ARG, "gx_text_select: device text must be 16-byte aligned");
         }
         // lines and the path as in gx_text_to_jsonl; then the selection's passes over the ids and offsets they left on the device
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0);
+        if (o.utf8 == 2) return fail(GX_E_ARG, "gx_text_select: gx_batch_opts.utf8 = 1 (lines are selected by their bytes)");
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
         const Selected s = select_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, want, counts, stream);
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: gx_text_select: a line longer than the split pass reported");
         *out_size = s.units;
@@ -1411,8 +1550,15 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
                               int32_t* states, const gx_batch_opts* opts, DeviceBatch* keep = nullptr) {
     return guarded([&]() -> int {
         if (!h || !offsets) return fail(GX_E_ARG, "gx_extract_batch: bad argument");
-        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const gx_batch_opts o = read_opts(opts);
+        if (o.utf8) {
+            if (o.utf16) return fail(GX_E_ARG, "gx_batch_opts.utf8 with utf16: the batch is either UTF-8 bytes or UTF-16 code units");
+            if (states) return fail(GX_E_ARG, "gx_batch_opts.utf8: gx_match_batch reads bytes as Latin-1 (the final states of UTF-8 lines: gx_utf8_to_utf16, then utf16)");
+            if (o.no_sync)
+                return fail(GX_E_ARG, "gx_batch_opts.utf8 with no_sync: the memory for the code units of the lines that hold a byte >= 0x80 is sized by a read "
+                                      "on the host; call it without no_sync");
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         if (o.kernel > GX_KERNEL_HOP_SLICES) return fail(GX_E_ARG, "gx_batch_opts.kernel: unknown kernel");
         const bool match_only = o.match_only || states || !h->T.has_capture;
         const bool compact = o.compact_results && !match_only;  // rows of u16[1 + slots] (2: u8[1 + slots]) through `caps`
@@ -1469,6 +1615,53 @@ static int extract_batch_impl(gx_handle* h, const uint8_t* bytes, const void* of
             d.enqueued = true;
             if (keep) *keep = d;   // (gx_extract_batch_multi_device waits for its shards itself)
             if (!o.no_sync) finish_device_batch(h, d);
+            if (o.utf8) {
+                // the lines that are not ASCII again, as Strings (behind finish_device_batch: a line it takes again is taken on bytes)
+                utf8_fixup(h, b, o.utf8, static_cast<const uint8_t*>(o.utf8_line_flags), stream);
+                GX_HIP(hipStreamSynchronize(stream));
+            }
+            return GX_OK;
+        }
+        if (o.utf8) {
+            // host pointers: the whole batch is staged to the device and back (as gx_select_lines does), not cut into chunks
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const uint64_t first = n ? off[0] : 0, total = n ? off[n] - first : 0;
+            if (total && !bytes) return fail(GX_E_ARG, "gx_extract_batch: bytes is NULL");
+            const size_t off_w = o.offsets64 ? 8 : 4, slots = 2 * static_cast<size_t>(h->T.max_groups);
+            const size_t rb = row_bytes(row_format(true, o.compact_results == 2), static_cast<uint32_t>(slots));
+            const size_t res_bytes = compact ? n * rb : n * 4, caps_bytes = (compact || match_only) ? 0 : n * slots * 4;
+            DevMem<uint8_t> d_bytes = dev_alloc<uint8_t>(total + 32), d_flags;
+            DevMem<> d_off = dev_alloc((n + 1) * off_w), d_res = dev_alloc(res_bytes), d_caps = dev_alloc(caps_bytes);
+            DevMem<unsigned long long> d_over = dev_alloc<unsigned long long>(8);
+            uint8_t* place = d_bytes.get() + 16;
+            // (line i at base + offsets[i], as in the caller's buffer; the base may lie below the allocation: made as an integer)
+            const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(place) - static_cast<uintptr_t>(first));
+            if (total) GX_HIP(hipMemcpyAsync(place, bytes + first, total, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemsetAsync(d_over.get(), 0, 8, stream));
+            if (o.utf8_line_flags && n) {
+                d_flags = dev_alloc<uint8_t>(n);
+                GX_HIP(hipMemcpyAsync(d_flags.get(), o.utf8_line_flags, n, hipMemcpyHostToDevice, stream));
+            }
+            gx_batch_opts od = o;
+            od.struct_size = sizeof(gx_batch_opts);
+            od.device_pointers = 1;
+            od.overflow = compact ? d_over.get() : nullptr;
+            od.utf8_line_flags = o.utf8_line_flags && n ? d_flags.get() : nullptr;
+            int32_t* d_mid = compact ? nullptr : static_cast<int32_t*>(d_res.get());
+            int32_t* d_rows = compact ? static_cast<int32_t*>(d_res.get()) : static_cast<int32_t*>(d_caps.get());
+            const int rc = extract_batch_impl(h, base, d_off.get(), n, d_mid, d_rows, nullptr, &od);
+            if (rc != GX_OK) return rc;
+            unsigned long long over = 0;
+            if (compact) {
+                if (res_bytes) GX_HIP(hipMemcpyAsync(caps, d_res.get(), res_bytes, hipMemcpyDeviceToHost, stream));
+                GX_HIP(hipMemcpyAsync(&over, d_over.get(), 8, hipMemcpyDeviceToHost, stream));
+            } else {
+                if (n) GX_HIP(hipMemcpyAsync(match_id, d_res.get(), n * 4, hipMemcpyDeviceToHost, stream));
+                if (caps_bytes) GX_HIP(hipMemcpyAsync(caps, d_caps.get(), caps_bytes, hipMemcpyDeviceToHost, stream));
+            }
+            GX_HIP(hipStreamSynchronize(stream));
+            if (compact && o.overflow) *static_cast<uint64_t*>(o.overflow) += over;
             return GX_OK;
         }
         // host pointers: the chunked pipeline (gx_handle::host_slot)
@@ -1526,6 +1719,7 @@ int gx_extract_batch_multi(gx_handle* const* handles, int32_t n_handles, const u
     if (!handles || n_handles <= 0 || !offsets) return fail(GX_E_ARG, "gx_extract_batch_multi: bad argument");
     return guarded([&]() -> int {
         const gx_batch_opts o = read_opts(opts);
+        if (o.utf8) return fail(GX_E_ARG, "gx_extract_batch_multi: gx_batch_opts.utf8 is for gx_extract_batch (one device); shard the batch and call it per handle");
         if (o.device_pointers) return fail(GX_E_ARG, "gx_extract_batch_multi: host buffers only (device buffers belong to one device: use gx_extract_batch per handle)");
         for (int32_t k = 0; k < n_handles; ++k) {
             if (!handles[k] || !handles[k]->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi: NULL or host-only handle");
@@ -1572,6 +1766,9 @@ int gx_extract_batch_multi_device(const gx_device_shard* shards, int32_t n_shard
     if (!shards || n_shards <= 0) return fail(GX_E_ARG, "gx_extract_batch_multi_device: bad argument");
     return guarded([&]() -> int {
         const gx_batch_opts o = read_opts(opts);
+        if (o.utf8)
+            return fail(GX_E_ARG, "gx_extract_batch_multi_device: gx_batch_opts.utf8 is for gx_extract_batch (its fix-up waits for a read on the host: one "
+                                  "device at a time); call it per shard");
         for (int32_t k = 0; k < n_shards; ++k)
             if (!shards[k].handle || !shards[k].handle->on_device) return fail(GX_E_ARG, "gx_extract_batch_multi_device: NULL or host-only handle");
         DeviceScope scope;

@@ -127,6 +127,9 @@ hipError_t launch_extract_generic(const GxDev& dev, const GxBatch& b, hipStream_
 hipError_t launch_narrow_units(const GxBatch& b, uint8_t* bytes_at_first_unit, uint8_t* flags, hipStream_t stream);
 // any_word != nullptr: every wave leaves at once unless *any_word == b.seq (the tile kernel's "there was such a line")
 hipError_t launch_extract_flagged(const GxDev& dev, const GxBatch& b, const uint8_t* flags, hipStream_t stream, const uint32_t* any_word = nullptr);
+// the same walk for the `count` lines whose numbers list[] holds: a lane per LISTED line, so that few flagged lines among many fill
+// their waves (UTF-16 code units, 64-bit offsets)
+hipError_t launch_extract_listed(const GxDev& dev, const GxBatch& b, const uint64_t* list, uint64_t count, hipStream_t stream);
 
 // Tile kernel (gx_tile.hip): 64-line tiles staged through LDS with coalesced loads, self-loop runs skipped by SWAR
 // tests and a per-chunk bitmap.  Byte input only.  `lds_image` is the device copy of the table image.
@@ -233,5 +236,30 @@ hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_unit
                                const SelectWs& w, hipStream_t stream);
 hipError_t launch_select_copy(const SelectOut& o, const void* data, const void* offsets, int offsets64, int wide, uint64_t n, const SelectWs& w,
                               hipStream_t stream);
+
+// UTF-8 lines as UTF-16 code units (gx_utf8.hip; the rule: gx_utf8.hpp).  The passes' device workspace, cut out of one allocation of
+// utf8_workspace_bytes(n) bytes:
+struct Utf8Ws {
+    uint64_t* unit_off;             // [n + 1] units before line i; [n]: all of them
+    uint64_t* block_sums;           // the scan's
+    unsigned long long* flagged;    // the lines that were counted (flagged ones, or all)
+    uint32_t* status;               // != 0: a line of 4 G units or more
+    uint32_t* counts;               // [n] the line's units, 0 for a line that is not flagged
+    uint8_t* flags;                 // [n] for the flag sweep, when the caller brings none
+    uint64_t* list;                 // [n] the flagged lines' numbers, *flagged of them, in the order the waves met them
+};
+size_t utf8_workspace_bytes(uint64_t n);
+Utf8Ws utf8_workspace(void* ws, uint64_t n);
+// flags[i] = 1 for every line that holds a byte >= 0x80, else 0 (what launch_split_lines' flags say)
+hipError_t launch_utf8_flags(const uint8_t* data, const void* offsets, int offsets64, uint64_t n, uint8_t* flags, hipStream_t stream);
+// flags == nullptr: every line.  Leaves w.unit_off (n = 0 too), *w.flagged and *w.status, and with flags w.list.
+hipError_t launch_utf8_count(const uint8_t* data, const void* offsets, int offsets64, uint64_t n, const uint8_t* flags, const Utf8Ws& w, hipStream_t stream);
+// unit_byte (optional, one u32 per unit): the byte, from the line's first, of the item the unit starts in
+hipError_t launch_utf8_write(const uint8_t* data, const void* offsets, int offsets64, uint64_t n, const uint8_t* flags, const uint64_t* unit_off, uint16_t* units,
+                             uint32_t* unit_byte, hipStream_t stream);
+hipError_t launch_utf8_offsets32(const uint64_t* unit_off, uint64_t n, uint32_t* out, hipStream_t stream);   // out[0 .. n]
+// b: the BYTE batch and its result rows; the rows of flagged lines go from unit offsets to byte offsets (clipped ones += *b.overflow)
+hipError_t launch_utf8_offsets_to_bytes(const GxDev& dev, const GxBatch& b, const uint8_t* flags, const uint64_t* unit_off, const uint32_t* unit_byte,
+                                        hipStream_t stream);
 
 }  // namespace gx

@@ -273,6 +273,19 @@ k_extract_flagged(GxDev T, const uint16_t* __restrict__ units, const OFF* __rest
         extract_line_global<uint16_t, MS>(T, m_next, units + b, len, i, out, nullptr, match_only);
     }
 }
+template <typename MS>
+__global__ void __launch_bounds__(256)
+k_extract_listed(GxDev T, const uint16_t* __restrict__ units, const uint64_t* __restrict__ off, const uint64_t* __restrict__ list, uint64_t count,
+                 RowOut out, int match_only, const MS* __restrict__ m_next, int strip_eol) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < count; t += stride) {
+        const uint64_t i = list[t];
+        const uint64_t b = off[i], e = off[i + 1];
+        int64_t len = static_cast<int64_t>(e - b);
+        if (strip_eol) len = trim_eol(units + b, len);
+        extract_line_global<uint16_t, MS>(T, m_next, units + b, len, i, out, nullptr, match_only);
+    }
+}
 
 // Follow-up of the tile kernel: the lines it could not stage (one line longer than its staging area, rare) are
 // taken here, one lane per line.  The tile kernel announces that there are any by storing the launch's sequence
@@ -1066,6 +1079,17 @@ hipError_t launch_extract_flagged(const GxDev& dev, const GxBatch& b, const uint
     if (b.offsets64) { if (dev.m_next16) GX_FLAGGED(uint64_t, uint16_t, dev.m_next16); else GX_FLAGGED(uint64_t, uint32_t, dev.m_next32); }
     else { if (dev.m_next16) GX_FLAGGED(uint32_t, uint16_t, dev.m_next16); else GX_FLAGGED(uint32_t, uint32_t, dev.m_next32); }
 #undef GX_FLAGGED
+    return hipGetLastError();
+}
+hipError_t launch_extract_listed(const GxDev& dev, const GxBatch& b, const uint64_t* list, uint64_t count, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    if (!b.wide || !b.offsets64) return hipErrorInvalidValue;
+    const uint64_t most = dev.pike_off ? dev.pike_blocks : 256u * 4u, need = (count + 255) / 256;
+    const dim3 grid(static_cast<unsigned>(need < most ? need : most)), block(256);
+    const uint16_t* units = static_cast<const uint16_t*>(b.data);
+    const uint64_t* off = static_cast<const uint64_t*>(b.offsets);
+    if (dev.m_next16) hipLaunchKernelGGL((k_extract_listed<uint16_t>), grid, block, 0, stream, dev, units, off, list, count, row_out(dev, b), b.match_only, dev.m_next16, b.strip_eol);
+    else hipLaunchKernelGGL((k_extract_listed<uint32_t>), grid, block, 0, stream, dev, units, off, list, count, row_out(dev, b), b.match_only, dev.m_next32, b.strip_eol);
     return hipGetLastError();
 }
 

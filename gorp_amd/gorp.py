@@ -407,14 +407,16 @@ class Gorp:
         text = out[:size.value].tobytes()
         return (text, loff) if want_line_offsets else text
 
-    def text_to_jsonl(self, text, id_as=None, utf8_passthrough=False):
+    def text_to_jsonl(self, text, id_as=None, utf8_passthrough=False, utf8=False):
         """gx_text_to_jsonl on a host buffer: raw log text -> JSON Lines of the matched lines.
+        utf8: the text is UTF-8 and is matched as the decoded Strings (gx_batch_opts.utf8 = 1; implies utf8_passthrough).
         Returns (jsonl bytes, n_lines, n_matched, n_exceptions)."""
         self._send_meta()
         raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
         o = N.gx_batch_opts()
         o.struct_size = C.sizeof(N.gx_batch_opts)
         o.utf8_passthrough = 1 if utf8_passthrough else 0
+        o.utf8 = 1 if utf8 else 0
         ida = id_as.encode("utf-8") if id_as is not None else None
         size, nl, nm, nx = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         ptr = raw.ctypes.data if raw.size else None
@@ -424,7 +426,7 @@ class Gorp:
                                         C.byref(nx), C.byref(o)))
         return out[:size.value].tobytes(), nl.value, nm.value, nx.value
 
-    def text_to_jsonl_device(self, text_ptr, size, out_ptr, out_cap, id_as=None, utf8_passthrough=False, stream=None):
+    def text_to_jsonl_device(self, text_ptr, size, out_ptr, out_cap, id_as=None, utf8_passthrough=False, stream=None, utf8=False):
         """gx_text_to_jsonl on device buffers (ints); out_ptr=None only asks for the size.
         Returns (text size, n_lines, n_matched, n_exceptions)."""
         self._send_meta()
@@ -432,6 +434,7 @@ class Gorp:
         o.struct_size = C.sizeof(N.gx_batch_opts)
         o.device_pointers = 1
         o.utf8_passthrough = 1 if utf8_passthrough else 0
+        o.utf8 = 1 if utf8 else 0
         o.stream = stream
         size_out, nl, nm, nx = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(N.lib().gx_text_to_jsonl(self._h.ptr, text_ptr, size, id_as.encode("utf-8") if id_as is not None else None, out_ptr, out_cap,
@@ -537,13 +540,17 @@ class Gorp:
         return ExtractionResult(extr.getName(), line, extr, extr._extractorNames, values)
 
     # -- batch API -----------------------------------------------------------
-    def extract_batch(self, data, offsets, match_only=False, strip_eol=False, kernel=0, line_bytes_hint=0, compact=False, uneven=0):
+    def extract_batch(self, data, offsets, match_only=False, strip_eol=False, kernel=0, line_bytes_hint=0, compact=False, uneven=0, utf8=None,
+                      utf8_line_flags=None):
         """Host buffers: data uint8[total] (Latin-1 code units) or uint16[total] (UTF-16 code units),
         offsets uint32|uint64[n+1] in code units.
         Returns (match_id int32[n], caps int32[n, 2*max_groups]); with compact=True (or 1) the compact rows
         uint16[n, 1 + 2*max_groups] and the number of offsets that did not fit them (see unpack_rows); with compact=2
         the u8 rows uint8[n, 1 + 2*max_groups] (lines shorter than 255 bytes, at most 126 extractions).
-        kernel: GX_KERNEL_* (0 = the library chooses)."""
+        kernel: GX_KERNEL_* (0 = the library chooses).
+        utf8: None: a byte is a Latin-1 code unit; "bytes" / "units": the lines are UTF-8 and are matched as the Strings Java
+        would see, capture offsets in bytes of the line / in UTF-16 code units of the String (gx_batch_opts.utf8 = 1 / 2).
+        utf8_line_flags: uint8[n], the flags split_lines(want_flags=True) gave for these lines (saves a sweep)."""
         utf16 = getattr(data, "dtype", None) == np.uint16
         data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
         offsets = np.ascontiguousarray(offsets)
@@ -561,6 +568,12 @@ class Gorp:
         o.kernel = int(kernel) or DEFAULT_KERNEL
         o.line_bytes_hint = int(line_bytes_hint)
         o.uneven_lines = int(uneven)  # gx_batch_opts.uneven_lines: 0 = the library looks at the offsets itself
+        o.utf8 = _utf8_mode(utf8)
+        if utf8_line_flags is not None:
+            utf8_line_flags = np.ascontiguousarray(utf8_line_flags, dtype=np.uint8)
+            if len(utf8_line_flags) != n:
+                raise ValueError("utf8_line_flags: one flag per line")
+            o.utf8_line_flags = utf8_line_flags.ctypes.data if n else None
         if compact and not match_only and self.stat(8):
             rows = np.zeros((n, 1 + 2 * self.max_groups), np.uint8 if int(compact) == 2 else np.uint16)
             over = C.c_uint64(0)
@@ -575,12 +588,13 @@ class Gorp:
 
     def extract_batch_device(self, data_ptr, offsets_ptr, n, match_id_ptr, caps_ptr, offsets64=False, match_only=False,
                              stream=None, no_sync=False, strip_eol=False, line_bytes_hint=0, kernel=0, compact=False,
-                             overflow_ptr=None, uneven=0, max_line_bytes=0, utf16=False):
+                             overflow_ptr=None, uneven=0, max_line_bytes=0, utf16=False, utf8=0, utf8_line_flags_ptr=None):
         """Device pointers (ints), e.g. torch tensors' data_ptr(); results stay in HBM.  line_bytes_hint sizes
         the kernel's staging area (0: 200 bytes with no_sync, else the batch's mean line length).
         max_line_bytes: the caller's promise that no line is longer (gx_batch_opts.max_line_bytes: no follow-up launch).
         compact=True: caps_ptr receives compact rows uint16[n, 1 + 2*max_groups] (match_id_ptr may be None),
-        overflow_ptr (device uint64, zeroed by the caller) counts the offsets that did not fit."""
+        overflow_ptr (device uint64, zeroed by the caller) counts the offsets that did not fit.
+        utf8: gx_batch_opts.utf8 (0, 1 = "bytes", 2 = "units"); utf8_line_flags_ptr: the device flags of split_lines_device."""
         o = N.gx_batch_opts()
         o.struct_size = C.sizeof(N.gx_batch_opts)
         o.device_pointers = 1
@@ -596,6 +610,8 @@ class Gorp:
         o.uneven_lines = int(uneven)  # 2: lines differ much in length (0 with a hint or no_sync: taken as 1, similar lengths)
         o.max_line_bytes = int(max_line_bytes)
         o.utf16 = 1 if utf16 else 0
+        o.utf8 = _utf8_mode(utf8)
+        o.utf8_line_flags = utf8_line_flags_ptr
         _check(N.lib().gx_extract_batch(self._h.ptr, data_ptr, offsets_ptr, n, match_id_ptr, caps_ptr, C.byref(o)))
 
     # -- outcomes of a finished batch (gx_count_outcomes / gx_select_lines / gx_text_select) --------------------------
@@ -721,36 +737,101 @@ class Gorp:
                                        out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, C.byref(k), C.byref(nbytes), C.byref(o)))
         return k.value, nbytes.value
 
-    def text_select(self, text, want=("unmatched", "exceptions")):
+    def text_select(self, text, want=("unmatched", "exceptions"), utf8=False):
         """gx_text_select on a host buffer: raw log text -> the text of the lines whose outcome `want` names, terminators included.
         Returns (selected text bytes, counts uint64[2K + 2], n_lines)."""
         raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
         ptr = raw.ctypes.data if raw.size else None
         out = np.zeros(max(1, raw.size), np.uint8)   # (one pass: the selected text is no larger than the text)
-        size, counts, n_lines = self.text_select_device(ptr, raw.size, want, out.ctypes.data, raw.size, device_pointers=False)
+        size, counts, n_lines = self.text_select_device(ptr, raw.size, want, out.ctypes.data, raw.size, device_pointers=False, utf8=utf8)
         return out[:size].tobytes(), counts, n_lines
 
-    def text_select_device(self, text_ptr, size, want, out_ptr, out_cap, stream=None, device_pointers=True):
-        """gx_text_select on device buffers (ints); out_ptr=None only asks for the sizes.  Returns (selected bytes, counts, n_lines)."""
+    def text_select_device(self, text_ptr, size, want, out_ptr, out_cap, stream=None, device_pointers=True, utf8=False):
+        """gx_text_select on device buffers (ints); out_ptr=None only asks for the sizes.  utf8: the text is UTF-8 and outcomes are those
+        of the decoded Strings.  Returns (selected bytes, counts, n_lines)."""
         mask = self.want_mask(want)
         counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
         o = N.gx_batch_opts()
         o.struct_size = C.sizeof(N.gx_batch_opts)
         o.device_pointers = 1 if device_pointers else 0
         o.stream = stream
+        o.utf8 = 1 if utf8 else 0
         out_size, nl = C.c_uint64(0), C.c_uint64(0)
         _check(N.lib().gx_text_select(self._h.ptr, text_ptr, size, mask.ctypes.data, out_ptr, out_cap, C.byref(out_size), counts.ctypes.data,
                                       C.byref(nl), C.byref(o)))
         return out_size.value, counts, nl.value
 
-    def results(self, data, offsets, match_id, caps, safe=False):
-        """Materialise ExtractionResult objects (or None) for a finished batch."""
+    def results(self, data, offsets, match_id, caps, safe=False, utf8=None):
+        """Materialise ExtractionResult objects (or None) for a finished batch.  utf8: what extract_batch was given -- "bytes":
+        the lines are UTF-8 and the offsets index their bytes; "units": they index the decoded Strings' UTF-16 code units."""
         out = []
         raw = bytes(np.ascontiguousarray(data, dtype=np.uint8))
+        mode = _utf8_mode(utf8)
         for i in range(len(match_id)):
-            line = raw[int(offsets[i]):int(offsets[i + 1])].decode("latin-1")
-            out.append(self._materialise(line, int(match_id[i]), caps[i], safe))
+            chunk = raw[int(offsets[i]):int(offsets[i + 1])]
+            if mode == 0:
+                out.append(self._materialise(chunk.decode("latin-1"), int(match_id[i]), caps[i], safe))
+                continue
+            line = chunk.decode("utf-8", "replace")
+            if mode == 2:
+                units = np.frombuffer(line.encode("utf-16-le", "surrogatepass"), dtype=np.uint16)
+                out.append(self._materialise(line, int(match_id[i]), caps[i], safe, units=units))
+            else:
+                r = self._materialise(_ByteSlices(chunk), int(match_id[i]), caps[i], safe)
+                if r is not None:
+                    r._input = line
+                out.append(r)
         return out
+
+
+class _ByteSlices:
+    """A UTF-8 line whose slices (by byte offsets) come back as decoded text."""
+
+    def __init__(self, raw):
+        self._raw = raw
+
+    def __getitem__(self, s):
+        return self._raw[s].decode("utf-8", "replace")
+
+
+def _utf8_mode(utf8):
+    """None / 0 / False -> 0; "bytes" / 1 / True -> 1; "units" / 2 -> 2 (gx_batch_opts.utf8)."""
+    modes = {None: 0, 0: 0, "bytes": 1, 1: 1, "units": 2, 2: 2}
+    if utf8 not in modes:
+        raise ValueError('utf8: None, "bytes" or "units"')
+    return modes[utf8]
+
+
+def utf8_to_utf16(data, offsets):
+    """gx_utf8_to_utf16 on host buffers: the UTF-8 lines of a CSR batch -> (units uint16[total], unit_offsets[n+1] of the
+    offsets' dtype): the code units of the Strings Java would see, directly a utf16 batch for extract_batch."""
+    data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets)
+    if offsets.dtype not in (np.uint32, np.uint64):
+        raise TypeError("offsets must be uint32 or uint64")
+    n = len(offsets) - 1
+    o = N.gx_batch_opts()
+    o.struct_size = C.sizeof(N.gx_batch_opts)
+    o.offsets64 = 1 if offsets.dtype == np.uint64 else 0
+    total = C.c_uint64(0)
+    ptr = data.ctypes.data if data.size else None
+    _check(N.lib().gx_utf8_to_utf16(ptr, offsets.ctypes.data, n, None, 0, None, C.byref(total), C.byref(o)))
+    units = np.zeros(max(1, total.value), np.uint16)
+    unit_offsets = np.zeros(n + 1, offsets.dtype)
+    _check(N.lib().gx_utf8_to_utf16(ptr, offsets.ctypes.data, n, units.ctypes.data, total.value, unit_offsets.ctypes.data, C.byref(total), C.byref(o)))
+    return units[:total.value], unit_offsets
+
+
+def utf8_to_utf16_device(data_ptr, offsets_ptr, n, units_ptr, units_cap, unit_offsets_ptr, offsets64=False, stream=None):
+    """gx_utf8_to_utf16 on device buffers (ints); units_ptr=None only asks for the size.  Returns the number of code units."""
+    o = N.gx_batch_opts()
+    o.struct_size = C.sizeof(N.gx_batch_opts)
+    o.device_pointers = 1
+    o.offsets64 = 1 if offsets64 else 0
+    o.stream = stream
+    total = C.c_uint64(0)
+    _check(N.lib().gx_utf8_to_utf16(data_ptr, offsets_ptr, n, units_ptr, units_cap, unit_offsets_ptr, C.byref(total), C.byref(o)))
+    return total.value
 
 
 def extract_batch_multi(gorps, data, offsets, match_only=False, strip_eol=False, compact=False):

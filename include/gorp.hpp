@@ -208,13 +208,18 @@ public:
     }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
-    std::string textSelect(const std::string& text, const Want& want, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr) const {
+    // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
+    std::string textSelect(const std::string& text, const Want& want, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr,
+                           bool utf8 = false) const {
         if (want.size() != 2 * extractions_.size() + 1) throw GorpError(GX_E_ARG, "textSelect: the want mask has 2K + 1 entries");
         if (counts) counts->assign(2 * extractions_.size() + 2, 0);
         uint64_t size = 0;
         std::string out(text.size() + 1, '\0');   // (one pass: the selected text is no larger than the text)
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
         int rc = gx_text_select(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), want.data(), reinterpret_cast<uint8_t*>(&out[0]), text.size(), &size,
-                                counts ? counts->data() : nullptr, nLines, nullptr);
+                                counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         out.resize(static_cast<size_t>(size));
         return out;
@@ -291,6 +296,21 @@ inline std::vector<uint32_t> splitLines(const uint8_t* bytes, uint64_t size) {
     if (rc != GX_OK) throw GorpError(rc, gx_last_error());
     offsets.resize(static_cast<size_t>(n) + 1);
     return offsets;
+}
+
+// gx_utf8_to_utf16: the UTF-8 lines of a CSR batch (offsets as splitLines gives them) as the UTF-16 code units of the Strings Java
+// would see -- new InputStreamReader(in, "UTF-8") -- with their offsets in units: directly a gx_batch_opts.utf16 batch.
+inline std::pair<std::u16string, std::vector<uint32_t>> utf8ToUtf16(const uint8_t* bytes, const std::vector<uint32_t>& offsets) {
+    if (offsets.empty()) throw GorpError(GX_E_ARG, "utf8ToUtf16: offsets has n + 1 entries");
+    const uint64_t n = offsets.size() - 1;
+    uint64_t units = 0;
+    int rc = gx_utf8_to_utf16(bytes, offsets.data(), n, nullptr, 0, nullptr, &units, nullptr);
+    if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+    std::u16string out(static_cast<size_t>(units), u'\0');
+    std::vector<uint32_t> unitOffsets(offsets.size());
+    rc = gx_utf8_to_utf16(bytes, offsets.data(), n, reinterpret_cast<uint16_t*>(&out[0]), units, unitOffsets.data(), &units, nullptr);
+    if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+    return {std::move(out), std::move(unitOffsets)};
 }
 
 // core/DefinitionReader.java

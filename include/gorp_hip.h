@@ -122,7 +122,8 @@ int32_t gx_max_groups(const gx_handle* h);
  * tier; 5: the tables leave no room for a wave); 27 = extractions whose capture automaton would be too large ahead of time and
  * whose regexp is therefore RUN as a program, thread lists in priority order (exact, linear in line x program; such a definition's
  * batches go through the per-line kernel); 28 = times the resident one-line wave was started (GX_CREATE_RESIDENT_ONE; -1: the
- * handle has none) */
+ * handle has none); 33 / 34 = for the most recent gx_batch_opts.utf8 batch (gx_extract_batch, gx_text_to_jsonl, gx_text_select): the lines that
+ * held a byte >= 0x80 and were walked again as Strings, and the UTF-16 code units made for them */
 int64_t gx_stat(const gx_handle* h, int32_t which);
 
 typedef struct gx_batch_opts {
@@ -176,7 +177,7 @@ typedef struct gx_batch_opts {
                                   of its code units (tables other than dense rows in LDS or hop tables, or a kernel named in
                                   `kernel`) counts the clipped offsets of a line that holds a unit above 0xFF twice (the byte
                                   kernel's pass over the low bytes, then the per-line walk that writes the row); the rows are
-                                  right. */
+                                  right.  A utf8 batch has the same exception for its lines that are not ASCII (see utf8). */
     uint32_t max_line_bytes;   /* gx_extract_batch with device_pointers.  The caller's PROMISE: no line of the batch -- offsets[i+1] -
                                   offsets[i], terminator included -- is longer than this many code units (0: no promise).
                                   gx_split_lines_max reports it for free; a log shipper knows its own cap.  Without it every batch
@@ -196,6 +197,28 @@ typedef struct gx_batch_opts {
                                   on one of them is reported to whichever of them calls next, and a synchronous call of one
                                   whose word another's later launch has overwritten is not made good but reported like a
                                   no_sync batch (by an error whose text then wrongly calls some batch complete: check rows). */
+    uint32_t utf8;             /* gx_extract_batch, gx_text_to_jsonl, gx_text_select (1 only).  The lines are UTF-8 and are read as the Strings
+                                  Java would see (new InputStreamReader(in, "UTF-8")): 0: off -- a byte is one Latin-1 code unit;
+                                  1: capture offsets are BYTES of the line as it lies in memory -- what a caller that holds bytes
+                                  slices with, and what gx_results_to_jsonl with utf8_passthrough = 1 needs; 2: capture offsets are
+                                  UTF-16 CODE UNITS of the decoded String, Matcher.start() / end().  Ill-formed input decodes to
+                                  U+FFFD per maximal subpart (Unicode 3.9; what CPython's "replace" handler does); a JDK may differ
+                                  in the NUMBER of U+FFFD for some ill-formed input (encoded surrogates ED A0 80, for instance),
+                                  never for well-formed input; no BOM handling (Java keeps U+FEFF too).  A sequence never
+                                  continues across a line's end.  The byte batch kernel runs as ever -- its rows are right for every
+                                  ASCII-only line -- and the lines that hold a byte >= 0x80 are transcoded and walked again, per
+                                  line, on their code units (gx_stat(h, 33) / (h, 34): how many lines, how many units).  That
+                                  fix-up reads two numbers on the host to size its memory: with no_sync it is refused (GX_E_ARG),
+                                  as with utf16, with gx_match_batch and in gx_extract_batch_multi / _multi_device.  Host pointers
+                                  stage the whole batch to the device and back (no chunk pipeline).  With compact rows, the clipped
+                                  offsets of a line that is walked again are counted more than once in *overflow (the byte pass,
+                                  the walk on units, and utf8 = 1's step back to bytes); the rows are right.  gx_text_to_jsonl
+                                  with utf8 writes with utf8_passthrough semantics: the line's bytes leave as they are, ill-formed
+                                  ones included (they are not repaired).  (This field lies in what was tail padding: struct_size
+                                  of the layout that ended with max_line_bytes reads as utf8 = 0.) */
+    void*    utf8_line_flags;  /* with utf8, optional: uint8_t[n], != 0 for every line that holds a byte >= 0x80 -- the line_flags of
+                                  gx_split_lines for exactly these lines (a device pointer with device_pointers).  Saves the sweep
+                                  over the batch that finds them.  A line wrongly flagged 0 is read as Latin-1. */
 } gx_batch_opts;
 
 enum { GX_KERNEL_AUTO = 0, GX_KERNEL_TILES = 1, GX_KERNEL_SLICES = 2, GX_KERNEL_PER_LINE = 3, GX_KERNEL_LANES = 4,
@@ -216,8 +239,8 @@ int gx_extract_batch(gx_handle* h, const uint8_t* bytes, const void* offsets, ui
  * writes offsets[0..n] with line i = bytes[offsets[i], offsets[i+1]) INCLUDING its terminator, ready for
  * gx_extract_batch with strip_eol = 1.  offsets holds cap_lines + 1 entries (uint32_t, or uint64_t with
  * opts->offsets64; a uint32_t buffer must be < 4 GiB).  line_flags (optional, cap_lines bytes) receives 1 for
- * every line containing a byte >= 0x80: such a line is Latin-1 only if the file is; UTF-8 text needs the
- * UTF-16 entry points.  Runs on the GPU (three bandwidth-bound passes); with opts->device_pointers = 1
+ * every line containing a byte >= 0x80: such a line is Latin-1 only if the file is; for UTF-8 text hand the
+ * flags to gx_extract_batch as gx_batch_opts.utf8_line_flags with gx_batch_opts.utf8 (or transcode with gx_utf8_to_utf16).  Runs on the GPU (three bandwidth-bound passes); with opts->device_pointers = 1
  * bytes / offsets / line_flags are device pointers (bytes 16-byte aligned) and *n_lines (host) is written
  * after a stream synchronisation.  GX_E_LIMIT when the buffer holds more than cap_lines lines (*n_lines is
  * still set, so the caller can retry with a larger offsets array). */
@@ -227,6 +250,18 @@ int gx_split_lines(const uint8_t* bytes, uint64_t size, void* offsets, uint64_t 
  * gx_batch_opts.max_line_bytes wants to hear (the pass that writes the offsets sees every line end anyway). */
 int gx_split_lines_max(const uint8_t* bytes, uint64_t size, void* offsets, uint64_t cap_lines, uint64_t* n_lines,
                        uint8_t* line_flags, uint64_t* max_line_bytes, const gx_batch_opts* opts);
+
+/* UTF-8 lines -> the UTF-16 code units of the Strings Java would see, EVERY line of a CSR batch (ASCII lines widened): what
+ * new InputStreamReader(in, "UTF-8") does before the reference sees a line.  The decoding rule is gx_batch_opts.utf8's.  line i =
+ * bytes[offsets[i] .. offsets[i+1]); nothing outside a line is looked at and nothing outside the batch is read.  units receives the
+ * code units (host byte order), unit_offsets n + 1 entries of the input offsets' width (opts->offsets64), starting at 0: together
+ * directly a gx_batch_opts.utf16 batch.  *n_units (host) is always set; units == NULL only asks for it; GX_E_LIMIT when units_cap
+ * (in units) is too small -- nothing has been written -- or when uint32_t offsets cannot hold the total.  opts: device_pointers
+ * (bytes / offsets / units / unit_offsets on the current device; else they are staged), stream, offsets64.  Three passes -- count,
+ * scan, write -- with one synchronisation between scan and write.  No handle: one workspace per device, kept between calls (12 bytes
+ * per line of the largest batch; gx_release_scratch gives it back). */
+int gx_utf8_to_utf16(const uint8_t* bytes, const void* offsets, uint64_t n, uint16_t* units, uint64_t units_cap, void* unit_offsets,
+                     uint64_t* n_units, const gx_batch_opts* opts);
 
 /* Result materialisation, the step after the path: ExtractionResult.asMap(idAs)
  * (core/ExtractionResult.java:65-88) for every matched line of a finished batch, written as one JSON object per
@@ -251,7 +286,8 @@ int gx_results_to_jsonl(gx_handle* h, const uint8_t* bytes, const void* offsets,
  * (README.md:26,63-79), with extractSafe semantics for lines the capture regexp rejects (no text, counted in
  * *n_exceptions).  Intermediate buffers live and die on the device.  *n_lines / *n_matched / *n_exceptions (each
  * optional) receive the counts; *out_size the size of the text; out == NULL only asks for the size; GX_E_LIMIT when
- * out_cap is too small.  opts: device_pointers (text and out on the device), stream, utf8_passthrough.  Text of 4 GiB
+ * out_cap is too small.  opts: device_pointers (text and out on the device), stream, utf8_passthrough, utf8 (1: the text is UTF-8 --
+ * outcomes, counts and JSON values are those of the decoded Strings; implies utf8_passthrough).  Text of 4 GiB
  * and more must be split by the caller (at a line boundary). */
 int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const char* id_as, uint8_t* out, uint64_t out_cap,
                      uint64_t* out_size, uint64_t* n_lines, uint64_t* n_matched, uint64_t* n_exceptions, const gx_batch_opts* opts);
@@ -300,7 +336,8 @@ int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64
  * lines gx_text_to_jsonl writes nothing for: the dead-letter file.  counts (optional, uint64_t[2K + 2], host) receives the
  * histogram of the same pass, *n_lines (optional) the number of lines, *out_size the size of the selected text; out == NULL only
  * asks for the sizes; GX_E_LIMIT when out_cap is too small.  opts: device_pointers (text -- 16-byte aligned -- and out on the
- * device), stream.  Text of 4 GiB and more must be split by the caller (at a line boundary). */
+ * device), stream, utf8 (1: the text is UTF-8 and outcomes are those of the decoded Strings; the selected lines are their original bytes).
+ * Text of 4 GiB and more must be split by the caller (at a line boundary). */
 int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap,
                    uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
