@@ -42,6 +42,7 @@ SYMBOLS = [
     "gx_host_register", "gx_host_unregister", "gx_split_lines_max", "gx_extract_batch_multi_device",
     "gx_create_on_devices", "gx_gather_rows", "gx_gather_wait", "gx_release_scratch",
     "gx_count_outcomes", "gx_select_lines", "gx_text_select", "gx_utf8_to_utf16",
+    "gx_partition_lines", "gx_text_to_jsonl_by_extraction",
 ]
 
 
@@ -214,6 +215,13 @@ def lib():
     L.gx_text_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
                                  C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_select.restype = C.c_int
+    L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_partition_lines.restype = C.c_int
+    L.gx_text_to_jsonl_by_extraction.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_to_jsonl_by_extraction.restype = C.c_int
     L.gx_utf8_to_utf16.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
                                    C.POINTER(gx_batch_opts)]
     L.gx_utf8_to_utf16.restype = C.c_int

@@ -249,9 +249,11 @@ struct gx_handle {
     std::atomic<uint32_t> last_fits{0}, last_limit{0};   // ... and its BatchPlan::fits and ::limit (gx_stat(h, 31) and (h, 32); 0: a kernel that leaves no line)
     // device scratch of gx_results_to_jsonl / gx_text_to_jsonl (sizes, split points, line offsets), kept between calls.  Used under
     // `mu` only, and every call that uses it ends with a stream synchronisation.
-    GrowBuf scratch[8];
-    // device workspace of gx_count_outcomes / gx_select_lines / gx_text_select (gx_device.hpp: SelectWs), kept between calls and used
-    // under `mu`.  A no_sync gx_select_lines leaves its copy pass reading it: the next user's stream waits for select_event first.
+    // (8 .. 11: the partitioned batch of gx_text_to_jsonl_by_extraction -- text, offsets, ids, capture rows)
+    GrowBuf scratch[12];
+    // device workspace of gx_count_outcomes / gx_select_lines / gx_text_select (gx_device.hpp: SelectWs) and of gx_partition_lines /
+    // gx_text_to_jsonl_by_extraction (PartWs), kept between calls and used under `mu`.  A no_sync gx_select_lines or gx_partition_lines
+    // leaves its copy pass reading it: the next user's stream waits for select_event first.
     GrowBuf select_ws;
     Event select_event;
     bool select_pending = false;
@@ -1382,6 +1384,213 @@ int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8
         if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(s.units); sel.bytes = d_out.get(); }
         GX_HIP(launch_select_copy(sel, src, tl.b.offsets, 0, 0, tl.n, s.w, stream));
         if (!o.device_pointers && s.units) GX_HIP(hipMemcpyAsync(out, sel.bytes, s.units, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+        return GX_OK;
+    });
+}
+
+// Keys, sort, scan and the groups on the handle's workspace (under h->mu); then the host reads what it must know before anything is
+// written -- the groups' boundaries, whose last entries are the number of kept lines and of kept code units, and whether a line was
+// too long to count: ONE small synchronisation of the stream (before it the want mask goes to the device, as select_pass sends it).
+// ids / offsets: device pointers; want: host, uint8_t[2K + 1], or nullptr = every outcome 0 .. 2K.  front: bytes at the head of the
+// workspace that the caller keeps for itself.
+struct Partitioned {
+    PartWs w;
+    std::vector<uint64_t> groups;   // [2K + 3] lines, then [2K + 3] code units
+    uint64_t lines = 0, units = 0;
+};
+static Partitioned partition_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64,
+                                  const uint8_t* want, size_t front, hipStream_t stream) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
+    if (h->select_pending) {
+        GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+        h->select_pending = false;
+    }
+    Partitioned s;
+    uint8_t* ws = static_cast<uint8_t*>(h->select_ws.get(front + partition_workspace_bytes(n, K)));
+    s.w = partition_workspace(ws + front, n, K);
+    if (want) GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
+    else GX_HIP(hipMemsetAsync(s.w.want, 1, bins - 1u, stream));
+    GX_HIP(launch_partition_sort(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+    s.groups.assign(2 * static_cast<size_t>(bins + 1), 0);
+    uint32_t status = 0;
+    GX_HIP(hipMemcpyAsync(s.groups.data(), s.w.groups, s.groups.size() * 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&status, s.w.status, 4, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (status) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be partitioned");
+    s.lines = s.groups[bins];
+    s.units = s.groups[2 * static_cast<size_t>(bins) + 1];
+    return s;
+}
+
+int gx_partition_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const uint8_t* want,
+                       uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines,
+                       uint64_t out_bytes_cap, uint64_t* group_lines, uint64_t* group_units, uint64_t* n_out, uint64_t* bytes_out,
+                       const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!h || !offsets || !n_out || !bytes_out || (n && !ids)) return fail(GX_E_ARG, "gx_partition_lines: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (n >= (1ull << 32)) return fail(GX_E_LIMIT, "gx_partition_lines: line numbers are 32 bits; split batches of 4 G lines and more");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) { caps = nullptr; out_caps = nullptr; }
+        if (out_caps && slots && n && !caps) return fail(GX_E_ARG, "gx_partition_lines: out_caps without caps");
+        if (!slots) out_caps = nullptr;
+        if (o.no_sync && !o.device_pointers) return fail(GX_E_ARG, "gx_partition_lines: no_sync needs device pointers");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        const size_t bins = 2 * static_cast<size_t>(h->T.n_rules) + 2;
+        const bool host = !o.device_pointers;
+        // host buffers are staged to the device and back; the passes are the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps, d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (host) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, "gx_partition_lines: bytes is NULL");
+            d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            // (the sizes and the groups depend on the ids and the offsets alone: the text travels only if it is asked for)
+            if (out_bytes) {
+                d_bytes = dev_alloc(in_bytes);
+                if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            }
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (out_caps && n) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        const Partitioned s = partition_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, 0, stream);
+        *n_out = s.lines;
+        *bytes_out = s.units * unit;
+        if (group_lines) std::copy(s.groups.begin(), s.groups.begin() + bins + 1, group_lines);
+        if (group_units) std::copy(s.groups.begin() + bins + 1, s.groups.end(), group_units);
+        if (!out_bytes && !out_index && !out_offsets && !out_ids && !out_caps) return GX_OK;   // size query
+        if ((out_index || out_offsets || out_ids || out_caps) && s.lines > cap_lines)
+            return fail(GX_E_LIMIT, "gx_partition_lines: cap_lines is smaller than the partition (see *n_out)");
+        if (out_bytes && s.units * unit > out_bytes_cap)
+            return fail(GX_E_LIMIT, "gx_partition_lines: out_bytes_cap is smaller than the kept text (see *bytes_out)");
+        SelectOut out{};
+        out.index = out_index; out.bytes = out_bytes; out.offsets = out_offsets;
+        void *dst_ids = out_ids, *dst_caps = out_caps;
+        if (host) {
+            if (out_index) { d_oindex = dev_alloc(s.lines * 4); out.index = static_cast<uint32_t*>(d_oindex.get()); }
+            if (out_bytes) { d_obytes = dev_alloc(s.units * unit); out.bytes = d_obytes.get(); }
+            if (out_offsets) { d_ooff = dev_alloc((s.lines + 1) * off_w); out.offsets = d_ooff.get(); }
+            if (out_ids) { d_oids = dev_alloc(s.lines * id_row); dst_ids = d_oids.get(); }
+            if (out_caps) { d_ocaps = dev_alloc(s.lines * slots * 4); dst_caps = d_ocaps.get(); }
+        }
+        if (out_ids) { out.col_src[0] = src_ids; out.col_dst[0] = dst_ids; out.col_width[0] = row_units; out.col_unit_bytes[0] = row_unit_bytes(fmt); }
+        if (out_caps) { out.col_src[1] = src_caps; out.col_dst[1] = dst_caps; out.col_width[1] = static_cast<uint32_t>(slots); out.col_unit_bytes[1] = 4; }
+        if (out.offsets && s.lines == 0) GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
+        GX_HIP(launch_partition_copy(out, src, src_off, o.offsets64 ? 1 : 0, o.utf16 ? 1 : 0, n, s.lines, s.w, stream));
+        if (host) {
+            if (out_index && s.lines) GX_HIP(hipMemcpyAsync(out_index, out.index, s.lines * 4, hipMemcpyDeviceToHost, stream));
+            if (out_bytes && s.units) GX_HIP(hipMemcpyAsync(out_bytes, out.bytes, s.units * unit, hipMemcpyDeviceToHost, stream));
+            if (out_offsets) GX_HIP(hipMemcpyAsync(out_offsets, out.offsets, (s.lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
+            if (out_ids && s.lines) GX_HIP(hipMemcpyAsync(out_ids, dst_ids, s.lines * id_row, hipMemcpyDeviceToHost, stream));
+            if (out_caps && s.lines) GX_HIP(hipMemcpyAsync(out_caps, dst_caps, s.lines * slots * 4, hipMemcpyDeviceToHost, stream));
+        }
+        if (o.no_sync) {
+            // (the copy pass still reads the workspace: whoever uses it next waits for this)
+            if (!h->select_event) GX_HIP(hipEventCreateWithFlags(h->select_event.out(), hipEventDisableTiming));
+            GX_HIP(hipEventRecord(h->select_event.get(), stream));
+            h->select_pending = true;
+            return GX_OK;
+        }
+        GX_HIP(hipStreamSynchronize(stream));
+        return GX_OK;
+    });
+}
+
+int gx_text_to_jsonl_by_extraction(gx_handle* h, const uint8_t* text, uint64_t size, const char* id_as, uint8_t* out, uint64_t out_cap,
+                                   uint64_t* out_size, uint64_t* group_out, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return guarded([&]() -> int {
+        if (!h || !out_size || (size && !text)) return fail(GX_E_ARG, "gx_text_to_jsonl_by_extraction: bad argument");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_to_jsonl_by_extraction: split texts of 4 GiB and more at a line boundary");
+        const gx_batch_opts o = read_opts(opts);
+        if (o.utf8 == 2) return fail(GX_E_ARG, "gx_text_to_jsonl_by_extraction: gx_batch_opts.utf8 = 1 (the text is written from its bytes)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (slots > 128) return fail(GX_E_LIMIT, "gx_text_to_jsonl_by_extraction: more than 64 capture groups per extraction");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        const GxJsonl& tm = jsonl_templates(h, id_as);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text, d_out;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, "gx_text_to_jsonl_by_extraction: device text must be 16-byte aligned");
+        }
+        const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
+        const int passthrough = (o.utf8_passthrough || o.utf8) ? 1 : 0;   // (utf8 implies it)
+        // 1. lines, 2. the path (no escape bits: they would belong to the original text, and the JSON passes read the partitioned one)
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        const uint64_t n = tl.n;
+        // 3. the histogram (the head of the workspace) and the partition of the matched lines, outcomes 0 .. K - 1
+        const size_t front = counts ? select_workspace_bytes(n, K, false) : 0;
+        std::vector<uint8_t> want(bins - 1u, 0);
+        std::fill(want.begin(), want.begin() + K, 1);
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        (void)h->select_ws.get(front + partition_workspace_bytes(n, K));   // (grown once: the histogram's part stays where it is)
+        if (counts) {
+            const SelectWs cw = select_workspace(h->select_ws.get(front), n, K, false);
+            GX_HIP(launch_select_flags(tl.b.match_id, ROWS_DENSE, 1, K, n, nullptr, 0, cw, stream));
+            GX_HIP(hipMemcpyAsync(counts, cw.counts, static_cast<size_t>(bins) * 8, hipMemcpyDeviceToHost, stream));
+        }
+        const Partitioned s = partition_pass(h, tl.b.match_id, ROWS_DENSE, 1, n, tl.b.offsets, false, want.data(), front, stream);
+        // (the extraction ran on the split pass's own longest line; a kernel that met a longer one after all left rows unwritten)
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: gx_text_to_jsonl_by_extraction: a line longer than the split pass reported");
+        const uint64_t m = s.lines;
+        GxBatch b{};
+        b.data = h->scratch[8].get(s.units + 16);
+        b.offsets = h->scratch[9].get((m + 1) * 4);
+        b.n = m;
+        b.match_id = static_cast<int32_t*>(h->scratch[10].get(m * 4 + 16));
+        b.caps = static_cast<int32_t*>(h->scratch[11].get(m * slots * 4 + 16));
+        b.strip_eol = 1;
+        SelectOut part{};
+        part.bytes = const_cast<void*>(b.data); part.offsets = const_cast<void*>(b.offsets);
+        part.col_src[0] = tl.b.match_id; part.col_dst[0] = b.match_id; part.col_width[0] = 1; part.col_unit_bytes[0] = 4;
+        if (slots) { part.col_src[1] = tl.b.caps; part.col_dst[1] = b.caps; part.col_width[1] = static_cast<uint32_t>(slots); part.col_unit_bytes[1] = 4; }
+        if (m == 0) GX_HIP(hipMemsetAsync(part.offsets, 0, 4, stream));
+        GX_HIP(launch_partition_copy(part, src, tl.b.offsets, 0, 0, n, m, s.w, stream));
+        // 4. the text, from the partitioned batch
+        void* ws_json = h->scratch[0].get(jsonl_workspace_bytes(m));
+        uint64_t* loff = static_cast<uint64_t*>(h->scratch[1].get((m + 1) * 8 + (static_cast<size_t>(K) + 1) * 8));
+        uint64_t* d_group_out = loff + m + 1;
+        const uint32_t mean_in = m ? static_cast<uint32_t>(std::min<uint64_t>((s.units + m - 1) / m, 1u << 20)) : 1u;
+        GX_HIP(launch_jsonl_sizes(tm, b, static_cast<int>(slots), passthrough, mean_in, loff, ws_json, stream));
+        uint64_t total = 0;
+        GX_HIP(hipMemcpyAsync(&total, loff + m, 8, hipMemcpyDeviceToHost, stream));
+        if (group_out) {
+            // (group k's objects begin where its first line's object does; the groups' boundaries are still in the workspace)
+            GX_HIP(launch_partition_pick(loff, s.w.groups, K + 1u, d_group_out, stream));
+            GX_HIP(hipMemcpyAsync(group_out, d_group_out, (static_cast<size_t>(K) + 1) * 8, hipMemcpyDeviceToHost, stream));
+        }
+        GX_HIP(hipStreamSynchronize(stream));
+        *out_size = total;
+        if (n_lines) *n_lines = n;
+        if (!out) return GX_OK;
+        if (total > out_cap) return fail(GX_E_LIMIT, "gx_text_to_jsonl_by_extraction: out_cap is smaller than the text (see *out_size)");
+        uint8_t* dst = out;
+        if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(total); dst = d_out.get(); }
+        const uint32_t mean_out = m ? static_cast<uint32_t>(std::min<uint64_t>((total + m - 1) / m, 1u << 20)) : 1u;
+        GX_HIP(launch_jsonl_write(tm, b, static_cast<int>(slots), passthrough, mean_in, mean_out, loff, dst, ws_json, stream));
+        if (!o.device_pointers && total) GX_HIP(hipMemcpyAsync(out, dst, total, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });

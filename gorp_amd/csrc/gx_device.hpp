@@ -237,6 +237,34 @@ hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_unit
 hipError_t launch_select_copy(const SelectOut& o, const void* data, const void* offsets, int offsets64, int wide, uint64_t n, const SelectWs& w,
                               hipStream_t stream);
 
+// The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
+// The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
+struct PartWs {
+    uint64_t* groups;             // [2K + 3] output lines before group x, then [2K + 3] the same in code units; [2K + 2]: the totals
+    uint32_t* status;             // behind them; != 0: a line of 4 G code units or more
+    uint8_t* want;                // [2K + 1] the mask, put there by the caller of launch_partition_sort
+    uint64_t* block_sums;         // the scans'
+    uint32_t* slab;               // [64][workgroups] a digit's counts
+    uint64_t* bases;              // ... scanned
+    uint64_t* dst_off;            // [n + 1] code units before output line j
+    uint32_t* keys[2];            // [n] the keys, before and behind a digit's scatter
+    uint32_t* perm[2];            // [n] the line numbers, likewise
+    uint32_t* klen;               // [n] the line's code units when it is kept, else 0
+    uint32_t* plen;               // [n] the same in output order
+    uint32_t* perm_sorted;        // perm[0] or perm[1]: the input line of output line j, left by launch_partition_sort
+    size_t bytes;
+};
+PartWs partition_workspace(void* ws, uint64_t n, uint32_t K);
+size_t partition_workspace_bytes(uint64_t n, uint32_t K);
+uint32_t partition_digits(uint32_t K);   // six-bit digits of the keys 0 .. 2K + 1
+// ids, offsets: as launch_select_flags takes them; w.want holds the mask
+hipError_t launch_partition_sort(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, PartWs& w,
+                                 hipStream_t stream);
+// kept: w.groups[2K + 2] as the host has read it
+hipError_t launch_partition_copy(const SelectOut& o, const void* data, const void* offsets, int offsets64, int wide, uint64_t n, uint64_t kept, const PartWs& w,
+                                 hipStream_t stream);
+hipError_t launch_partition_pick(const uint64_t* from, const uint64_t* at, uint32_t count, uint64_t* out, hipStream_t stream);   // out[i] = from[at[i]]
+
 // UTF-8 lines as UTF-16 code units (gx_utf8.hip; the rule: gx_utf8.hpp).  The passes' device workspace, cut out of one allocation of
 // utf8_workspace_bytes(n) bytes:
 struct Utf8Ws {

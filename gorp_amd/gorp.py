@@ -737,6 +737,96 @@ class Gorp:
                                        out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, C.byref(k), C.byref(nbytes), C.byref(o)))
         return k.value, nbytes.value
 
+    def partition_lines(self, data, offsets, ids, rows=None, want=None):
+        """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every
+        sink's lines at once.  want: as for select_lines, or None = every outcome 0 .. 2K.  Returns what select_lines returns plus
+        group_lines, group_units (uint64[2K + 3]): outcome x's lines are out_offsets[group_lines[x] : group_lines[x + 1] + 1], its code
+        units data[group_units[x] : group_units[x + 1]]."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        n = len(offsets) - 1
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = dict(offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False)
+        # one pass: no partition is larger than its input
+        total = int(offsets[n] - offsets[0]) if n else 0
+        index = np.zeros(n, np.uint32)
+        out = np.zeros(total, data.dtype)
+        out_off = np.zeros(n + 1, offsets.dtype)
+        out_ids = np.zeros(ids.shape, ids.dtype)
+        out_caps = None if caps is None else np.zeros((n, 2 * self.max_groups), np.int32)
+        k, nbytes, group_lines, group_units = self.partition_lines_device(
+            ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), want, out_index_ptr=index.ctypes.data, out_data_ptr=out.ctypes.data,
+            out_offsets_ptr=out_off.ctypes.data, out_ids_ptr=out_ids.ctypes.data, out_caps_ptr=None if out_caps is None else out_caps.ctypes.data,
+            cap_lines=n, out_bytes_cap=total * data.itemsize, **args)
+        index, out, out_off, out_ids = index[:k], out[:nbytes // data.itemsize], out_off[:k + 1], out_ids[:k]
+        out_caps = None if out_caps is None else out_caps[:k]
+        if compact:
+            return index, out, out_off, out_ids, group_lines, group_units
+        if caps is not None:
+            return index, out, out_off, out_ids, out_caps, group_lines, group_units
+        return index, out, out_off, group_lines, group_units
+
+    def partition_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, want=None, out_index_ptr=None, out_data_ptr=None,
+                               out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0, offsets64=False,
+                               utf16=False, compact=0, stream=None, no_sync=False, device_pointers=True):
+        """gx_partition_lines on device pointers (ints); every output optional, none at all only asks for the sizes and the groups.
+        want=None keeps every outcome 0 .. 2K.  Returns (lines, bytes, group_lines, group_units).  GorpError with code GX_E_LIMIT when
+        a capacity is too small."""
+        mask = None if want is None else self.want_mask(want)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        o.no_sync = 1 if no_sync else 0
+        k, nbytes = C.c_uint64(0), C.c_uint64(0)
+        group_lines = np.zeros(2 * self.num_extractions + 3, np.uint64)
+        group_units = np.zeros(2 * self.num_extractions + 3, np.uint64)
+        _check(N.lib().gx_partition_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, None if mask is None else mask.ctypes.data,
+                                          out_index_ptr, out_data_ptr, out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap,
+                                          group_lines.ctypes.data, group_units.ctypes.data, C.byref(k), C.byref(nbytes), C.byref(o)))
+        return k.value, nbytes.value, group_lines, group_units
+
+    def text_to_jsonl_by_extraction(self, text, id_as=None, utf8=False):
+        """gx_text_to_jsonl_by_extraction on a host buffer: raw log text -> the JSON Lines of text_to_jsonl regrouped stably by extraction.
+        Returns (jsonl bytes, group_out uint64[K + 1], counts uint64[2K + 2], n_lines): extraction k's objects are
+        jsonl[group_out[k] : group_out[k + 1]]."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        ptr = raw.ctypes.data if raw.size else None
+        size = self.text_to_jsonl_by_extraction_device(ptr, raw.size, None, 0, id_as=id_as, utf8=utf8, device_pointers=False)[0]
+        out = np.zeros(max(1, size), np.uint8)
+        size, group_out, counts, n_lines = self.text_to_jsonl_by_extraction_device(ptr, raw.size, out.ctypes.data, size, id_as=id_as, utf8=utf8,
+                                                                                   device_pointers=False)
+        return out[:size].tobytes(), group_out, counts, n_lines
+
+    def text_to_jsonl_by_extraction_device(self, text_ptr, size, out_ptr, out_cap, id_as=None, utf8_passthrough=False, stream=None, utf8=False,
+                                           device_pointers=True):
+        """gx_text_to_jsonl_by_extraction on device buffers (ints); out_ptr=None only asks for the sizes.
+        Returns (text size, group_out, counts, n_lines)."""
+        self._send_meta()
+        K = self.num_extractions
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.utf8_passthrough = 1 if utf8_passthrough else 0
+        o.utf8 = 1 if utf8 else 0
+        o.stream = stream
+        group_out = np.zeros(K + 1, np.uint64)
+        counts = np.zeros(2 * K + 2, np.uint64)
+        size_out, nl = C.c_uint64(0), C.c_uint64(0)
+        _check(N.lib().gx_text_to_jsonl_by_extraction(self._h.ptr, text_ptr, size, id_as.encode("utf-8") if id_as is not None else None, out_ptr,
+                                                      out_cap, C.byref(size_out), group_out.ctypes.data, counts.ctypes.data, C.byref(nl),
+                                                      C.byref(o)))
+        return size_out.value, group_out, counts, nl.value
+
     def text_select(self, text, want=("unmatched", "exceptions"), utf8=False):
         """gx_text_select on a host buffer: raw log text -> the text of the lines whose outcome `want` names, terminators included.
         Returns (selected text bytes, counts uint64[2K + 2], n_lines)."""

@@ -224,6 +224,46 @@ public:
         out.resize(static_cast<size_t>(size));
         return out;
     }
+    // Every sink's lines at once (gx_partition_lines): the kept lines ordered by (outcome index, input line number) as a new batch,
+    // and where every outcome's group begins -- outcome x's lines are offsets[groupLines[x] .. groupLines[x + 1]], its bytes
+    // bytes[groupUnits[x] .. groupUnits[x + 1]) (2K + 3 entries each).  want == nullptr keeps every outcome 0 .. 2K.
+    struct Partition { std::vector<uint32_t> index; std::vector<uint8_t> bytes; std::vector<uint32_t> offsets; std::vector<uint64_t> groupLines, groupUnits; };
+    Partition partitionLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const Want* want = nullptr) const {
+        if (want && want->size() != 2 * extractions_.size() + 1) throw GorpError(GX_E_ARG, "partitionLines: the want mask has 2K + 1 entries");
+        // one pass: no partition is larger than its input
+        const uint64_t total = offsets[n] - offsets[0];
+        uint64_t k = 0, size = 0;
+        const size_t groups = 2 * extractions_.size() + 3;
+        Partition s{std::vector<uint32_t>(static_cast<size_t>(n) + 1), std::vector<uint8_t>(static_cast<size_t>(total) + 1), std::vector<uint32_t>(static_cast<size_t>(n) + 1),
+                    std::vector<uint64_t>(groups), std::vector<uint64_t>(groups)};
+        int rc = gx_partition_lines(h_, bytes, offsets, n, match_id, nullptr, want ? want->data() : nullptr, s.index.data(), s.bytes.data(), s.offsets.data(), nullptr,
+                                    nullptr, n, total, s.groupLines.data(), s.groupUnits.data(), &k, &size, nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        s.index.resize(static_cast<size_t>(k));
+        s.bytes.resize(static_cast<size_t>(size));
+        s.offsets.resize(static_cast<size_t>(k) + 1);
+        return s;
+    }
+    // Whole files: raw text in, one homogeneous JSON Lines stream per extraction out (gx_text_to_jsonl_by_extraction): textToJsonl's
+    // lines regrouped stably by extraction; extraction k's objects are the returned text's [groupOut[k], groupOut[k + 1]).
+    std::string textToJsonlByExtraction(const std::string& text, const char* idAs = nullptr, std::vector<uint64_t>* groupOut = nullptr,
+                                        std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (groupOut) groupOut->assign(extractions_.size() + 1, 0);
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t size = 0;
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(text.data());
+        int rc = gx_text_to_jsonl_by_extraction(h_, p, text.size(), idAs, nullptr, 0, &size, nullptr, nullptr, nullptr, &o);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        std::string out(static_cast<size_t>(size) + 1, '\0');
+        rc = gx_text_to_jsonl_by_extraction(h_, p, text.size(), idAs, reinterpret_cast<uint8_t*>(&out[0]), size, &size, groupOut ? groupOut->data() : nullptr,
+                                            counts ? counts->data() : nullptr, nLines, &o);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        out.resize(static_cast<size_t>(size));
+        return out;
+    }
     int maxGroups() const { return gx_max_groups(h_); }
     gx_handle* handle() const { return h_; }
 

@@ -341,6 +341,41 @@ int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64
 int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap,
                    uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
+ * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
+ * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
+ * group; bin 2K + 1 is counted out and never written.  The result is an ordinary CSR batch (out_bytes / out_offsets, out_ids and
+ * out_caps or whole result rows, out_index = the lines' numbers in the input) and composes with gx_extract_batch,
+ * gx_results_to_jsonl and gx_select_lines as any other.
+ *   group_lines  (host, optional, uint64_t[2K + 3]) an exclusive prefix: outcome x's lines are the output lines
+ *                group_lines[x] .. group_lines[x + 1]; an outcome that is not wanted and bin 2K + 1 are empty groups, and
+ *                group_lines[2K + 2] == *n_out;
+ *   group_units  (host, optional, uint64_t[2K + 3]) the same in code units of out_bytes: out_offsets read at those lines, so that a
+ *                caller slices out_bytes per sink without touching device memory.
+ * *n_out and *bytes_out (host; bytes, also with utf16) and the two group arrays are always set; no output at all (all five NULL) only
+ * asks for them.  GX_E_LIMIT when cap_lines or out_bytes_cap is too small: the sizes are set and nothing has been written.  The passes
+ * on opts->stream -- keys, a stable radix sort of the line numbers (one six-bit digit for K <= 31, two up to K = 2047, three beyond),
+ * scan, copy -- read the id column once, whatever K is, and there is ONE small synchronisation, between scan and copy, where the host
+ * reads the sizes and the groups; opts->no_sync (device pointers) then means: do not wait for the copy pass.  n of 2^32 and more and a
+ * line of 2^32 code units and more are refused (GX_E_LIMIT).  The device workspace stays on the handle, shared with gx_select_lines:
+ * 32 bytes per INPUT line (destination offsets 8, two key and two line-number arrays of the sort 16, lengths before and behind the
+ * sort 8; gx_select_lines needs 21) plus 768 bytes of counts per 2 048 lines -- 320 MB after a batch of 10 M lines, until gx_destroy.
+ * Host buffers (device_pointers = 0) are staged; the text only when out_bytes is given: a size query sends the ids and offsets alone. */
+int gx_partition_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                       const uint8_t* want, uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps,
+                       uint64_t cap_lines, uint64_t out_bytes_cap, uint64_t* group_lines, uint64_t* group_units, uint64_t* n_out,
+                       uint64_t* bytes_out, const gx_batch_opts* opts);
+
+/* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
+ * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
+ * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
+ * out[group_out[k] .. group_out[k + 1]), group_out[K] == *out_size.  counts (optional, uint64_t[2K + 2], host) receives the
+ * histogram over the outcome index as gx_text_select gives it, *n_lines (optional) the number of lines; out == NULL only asks for the
+ * sizes; GX_E_LIMIT when out_cap is too small.  Options and limits are gx_text_to_jsonl's: device_pointers (text -- 16-byte aligned
+ * -- and out on the device), stream, utf8_passthrough, utf8 (1); text of 4 GiB and more must be split by the caller. */
+int gx_text_to_jsonl_by_extraction(gx_handle* h, const uint8_t* text, uint64_t size, const char* id_as, uint8_t* out, uint64_t out_cap,
+                                   uint64_t* out_size, uint64_t* group_out, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* Compact result rows for transport between GPUs (the gather of SURVEY.md section 8(e)): per line one int16 match id
  * followed by `slots` (= 2 * gx_max_groups) uint16 offsets, 0xFFFF = unset: 2 + 2*slots bytes instead of 4 + 4*slots.
  * Device buffers only.  *n_overflow (host) receives the number of offsets above 65534, which do not fit (they are
