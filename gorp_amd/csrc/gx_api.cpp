@@ -279,6 +279,21 @@ static void put_image(gx_handle* h, void* dst, const void* host, size_t bytes, c
     GX_HIP(hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice));
 }
 
+// The thread lists of the extractions that run as programs (gx_kernels.hip: pike_capture): a lane's ints -- the largest program's
+// lists, stack, marks and boundaries, then the winning thread's boundaries -- and as many workgroups of 256 lanes as the scratch
+// budget holds them for (64 at most, one at least).
+void pike_sizing(const Tables& T, uint32_t* lane_ints, uint32_t* blocks) {
+    uint32_t ints = 0;
+    for (size_t k = 0; k < T.rules.size(); ++k) {
+        const uint32_t ni = T.pike_off[k + 1] - T.pike_off[k], W = 1u + 2u * static_cast<uint32_t>(T.rules[k].n_groups);
+        if (ni) ints = std::max(ints, 2u * ni * W + 3u * (2u * ni + 2u) + ni + 2u * static_cast<uint32_t>(T.rules[k].n_groups));
+    }
+    ints += 2u * static_cast<uint32_t>(T.max_groups) + 2u;
+    *lane_ints = ints;
+    *blocks = static_cast<uint32_t>(std::min<uint64_t>(GX_PIKE_BLOCKS, GX_PIKE_SCRATCH_BYTES / (static_cast<uint64_t>(ints) * 4u * 256u)));
+    if (*blocks == 0) *blocks = 1;
+}
+
 void upload(gx_handle* h) {
     const Tables& T = h->T;
     int count = 0;
@@ -330,14 +345,7 @@ void upload(gx_handle* h) {
         o_pike_off = img.put(T.pike_off);
         o_pike_code = img.put(T.pike_code);
         o_pike_sets = img.put(T.pike_sets);
-        for (size_t k = 0; k < T.rules.size(); ++k) {
-            const uint32_t ni = T.pike_off[k + 1] - T.pike_off[k], W = 1u + 2u * static_cast<uint32_t>(T.rules[k].n_groups);
-            if (ni) pike_lane_ints = std::max(pike_lane_ints, 2u * ni * W + 3u * (2u * ni + 2u) + ni + 2u * static_cast<uint32_t>(T.rules[k].n_groups));
-        }
-        pike_lane_ints += 2u * static_cast<uint32_t>(T.max_groups) + 2u;
-        // as many workgroups of 256 lanes as the scratch budget holds thread lists for (64 at most, one at least)
-        pike_blocks = static_cast<uint32_t>(std::min<uint64_t>(GX_PIKE_BLOCKS, GX_PIKE_SCRATCH_BYTES / (static_cast<uint64_t>(pike_lane_ints) * 4u * 256u)));
-        if (pike_blocks == 0) pike_blocks = 1;
+        pike_sizing(T, &pike_lane_ints, &pike_blocks);
         if (static_cast<uint64_t>(pike_lane_ints) * 4u * (256u * pike_blocks + 1u) > (1ull << 30))
             throw GxError(GX_E_LIMIT, "capture program too large to run as it is (the thread lists of one workgroup beyond 1 GiB)");
     }
@@ -759,7 +767,7 @@ int gx_create_from_patterns(const char* const* automaton_rx, const char* const* 
             if (jdk_rx) j.push_back(utf8_to_u16(jdk_rx[i]));
         }
         std::unique_ptr<gx_handle> h(new gx_handle());
-        h->T = compile_tables(a, jdk_rx ? &j : nullptr);
+        h->T = compile_tables(a, jdk_rx ? &j : nullptr, (flags & GX_CREATE_PROGRAMS) != 0);
         return finish_create(h, flags, out);
     });
 }
@@ -834,6 +842,12 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     case 26: return I.hop_reason;
     case 28: return static_cast<int64_t>(h->svc.enabled ? h->svc.launches : -1);
     case 27: { int64_t c = 0; for (auto& r : h->T.rules) c += r.pike ? 1 : 0; return c; }
+    case 35: {   // workgroups a per-line launch is kept within: GxDev::pike_blocks (a host-only handle: what it would be)
+        if (!h->T.has_pike()) return -1;
+        uint32_t lane_ints = 0, blocks = 0;
+        pike_sizing(h->T, &lane_ints, &blocks);
+        return static_cast<int64_t>(blocks);
+    }
     case 23: return I.hop[1].ok ? static_cast<int64_t>(I.hop[1].img.full.n_hot) : 0; // ... whose records are in LDS
     case 19: { GxLds L; return plan_hop_slice_launch(I, &L) ? static_cast<int64_t>(L.nwaves) : 0; }  // ... of the hop slice kernel
     case 9: return !I.tile_ok ? 0 : !I.has_mo ? gx_stat(h, 7) : I.dense[1].L.tier == 3 ? 4 : I.dense[1].L.tier == 2 ? 3 : I.dense[1].L.tier == 1 ? 2 : 1;
@@ -2321,7 +2335,7 @@ int gx_create_from_definition(const char* definition_text, const char* source_re
         }
         std::unique_ptr<gx_handle> h(new gx_handle());
         try {
-            h->T = compile_tables(a, &j);
+            h->T = compile_tables(a, &j, (flags & GX_CREATE_PROGRAMS) != 0);
         } catch (GxError& e) {
             // core/Gorp.java:84-90
             if (e.code == GX_E_DEVICE || e.code == GX_E_NOMEM) throw;

@@ -787,7 +787,7 @@ private:
 }  // namespace
 
 // ===========================================================================
-Tables compile_tables(const std::vector<ustr>& automaton_rx, const std::vector<ustr>* jdk_rx) {
+Tables compile_tables(const std::vector<ustr>& automaton_rx, const std::vector<ustr>* jdk_rx, bool prefer_programs) {
     const size_t n = automaton_rx.size();
     if (n == 0) throw GxError(GX_E_ARG, "no extractions");
     if (jdk_rx && jdk_rx->size() != n) throw GxError(GX_E_ARG, "pattern list sizes differ");
@@ -869,17 +869,25 @@ Tables compile_tables(const std::vector<ustr>& automaton_rx, const std::vector<u
         bool any_pike = false;
         for (size_t k = 0; k < n; ++k) {
             MultiProg mp = join_programs({&jprog[k]});
-            const OpListPool ops_before = ops;
-            const std::vector<uint16_t> fin_before = T.fin_tags;
-            try {
-                TdfaBuilder b(mp, C, ops, T.fin_tags, nullptr, PROGRAM_INSTEAD_STATES);
-                T.rules.push_back(b.build());
-            } catch (GxError& e) {
-                if (e.code != GX_E_LIMIT || C.ncls > 256 || 2 * jprog[k].ngroups > MAX_TAGS) throw;
-                // Too large ahead of time.  java.util.regex backtracks at run time and never builds anything: the extraction keeps its
-                // program and the kernels run it as it is (gx_kernels.hip: pike_capture).
-                ops = ops_before;
-                T.fin_tags = fin_before;
+            // what can be run as a program at all: its sets are 256-bit masks over the classes, its threads carry MAX_TAGS boundaries
+            const bool can_be_program = C.ncls <= 256 && 2 * jprog[k].ngroups <= MAX_TAGS;
+            bool built = false;
+            if (!(prefer_programs && can_be_program)) {   // (asked for as a program: no automaton is built only to be thrown away)
+                const OpListPool ops_before = ops;
+                const std::vector<uint16_t> fin_before = T.fin_tags;
+                try {
+                    TdfaBuilder b(mp, C, ops, T.fin_tags, nullptr, PROGRAM_INSTEAD_STATES);
+                    T.rules.push_back(b.build());
+                    built = true;
+                } catch (GxError& e) {
+                    if (e.code != GX_E_LIMIT || !can_be_program) throw;
+                    ops = ops_before;
+                    T.fin_tags = fin_before;
+                }
+            }
+            if (!built) {
+                // Too large ahead of time (or GX_CREATE_PROGRAMS).  java.util.regex backtracks at run time and never builds anything: the
+                // extraction keeps its program and the kernels run it as it is (gx_kernels.hip: pike_capture).
                 RuleTables R;
                 R.n_groups = jprog[k].ngroups;
                 R.n_states = 1;

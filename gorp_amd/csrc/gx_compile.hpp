@@ -76,7 +76,9 @@ struct Tables {
 };
 
 // jdk == nullptr: match automaton only.
-Tables compile_tables(const std::vector<ustr>& automaton_rx, const std::vector<ustr>* jdk_rx);
+// prefer_programs (GX_CREATE_PROGRAMS): every extraction that can be run as a program keeps its program (RuleTables::pike) and no
+// capture automaton is attempted for it; without it the size of that automaton decides.
+Tables compile_tables(const std::vector<ustr>& automaton_rx, const std::vector<ustr>* jdk_rx, bool prefer_programs = false);
 
 std::vector<uint8_t> pack_blob(const Tables& t);
 Tables unpack_blob(const void* data, size_t size);

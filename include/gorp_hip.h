@@ -62,6 +62,11 @@ enum {
 #define GX_CREATE_TIER_HOP  64u    /* build the hop tier's tables (run + literal chain per state, hot states in LDS, dense rows in
                                       global memory as the backstop) even when the dense rows fit LDS; the default for capture
                                       batches when they do not */
+#define GX_CREATE_PROGRAMS  256u   /* every extraction that can be run as a program (at most 256 character classes, at most 32 groups)
+                                      keeps its program and no capture automaton is built for it: the per-line kernel runs it as it
+                                      does an extraction whose automaton would be too large (gx_stat(h, 27)).  Any other extraction keeps
+                                      its automaton.  Without it the size of that automaton alone decides.  gx_create_from_blob and
+                                      gx_create_on_devices ignore it: the blob says what it holds. */
 
 #define GX_CREATE_RESIDENT_ONE 128u /* gx_extract_one_utf16 without a kernel launch per call: while such calls keep coming the handle keeps
                                       one wave resident on the device (tables in LDS) that takes the line out of pinned host memory and
@@ -123,7 +128,9 @@ int32_t gx_max_groups(const gx_handle* h);
  * whose regexp is therefore RUN as a program, thread lists in priority order (exact, linear in line x program; such a definition's
  * batches go through the per-line kernel); 28 = times the resident one-line wave was started (GX_CREATE_RESIDENT_ONE; -1: the
  * handle has none); 33 / 34 = for the most recent gx_batch_opts.utf8 batch (gx_extract_batch, gx_text_to_jsonl, gx_text_select): the lines that
- * held a byte >= 0x80 and were walked again as Strings, and the UTF-16 code units made for them */
+ * held a byte >= 0x80 and were walked again as Strings, and the UTF-16 code units made for them;
+ * 35 = the workgroups of 256 lanes a per-line launch of this handle is kept within, every lane that may run a program having its own
+ * thread lists (-1: the handle has no extraction that runs as a program) */
 int64_t gx_stat(const gx_handle* h, int32_t which);
 
 typedef struct gx_batch_opts {

@@ -363,6 +363,17 @@ int main(int argc, char** argv) {
             auto blob = pack_blob(T);
             Tables U = unpack_blob(blob.data(), blob.size());
             (void)U;
+            {   // GX_CREATE_PROGRAMS: every extraction that can be one kept as a program; the blob carries them and reads back the same
+                Tables P = compile_tables(au, &jd, true);
+                const auto pblob = pack_blob(P);
+                const Tables Q = unpack_blob(pblob.data(), pblob.size());
+                size_t programs = 0;
+                for (auto& r : Q.rules) programs += r.pike ? 1 : 0;
+                if (pack_blob(Q) != pblob || (P.ncls <= 256 && programs != Q.rules.size())) {
+                    printf("programs: %s does not read back as it was written\n", argv[a]);
+                    return 1;
+                }
+            }
             for (uint32_t flags : FLAG_SETS) {
                 plans += check_plans(T, flags);
                 if (pin) printf("pin %s %u:%s\n", argv[a], flags, pinned_plans(T, flags).c_str());

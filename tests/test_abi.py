@@ -90,3 +90,12 @@ def test_unpack_rows_on_the_host():
     r8 = np.array([[127, 0, 254, 0xFF, 0xFF], [0xFF, 0xFF, 0xFF, 0xFF, 0xFF], [0x80, 1, 2, 3, 4]], np.uint8)
     m, c = unpack_rows(r8)
     assert m.tolist() == [127, -1, -128] and c.tolist() == [[0, 254, -1, -1], [-1, -1, -1, -1], [1, 2, 3, 4]]
+
+
+def test_create_flags_of_the_header_and_the_binding_agree():
+    """Every GX_CREATE_* bit of include/gorp_hip.h has the same value in gorp_amd/_native.py, and no two share a bit."""
+    text = open(os.path.join(ROOT, "include", "gorp_hip.h")).read()
+    header = {name: int(value) for name, value in re.findall(r"^#define\s+(GX_CREATE_[A-Z0-9_]+)\s+(\d+)u\b", text, flags=re.M)}
+    assert "GX_CREATE_PROGRAMS" in header and len(header) >= 9
+    assert header == {name: getattr(N, name) for name in dir(N) if name.startswith("GX_CREATE_")}
+    assert sum(header.values()) == (1 << len(header)) - 1

@@ -14,19 +14,40 @@ from gorp_amd.gorp import DefinitionParseException, FlattenedExtraction, Gorp, G
 from oracle import oracle as O
 
 
-def product_blob(autom, jdk):
+PROGRAMS = N.GX_CREATE_PROGRAMS
+
+
+def product_blob(autom, jdk, create_flags=0):
+    """The blob of a host-only handle.  With GX_CREATE_PROGRAMS every extraction of these tests' grammars can be run as a program
+    (none has more than 256 classes or 32 groups), so one that kept an automaton is a failure; the blob carries the programs and a
+    handle made from it has them again."""
     from gorp_amd.gorp import _create
-    h = _create(autom, jdk, N.GX_CREATE_HOST_ONLY)
+    h = _create(autom, jdk, N.GX_CREATE_HOST_ONLY | create_flags)
     # the table-image builders run for host-only handles too; forcing the record tier (fused and two-pass) runs its
     # self-check -- every (state, class) of the range records against the dense rows -- on this definition as well
     # (a definition with an extraction that is run as a program -- gx_stat 27 -- has the per-line kernel alone: tier 0)
     for flags in (N.GX_CREATE_TIER_RECORDS, N.GX_CREATE_TIER_RECORDS | N.GX_CREATE_NO_FUSED):
-        hf = _create(autom, jdk, N.GX_CREATE_HOST_ONLY | flags)
+        hf = _create(autom, jdk, N.GX_CREATE_HOST_ONLY | flags | create_flags)
         assert N.lib().gx_stat(hf.ptr, 7) in ((0,) if N.lib().gx_stat(hf.ptr, 27) else (2, 3, 4))
     n = N.lib().gx_blob_size(h.ptr)
     out = np.zeros(n, np.uint8)
     assert N.lib().gx_blob_copy(h.ptr, out.ctypes.data, n) == 0
-    return Blob(out)
+    b = Blob(out)
+    if create_flags & PROGRAMS and jdk is not None:
+        import ctypes as C
+        assert all(b.is_pike(k) for k in range(len(jdk))), [b.is_pike(k) for k in range(len(jdk))]
+        assert not b.union_ok
+        assert N.lib().gx_stat(h.ptr, 27) == len(jdk)
+        h2 = C.c_void_p()   # (the flag means nothing to a blob: it says what it holds)
+        assert N.lib().gx_create_from_blob(out.ctypes.data, n, N.GX_CREATE_HOST_ONLY, C.byref(h2)) == 0
+        try:
+            assert N.lib().gx_stat(h2, 27) == len(jdk) and N.lib().gx_blob_size(h2) == n
+            again = np.zeros(n, np.uint8)
+            assert N.lib().gx_blob_copy(h2, again.ctypes.data, n) == 0
+            assert again.tobytes() == out.tobytes()
+        finally:
+            N.lib().gx_destroy(h2)
+    return b
 
 
 def extract_both_ways(b, units):
@@ -37,14 +58,14 @@ def extract_both_ways(b, units):
     return got
 
 
-def both(extractions):
+def both(extractions, create_flags=0):
     fl = [FlattenedExtraction(e["name"], e["pieces"], e.get("append")) for e in extractions]
     built = [f.build() for f in fl]
     autom, jdk = [b[0] for b in built], [b[1] for b in built]
     # the product's RegexHelper must agree with the oracle's restatement of it
     for e, b in zip(extractions, built):
         assert O.build_regex_strings(e["pieces"]) == b
-    return product_blob(autom, jdk), O.OracleGorp(autom, jdk)
+    return product_blob(autom, jdk, create_flags), O.OracleGorp(autom, jdk)
 
 
 def test_regexhelper_golden(golden):
@@ -92,9 +113,9 @@ def test_polymatch_golden(golden):
             assert b.match(units_of(c["input"])) == c["match"]
 
 
-def test_full_extraction_golden(golden):
+def test_full_extraction_golden(golden, create_flags=0):
     for t in golden("full_extraction")["tests"]:
-        b, orc = both(t["extractions"])
+        b, orc = both(t["extractions"], create_flags)
         for c in t["cases"]:
             got = extract_both_ways(b, units_of(c["input"]))
             assert got == orc.extract(c["input"]), (t["name"], c["input"])
@@ -103,14 +124,22 @@ def test_full_extraction_golden(golden):
                 assert t["extractions"][got[0]]["name"] == c["id"]
 
 
-def test_configs_golden(golden):
+def test_full_extraction_golden_as_programs(golden):
+    test_full_extraction_golden(golden, PROGRAMS)
+
+
+def test_configs_golden(golden, create_flags=0):
     g = golden("configs")
     for key in ("simple_grp", "readme_3"):
-        b, orc = both(g[key]["extractions"])
+        b, orc = both(g[key]["extractions"], create_flags)
         for c in g[key]["cases"]:
             u = units_of(c["input"])
             assert b.match(u) == c["match"]
             assert extract_both_ways(b, u) == orc.extract(c["input"])
+
+
+def test_configs_golden_as_programs(golden):
+    test_configs_golden(golden, PROGRAMS)
 
 
 def test_fused_automaton_is_built_for_the_benchmark_definitions(golden):
@@ -287,7 +316,7 @@ def construct_both(make_product, make_oracle, tally):
     return None
 
 
-def test_random_definitions_match_and_extract():
+def test_random_definitions_match_and_extract(create_flags=0):
     """Whole-path differential: random flattened extractions (1-4 per definition)."""
     rng = random.Random(1234)
     n_defs = n_lines = n_hits = n_exc = 0
@@ -302,7 +331,7 @@ def test_random_definitions_match_and_extract():
                 assert O.build_regex_strings(e["pieces"]) == b
             return [b[0] for b in built], [b[1] for b in built]
 
-        pair = construct_both(lambda: product_blob(*regexes()), lambda: O.OracleGorp(*regexes()), tally)
+        pair = construct_both(lambda: product_blob(*regexes(), create_flags), lambda: O.OracleGorp(*regexes()), tally)
         if pair is None:
             continue
         b, orc = pair
@@ -322,6 +351,12 @@ def test_random_definitions_match_and_extract():
     print("refusals:", {k: v for k, v in tally.items() if not k.endswith("_messages")})
     assert tally.get("product_only", 0) == 0, tally.get("product_only_messages")
     assert tally.get("oracle_only", 0) == 0, tally.get("oracle_only_messages")
+
+
+def test_random_definitions_match_and_extract_as_programs():
+    """The same definitions and lines (the match automaton the lines are sampled from does not depend on the flag), every extraction
+    run as its program: the Pike VM's contract against the backtracking oracle."""
+    test_random_definitions_match_and_extract(PROGRAMS)
 
 
 def test_refusal_record_is_what_the_library_refuses():
@@ -377,7 +412,7 @@ def _sample_accepted(rng, rx, tries=40):
     return out
 
 
-def test_random_raw_regex_pairs_capture_parity():
+def test_random_raw_regex_pairs_capture_parity(create_flags=0):
     """Capture automaton vs the backtracking restatement on raw JDK-dialect regexes,
     including lazy quantifiers and groups under quantifiers/alternations."""
     rng = random.Random(99)
@@ -388,7 +423,7 @@ def test_random_raw_regex_pairs_capture_parity():
         jdk = pat  # capturing groups kept as written
         autom = ".*"  # let every line through the matcher so the capture automaton decides
         try:
-            b = product_blob([autom], [jdk])
+            b = product_blob([autom], [jdk], create_flags)
             orc = O.OracleGorp([autom], [jdk])
         except (O.OracleError, DefinitionParseException):
             continue
@@ -402,6 +437,12 @@ def test_random_raw_regex_pairs_capture_parity():
     assert checked > 20000 and matched > 2000
 
 
+def test_random_raw_regex_pairs_capture_parity_as_programs():
+    """... and the program itself, run as it is: lazy against greedy priority, alternation order, counted repetitions, groups under
+    quantifiers and alternations, groups that stay unset."""
+    test_random_raw_regex_pairs_capture_parity(PROGRAMS)
+
+
 def test_utf16_lines_and_high_classes():
     autom = ["[^a]+", "é+", "中.", "[Ā-࿿]x"]
     b = product_blob(autom, None)
@@ -410,7 +451,7 @@ def test_utf16_lines_and_high_classes():
         assert b.match(units_of(ln)) == orc.match(ln), ln
 
 
-def test_dialect_disagreement_yields_exception_code():
+def test_dialect_disagreement_yields_exception_code(create_flags=0):
     for pieces, line, want in [
         ([["text", "a"], ["extractor", "x", [["pattern", ".*"]]], ["text", "b"]], "a\rb", -2),
         ([["text", "k"], ["pattern", "\\s"], ["text", "v"]], "k\x08v", -2),
@@ -418,10 +459,42 @@ def test_dialect_disagreement_yields_exception_code():
         ([["pattern", "[(]x"]], "(x", 0),
         ([["pattern", "[(]x"]], "?x", -1),
     ]:
-        b, orc = both([{"name": "r", "pieces": pieces}])
+        b, orc = both([{"name": "r", "pieces": pieces}], create_flags)
         got = extract_both_ways(b, units_of(line))
         assert got == orc.extract(line)
         assert got[0] == want, (pieces, line)
+
+
+def test_dialect_disagreement_yields_exception_code_as_programs():
+    """-2 - k from the program's own refusal (the match automaton said yes)."""
+    test_dialect_disagreement_yields_exception_code(PROGRAMS)
+
+
+def test_programs_flag_is_a_request_not_a_promise():
+    """GX_CREATE_PROGRAMS leaves alone what cannot be run as a program -- more than 256 character classes: the automaton as without
+    the flag -- and a matcher without capture regexps has nothing to run."""
+    from gorp_amd.gorp import _create
+    autom = ["".join("[%s-%s]?" % (chr(0x100 + 2 * i), chr(0x101 + 2 * i)) for i in range(300))]
+    plain, flagged = _create(autom, autom, N.GX_CREATE_HOST_ONLY), _create(autom, autom, N.GX_CREATE_HOST_ONLY | PROGRAMS)
+    assert N.lib().gx_stat(plain.ptr, 1) > 256
+    assert N.lib().gx_stat(flagged.ptr, 27) == 0 and N.lib().gx_stat(flagged.ptr, 35) == -1
+
+    def blob(h):
+        out = np.zeros(N.lib().gx_blob_size(h.ptr), np.uint8)
+        assert N.lib().gx_blob_copy(h.ptr, out.ctypes.data, len(out)) == 0
+        return out.tobytes()
+    assert blob(plain) == blob(flagged)
+    m = _create(["a+", "b"], None, N.GX_CREATE_HOST_ONLY | PROGRAMS)
+    assert N.lib().gx_stat(m.ptr, 27) == 0 and N.lib().gx_stat(m.ptr, 8) == 0
+    # a host-only handle has no launch to limit, but says how many workgroups one would be kept within
+    g = Gorp.construct(_readme3(), host_only=True, flags=PROGRAMS)
+    assert g.stat(27) == 3 and g.stat(35) >= 1
+    assert Gorp.construct(_readme3(), host_only=True).stat(35) == -1
+
+
+def _readme3():
+    from gorp_amd import workloads as W
+    return W.readme3_definition()
 
 
 def test_tile_image_tiers_by_definition_size():
