@@ -26,6 +26,8 @@ GX_CREATE_TIER_RECORDS_GLOBAL = 32
 GX_CREATE_TIER_HOP = 64
 GX_CREATE_RESIDENT_ONE = 128
 GX_CREATE_PROGRAMS = 256
+(GX_WHERE_SET, GX_WHERE_EQ, GX_WHERE_PREFIX, GX_WHERE_SUFFIX, GX_WHERE_CONTAINS, GX_WHERE_INT_EQ, GX_WHERE_INT_LT, GX_WHERE_INT_LE, GX_WHERE_INT_GT,
+ GX_WHERE_INT_GE) = range(10)
 GX_KERNEL_AUTO, GX_KERNEL_TILES, GX_KERNEL_SLICES, GX_KERNEL_PER_LINE, GX_KERNEL_LANES, GX_KERNEL_HOPS, GX_KERNEL_HOP_SLICES = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/gorp_hip.h declares
@@ -44,6 +46,7 @@ SYMBOLS = [
     "gx_create_on_devices", "gx_gather_rows", "gx_gather_wait", "gx_release_scratch",
     "gx_count_outcomes", "gx_select_lines", "gx_text_select", "gx_utf8_to_utf16",
     "gx_partition_lines", "gx_text_to_jsonl_by_extraction",
+    "gx_select_lines_where", "gx_text_select_where",
 ]
 
 
@@ -67,6 +70,11 @@ class gx_batch_opts(C.Structure):
         ("utf8", C.c_uint32),
         ("utf8_line_flags", C.c_void_p),
     ]
+
+
+class gx_where_term(C.Structure):
+    _fields_ = [("extraction", C.c_int32), ("group", C.c_int32), ("op", C.c_uint32), ("negate", C.c_uint32), ("text", C.c_void_p),
+                ("text_units", C.c_uint32), ("number", C.c_int64)]
 
 
 class gx_device_shard(C.Structure):
@@ -216,6 +224,13 @@ def lib():
     L.gx_text_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
                                  C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_select.restype = C.c_int
+    L.gx_select_lines_where.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gx_where_term),
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_select_lines_where.restype = C.c_int
+    L.gx_text_select_where.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(gx_where_term), C.c_uint32, C.c_void_p, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_select_where.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

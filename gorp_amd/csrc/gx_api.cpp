@@ -4,6 +4,7 @@
 // every extract/match entry point runs the HIP kernels or fails with GX_E_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstddef>
@@ -22,6 +23,7 @@
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
+#include "gx_where.hpp"
 
 using namespace gx;
 
@@ -255,6 +257,7 @@ struct gx_handle {
     // gx_text_to_jsonl_by_extraction (PartWs), kept between calls and used under `mu`.  A no_sync gx_select_lines or gx_partition_lines
     // leaves its copy pass reading it: the next user's stream waits for select_event first.
     GrowBuf select_ws;
+    GrowBuf where_image;   // gx_select_lines_where's terms and literals (WhereHead, gx_where.hpp); read by its flags pass alone
     Event select_event;
     bool select_pending = false;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
@@ -1241,8 +1244,69 @@ struct Selected {
     SelectWs w;
     uint64_t lines = 0, units = 0;
 };
+// The terms of a gx_select_lines_where call as its flags pass reads them (gx_where.hpp: WhereHead, then the literals in the batch's
+// code units), checked against the handle; `none` when the call has no terms.  Needs no device.
+struct WhereImage {
+    std::vector<uint8_t> bytes;   // empty: no terms
+    bool none() const { return bytes.empty(); }
+};
+static WhereImage where_image(const gx_handle* h, const gx_where_term* terms, uint32_t n_terms, bool wide, const std::string& name) {
+    WhereImage img;
+    if (n_terms == 0) return img;
+    if (!terms) throw GxError(GX_E_ARG, name + ": terms is NULL");
+    if (n_terms > WHERE_MAX_TERMS) throw GxError(GX_E_LIMIT, name + ": more than 64 terms");
+    const int32_t K = static_cast<int32_t>(h->T.n_rules);
+    const size_t unit = wide ? 2 : 1;
+    std::vector<uint32_t> order(n_terms);
+    size_t lit_units = 0;
+    for (uint32_t t = 0; t < n_terms; ++t) {
+        const gx_where_term& m = terms[t];
+        order[t] = t;
+        if (m.extraction < 0 || m.extraction >= K) throw GxError(GX_E_ARG, name + ": a term's extraction is not in [0, K)");
+        if (m.group < 0 || m.group >= gx_num_groups(h, m.extraction)) throw GxError(GX_E_ARG, name + ": a term's group is not one of its extraction's");
+        if (m.op >= WHERE_OPS) throw GxError(GX_E_ARG, name + ": a term's op is no GX_WHERE_* value");
+        const bool text_op = m.op >= WHERE_EQ && m.op <= WHERE_CONTAINS;
+        if (text_op && m.text_units > WHERE_MAX_TEXT) throw GxError(GX_E_LIMIT, name + ": a term's text has more than 255 code units");
+        if (text_op && m.text_units && !m.text) throw GxError(GX_E_ARG, name + ": a term's text is NULL");
+        if (text_op) lit_units += m.text_units;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return terms[a].extraction < terms[b].extraction; });
+    img.bytes.assign((sizeof(WhereHead) + lit_units * unit + 15) & ~static_cast<size_t>(15), 0);
+    WhereHead head{};
+    head.n_terms = n_terms;
+    head.lit_units = static_cast<uint32_t>(lit_units);
+    uint8_t* lits = img.bytes.data() + sizeof(WhereHead);
+    size_t at = 0;
+    for (uint32_t q = 0; q < n_terms; ++q) {
+        const gx_where_term& m = terms[order[q]];
+        if (head.n_ext == 0 || head.ext[head.n_ext - 1] != static_cast<uint32_t>(m.extraction)) {
+            head.ext[head.n_ext] = static_cast<uint32_t>(m.extraction);
+            head.first[head.n_ext++] = static_cast<uint8_t>(q);
+        }
+        const bool text_op = m.op >= WHERE_EQ && m.op <= WHERE_CONTAINS;
+        WhereTerm& d = head.term[q];
+        d.group = static_cast<uint16_t>(m.group);
+        d.op = static_cast<uint8_t>(m.op);
+        d.negate = m.negate ? 1 : 0;
+        d.number = m.number;
+        d.lit_at = static_cast<uint16_t>(at);
+        d.lit_len = text_op ? static_cast<uint16_t>(m.text_units) : 0;
+        if (d.lit_len) memcpy(lits + at * unit, m.text, d.lit_len * unit);
+        at += d.lit_len;
+    }
+    head.first[head.n_ext] = static_cast<uint8_t>(n_terms);
+    memcpy(img.bytes.data(), &head, sizeof(head));
+    return img;
+}
+// what a flags pass with terms reads besides the ids and offsets (device pointers; caps: dense capture rows or nullptr)
+struct WhereBatch {
+    const WhereImage* image;
+    const void* data;
+    const int32_t* caps;
+    bool wide;
+};
 static Selected select_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const uint8_t* want,
-                     uint64_t* counts, hipStream_t stream) {
+                     uint64_t* counts, hipStream_t stream, const WhereBatch* where = nullptr) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
     if (h->select_pending) {
         GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
@@ -1251,7 +1315,16 @@ static Selected select_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32
     Selected s;
     s.w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, offsets != nullptr)), n, K, offsets != nullptr);
     if (offsets) GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
-    GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+    if (where && !where->image->none()) {
+        // (the terms and literals go beside the mask, the same way: a small transfer from pageable memory)
+        const std::vector<uint8_t>& img = where->image->bytes;
+        void* d_img = h->where_image.get(img.size());
+        GX_HIP(hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, stream));
+        const WhereArgs a{where->data, where->wide ? 1 : 0, where->caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(img.size())};
+        GX_HIP(launch_where_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, counts != nullptr, s.w, stream));
+    } else {
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+    }
     uint32_t status = 0;
     if (offsets) {
         GX_HIP(hipMemcpyAsync(&s.lines, s.w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -1286,21 +1359,33 @@ int gx_count_outcomes(gx_handle* h, const void* ids, uint64_t n, uint64_t* count
     });
 }
 
-int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const uint8_t* want,
-                    uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines,
-                    uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected, const gx_batch_opts* opts) {
+// gx_select_lines and gx_select_lines_where (where: the latter, whose refusals come before the look at the device)
+static int select_lines_call(const char* fn, bool where, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                             const uint8_t* want, const gx_where_term* terms, uint32_t n_terms, uint32_t* out_index, void* out_bytes, void* out_offsets,
+                             void* out_ids, int32_t* out_caps, uint64_t cap_lines, uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected,
+                             const gx_batch_opts* opts) {
+    const std::string name = fn;
     return guarded([&]() -> int {
-        if (!h || !want || !offsets || !n_selected || !bytes_selected || (n && !ids)) return fail(GX_E_ARG, "gx_select_lines: bad argument");
+        if (!h || !want || !offsets || !n_selected || !bytes_selected || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        WhereImage image;
+        if (where) {
+            const gx_batch_opts wo = read_opts(opts);
+            uint32_t units = 1;
+            const RowFormat wf = id_format(h, wo, &units);
+            if (wo.utf8 == 2) return fail(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are compared in the units the offsets count)");
+            image = where_image(h, terms, n_terms, wo.utf16 != 0, name);
+            if (!image.none() && wf == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": terms on dense ids need caps");
+        }
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        if (n >= (1ull << 32)) return fail(GX_E_LIMIT, "gx_select_lines: line numbers are 32 bits; split batches of 4 G lines and more");
+        if (n >= (1ull << 32)) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 4 G lines and more");
         const gx_batch_opts o = read_opts(opts);
         uint32_t row_units = 1;
         const RowFormat fmt = id_format(h, o, &row_units);
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         if (fmt != ROWS_DENSE) { caps = nullptr; out_caps = nullptr; }
-        if (out_caps && slots && n && !caps) return fail(GX_E_ARG, "gx_select_lines: out_caps without caps");
+        if (out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
         if (!slots) out_caps = nullptr;
-        if (o.no_sync && !o.device_pointers) return fail(GX_E_ARG, "gx_select_lines: no_sync needs device pointers");
+        if (o.no_sync && !o.device_pointers) return fail(GX_E_ARG, name + ": no_sync needs device pointers");
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
@@ -1312,25 +1397,26 @@ int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64
         if (host) {
             const HostOffsets off{offsets, o.offsets64 != 0, n};
             const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, "gx_select_lines: bytes is NULL");
+            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
             d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
             if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
             GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
             if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (out_caps && n) {
+            if ((out_caps || (caps && !image.none())) && n && slots) {
                 d_caps = dev_alloc(n * slots * 4);
                 GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
             }
             src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
         }
-        const Selected s = select_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, nullptr, stream);
+        const WhereBatch wb{&image, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0};
+        const Selected s = select_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, nullptr, stream, &wb);
         *n_selected = s.lines;
         *bytes_selected = s.units * unit;
         if (!out_bytes && !out_index && !out_offsets && !out_ids && !out_caps) return GX_OK;   // size query
         if ((out_index || out_offsets || out_ids || out_caps) && s.lines > cap_lines)
-            return fail(GX_E_LIMIT, "gx_select_lines: cap_lines is smaller than the selection (see *n_selected)");
+            return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the selection (see *n_selected)");
         if (out_bytes && s.units * unit > out_bytes_cap)
-            return fail(GX_E_LIMIT, "gx_select_lines: out_bytes_cap is smaller than the selected text (see *bytes_selected)");
+            return fail(GX_E_LIMIT, name + ": out_bytes_cap is smaller than the selected text (see *bytes_selected)");
         SelectOut out{};
         out.index = out_index; out.bytes = out_bytes; out.offsets = out_offsets;
         void *dst_ids = out_ids, *dst_caps = out_caps;
@@ -1364,12 +1450,35 @@ int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64
     });
 }
 
-int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap, uint64_t* out_size,
-                   uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const uint8_t* want,
+                    uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines,
+                    uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected, const gx_batch_opts* opts) {
+    return select_lines_call("gx_select_lines", false, h, bytes, offsets, n, ids, caps, want, nullptr, 0, out_index, out_bytes, out_offsets, out_ids, out_caps,
+                             cap_lines, out_bytes_cap, n_selected, bytes_selected, opts);
+}
+
+int gx_select_lines_where(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const uint8_t* want,
+                          const gx_where_term* terms, uint32_t n_terms, uint32_t* out_index, void* out_bytes, void* out_offsets, void* out_ids,
+                          int32_t* out_caps, uint64_t cap_lines, uint64_t out_bytes_cap, uint64_t* n_selected, uint64_t* bytes_selected,
+                          const gx_batch_opts* opts) {
+    return select_lines_call("gx_select_lines_where", true, h, bytes, offsets, n, ids, caps, want, terms, n_terms, out_index, out_bytes, out_offsets, out_ids,
+                             out_caps, cap_lines, out_bytes_cap, n_selected, bytes_selected, opts);
+}
+
+// gx_text_select and gx_text_select_where (where: the latter, whose refusals come before the look at the device)
+static int text_select_call(const char* fn, bool where, gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, const gx_where_term* terms,
+                            uint32_t n_terms, uint8_t* out, uint64_t out_cap, uint64_t* out_size, uint64_t* counts, uint64_t* n_lines,
+                            const gx_batch_opts* opts) {
+    const std::string name = fn;
     return guarded([&]() -> int {
-        if (!h || !want || !out_size || (size && !text)) return fail(GX_E_ARG, "gx_text_select: bad argument");
+        if (!h || !want || !out_size || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        WhereImage image;
+        if (where) {
+            if (read_opts(opts).utf8 == 2) return fail(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (lines are selected by their bytes)");
+            image = where_image(h, terms, n_terms, false, name);
+        }
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, "gx_text_select: split texts of 4 GiB and more at a line boundary");
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         const gx_batch_opts o = read_opts(opts);
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         GX_HIP(hipSetDevice(h->device));
@@ -1382,17 +1491,18 @@ int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8
             if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
             src = d_text.get();
         } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, "gx_text_select: device text must be 16-byte aligned");
+            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
         }
         // lines and the path as in gx_text_to_jsonl; then the selection's passes over the ids and offsets they left on the device
-        if (o.utf8 == 2) return fail(GX_E_ARG, "gx_text_select: gx_batch_opts.utf8 = 1 (lines are selected by their bytes)");
+        if (o.utf8 == 2) return fail(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (lines are selected by their bytes)");
         const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        const Selected s = select_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, want, counts, stream);
-        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: gx_text_select: a line longer than the split pass reported");
+        const WhereBatch wb{&image, src, tl.b.caps, false};
+        const Selected s = select_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, want, counts, stream, &wb);
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         *out_size = s.units;
         if (n_lines) *n_lines = tl.n;
         if (!out) return GX_OK;
-        if (s.units > out_cap) return fail(GX_E_LIMIT, "gx_text_select: out_cap is smaller than the selected text (see *out_size)");
+        if (s.units > out_cap) return fail(GX_E_LIMIT, name + ": out_cap is smaller than the selected text (see *out_size)");
         SelectOut sel{};
         sel.bytes = out;
         if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(s.units); sel.bytes = d_out.get(); }
@@ -1401,6 +1511,16 @@ int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });
+}
+
+int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap, uint64_t* out_size,
+                   uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_select_call("gx_text_select", false, h, text, size, want, nullptr, 0, out, out_cap, out_size, counts, n_lines, opts);
+}
+
+int gx_text_select_where(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, const gx_where_term* terms, uint32_t n_terms, uint8_t* out,
+                         uint64_t out_cap, uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_select_call("gx_text_select_where", true, h, text, size, want, terms, n_terms, out, out_cap, out_size, counts, n_lines, opts);
 }
 
 // Keys, sort, scan and the groups on the handle's workspace (under h->mu); then the host reads what it must know before anything is

@@ -236,6 +236,22 @@ hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_unit
                                const SelectWs& w, hipStream_t stream);
 hipError_t launch_select_copy(const SelectOut& o, const void* data, const void* offsets, int offsets64, int wide, uint64_t n, const SelectWs& w,
                               hipStream_t stream);
+constexpr uint32_t SELECT_LDS_BINS = 8192;   // bins a workgroup's LDS histogram takes (32 KiB, the want mask behind it)
+hipError_t launch_select_scans(uint64_t n, const SelectWs& w, hipStream_t stream);   // the two scans behind either flags pass
+
+// The flags pass of gx_select_lines_where (gx_where.hip; the rule: gx_where.hpp), in launch_select_flags' place: a kept line's outcome
+// is wanted AND, where its extraction has terms, every term holds on what the line captured.
+struct WhereArgs {
+    const void* data;      // the batch's code units
+    int wide;              // 1: UTF-16 code units
+    const int32_t* caps;   // ROWS_DENSE: [n][slots]; compact rows carry their offsets themselves
+    uint32_t slots;        // 2 * max_groups
+    const void* image;     // WhereHead + the literals, on the device, 16-byte aligned
+    uint32_t image_bytes;  // a multiple of 16
+};
+// counts: also the histogram of outcomes in w.counts
+hipError_t launch_where_flags(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64,
+                              const WhereArgs& a, bool counts, const SelectWs& w, hipStream_t stream);
 
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:

@@ -256,8 +256,6 @@ __global__ void __launch_bounds__(256) k_select_copy(SelectCopy a, const OFF* __
     }
 }
 
-constexpr uint32_t SELECT_LDS_BINS = 8192;   // bins a workgroup's LDS histogram takes (32 KiB, the want mask behind it)
-
 uint64_t pad16(uint64_t v) { return (v + 15) & ~static_cast<uint64_t>(15); }
 
 // workgroups of the flags pass (its slab has as many rows): one per 256 lines, 1 024 at most, fewer when the bins are many (the
@@ -309,6 +307,18 @@ void launch_flags_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t s
 }
 }  // namespace
 
+// The two scans behind a flags pass (k_select_flags, or gx_where.hip's k_where_flags) on the same stream: w.idx_off[0..n] from w.flags,
+// w.dst_off[0..n] from w.klen.
+hipError_t launch_select_scans(uint64_t n, const SelectWs& w, hipStream_t stream) {
+    if (n == 0) {
+        const hipError_t e = hipMemsetAsync(w.idx_off, 0, 8, stream);
+        return e != hipSuccess ? e : hipMemsetAsync(w.dst_off, 0, 8, stream);
+    }
+    const hipError_t e = launch_exclusive_scan<uint8_t>(w.flags, n, w.block_sums, w.idx_off, stream);
+    if (e != hipSuccess) return e;
+    return launch_exclusive_scan<uint32_t>(w.klen, n, w.block_sums, w.dst_off, stream);
+}
+
 // The flags pass.  offsets == nullptr: the histogram alone (w.counts[2K + 2]); else w.want holds the mask, and the pass and the two
 // scans behind it leave w.flags, w.idx_off[0..n], w.dst_off[0..n] and w.status (1: a line of 4 G code units or more).
 hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64,
@@ -317,10 +327,7 @@ hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_unit
     const bool select = offsets != nullptr;
     hipError_t e = hipMemsetAsync(w.counts, 0, static_cast<size_t>(bins) * 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(w.status, 0, 16, stream);
-    if (e == hipSuccess && select && n == 0) {
-        e = hipMemsetAsync(w.idx_off, 0, 8, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(w.dst_off, 0, 8, stream);
-    }
+    if (e == hipSuccess && select && n == 0) e = launch_select_scans(0, w, stream);
     if (e != hipSuccess || n == 0) return e;
     const uint32_t lds_bins = bins <= SELECT_LDS_BINS ? bins : 0u;
     const uint32_t lds = lds_bins ? lds_bins * 4u + static_cast<uint32_t>(pad16(bins)) : 0u;
@@ -331,9 +338,7 @@ hipError_t launch_select_flags(const void* ids, RowFormat fmt, uint32_t row_unit
     if (lds_bins) hipLaunchKernelGGL(k_select_sum, dim3(bins), dim3(256), 0, stream, w.slab, blocks, bins, w.counts);
     e = hipGetLastError();
     if (e != hipSuccess || !select) return e;
-    e = launch_exclusive_scan<uint8_t>(w.flags, n, w.block_sums, w.idx_off, stream);
-    if (e != hipSuccess) return e;
-    return launch_exclusive_scan<uint32_t>(w.klen, n, w.block_sums, w.dst_off, stream);
+    return launch_select_scans(n, w, stream);
 }
 
 // The copy pass, behind launch_select_flags on the same stream (and behind the host's look at the two totals: the outputs are as

@@ -269,6 +269,13 @@ class ExtractionResult:
         return result
 
 
+class WhereTerms:
+    """Gorp.where_terms' result: the gx_where_term array of a call, and the literals its text pointers point into."""
+
+    def __init__(self, array, n, literals, units):
+        self.array, self.n, self.literals, self.units = array, n, literals, units
+
+
 def _utf16(s):
     raw = s.encode("utf-16-le", "surrogatepass")
     return np.frombuffer(raw, dtype=np.uint16).copy() if raw else np.zeros(0, np.uint16)
@@ -736,6 +743,180 @@ class Gorp:
         _check(N.lib().gx_select_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, mask.ctypes.data, out_index_ptr, out_data_ptr,
                                        out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, C.byref(k), C.byref(nbytes), C.byref(o)))
         return k.value, nbytes.value
+
+    # -- lines by the values they captured (gx_select_lines_where / gx_text_select_where) ---------------------------------
+    _WHERE_OPS = {"set": (N.GX_WHERE_SET, 0), "unset": (N.GX_WHERE_SET, 1), "==": (N.GX_WHERE_EQ, 0), "!=": (N.GX_WHERE_EQ, 1),
+                  "startswith": (N.GX_WHERE_PREFIX, 0), "endswith": (N.GX_WHERE_SUFFIX, 0), "contains": (N.GX_WHERE_CONTAINS, 0),
+                  "not contains": (N.GX_WHERE_CONTAINS, 1), "<": (N.GX_WHERE_INT_LT, 0), "<=": (N.GX_WHERE_INT_LE, 0),
+                  ">": (N.GX_WHERE_INT_GT, 0), ">=": (N.GX_WHERE_INT_GE, 0)}
+
+    def where_terms(self, spec, units="latin-1"):
+        """Resolves a list of (extraction, extractor, op, value) -- value may be left out for "set" / "unset" -- into gx_where_term
+        records: extraction is a name or an index, extractor a name or a group index (a name two groups of the extraction share is a
+        ValueError), op one of "set", "unset", "==", "!=", "startswith", "endswith", "contains", "not contains", "<", "<=", ">",
+        ">=".  An int value selects the integer form of == / != (Long.parseLong's rule for ASCII input); a str is encoded to the
+        batch's code units (units: "latin-1" bytes, "utf-8" bytes or "utf-16" units), bytes are taken as they are.  Returns
+        (ctypes array, number of terms, what keeps the literals alive); a WhereTerms passes through."""
+        if isinstance(spec, WhereTerms):
+            return spec
+        if units not in ("latin-1", "utf-8", "utf-16"):
+            raise ValueError("units: latin-1, utf-8 or utf-16")
+        names = [x.getName() for x in self._extractions]
+        spec = list(spec)
+        arr = (N.gx_where_term * max(1, len(spec)))()
+        keep = []
+        for t, item in enumerate(spec):
+            item = tuple(item)
+            if len(item) == 3:
+                item = item + (None,)
+            if len(item) != 4:
+                raise ValueError("a term is (extraction, extractor, op, value)")
+            ex, group, op, value = item
+            if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+                if not 0 <= int(ex) < len(names):
+                    raise ValueError("no extraction %d" % int(ex))
+                k = int(ex)
+            elif ex in names:
+                k = names.index(ex)
+            else:
+                raise ValueError("unknown extraction %r" % (ex,))
+            groups = list(self._extractions[k]._extractorNames)
+            if isinstance(group, (int, np.integer)) and not isinstance(group, bool):
+                if not 0 <= int(group) < self.num_groups(k):
+                    raise ValueError("extraction %r has no group %d" % (names[k], int(group)))
+                g = int(group)
+            elif groups.count(group) == 1:
+                g = groups.index(group)
+            elif groups.count(group) > 1:
+                raise ValueError("extractor name %r is shared by %d groups of %r: name the group by its index" % (group, groups.count(group), names[k]))
+            else:
+                raise ValueError("extraction %r has no extractor %r" % (names[k], group))
+            if op not in self._WHERE_OPS:
+                raise ValueError("unknown op %r" % (op,))
+            code, negate = self._WHERE_OPS[op]
+            m = arr[t]
+            m.extraction, m.group, m.negate = k, g, negate
+            if code == N.GX_WHERE_SET:
+                if value is not None:
+                    raise ValueError("%r takes no value" % op)
+            elif isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+                if code == N.GX_WHERE_EQ:
+                    code = N.GX_WHERE_INT_EQ
+                elif code < N.GX_WHERE_INT_EQ:
+                    raise ValueError("%r takes text, not a number" % op)
+                if not -2 ** 63 <= int(value) < 2 ** 63:
+                    raise ValueError("a number must fit int64")
+                m.number = int(value)
+            elif isinstance(value, (str, bytes, bytearray)):
+                if code >= N.GX_WHERE_INT_EQ:
+                    raise ValueError("%r takes an int" % op)
+                if isinstance(value, str):
+                    lit = np.frombuffer(value.encode("utf-16-le"), dtype=np.uint16).copy() if units == "utf-16" else np.frombuffer(value.encode(units), dtype=np.uint8).copy()
+                elif units == "utf-16":
+                    raise ValueError("a utf-16 batch takes str literals")
+                else:
+                    lit = np.frombuffer(bytes(value), dtype=np.uint8).copy()
+                if lit.size > 255:
+                    raise ValueError("a literal has at most 255 code units")
+                keep.append(lit)
+                m.text = lit.ctypes.data if lit.size else None
+                m.text_units = lit.size
+            else:
+                raise ValueError("%r needs a value (str, bytes or int)" % op)
+            m.op = code
+        return WhereTerms(arr, len(spec), keep, units)
+
+    def _where_want(self, terms, want):
+        if isinstance(want, str) and want == "matched-by-terms":
+            mask = np.zeros(2 * self.num_extractions + 1, np.uint8)
+            for t in range(terms.n):
+                mask[terms.array[t].extraction] = 1
+            return mask
+        return self.want_mask(want)
+
+    def select_lines_where(self, data, offsets, ids, rows, where, want="matched-by-terms", utf8=None):
+        """gx_select_lines_where on host buffers: select_lines, and of the lines of an extraction that has terms only those on which
+        every term holds.  where: a list of (extraction, extractor, op, value) (where_terms).  want: as select_lines takes it; the
+        default marks exactly the extractions that have terms.  utf8="bytes": the batch is UTF-8 with byte offsets
+        (extract_batch(utf8="bytes")) and str literals are encoded as UTF-8.  Returns what select_lines returns."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are compared in the units the offsets count)')
+        terms = self.where_terms(where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        n = len(offsets) - 1
+        mask = self._where_want(terms, want)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = dict(offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8))
+        total = int(offsets[n] - offsets[0]) if n else 0
+        index = np.zeros(n, np.uint32)
+        out = np.zeros(total, data.dtype)
+        out_off = np.zeros(n + 1, offsets.dtype)
+        out_ids = np.zeros(ids.shape, ids.dtype)
+        out_caps = None if caps is None else np.zeros((n, 2 * self.max_groups), np.int32)
+        k, nbytes = self.select_lines_where_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), mask, terms, out_index_ptr=index.ctypes.data,
+                                                   out_data_ptr=out.ctypes.data, out_offsets_ptr=out_off.ctypes.data, out_ids_ptr=out_ids.ctypes.data,
+                                                   out_caps_ptr=None if out_caps is None else out_caps.ctypes.data, cap_lines=n,
+                                                   out_bytes_cap=total * data.itemsize, **args)
+        index, out, out_off, out_ids = index[:k], out[:nbytes // data.itemsize], out_off[:k + 1], out_ids[:k]
+        out_caps = None if out_caps is None else out_caps[:k]
+        if compact:
+            return index, out, out_off, out_ids
+        if caps is not None:
+            return index, out, out_off, out_ids, out_caps
+        return index, out, out_off
+
+    def select_lines_where_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, want, where, out_index_ptr=None, out_data_ptr=None,
+                                  out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0, offsets64=False,
+                                  utf16=False, compact=0, stream=None, no_sync=False, device_pointers=True, utf8=False):
+        """gx_select_lines_where on device pointers (ints), select_lines_device with terms (where_terms' result, or its input: then
+        str literals are encoded for the batch utf16 / utf8 name).  Returns (lines selected, bytes selected)."""
+        terms = self.where_terms(where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        mask = self._where_want(terms, want)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        o.no_sync = 1 if no_sync else 0
+        k, nbytes = C.c_uint64(0), C.c_uint64(0)
+        _check(N.lib().gx_select_lines_where(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, mask.ctypes.data, terms.array, terms.n, out_index_ptr,
+                                             out_data_ptr, out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, C.byref(k), C.byref(nbytes),
+                                             C.byref(o)))
+        return k.value, nbytes.value
+
+    def text_select_where(self, text, where, want="matched-by-terms", utf8=False):
+        """gx_text_select_where on a host buffer: text_select with terms.  Returns (selected text bytes, counts uint64[2K + 2] --
+        of outcomes, whatever the terms say --, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        ptr = raw.ctypes.data if raw.size else None
+        out = np.zeros(max(1, raw.size), np.uint8)
+        size, counts, n_lines = self.text_select_where_device(ptr, raw.size, want, where, out.ctypes.data, raw.size, device_pointers=False, utf8=utf8)
+        return out[:size].tobytes(), counts, n_lines
+
+    def text_select_where_device(self, text_ptr, size, want, where, out_ptr, out_cap, stream=None, device_pointers=True, utf8=False):
+        """gx_text_select_where on device buffers (ints); out_ptr=None only asks for the sizes.  Returns (selected bytes, counts, n_lines)."""
+        terms = self.where_terms(where, units="utf-8" if utf8 else "latin-1")
+        mask = self._where_want(terms, want)
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out_size, nl = C.c_uint64(0), C.c_uint64(0)
+        _check(N.lib().gx_text_select_where(self._h.ptr, text_ptr, size, mask.ctypes.data, terms.array, terms.n, out_ptr, out_cap, C.byref(out_size),
+                                            counts.ctypes.data, C.byref(nl), C.byref(o)))
+        return out_size.value, counts, nl.value
 
     def partition_lines(self, data, offsets, ids, rows=None, want=None):
         """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every

@@ -206,6 +206,96 @@ public:
         s.offsets.resize(static_cast<size_t>(k) + 1);
         return s;
     }
+    // Lines by the values they captured (gx_select_lines_where): the terms of a call, built by name.  where().on("GetRequest",
+    // "timeTakenInMsec").ge(500) is the caller's Long.parseLong(r.asMap().get("timeTakenInMsec")) >= 500 (README.md:26,63-79).  An
+    // extraction or extractor that does not exist, or an extractor name that two groups of the extraction share, is
+    // std::invalid_argument (name such a group by its index).  Text is Latin-1 code units, as selectLines' bytes are.
+    class Where {
+    public:
+        explicit Where(const Gorp* g) : g_(g) {}
+        Where& on(const std::string& extraction, const std::string& extractor) {
+            const size_t k = g_->extractionIndex(extraction);
+            const std::vector<std::string>& names = g_->extractions_[k].extractorNames;
+            size_t found = names.size(), count = 0;
+            for (size_t g = 0; g < names.size(); ++g)
+                if (names[g] == extractor) { found = g; ++count; }
+            if (count != 1) throw std::invalid_argument("extraction " + extraction + (count ? " has several extractors " : " has no extractor ") + extractor);
+            return on(k, found);
+        }
+        Where& on(size_t extraction, size_t group) {
+            if (extraction >= g_->extractions_.size() || group >= g_->extractions_[extraction].extractorNames.size())
+                throw std::invalid_argument("no such extraction or group");
+            k_ = static_cast<int32_t>(extraction);
+            g_at_ = static_cast<int32_t>(group);
+            return *this;
+        }
+        Where& isSet() { return add(GX_WHERE_SET, 0, nullptr, 0); }
+        Where& isUnset() { return add(GX_WHERE_SET, 1, nullptr, 0); }
+        Where& eq(const std::string& text) { return add(GX_WHERE_EQ, 0, &text, 0); }
+        Where& ne(const std::string& text) { return add(GX_WHERE_EQ, 1, &text, 0); }
+        Where& startsWith(const std::string& text) { return add(GX_WHERE_PREFIX, 0, &text, 0); }
+        Where& endsWith(const std::string& text) { return add(GX_WHERE_SUFFIX, 0, &text, 0); }
+        Where& contains(const std::string& text) { return add(GX_WHERE_CONTAINS, 0, &text, 0); }
+        Where& notContains(const std::string& text) { return add(GX_WHERE_CONTAINS, 1, &text, 0); }
+        Where& eq(int64_t number) { return add(GX_WHERE_INT_EQ, 0, nullptr, number); }
+        Where& ne(int64_t number) { return add(GX_WHERE_INT_EQ, 1, nullptr, number); }
+        Where& lt(int64_t number) { return add(GX_WHERE_INT_LT, 0, nullptr, number); }
+        Where& le(int64_t number) { return add(GX_WHERE_INT_LE, 0, nullptr, number); }
+        Where& gt(int64_t number) { return add(GX_WHERE_INT_GT, 0, nullptr, number); }
+        Where& ge(int64_t number) { return add(GX_WHERE_INT_GE, 0, nullptr, number); }
+        // the terms as the C call takes them (the pointers live as long as this object is not changed)
+        std::vector<gx_where_term> terms() const {
+            std::vector<gx_where_term> out = terms_;
+            for (size_t t = 0; t < out.size(); ++t) {
+                out[t].text = texts_[t].empty() ? nullptr : texts_[t].data();
+                out[t].text_units = static_cast<uint32_t>(texts_[t].size());
+            }
+            return out;
+        }
+        // the mask that marks exactly the extractions that have terms
+        Want want() const {
+            Want w(2 * g_->extractions_.size() + 1, 0);
+            for (const gx_where_term& t : terms_) w[static_cast<size_t>(t.extraction)] = 1;
+            return w;
+        }
+
+    private:
+        Where& add(uint32_t op, uint32_t negate, const std::string* text, int64_t number) {
+            if (k_ < 0) throw std::invalid_argument("Where: on(extraction, extractor) first");
+            gx_where_term t{};
+            t.extraction = k_; t.group = g_at_; t.op = op; t.negate = negate; t.number = number;
+            terms_.push_back(t);
+            texts_.push_back(text ? *text : std::string());
+            return *this;
+        }
+        const Gorp* g_;
+        int32_t k_ = -1, g_at_ = 0;
+        std::vector<gx_where_term> terms_;
+        std::vector<std::string> texts_;
+    };
+    Where where() const { return Where(this); }
+    size_t extractionIndex(const std::string& name) const {
+        for (size_t k = 0; k < extractions_.size(); ++k)
+            if (extractions_[k].name == name) return k;
+        throw std::invalid_argument("no extraction " + name);
+    }
+    // selectLines with terms: of the lines of an extraction that has terms only those on which every term holds; caps: the dense capture
+    // rows of the batch (extractBatch's)
+    Selection selectLinesWhere(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const Want& want,
+                               const Where& where) const {
+        if (want.size() != 2 * extractions_.size() + 1) throw GorpError(GX_E_ARG, "selectLinesWhere: the want mask has 2K + 1 entries");
+        const std::vector<gx_where_term> terms = where.terms();
+        const uint64_t total = offsets[n] - offsets[0];
+        uint64_t k = 0, size = 0;
+        Selection s{std::vector<uint32_t>(static_cast<size_t>(n) + 1), std::vector<uint8_t>(static_cast<size_t>(total) + 1), std::vector<uint32_t>(static_cast<size_t>(n) + 1)};
+        int rc = gx_select_lines_where(h_, bytes, offsets, n, match_id, caps, want.data(), terms.data(), static_cast<uint32_t>(terms.size()), s.index.data(),
+                                       s.bytes.data(), s.offsets.data(), nullptr, nullptr, n, total, &k, &size, nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        s.index.resize(static_cast<size_t>(k));
+        s.bytes.resize(static_cast<size_t>(size));
+        s.offsets.resize(static_cast<size_t>(k) + 1);
+        return s;
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes

@@ -348,6 +348,60 @@ int gx_select_lines(gx_handle* h, const void* bytes, const void* offsets, uint64
 int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, uint8_t* out, uint64_t out_cap,
                    uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* Lines by the VALUES they captured.  The next line of the reference caller's loop is a test on what the extraction found
+ * (README.md:26,63-79, on the README definition):
+ *     r = gorp.extract(line); if (r != null && Long.parseLong(r.asMap().get("timeTakenInMsec")) >= 500) ...
+ * A TERM is one such test on one group of one extraction; its result is test(value) XOR negate, the value being the code units
+ * line[begin, end) of the group's capture offsets:
+ *   GX_WHERE_SET                     the group took part in the match (Matcher.group(g) != null);
+ *   GX_WHERE_EQ / _PREFIX / _SUFFIX / _CONTAINS
+ *                                    the value against `text`, code unit by code unit (bytes; 16-bit units with opts->utf16; with
+ *                                    utf8 = 1 the literal is UTF-8 bytes).  An empty text is a prefix, a suffix and a part of every
+ *                                    value, and equal to the empty value alone;
+ *   GX_WHERE_INT_EQ / _LT / _LE / _GT / _GE
+ *                                    the value as a number against `number`, parsed as Long.parseLong parses ASCII input: one
+ *                                    optional '+' or '-', then one or more digits '0' .. '9', within int64; leading zeros are fine.
+ *                                    Anything else fails the test: the empty value, a bare sign, any other unit, overflow -- and a
+ *                                    digit that is not ASCII (U+FF11), which Java would accept: the one difference.
+ * An unset group fails every test (so with negate it passes). */
+enum { GX_WHERE_SET = 0, GX_WHERE_EQ, GX_WHERE_PREFIX, GX_WHERE_SUFFIX, GX_WHERE_CONTAINS,
+       GX_WHERE_INT_EQ, GX_WHERE_INT_LT, GX_WHERE_INT_LE, GX_WHERE_INT_GT, GX_WHERE_INT_GE };
+
+typedef struct gx_where_term {
+    int32_t  extraction;   /* k in [0, K) */
+    int32_t  group;        /* g in [0, gx_num_groups(h, k)) */
+    uint32_t op;           /* GX_WHERE_* */
+    uint32_t negate;       /* 1: the term holds where the test fails */
+    const void* text;      /* HOST pointer (always): the literal in the batch's code units, uint8_t, or uint16_t with opts->utf16 */
+    uint32_t text_units;   /* 0 .. 255 */
+    int64_t  number;
+} gx_where_term;
+
+/* gx_select_lines_where: gx_select_lines with terms.  A line is kept when its outcome index x has want[x] != 0 AND, if x is a matched
+ * extraction k that has terms, EVERY term of k holds.  Extractions without terms, unmatched lines and exceptions are decided by want
+ * alone: n_terms == 0 is gx_select_lines bit for bit, and the dead-letter mask composes.  Everything else -- inputs, outputs,
+ * capacities, the size query, GX_E_LIMIT with nothing written, offsets64, utf16, host staging, stream, no_sync after the one small
+ * synchronisation -- is gx_select_lines'; the terms and literals (at most 64 terms of at most 255 units: GX_E_LIMIT beyond) go to the
+ * device beside the want mask on every call.  Capture offsets come from caps with int32 ids (caps == NULL with terms: GX_E_ARG), and
+ * with compact_results 1 / 2 from the u16 / u8 result rows themselves (0xFFFF / 0xFF: unset).  A SATURATED offset of a compact row
+ * (65 534 / 254: gx_batch_opts.compact_results) is taken at face value -- where the batch's *overflow != 0, use dense rows.  The
+ * offsets are the caller's input to a kernel: a pair with begin < 0 <= end, end < begin or end beyond the line's
+ * offsets[i + 1] - offsets[i] units counts as UNSET and is never dereferenced; no code unit outside [offsets[0], offsets[n]) is
+ * read.  utf8 = 1 batches work as they are (byte offsets, UTF-8 literal); utf8 = 2 (offsets in units over a byte buffer) is
+ * GX_E_ARG.  A term with extraction, group or op out of range, or text == NULL with text_units > 0, is GX_E_ARG; these refusals need
+ * no device (a host-only handle gives them, and GX_E_DEVICE after them: there is no CPU path). */
+int gx_select_lines_where(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                          const uint8_t* want, const gx_where_term* terms, uint32_t n_terms, uint32_t* out_index, void* out_bytes,
+                          void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines, uint64_t out_bytes_cap,
+                          uint64_t* n_selected, uint64_t* bytes_selected, const gx_batch_opts* opts);
+
+/* gx_text_select with the same terms: raw text -> lines -> the match-and-extract path (which leaves dense capture rows on the
+ * device) -> the text of the lines that want and the terms keep.  counts is the histogram of OUTCOMES, as gx_text_select gives it:
+ * the terms do not change it.  With utf8 = 1 a term's text is UTF-8 bytes. */
+int gx_text_select_where(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, const gx_where_term* terms,
+                         uint32_t n_terms, uint8_t* out, uint64_t out_cap, uint64_t* out_size, uint64_t* counts, uint64_t* n_lines,
+                         const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
