@@ -47,6 +47,7 @@ SYMBOLS = [
     "gx_count_outcomes", "gx_select_lines", "gx_text_select", "gx_utf8_to_utf16",
     "gx_partition_lines", "gx_text_to_jsonl_by_extraction",
     "gx_select_lines_where", "gx_text_select_where",
+    "gx_capture_stats", "gx_text_capture_stats",
 ]
 
 
@@ -75,6 +76,15 @@ class gx_batch_opts(C.Structure):
 class gx_where_term(C.Structure):
     _fields_ = [("extraction", C.c_int32), ("group", C.c_int32), ("op", C.c_uint32), ("negate", C.c_uint32), ("text", C.c_void_p),
                 ("text_units", C.c_uint32), ("number", C.c_int64)]
+
+
+class gx_measure(C.Structure):
+    _fields_ = [("extraction", C.c_int32), ("group", C.c_int32), ("edges", C.c_void_p), ("n_edges", C.c_uint32)]
+
+
+class gx_measure_stats(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64),
+                ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64)]
 
 
 class gx_device_shard(C.Structure):
@@ -231,6 +241,12 @@ def lib():
     L.gx_text_select_where.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(gx_where_term), C.c_uint32, C.c_void_p, C.c_uint64,
                                        C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_select_where.restype = C.c_int
+    L.gx_capture_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_measure), C.c_uint32,
+                                   C.POINTER(gx_where_term), C.c_uint32, C.POINTER(gx_measure_stats), C.c_void_p, C.POINTER(gx_batch_opts)]
+    L.gx_capture_stats.restype = C.c_int
+    L.gx_text_capture_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_measure), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                        C.POINTER(gx_measure_stats), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_capture_stats.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -23,6 +23,7 @@
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
+#include "gx_stats.hpp"
 #include "gx_where.hpp"
 
 using namespace gx;
@@ -260,6 +261,9 @@ struct gx_handle {
     GrowBuf where_image;   // gx_select_lines_where's terms and literals (WhereHead, gx_where.hpp); read by its flags pass alone
     Event select_event;
     bool select_pending = false;
+    // gx_capture_stats: its measures, edges and terms on the device (StatsHead, gx_stats.hpp; WhereHead behind it), and the summed words
+    // and the workgroups' slabs (gx_stats.hip).  Used under `mu`; every call that uses them ends with a stream synchronisation.
+    GrowBuf stats_image, stats_ws;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
@@ -1521,6 +1525,196 @@ int gx_text_select(gx_handle* h, const uint8_t* text, uint64_t size, const uint8
 int gx_text_select_where(gx_handle* h, const uint8_t* text, uint64_t size, const uint8_t* want, const gx_where_term* terms, uint32_t n_terms, uint8_t* out,
                          uint64_t out_cap, uint64_t* out_size, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_select_call("gx_text_select_where", true, h, text, size, want, terms, n_terms, out, out_cap, out_size, counts, n_lines, opts);
+}
+
+// The measures of a gx_capture_stats call as its kernel reads them (gx_stats.hpp: StatsHead, then the edges), checked against the
+// handle.  The kernel's measures are ordered by extraction: order[q] is the caller's index of the kernel's measure q.  Needs no device.
+struct StatsImage {
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> order;
+    uint32_t n_bins = 0;
+};
+static StatsImage stats_image(const gx_handle* h, const gx_measure* measures, uint32_t n_measures, const std::string& name) {
+    StatsImage img;
+    if (n_measures == 0) return img;
+    if (!measures) throw GxError(GX_E_ARG, name + ": measures is NULL");
+    if (n_measures > STATS_MAX_MEASURES) throw GxError(GX_E_LIMIT, name + ": more than 64 measures");
+    const int32_t K = static_cast<int32_t>(h->T.n_rules);
+    size_t n_edges = 0;
+    img.order.resize(n_measures);
+    for (uint32_t t = 0; t < n_measures; ++t) {
+        const gx_measure& m = measures[t];
+        img.order[t] = t;
+        if (m.extraction < 0 || m.extraction >= K) throw GxError(GX_E_ARG, name + ": a measure's extraction is not in [0, K)");
+        if (m.group < 0 || m.group >= gx_num_groups(h, m.extraction)) throw GxError(GX_E_ARG, name + ": a measure's group is not one of its extraction's");
+        if (m.n_edges > STATS_MAX_EDGES) throw GxError(GX_E_LIMIT, name + ": a measure has more than 64 edges");
+        if (m.n_edges && !m.edges) throw GxError(GX_E_ARG, name + ": a measure's edges is NULL");
+        for (uint32_t j = 1; j < m.n_edges; ++j)
+            if (m.edges[j - 1] >= m.edges[j]) throw GxError(GX_E_ARG, name + ": a measure's edges are not strictly ascending");
+        n_edges += m.n_edges;
+    }
+    if (n_edges > STATS_MAX_EDGES_TOTAL) throw GxError(GX_E_LIMIT, name + ": more than 1024 edges in all");
+    std::stable_sort(img.order.begin(), img.order.end(), [&](uint32_t a, uint32_t b) { return measures[a].extraction < measures[b].extraction; });
+    std::vector<uint32_t> hist_at(n_measures);   // (the bins lie in the caller's order)
+    for (uint32_t t = 0; t < n_measures; ++t) {
+        hist_at[t] = img.n_bins;
+        img.n_bins += measures[t].n_edges + 1u;
+    }
+    img.bytes.assign((sizeof(StatsHead) + n_edges * 8 + 15) & ~static_cast<size_t>(15), 0);
+    StatsHead head{};
+    head.n_measures = n_measures;
+    head.n_edges = static_cast<uint32_t>(n_edges);
+    head.n_bins = img.n_bins;
+    uint8_t* edges = img.bytes.data() + sizeof(StatsHead);
+    size_t at = 0;
+    for (uint32_t q = 0; q < n_measures; ++q) {
+        const gx_measure& m = measures[img.order[q]];
+        if (head.n_ext == 0 || head.ext[head.n_ext - 1] != static_cast<uint32_t>(m.extraction)) {
+            head.ext[head.n_ext] = static_cast<uint32_t>(m.extraction);
+            head.first[head.n_ext++] = static_cast<uint8_t>(q);
+        }
+        StatsMeasure& d = head.m[q];
+        d.group = static_cast<uint16_t>(m.group);
+        d.n_edges = static_cast<uint16_t>(m.n_edges);
+        d.edge_at = static_cast<uint16_t>(at);
+        d.hist_at = static_cast<uint16_t>(hist_at[img.order[q]]);
+        if (m.n_edges) memcpy(edges + at * 8, m.edges, static_cast<size_t>(m.n_edges) * 8);
+        at += m.n_edges;
+    }
+    head.first[head.n_ext] = static_cast<uint8_t>(n_measures);
+    memcpy(img.bytes.data(), &head, sizeof(head));
+    return img;
+}
+
+// The reduction on the handle's buffers (under h->mu) and, with counts, the histogram of outcomes beside it (k_select_flags' counting
+// form); then ONE synchronisation of the stream, where the host reads the summed words.  ids / offsets / data / caps: device pointers.
+static void stats_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
+                       const int32_t* caps, bool wide, const StatsImage& si, const WhereImage& wi, uint32_t n_measures, gx_measure_stats* stats, uint64_t* hist,
+                       uint64_t* counts, hipStream_t stream) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    if (counts) {
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
+        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    const size_t words = static_cast<size_t>(n_measures) * STATS_WORDS, total = words + si.n_bins;
+    std::vector<uint64_t> got(total + 2, 0);   // (the words, the bins, the status word)
+    const bool run = n != 0 && n_measures != 0;
+    if (run) {
+        uint8_t* d_img = static_cast<uint8_t*>(h->stats_image.get(si.bytes.size() + wi.bytes.size()));
+        GX_HIP(hipMemcpyAsync(d_img, si.bytes.data(), si.bytes.size(), hipMemcpyHostToDevice, stream));
+        if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + si.bytes.size(), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+        const StatsArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(si.bytes.size()),
+                          wi.none() ? nullptr : d_img + si.bytes.size(), static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins};
+        void* ws = h->stats_ws.get(stats_workspace_bytes(n, n_measures, si.n_bins));
+        GX_HIP(launch_capture_stats(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, ws, stream));
+        GX_HIP(hipMemcpyAsync(got.data(), ws, (total + 2) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got[total] & 0xFFFFFFFFull) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be measured");
+    for (uint32_t q = 0; q < n_measures; ++q) {
+        gx_measure_stats& s = stats[si.order[q]];
+        const uint64_t* w = got.data() + static_cast<size_t>(q) * STATS_WORDS;
+        s.numbers = w[STATS_W_NUMBERS];
+        s.unset = w[STATS_W_UNSET];
+        s.not_numbers = w[STATS_W_NOT_NUMBERS];
+        s.lines = s.numbers + s.unset + s.not_numbers;
+        s.min = run ? static_cast<int64_t>(w[STATS_W_MIN]) : STATS_INT64_MAX;
+        s.max = run ? static_cast<int64_t>(w[STATS_W_MAX]) : STATS_INT64_MIN;
+        stats_sum128(w[STATS_W_LO], static_cast<int64_t>(w[STATS_W_HI]), &s.sum_lo, &s.sum_hi);
+    }
+    if (hist)
+        for (uint32_t b = 0; b < si.n_bins; ++b) hist[b] = got[words + b];
+}
+
+// what both capture-stats calls refuse before they look at the device
+static void stats_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_measure* measures, uint32_t n_measures, const gx_where_term* terms,
+                           uint32_t n_terms, bool wide, const gx_measure_stats* stats, const std::string& name, StatsImage* si, WhereImage* wi) {
+    if (n_measures && !stats) throw GxError(GX_E_ARG, name + ": stats is NULL");
+    *si = stats_image(h, measures, n_measures, name);
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the results are host values");
+}
+
+int gx_capture_stats(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_measure* measures,
+                     uint32_t n_measures, const gx_where_term* terms, uint32_t n_terms, gx_measure_stats* stats, uint64_t* hist, const gx_batch_opts* opts) {
+    const std::string name = "gx_capture_stats";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        StatsImage si;
+        WhereImage wi;
+        stats_refusals(h, o, measures, n_measures, terms, n_terms, o.utf16 != 0, stats, name, &si, &wi);
+        if ((n_measures || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": measures and terms on dense ids need caps");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (n >= (1ull << 32)) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 4 G lines and more");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        // host buffers are staged to the device; the pass is the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (!o.device_pointers) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
+            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (caps && n && slots) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        stats_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, si, wi, n_measures, stats,
+                   hist, nullptr, stream);
+        return GX_OK;
+    });
+}
+
+int gx_text_capture_stats(gx_handle* h, const uint8_t* text, uint64_t size, const gx_measure* measures, uint32_t n_measures, const gx_where_term* terms,
+                          uint32_t n_terms, gx_measure_stats* stats, uint64_t* hist, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    const std::string name = "gx_text_capture_stats";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        StatsImage si;
+        WhereImage wi;
+        stats_refusals(h, o, measures, n_measures, terms, n_terms, false, stats, name, &si, &wi);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
+        }
+        // lines and the path as in gx_text_select_where; then the reduction over the ids, offsets and capture rows they left on the device
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        stats_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, si, wi, n_measures, stats, hist, counts, stream);
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        if (n_lines) *n_lines = tl.n;
+        return GX_OK;
+    });
 }
 
 // Keys, sort, scan and the groups on the handle's workspace (under h->mu); then the host reads what it must know before anything is

@@ -253,6 +253,26 @@ struct WhereArgs {
 hipError_t launch_where_flags(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64,
                               const WhereArgs& a, bool counts, const SelectWs& w, hipStream_t stream);
 
+// The reduction of gx_capture_stats (gx_stats.hip; the rule: gx_stats.hpp): per measure -- one group of one extraction -- the lines
+// that count, classed as numbers / unset / no numbers, and the numbers' minimum, maximum, exact sum and histogram.
+struct StatsArgs {
+    const void* data;            // the batch's code units
+    int wide;                    // 1: UTF-16 code units
+    const int32_t* caps;         // ROWS_DENSE: [n][slots]; compact rows carry their offsets themselves
+    uint32_t slots;              // 2 * max_groups
+    const void* image;           // StatsHead + the edges, on the device, 16-byte aligned
+    uint32_t image_bytes;        // a multiple of 16
+    const void* where_image;     // WhereHead + the literals, or nullptr: no terms
+    uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
+    uint32_t n_measures, n_bins;
+};
+uint32_t stats_blocks(uint64_t n);
+size_t stats_workspace_bytes(uint64_t n, uint32_t n_measures, uint32_t n_bins);
+// n > 0, a.n_measures > 0.  Leaves in ws: n_measures x STATS_WORDS 64-bit words, then n_bins 64-bit bins, then the status word
+// (!= 0: a line of 4 G code units or more).
+hipError_t launch_capture_stats(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const StatsArgs& a,
+                                void* ws, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

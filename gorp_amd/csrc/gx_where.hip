@@ -6,7 +6,8 @@
 // gx_select.hip's, unchanged: the copy pass knows nothing of why a line was kept.
 //
 // One lane per line, the grid shape of k_select_flags.  The terms, their literals and the want mask are copied to LDS once per
-// workgroup.  A line is kept when want[outcome] != 0 and, if the outcome is a matched extraction that has terms, every term holds.
+// workgroup.  A line is kept when want[outcome] != 0 and, if the outcome is a matched extraction that has terms, every term holds
+// (where_line_holds, gx_where_dev.hpp: stated once, for this pass and for gx_stats.hip).
 // No atomics per line (one atomicOr for a line of 4 G units, which the host refuses), no histogram (gx_text_select_where takes it from
 // k_select_flags' counting form, a read of the id column alone).  DESIGN.md section 5.4.
 #include <algorithm>
@@ -16,30 +17,12 @@
 #include "gx_device.hpp"
 #include "gx_outcome.hpp"
 #include "gx_where.hpp"
+#include "gx_where_dev.hpp"
 
 namespace gx {
 namespace {
 
 extern __shared__ __attribute__((aligned(16))) uint32_t where_smem[];
-
-// a group's capture offsets in any row format: dense rows int32 caps[i][slots], compact rows behind the id in the line's result row
-template <RowFormat F>
-__device__ __forceinline__ void pair_of(const void* ids, const int32_t* caps, uint64_t i, uint32_t row_units, uint32_t slots, uint32_t g, int32_t& pb,
-                                        int32_t& pe) {
-    if (F == ROWS_DENSE) {
-        const int32_t* row = caps + i * static_cast<uint64_t>(slots) + 2u * g;
-        pb = row[0];
-        pe = row[1];
-    } else if (F == ROWS_U16) {
-        const uint16_t* row = static_cast<const uint16_t*>(ids) + i * row_units + 1u + 2u * g;
-        pb = decode_offset(F, row[0]);
-        pe = decode_offset(F, row[1]);
-    } else {
-        const uint8_t* row = static_cast<const uint8_t*>(ids) + i * row_units + 1u + 2u * g;
-        pb = decode_offset(F, row[0]);
-        pe = decode_offset(F, row[1]);
-    }
-}
 
 // image: WhereHead + literals (image_bytes, a multiple of 16).  want_lds != 0: the mask's 2K + 1 bytes go to LDS behind them.
 template <typename OFF, RowFormat F, typename UNIT>
@@ -69,20 +52,8 @@ __global__ void __launch_bounds__(256) k_where_flags(const void* __restrict__ id
         const uint64_t len = o1 - o0;
         if (len > 0xFFFFFFFFull) atomicOr(status, 1u);   // (a line of 4 G code units, or offsets that go backwards: refused by the host)
         if (kept && oc >= ext_lo && oc <= ext_hi) {   // (oc <= ext_hi < K: a matched extraction)
-            const uint32_t e = where_find(head->ext, n_ext, oc);
-            if (e < n_ext) {
-                const uint64_t line_units = len > 0xFFFFFFFFull ? 0u : len;   // (no value is looked at in a line that is refused anyway)
-                const uint32_t t1 = head->first[e + 1u];
-                for (uint32_t t = head->first[e]; kept && t < t1; ++t) {   // (in the caller's order; a line leaves at its first term that fails)
-                    const WhereTerm& m = head->term[t];
-                    int32_t pb, pe;
-                    pair_of<F>(ids, caps, i, row_units, slots, m.group, pb, pe);
-                    bool holds = false;
-                    if (where_pair_set(pb, pe, line_units))
-                        holds = where_test(m.op, data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), lits + m.lit_at, m.lit_len, m.number);
-                    kept = kept && (holds != (m.negate != 0));
-                }
-            }
+            const uint64_t line_units = len > 0xFFFFFFFFull ? 0u : len;   // (no value is looked at in a line that is refused anyway)
+            kept = where_line_holds<F, UNIT>(head, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units);
         }
         flags[i] = kept ? 1 : 0;
         klen[i] = kept ? static_cast<uint32_t>(len) : 0u;

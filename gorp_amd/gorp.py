@@ -276,6 +276,17 @@ class WhereTerms:
         self.array, self.n, self.literals, self.units = array, n, literals, units
 
 
+class Measures:
+    """Gorp.measures' result: the gx_measure array of a call, and the edge arrays its pointers point into."""
+
+    def __init__(self, array, n, edges):
+        self.array, self.n, self.edges = array, n, edges
+
+    @property
+    def n_bins(self):
+        return sum(len(e) + 1 for e in self.edges)
+
+
 def _utf16(s):
     raw = s.encode("utf-16-le", "surrogatepass")
     return np.frombuffer(raw, dtype=np.uint16).copy() if raw else np.zeros(0, np.uint16)
@@ -917,6 +928,139 @@ class Gorp:
         _check(N.lib().gx_text_select_where(self._h.ptr, text_ptr, size, mask.ctypes.data, terms.array, terms.n, out_ptr, out_cap, C.byref(out_size),
                                             counts.ctypes.data, C.byref(nl), C.byref(o)))
         return out_size.value, counts, nl.value
+
+    # -- captured numbers, summarised (gx_capture_stats / gx_text_capture_stats) -------------------------------------------
+    def _extraction_and_group(self, ex, group):
+        """(k, g) of an extraction given by name or index and one of its groups given by extractor name or index."""
+        names = [x.getName() for x in self._extractions]
+        if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+            if not 0 <= int(ex) < len(names):
+                raise ValueError("no extraction %d" % int(ex))
+            k = int(ex)
+        elif ex in names:
+            k = names.index(ex)
+        else:
+            raise ValueError("unknown extraction %r" % (ex,))
+        groups = list(self._extractions[k]._extractorNames)
+        if isinstance(group, (int, np.integer)) and not isinstance(group, bool):
+            if not 0 <= int(group) < self.num_groups(k):
+                raise ValueError("extraction %r has no group %d" % (names[k], int(group)))
+            return k, int(group)
+        if groups.count(group) == 1:
+            return k, groups.index(group)
+        if groups.count(group) > 1:
+            raise ValueError("extractor name %r is shared by %d groups of %r: name the group by its index" % (group, groups.count(group), names[k]))
+        raise ValueError("extraction %r has no extractor %r" % (names[k], group))
+
+    def measures(self, spec):
+        """Resolves a list of (extraction, extractor) or (extraction, extractor, edges) into gx_measure records: extraction is a name or
+        an index, extractor a name or a group index (a name two groups of the extraction share is a ValueError), edges an optional
+        strictly ascending list of at most 64 int64 histogram edges.  At most 64 measures and 1 024 edges in all.  Returns a Measures
+        (which keeps the edge arrays alive); a Measures passes through."""
+        if isinstance(spec, Measures):
+            return spec
+        spec = list(spec)
+        if len(spec) > 64:
+            raise ValueError("at most 64 measures")
+        arr = (N.gx_measure * max(1, len(spec)))()
+        keep = []
+        for t, item in enumerate(spec):
+            item = tuple(item)
+            if len(item) == 2:
+                item = item + (None,)
+            if len(item) != 3:
+                raise ValueError("a measure is (extraction, extractor[, edges])")
+            k, g = self._extraction_and_group(item[0], item[1])
+            raw = [] if item[2] is None else list(item[2])
+            if any(isinstance(e, bool) or not isinstance(e, (int, np.integer)) for e in raw):
+                raise ValueError("edges are ints")
+            if any(not -2 ** 63 <= int(e) < 2 ** 63 for e in raw):
+                raise ValueError("an edge must fit int64")
+            edges = np.array([int(e) for e in raw], dtype=np.int64)
+            if edges.size > 64:
+                raise ValueError("a measure has at most 64 edges")
+            if edges.size > 1 and not (edges[1:] > edges[:-1]).all():
+                raise ValueError("edges must be strictly ascending")
+            keep.append(edges)
+            m = arr[t]
+            m.extraction, m.group, m.n_edges = k, g, edges.size
+            m.edges = edges.ctypes.data if edges.size else None
+        if sum(e.size for e in keep) > 1024:
+            raise ValueError("at most 1024 edges in all")
+        return Measures(arr, len(spec), keep)
+
+    @staticmethod
+    def _stats_result(measures, stats, hist):
+        out, at = [], 0
+        for t in range(measures.n):
+            s = stats[t]
+            bins = measures.array[t].n_edges + 1
+            out.append({"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                        "min": s.min if s.numbers else None, "max": s.max if s.numbers else None, "sum": (s.sum_hi << 64) + s.sum_lo,
+                        "hist": hist[at:at + bins].copy()})
+            at += bins
+        return out
+
+    def capture_stats(self, data, offsets, ids, rows, measures, where=None, utf8=None):
+        """gx_capture_stats on host buffers: per measure (measures: Gorp.measures or its input) the lines of its extraction on which
+        every term of `where` holds (where_terms; None: all of them), classed by what the group captured.  data / offsets / ids / rows
+        and utf8 as select_lines_where takes them.  Returns one dict per measure: lines, numbers, unset, not_numbers, min, max (None
+        without a number), sum (exact, a Python int) and hist (uint64[n_edges + 1])."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        return self.capture_stats_device(ptr(data), offsets.ctypes.data, len(offsets) - 1, ptr(ids), ptr(caps), measures, where,
+                                         offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8))
+
+    def capture_stats_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, measures, where=None, offsets64=False, utf16=False, compact=0,
+                             stream=None, device_pointers=True, utf8=False):
+        """gx_capture_stats on device pointers (ints).  Returns what capture_stats returns."""
+        measures = self.measures(measures)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        stats = (N.gx_measure_stats * max(1, measures.n))()
+        hist = np.zeros(measures.n_bins, np.uint64)
+        _check(N.lib().gx_capture_stats(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, measures.array, measures.n, terms.array, terms.n, stats,
+                                        hist.ctypes.data, C.byref(o)))
+        return self._stats_result(measures, stats, hist)
+
+    def text_capture_stats(self, text, measures, where=None, utf8=False):
+        """gx_text_capture_stats on a host buffer: raw text -> lines -> extraction -> capture_stats.  Returns (the list capture_stats
+        returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        return self.text_capture_stats_device(raw.ctypes.data if raw.size else None, raw.size, measures, where, device_pointers=False, utf8=utf8)
+
+    def text_capture_stats_device(self, text_ptr, size, measures, where=None, stream=None, device_pointers=True, utf8=False):
+        """gx_text_capture_stats on a device buffer (int).  Returns (stats, counts, n_lines)."""
+        measures = self.measures(measures)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        stats = (N.gx_measure_stats * max(1, measures.n))()
+        hist = np.zeros(measures.n_bins, np.uint64)
+        nl = C.c_uint64(0)
+        _check(N.lib().gx_text_capture_stats(self._h.ptr, text_ptr, size, measures.array, measures.n, terms.array, terms.n, stats, hist.ctypes.data,
+                                             counts.ctypes.data, C.byref(nl), C.byref(o)))
+        return self._stats_result(measures, stats, hist), counts, nl.value
 
     def partition_lines(self, data, offsets, ids, rows=None, want=None):
         """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every

@@ -296,6 +296,81 @@ public:
         s.offsets.resize(static_cast<size_t>(k) + 1);
         return s;
     }
+    // Captured numbers, summarised (gx_capture_stats): the measures of a call, built by name.  measures().of("GetRequest",
+    // "timeTakenInMsec", {10, 100, 500, 1000}) is the caller's metrics.record(Long.parseLong(r.asMap().get("timeTakenInMsec")))
+    // (README.md:26,63-79) with a latency histogram.  Names resolve as Where's do; edges are strictly ascending, at most 64.
+    class Measures {
+    public:
+        explicit Measures(const Gorp* g) : g_(g) {}
+        Measures& of(const std::string& extraction, const std::string& extractor, const std::vector<int64_t>& edges = {}) {
+            Where at(g_);
+            at.on(extraction, extractor).isSet();
+            const gx_where_term t = at.terms()[0];
+            return of(static_cast<size_t>(t.extraction), static_cast<size_t>(t.group), edges);
+        }
+        Measures& of(size_t extraction, size_t group, const std::vector<int64_t>& edges = {}) {
+            if (extraction >= g_->extractions_.size() || group >= g_->extractions_[extraction].extractorNames.size())
+                throw std::invalid_argument("no such extraction or group");
+            gx_measure m{};
+            m.extraction = static_cast<int32_t>(extraction);
+            m.group = static_cast<int32_t>(group);
+            measures_.push_back(m);
+            edges_.push_back(edges);
+            return *this;
+        }
+        // the measures as the C call takes them (the pointers live as long as this object is not changed)
+        std::vector<gx_measure> measures() const {
+            std::vector<gx_measure> out = measures_;
+            for (size_t t = 0; t < out.size(); ++t) {
+                out[t].edges = edges_[t].empty() ? nullptr : edges_[t].data();
+                out[t].n_edges = static_cast<uint32_t>(edges_[t].size());
+            }
+            return out;
+        }
+        size_t bins() const {
+            size_t b = 0;
+            for (const std::vector<int64_t>& e : edges_) b += e.size() + 1;
+            return b;
+        }
+
+    private:
+        const Gorp* g_;
+        std::vector<gx_measure> measures_;
+        std::vector<std::vector<int64_t>> edges_;
+    };
+    Measures measures() const { return Measures(this); }
+    // One measure's summary: gx_measure_stats (lines, numbers, unset, not_numbers, min, max, and the exact sum as the 128-bit
+    // two's-complement integer sum_hi : sum_lo) and its n_edges + 1 histogram buckets.
+    struct MeasureStats { gx_measure_stats stats; std::vector<uint64_t> hist; };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other
+    // layout), per measure: those of its extraction on which every term of `where` holds, classed by what the group captured
+    std::vector<MeasureStats> captureStats(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps,
+                                           const Measures& measures, const Where* where = nullptr) const {
+        const std::vector<gx_measure> m = measures.measures();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        std::vector<gx_measure_stats> stats(m.size() + 1);
+        std::vector<uint64_t> hist(measures.bins() + 1, 0);
+        int rc = gx_capture_stats(h_, bytes, offsets, n, match_id, caps, m.data(), static_cast<uint32_t>(m.size()), terms.data(), static_cast<uint32_t>(terms.size()),
+                                  stats.data(), hist.data(), nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return statsOf(m, stats, hist);
+    }
+    // Whole files: raw text in, the same summary out (gx_text_capture_stats).  counts (optional): lines per outcome index.
+    std::vector<MeasureStats> textCaptureStats(const std::string& text, const Measures& measures, const Where* where = nullptr,
+                                               std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        const std::vector<gx_measure> m = measures.measures();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        std::vector<gx_measure_stats> stats(m.size() + 1);
+        std::vector<uint64_t> hist(measures.bins() + 1, 0);
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        int rc = gx_text_capture_stats(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), m.data(), static_cast<uint32_t>(m.size()), terms.data(),
+                                       static_cast<uint32_t>(terms.size()), stats.data(), hist.data(), counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return statsOf(m, stats, hist);
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
@@ -360,6 +435,15 @@ public:
 private:
     friend class DefinitionReader;
     Gorp(gx_handle* h, std::vector<CookedExtraction> x) : h_(h), extractions_(std::move(x)) {}
+    static std::vector<MeasureStats> statsOf(const std::vector<gx_measure>& m, const std::vector<gx_measure_stats>& stats, const std::vector<uint64_t>& hist) {
+        std::vector<MeasureStats> out;
+        size_t at = 0;
+        for (size_t t = 0; t < m.size(); ++t) {
+            out.push_back(MeasureStats{stats[t], std::vector<uint64_t>(hist.begin() + at, hist.begin() + at + m[t].n_edges + 1)});
+            at += m[t].n_edges + 1;
+        }
+        return out;
+    }
     gx_handle* h_;
     std::vector<CookedExtraction> extractions_;
 

@@ -402,6 +402,60 @@ int gx_text_select_where(gx_handle* h, const uint8_t* text, uint64_t size, const
                          uint32_t n_terms, uint8_t* out, uint64_t out_cap, uint64_t* out_size, uint64_t* counts, uint64_t* n_lines,
                          const gx_batch_opts* opts);
 
+/* Captured numbers, summarised.  The other thing the reference caller's loop does with a captured number is measure it
+ * (README.md:26,63-79, on the README definition):
+ *     r = gorp.extract(line); if (r != null) metrics.record(Long.parseLong(r.asMap().get("timeTakenInMsec")));
+ * A MEASURE is one group of one extraction, with optional histogram edges.  A line COUNTS for measure m when its outcome is the
+ * matched extraction m.extraction and every term of that extraction holds (gx_select_lines_where's rule with every matched extraction
+ * wanted; n_terms == 0: every line of the extraction).  Its value -- the code units line[begin, end) of group m.group -- is classed:
+ *   unset        the offset pair names no value (the group is unset, or begin < 0 <= end, end < begin, end beyond the line: never
+ *                dereferenced);
+ *   not_numbers  the value is set and Long.parseLong would throw: the empty value, a bare sign, any other unit, out of int64 -- and
+ *                a digit that is not ASCII (U+FF11), which Java would accept: the one difference (GX_WHERE_INT_*'s rule);
+ *   numbers      everything else: adds to min, max, the sum and one histogram bucket.
+ * lines == numbers + unset + not_numbers.  The sum is EXACT: a 128-bit two's-complement integer (sum_hi : sum_lo) that neither wraps
+ * nor saturates, and integer addition makes it the same bits on every run.  An extraction may have several measures (two groups, or
+ * one group with different edges). */
+typedef struct gx_measure {
+    int32_t  extraction;   /* k in [0, K) */
+    int32_t  group;        /* g in [0, gx_num_groups(h, k)) */
+    const int64_t* edges;  /* HOST pointer (always): histogram edges, strictly ascending; NULL with n_edges == 0 */
+    uint32_t n_edges;      /* 0 .. 64 */
+} gx_measure;
+
+typedef struct gx_measure_stats {   /* 64 bytes, host */
+    uint64_t lines;         /* lines of the extraction that count */
+    uint64_t numbers;       /* ... whose value parsed */
+    uint64_t unset;         /* ... whose offset pair names no value */
+    uint64_t not_numbers;   /* ... whose value is set but is no number */
+    int64_t  min, max;      /* over the numbers; numbers == 0: INT64_MAX / INT64_MIN */
+    uint64_t sum_lo;        /* the exact sum, bits 0 .. 63 */
+    int64_t  sum_hi;        /* ... bits 64 .. 127 */
+} gx_measure_stats;
+
+/* gx_capture_stats: stats[n_measures] (host) receives every measure's summary of the batch bytes / offsets / n / ids / caps, which are
+ * read exactly as gx_select_lines_where reads them (int32 ids with dense caps, or u16 / u8 result rows with compact_results 1 / 2, a
+ * saturated offset taken at face value; offsets64; utf16; utf8 = 1; device_pointers, else the inputs are staged; stream).  hist
+ * (host, optional): measure m owns n_edges + 1 consecutive entries, measure after measure in the caller's order; a number v lands in
+ * bucket b = the number of edges <= v (bucket 0: v < edges[0]; the last: v >= edges[n_edges - 1]; no edges: one bucket == numbers).
+ * One reduction pass and a small second kernel on opts->stream, no atomics in global memory; the call synchronises the stream once,
+ * to deliver the results.  GX_E_ARG: measures == NULL or stats == NULL with n_measures > 0, a measure's extraction or group out of
+ * range, edges == NULL with n_edges > 0, edges not strictly ascending, every refusal of a term (gx_select_lines_where), terms or
+ * measures on dense ids without caps, utf8 = 2, no_sync (the results are host values).  GX_E_LIMIT: more than 64 measures, more
+ * than 64 edges in a measure or 1 024 in all, n of 2^32 and more, a line of 2^32 code units and more.  All but the last need no device
+ * (a host-only handle gives them, and GX_E_DEVICE after them: there is no CPU path).  n_measures == 0 is legal. */
+int gx_capture_stats(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                     const gx_measure* measures, uint32_t n_measures, const gx_where_term* terms, uint32_t n_terms,
+                     gx_measure_stats* stats, uint64_t* hist, const gx_batch_opts* opts);
+
+/* The whole-file form, next to gx_text_select_where: raw text -> lines -> the match-and-extract path (which leaves ids and dense
+ * capture rows on the device) -> the same summary.  counts (optional, uint64_t[2K + 2], host) is the histogram of outcomes as
+ * gx_text_select gives it, *n_lines (optional) the number of lines; both are delivered with n_measures == 0 too.  Limits and options
+ * are gx_text_select_where's: text below 4 GiB, device text 16-byte aligned, utf8 0 / 1. */
+int gx_text_capture_stats(gx_handle* h, const uint8_t* text, uint64_t size, const gx_measure* measures, uint32_t n_measures,
+                          const gx_where_term* terms, uint32_t n_terms, gx_measure_stats* stats, uint64_t* hist, uint64_t* counts,
+                          uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
