@@ -48,6 +48,7 @@ SYMBOLS = [
     "gx_partition_lines", "gx_text_to_jsonl_by_extraction",
     "gx_select_lines_where", "gx_text_select_where",
     "gx_capture_stats", "gx_text_capture_stats",
+    "gx_group_lines", "gx_text_group_lines",
 ]
 
 
@@ -85,6 +86,23 @@ class gx_measure(C.Structure):
 class gx_measure_stats(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64),
                 ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64)]
+
+
+GX_GROUP_WEAK_HASH = 1
+
+
+class gx_group_part(C.Structure):
+    _fields_ = [("extraction", C.c_int32), ("key_group", C.c_int32), ("value_group", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class gx_group_out(C.Structure):
+    _fields_ = [("key_units", C.c_void_p), ("key_units_cap", C.c_uint64), ("key_offsets", C.c_void_p), ("key_first_line", C.c_void_p),
+                ("key_lines", C.c_void_p), ("key_stats", C.c_void_p), ("line_key", C.c_void_p), ("max_keys", C.c_uint64)]
+
+
+class gx_group_totals(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("key_units", C.c_uint64), ("lines", C.c_uint64), ("keyed", C.c_uint64), ("unset", C.c_uint64),
+                ("exact", C.c_uint64)]
 
 
 class gx_device_shard(C.Structure):
@@ -247,6 +265,14 @@ def lib():
     L.gx_text_capture_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_measure), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
                                         C.POINTER(gx_measure_stats), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_capture_stats.restype = C.c_int
+    L.gx_group_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32,
+                                 C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_group_totals),
+                                 C.POINTER(gx_batch_opts)]
+    L.gx_group_lines.restype = C.c_int
+    L.gx_text_group_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                      C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_group_totals), C.c_void_p, C.POINTER(C.c_uint64),
+                                      C.POINTER(gx_batch_opts)]
+    L.gx_text_group_lines.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

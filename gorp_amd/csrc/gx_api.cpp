@@ -20,6 +20,7 @@
 #include "gx_compile.hpp"
 #include "gx_device.hpp"
 #include "gx_dsl.hpp"
+#include "gx_group.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
@@ -264,6 +265,12 @@ struct gx_handle {
     // gx_capture_stats: its measures, edges and terms on the device (StatsHead, gx_stats.hpp; WhereHead behind it), and the summed words
     // and the workgroups' slabs (gx_stats.hip).  Used under `mu`; every call that uses them ends with a stream synchronisation.
     GrowBuf stats_image, stats_ws;
+    // gx_group_lines: its parts and terms on the device (GroupHead, gx_group.hpp; WhereHead behind it), the slots' words and the per-line
+    // arrays (gx_group.hip).  Used under `mu`.  With device pointers the emit pass is left running on the caller's stream: the next
+    // call's stream waits for group_event first.
+    GrowBuf group_image, group_table, group_lines;
+    Event group_event;
+    bool group_pending = false;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
@@ -1714,6 +1721,246 @@ int gx_text_capture_stats(gx_handle* h, const uint8_t* text, uint64_t size, cons
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         if (n_lines) *n_lines = tl.n;
         return GX_OK;
+    });
+}
+
+// The parts of a gx_group_lines call as its kernels read them (gx_group.hpp: GroupHead), checked against the handle.  Needs no device.
+struct GroupImage {
+    GroupHead head{};
+    bool values = false;
+};
+static GroupImage group_image(const gx_handle* h, const gx_group_part* parts, uint32_t n_parts, uint32_t flags, const std::string& name) {
+    GroupImage img;
+    if (flags & ~static_cast<uint32_t>(GX_GROUP_WEAK_HASH)) throw GxError(GX_E_ARG, name + ": unknown flag bits");
+    img.head.flags = flags;
+    if (n_parts == 0) return img;
+    if (!parts) throw GxError(GX_E_ARG, name + ": parts is NULL");
+    if (n_parts > GROUP_MAX_PARTS) throw GxError(GX_E_LIMIT, name + ": more than 64 parts");
+    const int32_t K = static_cast<int32_t>(h->T.n_rules);
+    std::vector<uint32_t> order(n_parts);
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const gx_group_part& p = parts[t];
+        order[t] = t;
+        if (p.extraction < 0 || p.extraction >= K) throw GxError(GX_E_ARG, name + ": a part's extraction is not in [0, K)");
+        const int32_t groups = gx_num_groups(h, p.extraction);
+        if (p.key_group < 0 || p.key_group >= groups) throw GxError(GX_E_ARG, name + ": a part's key_group is not one of its extraction's");
+        if (p.value_group < -1 || p.value_group >= groups) throw GxError(GX_E_ARG, name + ": a part's value_group is neither -1 nor one of its extraction's");
+        if (p.reserved != 0) throw GxError(GX_E_ARG, name + ": a part's reserved is not 0");
+        if (p.value_group >= 0) img.values = true;
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return parts[a].extraction < parts[b].extraction; });
+    for (uint32_t q = 0; q < n_parts; ++q) {
+        const gx_group_part& p = parts[order[q]];
+        if (q && parts[order[q - 1]].extraction == p.extraction) throw GxError(GX_E_ARG, name + ": two parts for one extraction");
+        img.head.ext[q] = static_cast<uint32_t>(p.extraction);
+        img.head.part[q].key_group = static_cast<uint16_t>(p.key_group);
+        img.head.part[q].value_group = p.value_group < 0 ? static_cast<uint16_t>(GROUP_NO_VALUE) : static_cast<uint16_t>(p.value_group);
+    }
+    img.head.n_parts = n_parts;
+    img.head.has_values = img.values ? 1u : 0u;
+    return img;
+}
+
+// what both group calls refuse before they look at the device
+static void group_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                           uint32_t flags, bool wide, const gx_group_out& out, const gx_group_totals* totals, const std::string& name, GroupImage* gi,
+                           WhereImage* wi) {
+    if (!totals) throw GxError(GX_E_ARG, name + ": totals is NULL");
+    *gi = group_image(h, parts, n_parts, flags, name);
+    if (out.key_stats && !gi->values) throw GxError(GX_E_ARG, name + ": key_stats without a value_group");
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the totals are host values");
+    if (out.max_keys > GROUP_MAX_KEYS) throw GxError(GX_E_LIMIT, name + ": max_keys above 2^30");
+}
+
+// The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
+// totals and checks the capacities; then the emit.  ids / offsets / data / caps: device pointers; out: the caller's, device or host
+// (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes (gx_text_group_lines).
+static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
+                      const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
+                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    if (counts) {
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
+        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    *totals = gx_group_totals{};
+    totals->exact = 1;
+    const bool run = n != 0 && gi.head.n_parts != 0;
+    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key;
+    if (!run) {
+        GX_HIP(hipStreamSynchronize(stream));
+        // no keys: the offsets' one entry and every line's "none"
+        const uint64_t zero = 0;
+        if (out.key_offsets) {
+            if (host_out) memcpy(out.key_offsets, &zero, out64 ? 8 : 4);
+            else GX_HIP(hipMemsetAsync(out.key_offsets, 0, out64 ? 8 : 4, stream));
+        }
+        if (out.line_key && n) {
+            if (host_out) memset(out.line_key, 0xFF, n * 4);
+            else GX_HIP(hipMemsetAsync(out.line_key, 0xFF, n * 4, stream));
+        }
+        return GX_OK;
+    }
+    if (h->group_pending) {
+        GX_HIP(hipStreamWaitEvent(stream, h->group_event.get(), 0));
+        h->group_pending = false;
+    }
+    const uint32_t n_slots = group_slots(out.max_keys);
+    uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
+                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u};
+    const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
+    GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
+    GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&key_units, w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got[2] & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be grouped");
+    totals->lines = got[0];
+    totals->unset = got[1];
+    totals->keyed = got[0] - got[1];
+    totals->n_keys = n_keys;
+    totals->key_units = key_units;
+    if (got[2] & 2u) {
+        totals->exact = 0;
+        totals->n_keys = static_cast<uint64_t>(n_slots) + 1u;
+        return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
+    }
+    if (!any_out) return GX_OK;
+    const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats;
+    if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
+    if (out.key_units && key_units > out.key_units_cap)
+        return fail(GX_E_LIMIT, name + ": " + std::to_string(key_units) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
+    if (out.key_offsets && !out64 && key_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
+    const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
+    GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
+    DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey;
+    if (host_out) {
+        if (out.key_units) { d_units = dev_alloc(key_units * unit); o.key_units = d_units.get(); }
+        if (out.key_offsets) { d_offs = dev_alloc((n_keys + 1) * off_w); o.key_offsets = d_offs.get(); }
+        if (out.key_first_line) { d_first = dev_alloc(n_keys * 4); o.key_first_line = static_cast<uint32_t*>(d_first.get()); }
+        if (out.key_lines) { d_lines = dev_alloc(n_keys * 8); o.key_lines = static_cast<uint64_t*>(d_lines.get()); }
+        if (out.key_stats) { d_stats = dev_alloc(n_keys * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
+        if (out.line_key) { d_lkey = dev_alloc(n * 4); o.line_key = static_cast<uint32_t*>(d_lkey.get()); }
+    }
+    GX_HIP(launch_group_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
+    if (host_out) {
+        if (out.key_units && key_units) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, key_units * unit, hipMemcpyDeviceToHost, stream));
+        if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_keys + 1) * off_w, hipMemcpyDeviceToHost, stream));
+        if (out.key_first_line && n_keys) GX_HIP(hipMemcpyAsync(out.key_first_line, o.key_first_line, n_keys * 4, hipMemcpyDeviceToHost, stream));
+        if (out.key_lines && n_keys) GX_HIP(hipMemcpyAsync(out.key_lines, o.key_lines, n_keys * 8, hipMemcpyDeviceToHost, stream));
+        if (out.key_stats && n_keys) GX_HIP(hipMemcpyAsync(out.key_stats, o.key_stats, n_keys * 64, hipMemcpyDeviceToHost, stream));
+        if (out.line_key) GX_HIP(hipMemcpyAsync(out.line_key, o.line_key, n * 4, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+    } else {
+        if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
+        GX_HIP(hipEventRecord(h->group_event.get(), stream));
+        h->group_pending = true;
+    }
+    return GX_OK;
+}
+
+int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                   uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals,
+                   const gx_batch_opts* opts) {
+    const std::string name = "gx_group_lines";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        const gx_group_out none{};
+        const gx_group_out& go = out ? *out : none;
+        GroupImage gi;
+        WhereImage wi;
+        group_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, go, totals, name, &gi, &wi);
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
+        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the build pass
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            for (uint64_t i = 0; i < n; ++i)
+                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be grouped");
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        // host buffers are staged to the device; the passes are the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (!o.device_pointers) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
+            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (caps && n && slots) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
+                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name);
+    });
+}
+
+int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
+                        uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                        const gx_batch_opts* opts) {
+    const std::string name = "gx_text_group_lines";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        const gx_group_out none{};
+        const gx_group_out& go = out ? *out : none;
+        GroupImage gi;
+        WhereImage wi;
+        group_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, go, totals, name, &gi, &wi);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
+        }
+        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        if (n_lines) *n_lines = tl.n;
+        const int rc = group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
+                                  !o.device_pointers, totals, counts, stream, name);
+        // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
+        // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
+        // wait that delivered them was that already).
+        if (h->group_pending) {
+            GX_HIP(hipStreamSynchronize(stream));
+            h->group_pending = false;
+        }
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
     });
 }
 

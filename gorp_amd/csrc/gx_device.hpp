@@ -273,6 +273,54 @@ size_t stats_workspace_bytes(uint64_t n, uint32_t n_measures, uint32_t n_bins);
 hipError_t launch_capture_stats(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const StatsArgs& a,
                                 void* ws, hipStream_t stream);
 
+// The lines of a finished batch grouped by the text they captured (gx_group.hip; the rule: gx_group.hpp): a hash table of the distinct
+// values, per value its first line, its lines and -- with a value group -- what gx_capture_stats would say of them, and per line the
+// number of its value.
+struct GroupArgs {
+    const void* data;            // the batch's code units
+    int wide;                    // 1: UTF-16 code units
+    const int32_t* caps;         // ROWS_DENSE: [n][slots]; compact rows carry their offsets themselves
+    uint32_t slots;              // 2 * max_groups
+    const void* image;           // GroupHead, on the device, 16-byte aligned
+    const void* where_image;     // WhereHead + the literals, or nullptr: no terms
+    uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
+    uint32_t has_values;         // a part has a value group: the slots have stats words
+};
+// The passes' device workspace: the slots' words (group_table_bytes) and the per-line arrays (group_lines_bytes).
+struct GroupWs {
+    uint32_t n_slots;             // a power of two
+    uint64_t* table;              // [n_slots] the slot words
+    uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS]
+    uint64_t* stats_words;        // [n_slots][GROUP_STATS_WORDS], with values
+    uint64_t* totals;             // [8]: lines that count, lines without a key, status bits (1: a line of 4 G units, 2: the table is full)
+    uint32_t* keynum;             // [n_slots] the slot's key number, written by the emit pass
+    uint64_t* idx_off;            // [n + 1] first lines before line i; [n]: the keys
+    uint64_t* dst_off;            // [n + 1] key units before line i's; [n]: all of them
+    uint64_t *sums_a, *sums_b;    // the scans'
+    uint32_t* slot_of;            // [n] the line's slot, GROUP_NONE: it has no key
+    uint32_t* klen;               // [n] the key's units where the line is its key's first, else 0
+    uint8_t* flags;               // [n] the line is its key's first
+};
+// what the emit pass writes, each part optional (nullptr)
+struct GroupOut {
+    void* key_units;
+    void* key_offsets;
+    uint32_t* key_first_line;
+    uint64_t* key_lines;
+    uint64_t* key_stats;          // [n_keys][8]: gx_measure_stats' fields
+    uint32_t* line_key;
+    int offsets64;                // key_offsets: uint64, else uint32
+};
+size_t group_table_zero_bytes(uint32_t n_slots, bool values);
+size_t group_table_bytes(uint32_t n_slots, bool values);
+size_t group_lines_bytes(uint64_t n);
+GroupWs group_workspace(void* table_mem, void* lines_mem, uint64_t n, uint32_t n_slots, bool values);
+// n > 0, parts > 0.  Build, flags and the two scans; then -- behind the host's look at w.totals, w.idx_off[n], w.dst_off[n] -- the emit.
+hipError_t launch_group_build(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                              const GroupWs& w, hipStream_t stream);
+hipError_t launch_group_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                             const GroupWs& w, const GroupOut& out, uint64_t n_keys, uint64_t key_units, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

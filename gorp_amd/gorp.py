@@ -287,6 +287,17 @@ class Measures:
         return sum(len(e) + 1 for e in self.edges)
 
 
+class GroupParts:
+    """Gorp.group_parts' result: the gx_group_part array of a call."""
+
+    def __init__(self, array, n):
+        self.array, self.n = array, n
+
+    @property
+    def has_values(self):
+        return any(self.array[t].value_group >= 0 for t in range(self.n))
+
+
 def _utf16(s):
     raw = s.encode("utf-16-le", "surrogatepass")
     return np.frombuffer(raw, dtype=np.uint16).copy() if raw else np.zeros(0, np.uint16)
@@ -1061,6 +1072,165 @@ class Gorp:
         _check(N.lib().gx_text_capture_stats(self._h.ptr, text_ptr, size, measures.array, measures.n, terms.array, terms.n, stats, hist.ctypes.data,
                                              counts.ctypes.data, C.byref(nl), C.byref(o)))
         return self._stats_result(measures, stats, hist), counts, nl.value
+
+    # -- lines grouped by the text they captured (gx_group_lines / gx_text_group_lines) ----------------------------------------
+    def group_parts(self, spec):
+        """Resolves a list of (extraction, key extractor) or (extraction, key extractor, value extractor) into gx_group_part records:
+        extraction is a name or an index, an extractor a name or a group index (a name two groups of the extraction share is a
+        ValueError), the value extractor None for a part that only counts.  At most one part per extraction, at most 64 parts.
+        Returns a GroupParts; a GroupParts passes through."""
+        if isinstance(spec, GroupParts):
+            return spec
+        spec = list(spec)
+        if len(spec) > 64:
+            raise ValueError("at most 64 parts")
+        arr = (N.gx_group_part * max(1, len(spec)))()
+        seen = set()
+        for t, item in enumerate(spec):
+            item = tuple(item)
+            if len(item) == 2:
+                item = item + (None,)
+            if len(item) != 3:
+                raise ValueError("a part is (extraction, key extractor[, value extractor])")
+            k, g = self._extraction_and_group(item[0], item[1])
+            if k in seen:
+                raise ValueError("two parts for extraction %r" % (item[0],))
+            seen.add(k)
+            arr[t].extraction, arr[t].key_group, arr[t].value_group = k, g, -1 if item[2] is None else self._extraction_and_group(k, item[2])[1]
+        return GroupParts(arr, len(spec))
+
+    @staticmethod
+    def _group_totals(t):
+        return {"n_keys": t.n_keys, "key_units": t.key_units, "lines": t.lines, "keyed": t.keyed, "unset": t.unset, "exact": bool(t.exact)}
+
+    def group_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                           key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, offsets64=False, utf16=False,
+                           compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_group_lines on device pointers (ints); the outputs are the caller's buffers, each optional (none at all: the size query;
+        max_keys still sizes the table).  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says
+        what the outputs need (n_keys, key_units; exact False: the table overflowed, max_keys = n always suffices); every other
+        error raises."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        totals = N.gx_group_totals()
+        rc = N.lib().gx_group_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n,
+                                    N.GX_GROUP_WEAK_HASH if weak_hash else 0, C.byref(out), C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._group_totals(totals)
+
+    def text_group_lines_device(self, text_ptr, size, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None, key_first_line_ptr=None,
+                                key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, offsets64=False, stream=None, device_pointers=True,
+                                utf8=False, weak_hash=False):
+        """gx_text_group_lines on a device buffer (int); outputs as group_lines_device takes them (line_key: one entry per line of the
+        text).  Returns (rc, totals, counts, n_lines)."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        totals = N.gx_group_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_lines(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, N.GX_GROUP_WEAK_HASH if weak_hash else 0,
+                                         C.byref(out), C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._group_totals(totals), counts, nl.value
+
+    def _group_host(self, call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap):
+        """Runs `call(out arrays..., max_keys, key_units_cap)` on host arrays; on GX_E_LIMIT once more with the sizes it reported when
+        they are exact, else with the number of lines (which may report exact sizes in turn).  Builds the result dict."""
+        max_keys = min(n_lines_cap, 1024) if max_keys is None else max_keys
+        key_units_cap = 65536 if key_units_cap is None else key_units_cap
+        for attempt in range(3):
+            units = np.zeros(max(1, key_units_cap), unit_dtype)
+            koff = np.zeros(max_keys + 1, offsets_dtype)
+            first = np.zeros(max(1, max_keys), np.uint32)
+            lines = np.zeros(max(1, max_keys), np.uint64)
+            stats = (N.gx_measure_stats * max(1, max_keys))() if parts.has_values else None
+            line_key = np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32)
+            got = call(units.ctypes.data, key_units_cap, koff.ctypes.data, first.ctypes.data, lines.ctypes.data, None if stats is None else C.addressof(stats),
+                       line_key.ctypes.data, max_keys)
+            rc, totals = got[0], got[1]
+            if rc == N.GX_OK:
+                break
+            if attempt == 2:
+                raise GorpError(rc, N.last_error())
+            if totals["exact"]:
+                max_keys, key_units_cap = max(max_keys, totals["n_keys"]), max(key_units_cap, totals["key_units"])
+            else:
+                max_keys = n_lines_cap
+        k = totals["n_keys"]
+        koff, units = koff[:k + 1], units[:totals["key_units"]]
+        res = {"key_units": units, "key_offsets": koff, "first_line": first[:k], "lines": lines[:k], "totals": totals, "line_key": line_key,
+               "stats": None if stats is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                                                      "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
+                                                      "sum": (s.sum_hi << 64) + s.sum_lo} for s in stats[:k]]}
+        if keys == "list":
+            res["keys"] = [decode(units[int(koff[j]):int(koff[j + 1])]) for j in range(k)]
+        elif keys != "csr":
+            raise ValueError('keys: "list" or "csr"')
+        return res, got[2:]
+
+    def group_lines(self, data, offsets, ids, rows, parts, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None, weak_hash=False):
+        """gx_group_lines on host buffers: the lines grouped by the value the part of their extraction names as the key (parts:
+        Gorp.group_parts or its input), of the lines on which every term of `where` holds.  data / offsets / ids / rows and utf8 as
+        capture_stats takes them.  Returns a dict: keys (a list in order of first appearance: bytes, or str for a UTF-16 batch and
+        with utf8; keys="csr": left out), key_units / key_offsets (the same as CSR arrays), first_line, lines (per key), stats (per
+        key, a dict as capture_stats gives one without hist; None when no part has a value extractor), line_key (uint32 per input
+        line, 0xFFFFFFFF: none) and totals.  On GX_E_LIMIT the call is repeated with the sizes it reported when they are exact; when the
+        table itself overflowed, with max_keys = the number of lines, which may in turn report exact sizes: three calls at the most."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.group_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            return self.group_lines_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), parts, where, units, cap, koff, first, lines, stats, line_key, mk,
+                                           offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8),
+                                           weak_hash=weak_hash)
+        res, _ = self._group_host(call, n, parts, data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap)
+        res["line_key"] = res["line_key"][:n]
+        return res
+
+    def text_group_lines(self, text, parts, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None):
+        """gx_text_group_lines on a host buffer: raw text -> lines -> extraction -> group_lines.  Returns (the dict group_lines returns,
+        counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.group_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            return self.text_group_lines_device(raw.ctypes.data if raw.size else None, raw.size, parts, where, units, cap, koff, first, lines, stats, line_key, mk,
+                                                device_pointers=False, utf8=utf8)
+        res, (counts, n_lines) = self._group_host(call, cap_lines, parts, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
+        res["line_key"] = res["line_key"][:n_lines]
+        return res, counts, n_lines
 
     def partition_lines(self, data, offsets, ids, rows=None, want=None):
         """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every

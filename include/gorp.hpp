@@ -371,6 +371,82 @@ public:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         return statsOf(m, stats, hist);
     }
+    // Lines grouped by the text they captured (gx_group_lines): the parts of a call, built by name.  groupParts().of("GetRequest",
+    // "verb").of("OtherRequest", "verb") is the caller's byVerb.merge(r.asMap().get("verb"), 1L, Long::sum) (README.md:26,63-79);
+    // of("GetRequest", "path", "timeTakenInMsec") also measures a number per key.  Names resolve as Where's do; one part per extraction.
+    class GroupParts {
+    public:
+        explicit GroupParts(const Gorp* g) : g_(g) {}
+        GroupParts& of(const std::string& extraction, const std::string& key, const std::string& value = std::string()) {
+            Where at(g_);
+            at.on(extraction, key).isSet();
+            const gx_where_term k = at.terms()[0];
+            int32_t v = -1;
+            if (!value.empty()) {
+                at.on(extraction, value).isSet();
+                v = at.terms()[1].group;
+            }
+            return of(static_cast<size_t>(k.extraction), static_cast<size_t>(k.group), v);
+        }
+        GroupParts& of(size_t extraction, size_t keyGroup, int32_t valueGroup = -1) {
+            if (extraction >= g_->extractions_.size() || keyGroup >= g_->extractions_[extraction].extractorNames.size() || valueGroup < -1 ||
+                (valueGroup >= 0 && static_cast<size_t>(valueGroup) >= g_->extractions_[extraction].extractorNames.size()))
+                throw std::invalid_argument("no such extraction or group");
+            for (const gx_group_part& p : parts_)
+                if (p.extraction == static_cast<int32_t>(extraction)) throw std::invalid_argument("two parts for one extraction");
+            gx_group_part p{};
+            p.extraction = static_cast<int32_t>(extraction);
+            p.key_group = static_cast<int32_t>(keyGroup);
+            p.value_group = valueGroup;
+            parts_.push_back(p);
+            return *this;
+        }
+        const std::vector<gx_group_part>& parts() const { return parts_; }
+        bool hasValues() const {
+            for (const gx_group_part& p : parts_)
+                if (p.value_group >= 0) return true;
+            return false;
+        }
+
+    private:
+        const Gorp* g_;
+        std::vector<gx_group_part> parts_;
+    };
+    GroupParts groupParts() const { return GroupParts(this); }
+    // The groups of a call: the distinct keys in the order of their first line (a LinkedHashMap's insertion order), per key its first
+    // line, its lines and -- when a part has a value -- its gx_measure_stats; per input line its key's number (0xFFFFFFFF: none).
+    struct Groups {
+        std::vector<std::string> keys;
+        std::vector<uint32_t> firstLine;
+        std::vector<uint64_t> lines;
+        std::vector<gx_measure_stats> stats;   // empty when no part has a value
+        std::vector<uint32_t> lineKey;
+        gx_group_totals totals{};
+    };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other
+    // layout): those whose extraction has a part and on which every term of `where` holds, grouped by the part's key
+    Groups groupLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const GroupParts& parts,
+                      const Where* where = nullptr) const {
+        return groupsOf(parts, where, &n, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out, gx_group_totals* totals) {
+            return gx_group_lines(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, 0, out, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same groups out (gx_text_group_lines).  counts (optional): lines per outcome index.
+    Groups textGroupLines(const std::string& text, const GroupParts& parts, const Where* where = nullptr, std::vector<uint64_t>* counts = nullptr,
+                          uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        Groups g = groupsOf(parts, where, &lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                      gx_group_totals* totals) {
+            return gx_text_group_lines(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, 0, out, totals, counts ? counts->data() : nullptr,
+                                       &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return g;
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
@@ -435,6 +511,44 @@ public:
 private:
     friend class DefinitionReader;
     Gorp(gx_handle* h, std::vector<CookedExtraction> x) : h_(h), extractions_(std::move(x)) {}
+    // The size query with a table for a modest number of keys -- if that table overflows (GX_E_LIMIT, exact == 0), once more with as many
+    // keys as lines, which always suffices -- then the call with exactly the sizes it reported.  *lines: the batch's lines (for a text:
+    // what the call itself reports).
+    template <typename Call>
+    Groups groupsOf(const GroupParts& parts, const Where* where, const uint64_t* lines, Call&& call) const {
+        const std::vector<gx_group_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
+        Groups g;
+        gx_group_out query{};
+        query.max_keys = 1024;
+        int rc = call(p.data(), np, terms.data(), nt, &query, &g.totals);
+        if (rc == GX_E_LIMIT && g.totals.n_keys != 0 && g.totals.exact == 0) {
+            query.max_keys = *lines;
+            rc = call(p.data(), np, terms.data(), nt, &query, &g.totals);
+        }
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t k = static_cast<size_t>(g.totals.n_keys);
+        std::vector<uint8_t> units(static_cast<size_t>(g.totals.key_units) + 1);
+        std::vector<uint32_t> offsets(k + 1, 0);
+        g.firstLine.assign(k, 0);
+        g.lines.assign(k, 0);
+        if (parts.hasValues()) g.stats.assign(k, gx_measure_stats{});
+        g.lineKey.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        gx_group_out out{};
+        out.key_units = units.data();
+        out.key_units_cap = g.totals.key_units;
+        out.key_offsets = offsets.data();
+        out.key_first_line = g.firstLine.data();
+        out.key_lines = g.lines.data();
+        out.key_stats = parts.hasValues() ? g.stats.data() : nullptr;
+        out.line_key = g.lineKey.data();
+        out.max_keys = g.totals.n_keys;   // (the arrays' capacity; a table of twice as many slots holds them all)
+        rc = call(p.data(), np, terms.data(), nt, &out, &g.totals);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
+        return g;
+    }
     static std::vector<MeasureStats> statsOf(const std::vector<gx_measure>& m, const std::vector<gx_measure_stats>& stats, const std::vector<uint64_t>& hist) {
         std::vector<MeasureStats> out;
         size_t at = 0;

@@ -456,6 +456,79 @@ int gx_text_capture_stats(gx_handle* h, const uint8_t* text, uint64_t size, cons
                           const gx_where_term* terms, uint32_t n_terms, gx_measure_stats* stats, uint64_t* hist, uint64_t* counts,
                           uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* Lines grouped by the text they captured.  The reference caller's remaining everyday move behind the extraction is to key on a
+ * captured text (README.md:26,63-79, on the README definition):
+ *     r = gorp.extract(line);
+ *     if (r != null) { byVerb.merge(r.asMap().get("verb"), 1L, Long::sum);
+ *                      latency.computeIfAbsent(r.asMap().get("path"), p -> new Stats()).record(Long.parseLong(r.asMap().get("timeTakenInMsec"))); }
+ * A PART names, for the lines of one extraction, the group whose value is the line's KEY and optionally a group that is measured per key
+ * as gx_capture_stats measures one.  A line COUNTS when its outcome is a matched extraction that has a part and every term of that
+ * extraction holds (gx_capture_stats' rule).  Its key is the code units line[begin, end) of key_group; a pair that names no value (the
+ * group is unset, or begin < 0 <= end, end < begin, end beyond the line: never dereferenced) adds to `unset` and gives the line no key.
+ * The empty value is a key like any other.  Keys of different parts live in ONE key space: "GET" captured by GetRequest and by
+ * OtherRequest is the same key.  Two values are the same key when they have the same number of units and the same units (bytes; 16-bit
+ * units with utf16; UTF-8 bytes with utf8 = 1).  Keys leave ORDERED by the first input line that holds them -- the insertion order of a
+ * LinkedHashMap filled line by line -- and every result is exact and the same bits on every run.  This is also the dictionary encoding
+ * of the column: the distinct values plus a key number per line. */
+#define GX_GROUP_WEAK_HASH 1u   /* test hook (as GX_CREATE_PROGRAMS is): the hash is cut to its low 3 bits, so distinct values share tag
+                                   AND first slot; results are identical, only slower */
+
+typedef struct gx_group_part {  /* the lines of ONE extraction: which group is the key, which (if any) the number */
+    int32_t extraction;         /* k in [0, K); at most one part per extraction */
+    int32_t key_group;          /* g in [0, gx_num_groups(h, k)) */
+    int32_t value_group;        /* -1: count only; else a group parsed as gx_capture_stats parses one */
+    uint32_t reserved;          /* 0 */
+} gx_group_part;
+
+typedef struct gx_group_out {   /* every pointer optional; device memory with opts->device_pointers, else host */
+    void*     key_units;        /* the distinct values, one behind the other, in the batch's code units (u8; u16 with utf16) */
+    uint64_t  key_units_cap;
+    void*     key_offsets;      /* n_keys + 1, uint32 or uint64 as opts->offsets64: key j is key_units[key_offsets[j], key_offsets[j+1]) */
+    uint32_t* key_first_line;   /* the first input line that holds key j: keys are ORDERED by it */
+    uint64_t* key_lines;        /* lines that hold key j */
+    gx_measure_stats* key_stats;/* per key, over its lines whose part has a value_group (exact 128-bit sum; no histogram) */
+    uint32_t* line_key;         /* n entries: the key number of every input line, 0xFFFFFFFF for a line that has none */
+    uint64_t  max_keys;         /* capacity of the four per-key arrays (key_offsets: max_keys + 1) */
+} gx_group_out;
+
+typedef struct gx_group_totals {/* host, always */
+    uint64_t n_keys, key_units; /* what the outputs need */
+    uint64_t lines;             /* lines that count (their extraction has a part and every term of it holds) */
+    uint64_t keyed, unset;      /* ... whose key pair names a value / names none: lines == keyed + unset */
+    uint64_t exact;             /* 1: n_keys and key_units are exact; 0: the table overflowed, n_keys is only a lower bound */
+} gx_group_totals;
+
+/* gx_group_lines: the batch bytes / offsets / n / ids / caps is read exactly as gx_capture_stats reads it (row formats, offsets64,
+ * utf16, utf8 = 1, device_pointers or staging, stream).  key_stats[j] summarises key j's lines whose part has a value_group: lines ==
+ * numbers + unset + not_numbers, min / max INT64_MAX / INT64_MIN without a number, the sum exact; where no part has a value group
+ * key_stats must be NULL.  The keys are found in a hash table on the device of the smallest power of two >= max(64, 2 * max_keys) slots.
+ * With every output pointer NULL (or out == NULL) the call is the size query: only *totals is delivered, and max_keys is still read, as
+ * the table's size.  If a per-key array is given and n_keys > max_keys, or key_units is given and totals->key_units > key_units_cap, the
+ * call returns GX_E_LIMIT, writes nothing to any output and fills *totals.  If a line finds no free slot the call returns GX_E_LIMIT
+ * with exact = 0 and n_keys = slots + 1; the number of lines is always a sufficient max_keys.  The call synchronises the stream once,
+ * where the host reads the totals; with host outputs a second wait delivers them.
+ * GX_E_ARG: parts == NULL with n_parts > 0, totals == NULL, a part's extraction or group out of range, two parts for one extraction,
+ * reserved != 0, unknown flag bits, key_stats without a value_group, every refusal of a term (gx_select_lines_where), parts or terms on
+ * dense ids without caps, utf8 = 2, no_sync.  GX_E_LIMIT: more than 64 parts, n of 2^32 - 1 and more, max_keys above 2^30, a line of
+ * 2^32 code units and more (or offsets that go backwards).  All need no device (a host-only handle gives them, and GX_E_DEVICE after
+ * them: there is no CPU path) but the last with device_pointers, where the offsets lie on the device and the build pass finds it.
+ * n_parts == 0 is legal: no keys, all zeros.
+ * With device_pointers the emit pass is left running on opts->stream when the call returns (stream order delivers the outputs); the
+ * handle's next gx_group_lines on another stream waits for it, and the batch must stay unchanged until it has run. */
+int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                   const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                   const gx_group_out* out, gx_group_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_capture_stats' chain with the grouping at its end: raw text -> lines -> the match-and-extract path ->
+ * the same result.  counts (optional, uint64_t[2K + 2], host) and *n_lines (optional) as gx_text_capture_stats delivers them, with
+ * n_parts == 0 too.  out->line_key, if given, has one entry per line of the text (the size query delivers *n_lines).  Limits and options
+ * are gx_text_capture_stats': text below 4 GiB, device text 16-byte aligned, utf8 0 / 1.  Like every gx_text_* call it returns with
+ * all its work on opts->stream done, with device_pointers too: its passes read the lines' offsets, ids and capture rows from the handle's
+ * buffers, which the next whole-file call reuses. */
+int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                        const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
+                        gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
