@@ -25,6 +25,7 @@
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
 #include "gx_stats.hpp"
+#include "gx_top.hpp"
 #include "gx_where.hpp"
 
 using namespace gx;
@@ -271,6 +272,12 @@ struct gx_handle {
     GrowBuf group_image, group_table, group_lines;
     Event group_event;
     bool group_pending = false;
+    // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
+    // TopWs).  Used under `mu`.  With device pointers the emit pass is left running on the caller's stream and still reads the
+    // workspace: the next call's stream waits for top_event first (gx_partition_lines' rule for its no_sync copy pass).
+    GrowBuf top_image, top_ws;
+    Event top_event;
+    bool top_pending = false;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
@@ -1958,6 +1965,252 @@ int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const 
         if (h->group_pending) {
             GX_HIP(hipStreamSynchronize(stream));
             h->group_pending = false;
+        }
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
+    });
+}
+
+// The parts of a gx_top_lines call as its keys pass reads them (gx_top.hpp: TopHead), checked against the handle.  Needs no device.
+static TopHead top_image(const gx_handle* h, const gx_top_part* parts, uint32_t n_parts, uint32_t flags, const std::string& name) {
+    TopHead head{};
+    if (flags & ~static_cast<uint32_t>(GX_TOP_SMALLEST)) throw GxError(GX_E_ARG, name + ": unknown flag bits");
+    head.smallest = (flags & GX_TOP_SMALLEST) ? 1u : 0u;
+    if (n_parts == 0) return head;
+    if (!parts) throw GxError(GX_E_ARG, name + ": parts is NULL");
+    if (n_parts > TOP_MAX_PARTS) throw GxError(GX_E_LIMIT, name + ": more than 64 parts");
+    const int32_t K = static_cast<int32_t>(h->T.n_rules);
+    std::vector<uint32_t> order(n_parts);
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const gx_top_part& p = parts[t];
+        order[t] = t;
+        if (p.extraction < 0 || p.extraction >= K) throw GxError(GX_E_ARG, name + ": a part's extraction is not in [0, K)");
+        if (p.value_group < 0 || p.value_group >= gx_num_groups(h, p.extraction))
+            throw GxError(GX_E_ARG, name + ": a part's value_group is not one of its extraction's");
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return parts[a].extraction < parts[b].extraction; });
+    for (uint32_t q = 0; q < n_parts; ++q) {
+        const gx_top_part& p = parts[order[q]];
+        if (q && parts[order[q - 1]].extraction == p.extraction) throw GxError(GX_E_ARG, name + ": two parts for one extraction");
+        head.ext[q] = static_cast<uint32_t>(p.extraction);
+        head.group[q] = static_cast<uint16_t>(p.value_group);
+    }
+    head.n_parts = n_parts;
+    return head;
+}
+
+// what both top-lines calls refuse before they look at the device
+static void top_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                         uint32_t n_wanted, uint32_t flags, bool wide, const gx_top_totals* totals, const std::string& name, TopHead* ti, WhereImage* wi) {
+    if (!totals) throw GxError(GX_E_ARG, name + ": totals is NULL");
+    *ti = top_image(h, parts, n_parts, flags, name);
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the totals are host values");
+    if (n_wanted > GX_TOP_MAX_LINES) throw GxError(GX_E_LIMIT, name + ": n_wanted above GX_TOP_MAX_LINES");
+}
+
+// where the delivered lines go: the caller's pointers, device or host (host_out: staged, and a second wait delivers them)
+struct TopOut {
+    uint32_t* index;
+    int64_t* values;
+    void* bytes;
+    void* offsets;
+    void* ids;
+    int32_t* caps;
+    uint64_t cap_lines, bytes_cap;
+    bool any() const { return index || values || bytes || offsets || ids || caps; }
+};
+
+// The passes on the handle's workspace (under h->mu): keys, select, choose and order; ONE synchronisation of the stream, where the host
+// reads the totals and checks the capacities; then the emit (launch_partition_copy).  ids / offsets / data / caps: device pointers.
+// counts: also the histogram of outcomes (gx_text_top_lines).
+static int top_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
+                    const int32_t* caps, bool wide, const TopHead& ti, const WhereImage& wi, uint32_t n_wanted, const TopOut& out, bool host_out,
+                    gx_top_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    if (counts) {
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
+        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    *totals = gx_top_totals{};
+    const size_t unit = wide ? 2 : 1, off_w = off64 ? 8 : 4, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+    const uint64_t zero = 0;
+    if (n == 0 || ti.n_parts == 0) {
+        GX_HIP(hipStreamSynchronize(stream));
+        if (out.offsets) {   // no lines: the offsets' one entry
+            if (host_out) memcpy(out.offsets, &zero, off_w);
+            else GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
+        }
+        return GX_OK;
+    }
+    if (h->top_pending) {
+        GX_HIP(hipStreamWaitEvent(stream, h->top_event.get(), 0));
+        h->top_pending = false;
+    }
+    uint8_t* d_img = static_cast<uint8_t*>(h->top_image.get(sizeof(TopHead) + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + sizeof(TopHead),
+                    static_cast<uint32_t>(wi.bytes.size()), ti.smallest, n_wanted};
+    const TopWs w = top_workspace(h->top_ws.get(top_workspace_bytes(n)), n);
+    GX_HIP(launch_top_select(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    struct { uint32_t counts[TOP_COUNTS]; TopSelect sel; } got{};
+    static_assert(sizeof(got) == offsetof(TopDev, spare), "the head's first words");
+    uint64_t both = 0, units = 0;
+    GX_HIP(hipMemcpyAsync(&got, w.head, sizeof(got), hipMemcpyDeviceToHost, stream));
+    if (n_wanted) {
+        GX_HIP(hipMemcpyAsync(&both, w.before + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&units, w.dst_off + n_wanted, 8, hipMemcpyDeviceToHost, stream));
+    }
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got.counts[TOP_C_STATUS]) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be ranked");
+    totals->numbers = got.counts[TOP_C_NUMBERS];
+    totals->unset = got.counts[TOP_C_UNSET];
+    totals->not_numbers = got.counts[TOP_C_NOT_NUMBERS];
+    totals->lines = totals->numbers + totals->unset + totals->not_numbers;
+    const uint64_t n_top = got.sel.n_top;
+    totals->n_top = n_top;
+    totals->units_top = units;
+    if (n_top) {
+        // the last delivered line holds the threshold key: the select always takes at least one of its ties
+        totals->last_value = top_value(got.sel.prefix, ti.smallest != 0);
+        totals->ties_left = (both >> 32) - got.sel.remaining;
+    }
+    if (!out.any()) return GX_OK;   // size query
+    if ((out.index || out.values || out.offsets || out.ids || out.caps) && n_top > out.cap_lines)
+        return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->n_top)");
+    if (out.bytes && units * unit > out.bytes_cap) return fail(GX_E_LIMIT, name + ": the delivered text is larger than the capacity (see totals->units_top)");
+    if (out.offsets && !off64 && units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+    SelectOut so{};
+    so.index = out.index; so.bytes = out.bytes; so.offsets = out.offsets;
+    void *dst_ids = out.ids, *dst_caps = out.caps;
+    DevMem<> d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
+    if (host_out) {
+        if (out.index) { d_oindex = dev_alloc(n_top * 4); so.index = static_cast<uint32_t*>(d_oindex.get()); }
+        if (out.bytes) { d_obytes = dev_alloc(units * unit); so.bytes = d_obytes.get(); }
+        if (out.offsets) { d_ooff = dev_alloc((n_top + 1) * off_w); so.offsets = d_ooff.get(); }
+        if (out.ids) { d_oids = dev_alloc(n_top * id_row); dst_ids = d_oids.get(); }
+        if (out.caps) { d_ocaps = dev_alloc(n_top * slots * 4); dst_caps = d_ocaps.get(); }
+    }
+    if (out.ids) { so.col_src[0] = ids; so.col_dst[0] = dst_ids; so.col_width[0] = row_units; so.col_unit_bytes[0] = row_unit_bytes(fmt); }
+    if (out.caps) { so.col_src[1] = caps; so.col_dst[1] = dst_caps; so.col_width[1] = static_cast<uint32_t>(slots); so.col_unit_bytes[1] = 4; }
+    if (so.offsets && n_top == 0) GX_HIP(hipMemsetAsync(so.offsets, 0, off_w, stream));
+    PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
+    pw.perm_sorted = w.perm;
+    pw.dst_off = w.dst_off;
+    GX_HIP(launch_partition_copy(so, data, offsets, off64 ? 1 : 0, wide ? 1 : 0, n, n_top, pw, stream));
+    if (out.values && n_top) GX_HIP(hipMemcpyAsync(out.values, w.values, n_top * 8, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+    if (host_out) {
+        if (out.index && n_top) GX_HIP(hipMemcpyAsync(out.index, so.index, n_top * 4, hipMemcpyDeviceToHost, stream));
+        if (out.bytes && units) GX_HIP(hipMemcpyAsync(out.bytes, so.bytes, units * unit, hipMemcpyDeviceToHost, stream));
+        if (out.offsets) GX_HIP(hipMemcpyAsync(out.offsets, so.offsets, (n_top + 1) * off_w, hipMemcpyDeviceToHost, stream));
+        if (out.ids && n_top) GX_HIP(hipMemcpyAsync(out.ids, dst_ids, n_top * id_row, hipMemcpyDeviceToHost, stream));
+        if (out.caps && n_top) GX_HIP(hipMemcpyAsync(out.caps, dst_caps, n_top * slots * 4, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+    } else {
+        if (!h->top_event) GX_HIP(hipEventCreateWithFlags(h->top_event.out(), hipEventDisableTiming));
+        GX_HIP(hipEventRecord(h->top_event.get(), stream));
+        h->top_pending = true;
+    }
+    return GX_OK;
+}
+
+int gx_top_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_top_part* parts,
+                 uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t n_wanted, uint32_t flags, uint32_t* out_index, int64_t* out_values,
+                 void* out_bytes, void* out_offsets, void* out_ids, int32_t* out_caps, uint64_t cap_lines, uint64_t out_bytes_cap, gx_top_totals* totals,
+                 const gx_batch_opts* opts) {
+    const std::string name = "gx_top_lines";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        TopHead ti;
+        WhereImage wi;
+        top_refusals(h, o, parts, n_parts, terms, n_terms, n_wanted, flags, o.utf16 != 0, totals, name, &ti, &wi);
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 2^32 - 1 lines and more");
+        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the keys pass
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            for (uint64_t i = 0; i < n; ++i)
+                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be ranked");
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) { caps = nullptr; out_caps = nullptr; }
+        if (out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
+        if (!slots) out_caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        // host buffers are staged to the device; the passes are the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (!o.device_pointers) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
+            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (caps && n && slots) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        const TopOut out{out_index, out_values, out_bytes, out_offsets, out_ids, out_caps, cap_lines, out_bytes_cap};
+        return top_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, ti, wi, n_wanted, out,
+                        !o.device_pointers, totals, nullptr, stream, name);
+    });
+}
+
+int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                      uint32_t n_wanted, uint32_t flags, uint32_t* out_index, int64_t* out_values, uint8_t* out, uint64_t out_cap, uint64_t* out_size,
+                      gx_top_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    const std::string name = "gx_text_top_lines";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        TopHead ti;
+        WhereImage wi;
+        top_refusals(h, o, parts, n_parts, terms, n_terms, n_wanted, flags, false, totals, name, &ti, &wi);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
+        }
+        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        if (n_lines) *n_lines = tl.n;
+        const TopOut to{out_index, out_values, out, nullptr, nullptr, nullptr, n_wanted, out_cap};
+        const int rc = top_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, ti, wi, n_wanted, to, !o.device_pointers,
+                                totals, counts, stream, name);
+        if (out_size) *out_size = totals->units_top;
+        // The emit pass reads the offsets that text_lines left in the handle's scratch buffers, which the next whole-file call on any
+        // stream overwrites: like every gx_text_* call this one returns with its work done.
+        if (h->top_pending) {
+            GX_HIP(hipStreamSynchronize(stream));
+            h->top_pending = false;
         }
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         return rc;

@@ -321,6 +321,43 @@ hipError_t launch_group_build(const void* ids, RowFormat fmt, uint32_t row_units
 hipError_t launch_group_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
                              const GroupWs& w, const GroupOut& out, uint64_t n_keys, uint64_t key_units, hipStream_t stream);
 
+// The lines of a finished batch ranked by a number they captured (gx_top.hip; the rule: gx_top.hpp): the n_wanted largest (or smallest)
+// numbers' lines, ordered by (value, input line).
+struct TopArgs {
+    const void* data;            // the batch's code units
+    int wide;                    // 1: UTF-16 code units
+    const int32_t* caps;         // ROWS_DENSE: [n][slots]; compact rows carry their offsets themselves
+    uint32_t slots;              // 2 * max_groups
+    const void* image;           // TopHead, on the device, 16-byte aligned
+    const void* where_image;     // WhereHead + the literals, or nullptr: no terms
+    uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
+    uint32_t smallest;           // GX_TOP_SMALLEST
+    uint32_t n_wanted;           // <= TOP_MAX_LINES
+};
+// The passes' device workspace, cut out of one allocation of top_workspace_bytes(n) bytes:
+struct TopWs {
+    uint8_t* head;                // TopDev (gx_top.hpp): the class counts, the select's state, a digit's histogram
+    uint32_t* slab;               // the workgroups' counts, then their histograms
+    uint64_t* block_sums;         // the scans'
+    uint64_t* keys;               // [n] a candidate's key
+    uint64_t* col;                // [n] 1: a candidate above the threshold, 2^32: one equal to it
+    uint64_t* before;             // [n + 1] col scanned: both kinds before line i; [n]: all of them
+    uint64_t* ckeys;              // [TOP_MAX_LINES] the chosen candidates in line order: keys ...
+    int64_t* values;              // [TOP_MAX_LINES] the delivered lines' numbers, in rank order
+    uint64_t* dst_off;            // [n_wanted + 1] code units before output line j
+    uint32_t* clines;             // ... and lines
+    uint32_t* perm;               // [TOP_MAX_LINES] the input line of output line j
+    uint32_t* plen;               // [n_wanted] its code units, 0 from n_top on
+    uint8_t* cand;                // [n] the line's value is a number
+    size_t bytes;
+};
+TopWs top_workspace(void* ws, uint64_t n);
+size_t top_workspace_bytes(uint64_t n);
+// n > 0, parts > 0.  Everything before the emit; behind the host's look at the head, w.before[n] and w.dst_off[n_wanted] the emit is
+// launch_partition_copy with w.perm and w.dst_off.
+hipError_t launch_top_select(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                             const TopWs& w, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

@@ -298,6 +298,13 @@ class GroupParts:
         return any(self.array[t].value_group >= 0 for t in range(self.n))
 
 
+class TopParts:
+    """Parts for top_lines (Gorp.top_parts)."""
+
+    def __init__(self, array, n):
+        self.array, self.n = array, n
+
+
 def _utf16(s):
     raw = s.encode("utf-16-le", "surrogatepass")
     return np.frombuffer(raw, dtype=np.uint16).copy() if raw else np.zeros(0, np.uint16)
@@ -1231,6 +1238,133 @@ class Gorp:
         res, (counts, n_lines) = self._group_host(call, cap_lines, parts, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
         res["line_key"] = res["line_key"][:n_lines]
         return res, counts, n_lines
+
+    # -- lines ranked by a number they captured (gx_top_lines / gx_text_top_lines) ------------------------------------------------
+    def top_parts(self, spec):
+        """Resolves a list of (extraction, value extractor) into gx_top_part records: extraction is a name or an index, the extractor a
+        name or a group index (a name two groups of the extraction share is a ValueError).  At most one part per extraction, at most
+        64 parts; all parts share one number space.  Returns a TopParts; a TopParts passes through."""
+        if isinstance(spec, TopParts):
+            return spec
+        spec = list(spec)
+        if len(spec) > 64:
+            raise ValueError("at most 64 parts")
+        arr = (N.gx_top_part * max(1, len(spec)))()
+        seen = set()
+        for t, item in enumerate(spec):
+            item = tuple(item)
+            if len(item) != 2:
+                raise ValueError("a part is (extraction, value extractor)")
+            k, g = self._extraction_and_group(item[0], item[1])
+            if k in seen:
+                raise ValueError("two parts for extraction %r" % (item[0],))
+            seen.add(k)
+            arr[t].extraction, arr[t].value_group = k, g
+        return TopParts(arr, len(spec))
+
+    @staticmethod
+    def _top_totals(t):
+        return {"lines": t.lines, "numbers": t.numbers, "unset": t.unset, "not_numbers": t.not_numbers, "n_top": t.n_top, "units_top": t.units_top,
+                "last_value": t.last_value, "ties_left": t.ties_left}
+
+    def top_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, by, n_wanted, largest=True, where=None, out_index_ptr=None, out_values_ptr=None,
+                         out_data_ptr=None, out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0, offsets64=False,
+                         utf16=False, compact=0, stream=None, device_pointers=True, utf8=False):
+        """gx_top_lines on device pointers (ints); the outputs are the caller's buffers, each optional (none at all: the size query).
+        Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says what the outputs need (n_top,
+        units_top); every other error raises."""
+        parts = self.top_parts(by)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        totals = N.gx_top_totals()
+        rc = N.lib().gx_top_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, n_wanted,
+                                  0 if largest else N.GX_TOP_SMALLEST, out_index_ptr, out_values_ptr, out_data_ptr, out_offsets_ptr, out_ids_ptr, out_caps_ptr,
+                                  cap_lines, out_bytes_cap, C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_top):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._top_totals(totals)
+
+    def top_lines(self, data, offsets, ids, rows, by, n, largest=True, where=None, utf8=None):
+        """gx_top_lines on host buffers: the n lines that captured the largest numbers (largest=False: the smallest), ordered by (value,
+        input line); ties at the cut go to the earliest lines.  by: Gorp.top_parts or its input, one (extraction, value extractor) per
+        extraction that takes part; where: terms as capture_stats takes them.  data / offsets / ids / rows and utf8 as capture_stats
+        takes them.  Makes the size query first and then the call.  Returns (index, values, data2, offsets2, ids2, rows2, totals): the
+        delivered lines' input line numbers (uint32), their numbers (int64), the lines as a CSR batch with their ids and rows (rows2
+        None without dense rows), and totals (lines, numbers, unset, not_numbers, n_top, units_top, last_value, ties_left)."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.top_parts(by)
+        nl = len(offsets) - 1
+        args = dict(largest=largest, where=where, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8))
+        _, totals = self.top_lines_device(ptr(data), offsets.ctypes.data, nl, ptr(ids), ptr(caps), parts, n, **args)
+        k, units = totals["n_top"], totals["units_top"]
+        index = np.zeros(max(1, k), np.uint32)
+        values = np.zeros(max(1, k), np.int64)
+        out = np.zeros(max(1, units), data.dtype)
+        out_off = np.zeros(k + 1, offsets.dtype)
+        out_ids = np.zeros((max(1, k),) + ids.shape[1:], ids.dtype)
+        out_caps = None if caps is None else np.zeros((max(1, k), 2 * self.max_groups), np.int32)
+        rc, totals = self.top_lines_device(ptr(data), offsets.ctypes.data, nl, ptr(ids), ptr(caps), parts, n, out_index_ptr=index.ctypes.data,
+                                           out_values_ptr=values.ctypes.data, out_data_ptr=out.ctypes.data, out_offsets_ptr=out_off.ctypes.data,
+                                           out_ids_ptr=out_ids.ctypes.data, out_caps_ptr=None if out_caps is None else out_caps.ctypes.data,
+                                           cap_lines=k, out_bytes_cap=units * data.itemsize, **args)
+        if rc != N.GX_OK:
+            raise GorpError(rc, N.last_error())
+        return index[:k], values[:k], out[:units], out_off, out_ids[:k], None if out_caps is None else out_caps[:k], totals
+
+    def text_top_lines_device(self, text_ptr, size, by, n_wanted, largest=True, where=None, out_index_ptr=None, out_values_ptr=None, out_ptr=None, out_cap=0,
+                              stream=None, device_pointers=True, utf8=False):
+        """gx_text_top_lines on a device buffer (int): out_index_ptr / out_values_ptr have room for n_wanted entries, out_ptr for out_cap
+        bytes; all None: the size query.  Returns (rc, totals, out_size, counts, n_lines); rc as top_lines_device returns it."""
+        parts = self.top_parts(by)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        totals = N.gx_top_totals()
+        out_size, nl = C.c_uint64(0), C.c_uint64(0)
+        rc = N.lib().gx_text_top_lines(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, n_wanted, 0 if largest else N.GX_TOP_SMALLEST,
+                                       out_index_ptr, out_values_ptr, out_ptr, out_cap, C.byref(out_size), C.byref(totals), counts.ctypes.data, C.byref(nl),
+                                       C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_top):
+            _check(rc)
+        return rc, self._top_totals(totals), out_size.value, counts, nl.value
+
+    def text_top_lines(self, text, by, n, largest=True, where=None, utf8=False):
+        """gx_text_top_lines on a host buffer: raw text -> lines -> extraction -> top_lines.  Returns (index, values, the delivered
+        lines' text as bytes -- each with its terminator, in rank order --, totals, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        ptr = raw.ctypes.data if raw.size else None
+        parts = self.top_parts(by)
+        _, totals, size, _, _ = self.text_top_lines_device(ptr, raw.size, parts, n, largest, where, device_pointers=False, utf8=utf8)
+        index = np.zeros(max(1, n), np.uint32)
+        values = np.zeros(max(1, n), np.int64)
+        out = np.zeros(max(1, size), np.uint8)
+        rc, totals, size, counts, n_lines = self.text_top_lines_device(ptr, raw.size, parts, n, largest, where, index.ctypes.data, values.ctypes.data,
+                                                                       out.ctypes.data, size, device_pointers=False, utf8=utf8)
+        if rc != N.GX_OK:
+            raise GorpError(rc, N.last_error())
+        k = totals["n_top"]
+        return index[:k], values[:k], out[:size].tobytes(), totals, counts, n_lines
 
     def partition_lines(self, data, offsets, ids, rows=None, want=None):
         """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every

@@ -447,6 +447,71 @@ public:
         if (nLines) *nLines = lines;
         return g;
     }
+    // Lines ranked by a number they captured (gx_top_lines): the parts of a call, built by name.  topParts().of("GetRequest",
+    // "timeTakenInMsec").of("OtherRequest", "timeTakenInMsec") with topLines(..., 10) is the caller's "which requests were the slowest?",
+    // sorted(results, by timeTakenInMsec).take(10) (README.md:26,63-79).  Names resolve as Where's do; one part per extraction; all
+    // parts share one number space.
+    class TopParts {
+    public:
+        explicit TopParts(const Gorp* g) : g_(g) {}
+        TopParts& of(const std::string& extraction, const std::string& value) {
+            Where at(g_);
+            at.on(extraction, value).isSet();
+            const gx_where_term t = at.terms()[0];
+            return of(static_cast<size_t>(t.extraction), static_cast<size_t>(t.group));
+        }
+        TopParts& of(size_t extraction, size_t valueGroup) {
+            if (extraction >= g_->extractions_.size() || valueGroup >= g_->extractions_[extraction].extractorNames.size())
+                throw std::invalid_argument("no such extraction or group");
+            for (const gx_top_part& p : parts_)
+                if (p.extraction == static_cast<int32_t>(extraction)) throw std::invalid_argument("two parts for one extraction");
+            parts_.push_back(gx_top_part{static_cast<int32_t>(extraction), static_cast<int32_t>(valueGroup)});
+            return *this;
+        }
+        const std::vector<gx_top_part>& parts() const { return parts_; }
+
+    private:
+        const Gorp* g_;
+        std::vector<gx_top_part> parts_;
+    };
+    TopParts topParts() const { return TopParts(this); }
+    // The ranked lines of a call, ordered by (value descending -- ascending for the smallest --, input line ascending): their input line
+    // numbers, their numbers, and the lines themselves as a batch (topLines: bytes + offsets) or as text (textTopLines: bytes alone,
+    // each line with its terminator).
+    struct Top {
+        std::vector<uint32_t> index;
+        std::vector<int64_t> values;
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> offsets;
+        gx_top_totals totals{};
+    };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other
+    // layout): the n whose extraction has a part, on which every term of `where` holds and whose value is a number, largest first
+    Top topLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const TopParts& parts, uint32_t wanted,
+                 bool largest = true, const Where* where = nullptr) const {
+        return topOf(parts, where, [&](const gx_top_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, Top& out, bool deliver) {
+            out.offsets.resize(out.index.size() + 1);
+            return gx_top_lines(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, wanted, largest ? 0u : GX_TOP_SMALLEST, deliver ? out.index.data() : nullptr,
+                                deliver ? out.values.data() : nullptr, deliver ? out.bytes.data() : nullptr, deliver ? out.offsets.data() : nullptr, nullptr, nullptr,
+                                out.index.size(), out.bytes.size(), &out.totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same ranking out (gx_text_top_lines).  counts (optional): lines per outcome index.
+    Top textTopLines(const std::string& text, const TopParts& parts, uint32_t wanted, bool largest = true, const Where* where = nullptr,
+                     std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        return topOf(parts, where, [&](const gx_top_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, Top& out, bool deliver) {
+            uint64_t size = 0;
+            out.index.resize(wanted);    // (the whole-file call's per-line outputs have room for `wanted` entries)
+            out.values.resize(wanted);
+            return gx_text_top_lines(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, wanted, largest ? 0u : GX_TOP_SMALLEST,
+                                     deliver ? out.index.data() : nullptr, deliver ? out.values.data() : nullptr, deliver ? out.bytes.data() : nullptr,
+                                     out.bytes.size(), &size, &out.totals, counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
+        });
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
@@ -548,6 +613,27 @@ private:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
         return g;
+    }
+    // The size query, then the call with exactly the sizes it reported.  call(..., top, deliver): deliver == false is the size query,
+    // which fills top.totals alone; with deliver the outputs' capacities are the vectors' sizes.
+    template <typename Call>
+    Top topOf(const TopParts& parts, const Where* where, Call&& call) const {
+        const std::vector<gx_top_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
+        Top top;
+        int rc = call(p.data(), np, terms.data(), nt, top, false);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t k = static_cast<size_t>(top.totals.n_top), units = static_cast<size_t>(top.totals.units_top);
+        top.index.assign(k, 0);
+        top.values.assign(k, 0);
+        top.bytes.assign(units, 0);
+        top.offsets.clear();
+        rc = call(p.data(), np, terms.data(), nt, top, true);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        top.index.resize(k);
+        top.values.resize(k);
+        return top;
     }
     static std::vector<MeasureStats> statsOf(const std::vector<gx_measure>& m, const std::vector<gx_measure_stats>& stats, const std::vector<uint64_t>& hist) {
         std::vector<MeasureStats> out;

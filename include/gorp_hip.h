@@ -529,6 +529,62 @@ int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
                         gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* Lines ranked by a number they captured.  The reference caller's question "which requests were the slowest?" (README.md:26,63-79, on
+ * the README definition) is
+ *     r = gorp.extract(line); if (r != null) results.add(r); ... sorted(results, by Long.parseLong(timeTakenInMsec)).take(N)
+ * A PART names, for the lines of one extraction, the group whose value is the line's number; all parts share ONE number space ("the
+ * slowest requests, GetRequest or OtherRequest").  A line COUNTS when its outcome is a matched extraction that has a part and every
+ * term of that extraction holds (gx_capture_stats' rule), and its value is classed exactly as gx_capture_stats classes one: unset, not a
+ * number, or a number.  Only numbers are candidates.  The result is the n_top = min(n_wanted, numbers) candidates ordered by (value
+ * descending, input line ascending) -- with GX_TOP_SMALLEST by (value ascending, input line ascending) -- so ties at the cut go to the
+ * earliest lines.  Every output is exact and the same bits on every run. */
+#define GX_TOP_SMALLEST 1u
+#define GX_TOP_MAX_LINES 4096u  /* the cap on n_wanted */
+
+typedef struct gx_top_part {    /* the lines of ONE extraction: which group is the number */
+    int32_t extraction;         /* k in [0, K); at most one part per extraction */
+    int32_t value_group;        /* g in [0, gx_num_groups(h, k)), parsed as gx_capture_stats parses one */
+} gx_top_part;
+
+typedef struct gx_top_totals {  /* host, always */
+    uint64_t lines, numbers, unset, not_numbers;   /* as gx_measure_stats, over all parts: lines == numbers + unset + not_numbers */
+    uint64_t n_top, units_top;  /* what the outputs need: delivered lines, and their code units */
+    int64_t  last_value;        /* value of the last delivered line; 0 when n_top == 0 */
+    uint64_t ties_left;         /* numbers equal to last_value that were NOT delivered */
+} gx_top_totals;
+
+/* gx_top_lines: the batch bytes / offsets / n / ids / caps is read exactly as gx_capture_stats reads it (row formats, where a saturated
+ * compact offset is taken at face value; offsets64, utf16, utf8 = 1, device_pointers or staging, stream).  The outputs, their capacities
+ * and the size query behave as gx_select_lines' do: every output pointer is optional -- out_index (the delivered lines' input line
+ * numbers), out_values (their numbers), out_bytes / out_offsets (their code units and n_top + 1 offsets of the input's width), out_ids
+ * and out_caps (their result rows), all in rank order; with all of them NULL only *totals is delivered.  If a per-line output is given
+ * and n_top > cap_lines, or out_bytes is given and the delivered text is larger than out_bytes_cap bytes, the call returns GX_E_LIMIT,
+ * writes nothing to any output and fills *totals; cap_lines >= n_wanted always suffices.  The call synchronises the stream once, where
+ * the host reads the totals and checks the capacities; with host outputs a second wait delivers them.  With device_pointers the emit
+ * pass is left running on opts->stream when the call returns (stream order delivers the outputs); the handle's next gx_top_lines on
+ * another stream waits for it, and the batch must stay unchanged until it has run.
+ * GX_E_ARG: totals == NULL, parts == NULL with n_parts > 0, a part's extraction or group out of range, two parts for one extraction,
+ * unknown flag bits, every refusal of a term (gx_select_lines_where), parts or terms on dense ids without caps, utf8 = 2, no_sync.
+ * GX_E_LIMIT: more than 64 parts, n_wanted > GX_TOP_MAX_LINES, n of 2^32 - 1 and more, a line of 2^32 code units and more (or offsets
+ * that go backwards).  All need no device (a host-only handle gives them, and GX_E_DEVICE after them: there is no CPU path) but the
+ * last with device_pointers, where the offsets lie on the device and the keys pass finds it.  n_parts == 0 and n_wanted == 0 are legal
+ * and give no lines (n_wanted == 0 still fills the four counts). */
+int gx_top_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                 const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t n_wanted,
+                 uint32_t flags, uint32_t* out_index, int64_t* out_values, void* out_bytes, void* out_offsets, void* out_ids,
+                 int32_t* out_caps, uint64_t cap_lines, uint64_t out_bytes_cap, gx_top_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_capture_stats' chain with the ranking at its end: raw text -> lines -> the match-and-extract path -> the
+ * same result.  The chosen lines' text leaves in `out` as gx_text_select_where delivers kept lines (each with its terminator as the
+ * text has it), in rank order; out_index / out_values (optional, room for n_wanted entries) are the lines' numbers in the text and their
+ * values.  *out_size: the bytes the text needs (out == NULL: the size query).  counts (optional, uint64_t[2K + 2], host) and *n_lines
+ * (optional) as gx_text_capture_stats delivers them.  Limits and options are gx_text_capture_stats': text below 4 GiB, device text
+ * 16-byte aligned, utf8 0 / 1.  Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts,
+                      const gx_where_term* terms, uint32_t n_terms, uint32_t n_wanted, uint32_t flags, uint32_t* out_index,
+                      int64_t* out_values, uint8_t* out, uint64_t out_cap, uint64_t* out_size, gx_top_totals* totals, uint64_t* counts,
+                      uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
