@@ -50,6 +50,7 @@ SYMBOLS = [
     "gx_capture_stats", "gx_text_capture_stats",
     "gx_group_lines", "gx_text_group_lines",
     "gx_top_lines", "gx_text_top_lines",
+    "gx_capture_quantiles", "gx_text_capture_quantiles",
 ]
 
 
@@ -92,6 +93,7 @@ class gx_measure_stats(C.Structure):
 GX_GROUP_WEAK_HASH = 1
 GX_TOP_SMALLEST = 1
 GX_TOP_MAX_LINES = 4096
+GX_QUANTILE_MAX = 16
 
 
 class gx_group_part(C.Structure):
@@ -105,6 +107,18 @@ class gx_top_part(C.Structure):
 class gx_top_totals(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("n_top", C.c_uint64),
                 ("units_top", C.c_uint64), ("last_value", C.c_int64), ("ties_left", C.c_uint64)]
+
+
+class gx_quantile(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
+
+
+class gx_quantile_out(C.Structure):
+    _fields_ = [("value", C.c_int64), ("rank", C.c_uint64), ("below", C.c_uint64), ("equal", C.c_uint64)]
+
+
+class gx_quantile_totals(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64)]
 
 
 class gx_group_out(C.Structure):
@@ -293,6 +307,14 @@ def lib():
                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(gx_top_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_top_lines.restype = C.c_int
+    L.gx_capture_quantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_top_part), C.c_uint32,
+                                       C.POINTER(gx_where_term), C.c_uint32, C.POINTER(gx_quantile), C.c_uint32, C.POINTER(gx_quantile_out),
+                                       C.POINTER(gx_quantile_totals), C.POINTER(gx_batch_opts)]
+    L.gx_capture_quantiles.restype = C.c_int
+    L.gx_text_capture_quantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_top_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                            C.POINTER(gx_quantile), C.c_uint32, C.POINTER(gx_quantile_out), C.POINTER(gx_quantile_totals), C.c_void_p,
+                                            C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_capture_quantiles.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -25,6 +25,7 @@
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
 #include "gx_stats.hpp"
+#include "gx_quantile.hpp"
 #include "gx_top.hpp"
 #include "gx_where.hpp"
 
@@ -278,6 +279,9 @@ struct gx_handle {
     GrowBuf top_image, top_ws;
     Event top_event;
     bool top_pending = false;
+    // gx_capture_quantiles: its parts, quantiles and terms on the device (TopHead, QuantHead, WhereHead) and the passes' workspace
+    // (gx_quantile.hip: QuantWs).  Used under `mu`; every call that uses them ends with a stream synchronisation.
+    GrowBuf quant_image, quant_ws;
     // stream-ordered memory of the UTF-16 batch path (the narrowed copy of a batch): a pool of the handle's own that keeps what a
     // batch frees for the next one (the device's default pool gives everything back at the next synchronisation: an allocation of
     // gigabytes per call, 0.6 of that path's 2.4 ms per 10 M lines)
@@ -2212,6 +2216,156 @@ int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx
             GX_HIP(hipStreamSynchronize(stream));
             h->top_pending = false;
         }
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
+    });
+}
+
+// what both quantile calls refuse before they look at the device
+static void quant_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                           const gx_quantile* quantiles, uint32_t n_quantiles, const gx_quantile_out* out, bool wide, const gx_quantile_totals* totals,
+                           const std::string& name, TopHead* ti, QuantHead* qh, WhereImage* wi) {
+    if (!totals) throw GxError(GX_E_ARG, name + ": totals is NULL");
+    if (n_quantiles && (!quantiles || !out)) throw GxError(GX_E_ARG, name + ": quantiles or out is NULL");
+    if (n_quantiles > GX_QUANTILE_MAX) throw GxError(GX_E_LIMIT, name + ": n_quantiles above GX_QUANTILE_MAX");
+    *qh = QuantHead{};
+    qh->n_q = n_quantiles;
+    for (uint32_t q = 0; q < n_quantiles; ++q) {
+        if (quantiles[q].den == 0) throw GxError(GX_E_ARG, name + ": a quantile's den is 0");
+        if (quantiles[q].num > quantiles[q].den) throw GxError(GX_E_ARG, name + ": a quantile's num is above its den");
+        qh->ask[q] = QuantAsk{quantiles[q].num, quantiles[q].den};
+    }
+    *ti = top_image(h, parts, n_parts, 0, name);
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the results are host values");
+}
+
+// The passes on the handle's workspace (under h->mu) and ONE synchronisation of the stream, where the host reads the counts and the
+// result rows.  ids / offsets / data / caps: device pointers.  counts: also the histogram of outcomes (gx_text_capture_quantiles).
+static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut) && offsetof(gx_quantile_out, below) == offsetof(QuantOut, below), "the rows are copied as they are");
+static int quant_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
+                      const int32_t* caps, bool wide, const TopHead& ti, const QuantHead& qh, const WhereImage& wi, gx_quantile_out* out,
+                      gx_quantile_totals* totals, uint64_t* counts, hipStream_t stream) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    if (counts) {
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
+        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    *totals = gx_quantile_totals{};
+    for (uint32_t q = 0; q < qh.n_q; ++q) out[q] = gx_quantile_out{};
+    if (n == 0 || ti.n_parts == 0) {
+        GX_HIP(hipStreamSynchronize(stream));
+        return GX_OK;
+    }
+    // the image: the parts, the quantiles, the terms
+    const size_t at_terms = sizeof(TopHead) + sizeof(QuantHead);
+    uint8_t* d_img = static_cast<uint8_t*>(h->quant_image.get(at_terms + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
+    GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), &qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + at_terms,
+                    static_cast<uint32_t>(wi.bytes.size()), 0u, 0u};
+    const QuantWs w = quant_workspace(h->quant_ws.get(quant_workspace_bytes(n)), n);
+    GX_HIP(launch_quantiles(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_img + sizeof(TopHead), qh.n_q, w, stream));
+    struct { uint32_t counts[TOP_COUNTS]; QuantOut out[QUANT_MAX]; } got{};
+    static_assert(sizeof(got) == offsetof(QuantDev, sel), "the head's first words");
+    GX_HIP(hipMemcpyAsync(&got, w.head, sizeof(got), hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got.counts[TOP_C_STATUS]) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be measured");
+    totals->numbers = got.counts[TOP_C_NUMBERS];
+    totals->unset = got.counts[TOP_C_UNSET];
+    totals->not_numbers = got.counts[TOP_C_NOT_NUMBERS];
+    totals->lines = totals->numbers + totals->unset + totals->not_numbers;
+    for (uint32_t q = 0; q < qh.n_q; ++q) out[q] = gx_quantile_out{got.out[q].value, got.out[q].rank, got.out[q].below, got.out[q].equal};
+    return GX_OK;
+}
+
+int gx_capture_quantiles(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_top_part* parts,
+                         uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* out,
+                         gx_quantile_totals* totals, const gx_batch_opts* opts) {
+    const std::string name = "gx_capture_quantiles";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        TopHead ti;
+        QuantHead qh;
+        WhereImage wi;
+        quant_refusals(h, o, parts, n_parts, terms, n_terms, quantiles, n_quantiles, out, o.utf16 != 0, totals, name, &ti, &qh, &wi);
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 2^32 - 1 lines and more");
+        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the keys pass
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            for (uint64_t i = 0; i < n; ++i)
+                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be measured");
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        // host buffers are staged to the device; the passes are the same
+        DevMem<> d_bytes, d_off, d_ids, d_caps;
+        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
+        if (!o.device_pointers) {
+            const HostOffsets off{offsets, o.offsets64 != 0, n};
+            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
+            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
+            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
+            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+            if (caps && n && slots) {
+                d_caps = dev_alloc(n * slots * 4);
+                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+            }
+            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
+        }
+        return quant_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, ti, qh, wi, out, totals,
+                          nullptr, stream);
+    });
+}
+
+int gx_text_capture_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms,
+                              uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* out, gx_quantile_totals* totals,
+                              uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    const std::string name = "gx_text_capture_quantiles";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        TopHead ti;
+        QuantHead qh;
+        WhereImage wi;
+        quant_refusals(h, o, parts, n_parts, terms, n_terms, quantiles, n_quantiles, out, false, totals, name, &ti, &qh, &wi);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        DevMem<uint8_t> d_text;
+        const uint8_t* src = text;
+        if (!o.device_pointers) {
+            d_text = dev_alloc<uint8_t>(size);
+            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
+            src = d_text.get();
+        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
+        }
+        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
+        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        if (n_lines) *n_lines = tl.n;
+        const int rc = quant_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, ti, qh, wi, out, totals, counts, stream);
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         return rc;
     });

@@ -357,6 +357,30 @@ size_t top_workspace_bytes(uint64_t n);
 // launch_partition_copy with w.perm and w.dst_off.
 hipError_t launch_top_select(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
                              const TopWs& w, hipStream_t stream);
+// The keys pass of launch_top_select alone and the sum of its class counts, for the calls that share it (gx_quantile.hip): n > 0,
+// parts > 0.  Of w it uses keys, cand and slab (top_keys_blocks(n) * TOP_COUNTS words); counts[TOP_COUNTS] lies on the device.
+uint32_t top_keys_blocks(uint64_t n);
+hipError_t launch_top_keys(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                           const TopWs& w, uint32_t* counts, hipStream_t stream);
+
+// The percentiles of a number the lines of a finished batch captured (gx_quantile.hip; the rule: gx_quantile.hpp).  The lines that
+// count, their class and the key are gx_top_lines': TopArgs with smallest = 0 (n_wanted is not looked at), whose image holds a
+// QuantHead between the TopHead and the terms.
+struct QuantWs {
+    uint8_t* head;                // QuantDev (gx_quantile.hpp): the class counts, the result rows, the selects' state
+    uint32_t* slab;               // the workgroups' counts, then their histograms: [workgroup][group][256]
+    uint64_t* block_sums;         // the scan's
+    uint64_t* keys;               // [n] a candidate's key
+    uint64_t* before;             // [n + 1] cand scanned: the candidates before line i
+    uint64_t* ckeys;              // [n] the candidates' keys, dense, in line order
+    uint8_t* cand;                // [n] the line's value is a number
+    size_t bytes;
+};
+QuantWs quant_workspace(void* ws, uint64_t n);
+size_t quant_workspace_bytes(uint64_t n);
+// n > 0, parts > 0.  Every pass; behind it the head's counts and rows are final.  quant_head: the QuantHead inside the image.
+hipError_t launch_quantiles(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                            const void* quant_head, uint32_t n_quantiles, const QuantWs& w, hipStream_t stream);
 
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:

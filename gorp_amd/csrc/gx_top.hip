@@ -276,16 +276,14 @@ TopWs top_workspace(void* ws, uint64_t n) {
 }
 size_t top_workspace_bytes(uint64_t n) { return top_workspace(nullptr, n).bytes; }
 
-// Every pass before the emit, on `stream`; n > 0, parts > 0, n_wanted <= TOP_MAX_LINES.  Leaves the class counts and the select's
-// state at the workspace's head, and for n_wanted > 0: w.before[n] (its upper half: the candidates equal to T), w.perm, w.values and
-// w.dst_off[0 .. n_wanted] (entries from n_top on: the units of all delivered lines).
-hipError_t launch_top_select(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
-                             const TopWs& w, hipStream_t stream) {
-    TopDev* head = reinterpret_cast<TopDev*>(w.head);
-    hipError_t e = hipMemsetAsync(head, 0, sizeof(TopDev), stream);
-    if (e != hipSuccess) return e;
+uint32_t top_keys_blocks(uint64_t n) { return keys_blocks(n); }
+
+// The keys pass and the sum of its class counts, on `stream`; n > 0, parts > 0.  Of the workspace it uses keys, cand and slab (room for
+// top_keys_blocks(n) * TOP_COUNTS words); counts[TOP_COUNTS] is on the device.
+hipError_t launch_top_keys(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                           const TopWs& w, uint32_t* counts, hipStream_t stream) {
     const uint32_t lds = static_cast<uint32_t>(sizeof(TopHead)) + a.where_image_bytes;
-    if (lds > 60u * 1024u || a.n_wanted > TOP_MAX_LINES) return hipErrorInvalidValue;   // (64 terms of 255 two-byte units: 35 KiB)
+    if (lds > 60u * 1024u) return hipErrorInvalidValue;   // (64 terms of 255 two-byte units: 35 KiB)
     const unsigned kb = keys_blocks(n);
     if (a.wide) {
         if (offsets64) launch_keys_as<uint64_t, uint16_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
@@ -294,10 +292,25 @@ hipError_t launch_top_select(const void* ids, RowFormat fmt, uint32_t row_units,
         if (offsets64) launch_keys_as<uint64_t, uint8_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
         else launch_keys_as<uint32_t, uint8_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
     }
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_top_sum, dim3(TOP_COUNTS), dim3(256), 0, stream, w.slab, kb, TOP_COUNTS, head->counts);
-    if (a.n_wanted == 0u) return hipGetLastError();
+    hipLaunchKernelGGL(k_top_sum, dim3(TOP_COUNTS), dim3(256), 0, stream, w.slab, kb, TOP_COUNTS, counts);
+    return hipGetLastError();
+}
+
+// Every pass before the emit, on `stream`; n > 0, parts > 0, n_wanted <= TOP_MAX_LINES.  Leaves the class counts and the select's
+// state at the workspace's head, and for n_wanted > 0: w.before[n] (its upper half: the candidates equal to T), w.perm, w.values and
+// w.dst_off[0 .. n_wanted] (entries from n_top on: the units of all delivered lines).
+hipError_t launch_top_select(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                             const TopWs& w, hipStream_t stream) {
+    TopDev* head = reinterpret_cast<TopDev*>(w.head);
+    hipError_t e = hipMemsetAsync(head, 0, sizeof(TopDev), stream);
+    if (e != hipSuccess) return e;
+    if (a.n_wanted > TOP_MAX_LINES) return hipErrorInvalidValue;
+    e = launch_top_keys(ids, fmt, row_units, K, n, offsets, offsets64, a, w, head->counts, stream);
+    if (e != hipSuccess) return e;
+    if (a.n_wanted == 0u) return hipSuccess;
+    const unsigned kb = keys_blocks(n);
     hipLaunchKernelGGL(k_top_begin, dim3(1), dim3(64), 0, stream, head, a.n_wanted);
     const unsigned sb = sweep_blocks(n);
     for (uint32_t d = TOP_DIGITS; d-- > 0u;) {

@@ -12,6 +12,7 @@ byte buffer.  All matching runs in the HIP kernels; nothing here computes a
 match on the CPU.
 """
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
@@ -1365,6 +1366,107 @@ class Gorp:
             raise GorpError(rc, N.last_error())
         k = totals["n_top"]
         return index[:k], values[:k], out[:size].tobytes(), totals, counts, n_lines
+
+    # -- percentiles of a number the lines captured (gx_capture_quantiles / gx_text_capture_quantiles) -------------------------------
+    @staticmethod
+    def quantile_asks(quantiles):
+        """Resolves quantiles into gx_quantile records (num, den): a quantile is a pair (num, den) taken as it is, a
+        fractions.Fraction, an int 0 or 1, or a float or decimal string taken at its decimal face value (Fraction(repr(q)): 0.99 is
+        99/100).  A quantile outside [0, 1], a denominator of 0 or beyond 32 bits, or more than 16 of them: GorpError, before the
+        library is called.  Returns (array, n)."""
+        quantiles = list(quantiles)
+        if len(quantiles) > N.GX_QUANTILE_MAX:
+            raise GorpError(N.GX_E_LIMIT, "at most %d quantiles" % N.GX_QUANTILE_MAX)
+        arr = (N.gx_quantile * max(1, len(quantiles)))()
+        for t, q in enumerate(quantiles):
+            if isinstance(q, bool):
+                raise GorpError(N.GX_E_ARG, "a quantile is (num, den), a Fraction, a float or a decimal string: %r" % (q,))
+            if isinstance(q, (tuple, list)):
+                if len(q) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in q):
+                    raise GorpError(N.GX_E_ARG, "a quantile pair is (num, den) in integers: %r" % (q,))
+                num, den = int(q[0]), int(q[1])
+            else:
+                try:
+                    f = Fraction(repr(float(q))) if isinstance(q, float) else Fraction(q)
+                except (ValueError, TypeError, ZeroDivisionError):
+                    raise GorpError(N.GX_E_ARG, "not a quantile: %r" % (q,))
+                num, den = f.numerator, f.denominator
+            if den < 1 or num < 0 or num > den:
+                raise GorpError(N.GX_E_ARG, "a quantile lies in [0, 1]: %r" % (q,))
+            if den > 0xFFFFFFFF:
+                raise GorpError(N.GX_E_LIMIT, "a quantile's denominator has at most 32 bits: %r" % (q,))
+            arr[t].num, arr[t].den = num, den
+        return arr, len(quantiles)
+
+    @staticmethod
+    def _quantile_results(out, n_q, t):
+        totals = {"lines": t.lines, "numbers": t.numbers, "unset": t.unset, "not_numbers": t.not_numbers}
+        some = t.numbers != 0
+        return [{"value": out[q].value if some else None, "rank": out[q].rank, "below": out[q].below, "equal": out[q].equal} for q in range(n_q)], totals
+
+    def capture_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, by, quantiles, where=None, offsets64=False, utf16=False, compact=0,
+                                 stream=None, device_pointers=True, utf8=False):
+        """gx_capture_quantiles on device pointers (ints).  Returns (results, totals): per quantile, in input order, a dict value / rank /
+        below / equal (value None when there are no numbers), and totals (lines, numbers, unset, not_numbers)."""
+        parts = self.top_parts(by)
+        asks, n_q = self.quantile_asks(quantiles)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = (N.gx_quantile_out * max(1, n_q))()
+        totals = N.gx_quantile_totals()
+        _check(N.lib().gx_capture_quantiles(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, asks, n_q, out,
+                                            C.byref(totals), C.byref(o)))
+        return self._quantile_results(out, n_q, totals)
+
+    def capture_quantiles(self, data, offsets, ids, rows, by, quantiles, where=None, utf8=None):
+        """gx_capture_quantiles on host buffers: nearest-rank quantiles -- sorted(values)[ceil(q * numbers) - 1] -- of the numbers the
+        lines captured.  by: Gorp.top_parts or its input; quantiles: see quantile_asks; where: terms as capture_stats takes them.
+        data / offsets / ids / rows and utf8 as capture_stats takes them.  Returns what capture_quantiles_device returns."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        return self.capture_quantiles_device(ptr(data), offsets.ctypes.data, len(offsets) - 1, ptr(ids), ptr(caps), by, quantiles, where=where,
+                                             offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8))
+
+    def text_capture_quantiles_device(self, text_ptr, size, by, quantiles, where=None, stream=None, device_pointers=True, utf8=False):
+        """gx_text_capture_quantiles on a device buffer (int).  Returns (results, totals, counts uint64[2K + 2] of outcomes, n_lines)."""
+        parts = self.top_parts(by)
+        asks, n_q = self.quantile_asks(quantiles)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out = (N.gx_quantile_out * max(1, n_q))()
+        totals = N.gx_quantile_totals()
+        nl = C.c_uint64(0)
+        _check(N.lib().gx_text_capture_quantiles(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, asks, n_q, out, C.byref(totals),
+                                                 counts.ctypes.data, C.byref(nl), C.byref(o)))
+        results, totals = self._quantile_results(out, n_q, totals)
+        return results, totals, counts, nl.value
+
+    def text_capture_quantiles(self, text, by, quantiles, where=None, utf8=False):
+        """gx_text_capture_quantiles on a host buffer: raw text -> lines -> extraction -> capture_quantiles.  Returns (results, totals,
+        counts, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        return self.text_capture_quantiles_device(raw.ctypes.data if raw.size else None, raw.size, by, quantiles, where, device_pointers=False, utf8=utf8)
 
     def partition_lines(self, data, offsets, ids, rows=None, want=None):
         """gx_partition_lines on host buffers: the kept lines of the CSR batch ordered by (outcome index, input line number) -- every

@@ -512,6 +512,43 @@ public:
                                      out.bytes.size(), &size, &out.totals, counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
         });
     }
+    // Percentiles of a number the lines captured (gx_capture_quantiles): nearest-rank quantiles num / den of the numbers that the parts
+    // name -- sorted(values)[ceil(q * numbers) - 1], in integers alone -- each with its rank and the counts of the numbers below and
+    // equal to it.  captureQuantiles(..., topParts().of("GetRequest", "timeTakenInMsec"), {{50, 100}, {95, 100}, {99, 100}}) is the
+    // caller's median, p95 and p99 of its results' timeTakenInMsec (README.md:26,63-79).  With no numbers every row is all zeros.
+    struct Quantiles {
+        std::vector<gx_quantile_out> out;   // one per quantile, in input order
+        gx_quantile_totals totals{};
+    };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other layout)
+    Quantiles captureQuantiles(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const TopParts& parts,
+                               const std::vector<gx_quantile>& quantiles, const Where* where = nullptr) const {
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        Quantiles q;
+        q.out.assign(quantiles.size(), gx_quantile_out{});
+        const int rc = gx_capture_quantiles(h_, bytes, offsets, n, match_id, caps, parts.parts().data(), static_cast<uint32_t>(parts.parts().size()), terms.data(),
+                                            static_cast<uint32_t>(terms.size()), quantiles.data(), static_cast<uint32_t>(quantiles.size()), q.out.data(), &q.totals,
+                                            nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return q;
+    }
+    // Whole files: raw text in, the same result out (gx_text_capture_quantiles).  counts (optional): lines per outcome index.
+    Quantiles textCaptureQuantiles(const std::string& text, const TopParts& parts, const std::vector<gx_quantile>& quantiles, const Where* where = nullptr,
+                                   std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        Quantiles q;
+        q.out.assign(quantiles.size(), gx_quantile_out{});
+        const int rc = gx_text_capture_quantiles(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), parts.parts().data(),
+                                                 static_cast<uint32_t>(parts.parts().size()), terms.data(), static_cast<uint32_t>(terms.size()), quantiles.data(),
+                                                 static_cast<uint32_t>(quantiles.size()), q.out.data(), &q.totals, counts ? counts->data() : nullptr, nLines,
+                                                 utf8 ? &o : nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return q;
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes

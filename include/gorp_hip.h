@@ -585,6 +585,41 @@ int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx
                       int64_t* out_values, uint8_t* out, uint64_t out_cap, uint64_t* out_size, gx_top_totals* totals, uint64_t* counts,
                       uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- percentiles of a number the lines captured --------------------------------------------------------------------------------
+ * The reference's caller asks for the median and the p95 / p99 of a captured number right behind the extraction (README.md:26,63-79:
+ * the results' timeTakenInMsec).  Parts are gx_top_part records with gx_top_lines' meaning -- at most one per extraction, one number
+ * space -- and a line COUNTS, and its value is classed unset / not a number / number, exactly as there.  The numbers are the
+ * population.  A quantile is num / den, and its rank is nearest-rank in integers alone, with p = (uint64_t)num * numbers:
+ *     rank = p / den + (p % den != 0), a rank of 0 raised to 1
+ * so 1 <= rank <= numbers, num == 0 is the minimum and num == den the maximum: sorted(values)[ceil(q * numbers) - 1].  No floating
+ * point appears anywhere.  Per quantile: value, the rank-th smallest number; rank; below, the numbers strictly below value; equal,
+ * the numbers equal to it (below < rank <= below + equal).  With numbers == 0 every entry is all zeros.  Quantiles may come in any
+ * order and may repeat; each gets its own entry, in input order.  Every output is exact and the same bits on every run. */
+#define GX_QUANTILE_MAX 16u
+typedef struct gx_quantile     { uint32_t num, den; } gx_quantile;          /* q = num / den; den >= 1, num <= den */
+typedef struct gx_quantile_out { int64_t value; uint64_t rank, below, equal; } gx_quantile_out;   /* 32 bytes, host */
+typedef struct gx_quantile_totals { uint64_t lines, numbers, unset, not_numbers; } gx_quantile_totals;   /* 32 bytes, host */
+
+/* gx_capture_quantiles: the batch bytes / offsets / n / ids / caps is read exactly as gx_top_lines reads it (row formats, offsets64,
+ * utf16, utf8 = 1, device_pointers or staging, stream).  out[n_quantiles] and *totals are host values.  The call synchronises the
+ * stream once; the host reads nothing between the passes, and nothing of the call is left running when it returns.
+ * GX_E_ARG: totals == NULL, quantiles == NULL or out == NULL with n_quantiles > 0, den == 0, num > den, every refusal of parts and terms
+ * that gx_top_lines makes, parts or terms on dense ids without caps, utf8 = 2, no_sync.  GX_E_LIMIT: n_quantiles > GX_QUANTILE_MAX, more
+ * than 64 parts, n of 2^32 - 1 and more, a line of 2^32 code units and more (or offsets that go backwards).  All need no device (a
+ * host-only handle gives them, and GX_E_DEVICE after them: there is no CPU path) but the last with device_pointers, where the keys
+ * pass finds it.  n == 0 and n_parts == 0 are legal and give zeros; n_quantiles == 0 fills the totals alone. */
+int gx_capture_quantiles(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                         const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                         const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* out, gx_quantile_totals* totals,
+                         const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_capture_stats' chain with the quantiles at its end: raw text -> lines -> the match-and-extract path ->
+ * the same result.  counts (optional, uint64_t[2K + 2], host), *n_lines (optional), limits and options are gx_text_capture_stats'. */
+int gx_text_capture_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts,
+                              const gx_where_term* terms, uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles,
+                              gx_quantile_out* out, gx_quantile_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                              const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
