@@ -51,6 +51,7 @@ SYMBOLS = [
     "gx_group_lines", "gx_text_group_lines",
     "gx_top_lines", "gx_text_top_lines",
     "gx_capture_quantiles", "gx_text_capture_quantiles",
+    "gx_group_quantiles", "gx_text_group_quantiles",
 ]
 
 
@@ -315,6 +316,14 @@ def lib():
                                             C.POINTER(gx_quantile), C.c_uint32, C.POINTER(gx_quantile_out), C.POINTER(gx_quantile_totals), C.c_void_p,
                                             C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_capture_quantiles.restype = C.c_int
+    L.gx_group_quantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32,
+                                     C.POINTER(gx_where_term), C.c_uint32, C.POINTER(gx_quantile), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out),
+                                     C.c_void_p, C.POINTER(gx_group_totals), C.POINTER(gx_batch_opts)]
+    L.gx_group_quantiles.restype = C.c_int
+    L.gx_text_group_quantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                          C.POINTER(gx_quantile), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.c_void_p,
+                                          C.POINTER(gx_group_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_quantiles.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -21,6 +21,7 @@
 #include "gx_device.hpp"
 #include "gx_dsl.hpp"
 #include "gx_group.hpp"
+#include "gx_group_quantile.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
@@ -271,6 +272,9 @@ struct gx_handle {
     // arrays (gx_group.hip).  Used under `mu`.  With device pointers the emit pass is left running on the caller's stream: the next
     // call's stream waits for group_event first.
     GrowBuf group_image, group_table, group_lines;
+    // gx_group_quantiles behind them: its value parts, quantiles and terms (TopHead, QuantHead, WhereHead) and its workspace; they are
+    // covered by group_event too
+    GrowBuf gq_image, gq_ws;
     Event group_event;
     bool group_pending = false;
     // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
@@ -1788,9 +1792,18 @@ static void group_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_
 // The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
 // totals and checks the capacities; then the emit.  ids / offsets / data / caps: device pointers; out: the caller's, device or host
 // (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes (gx_text_group_lines).
+// gq (gx_group_quantiles; nullptr or n_q == 0: gx_group_lines as it is): before the read of the totals also the candidates' pairs, their
+// number and the OR and AND of their value keys (launch_gq_collect), read in the same wait; behind the emit the sort by the digit
+// plan made from them and the pick.
+struct GroupQuant {
+    TopHead ti{};                 // the parts that have a value group
+    QuantHead qh{};
+    gx_quantile_out* rows = nullptr;   // the caller's, device or host as the other per-key arrays; nullptr: not wanted
+};
+static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut), "the rows are copied as they are");
 static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
                       const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
-                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
+                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupQuant* gq = nullptr) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
     if (counts) {
         if (h->select_pending) {
@@ -1804,7 +1817,9 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     *totals = gx_group_totals{};
     totals->exact = 1;
     const bool run = n != 0 && gi.head.n_parts != 0;
-    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key;
+    gx_quantile_out* q_rows = gq && gq->qh.n_q ? gq->rows : nullptr;
+    const uint32_t n_q = q_rows ? gq->qh.n_q : 0u;
+    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows;
     if (!run) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -1831,6 +1846,23 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
                       static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u};
     const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
     GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    // the quantiles' candidates: only where rows are wanted and a part has a value (else every population is empty)
+    const bool sort = q_rows && gq->ti.n_parts != 0;
+    GqWs qw{};
+    GqDev qd{};
+    uint8_t* d_qimg = nullptr;
+    if (sort) {
+        const size_t at_terms = sizeof(TopHead) + sizeof(QuantHead);
+        d_qimg = static_cast<uint8_t*>(h->gq_image.get(at_terms + wi.bytes.size()));
+        GX_HIP(hipMemcpyAsync(d_qimg, &gq->ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
+        GX_HIP(hipMemcpyAsync(d_qimg + sizeof(TopHead), &gq->qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
+        if (!wi.none()) GX_HIP(hipMemcpyAsync(d_qimg + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+        const TopArgs ta{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_qimg, wi.none() ? nullptr : d_qimg + at_terms,
+                         static_cast<uint32_t>(wi.bytes.size()), 0u, 0u};
+        qw = gq_workspace(h->gq_ws.get(gq_workspace_bytes(n)), n);
+        GX_HIP(launch_gq_collect(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, ta, w.slot_of, qw, stream));
+        GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, stream));
+    }
     uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
     GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
     GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -1848,14 +1880,17 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
     }
     if (!any_out) return GX_OK;
-    const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats;
+    const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || q_rows;
     if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
     if (out.key_units && key_units > out.key_units_cap)
         return fail(GX_E_LIMIT, name + ": " + std::to_string(key_units) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && key_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
     const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
     GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
-    DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey;
+    DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey, d_rows;
+    void* rows = q_rows;
+    const size_t rows_bytes = static_cast<size_t>(n_keys) * n_q * sizeof(QuantOut);
+    if (host_out && rows_bytes) { d_rows = dev_alloc(rows_bytes); rows = d_rows.get(); }
     if (host_out) {
         if (out.key_units) { d_units = dev_alloc(key_units * unit); o.key_units = d_units.get(); }
         if (out.key_offsets) { d_offs = dev_alloc((n_keys + 1) * off_w); o.key_offsets = d_offs.get(); }
@@ -1865,7 +1900,16 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.line_key) { d_lkey = dev_alloc(n * 4); o.line_key = static_cast<uint32_t*>(d_lkey.get()); }
     }
     GX_HIP(launch_group_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
+    if (rows_bytes) {
+        if (sort && qd.candidates != 0) {
+            const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, n_keys, gq_sorts_all_digits());
+            GX_HIP(launch_gq_sort_pick(qw, qd.candidates, plan, w.keynum, w.n_slots, d_qimg + sizeof(TopHead), n_q, n_keys, rows, stream));
+        } else {
+            GX_HIP(hipMemsetAsync(rows, 0, rows_bytes, stream));   // no key has a number
+        }
+    }
     if (host_out) {
+        if (rows_bytes) GX_HIP(hipMemcpyAsync(q_rows, rows, rows_bytes, hipMemcpyDeviceToHost, stream));
         if (out.key_units && key_units) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, key_units * unit, hipMemcpyDeviceToHost, stream));
         if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_keys + 1) * off_w, hipMemcpyDeviceToHost, stream));
         if (out.key_first_line && n_keys) GX_HIP(hipMemcpyAsync(out.key_first_line, o.key_first_line, n_keys * 4, hipMemcpyDeviceToHost, stream));
@@ -1881,10 +1925,31 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     return GX_OK;
 }
 
-int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
-                   uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals,
-                   const gx_batch_opts* opts) {
-    const std::string name = "gx_group_lines";
+// what gx_group_quantiles adds to the refusals of gx_group_lines, behind them and before the look at the device: the quantiles
+// (gx_capture_quantiles' rule), and the parts that have a value group as the keys pass reads them
+static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* rows, const std::string& name, GroupQuant* gq) {
+    if (n_quantiles && !quantiles) throw GxError(GX_E_ARG, name + ": quantiles is NULL");
+    if (n_quantiles > GX_QUANTILE_MAX) throw GxError(GX_E_LIMIT, name + ": n_quantiles above GX_QUANTILE_MAX");
+    *gq = GroupQuant{};
+    gq->qh.n_q = n_quantiles;
+    for (uint32_t q = 0; q < n_quantiles; ++q) {
+        if (quantiles[q].den == 0) throw GxError(GX_E_ARG, name + ": a quantile's den is 0");
+        if (quantiles[q].num > quantiles[q].den) throw GxError(GX_E_ARG, name + ": a quantile's num is above its den");
+        gq->qh.ask[q] = QuantAsk{quantiles[q].num, quantiles[q].den};
+    }
+    for (uint32_t e = 0; e < gi.head.n_parts; ++e) {   // (ascending by extraction already)
+        if (gi.head.part[e].value_group == GROUP_NO_VALUE) continue;
+        gq->ti.ext[gq->ti.n_parts] = gi.head.ext[e];
+        gq->ti.group[gq->ti.n_parts++] = gi.head.part[e].value_group;
+    }
+    gq->rows = rows;
+}
+
+// gx_group_lines and, with quant, gx_group_quantiles
+static int group_lines_call(const std::string& name, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                            const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
+                            gx_group_totals* totals, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
+                            gx_quantile_out* key_quantiles) {
     return guarded([&]() -> int {
         if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -1895,6 +1960,8 @@ int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_
         GroupImage gi;
         WhereImage wi;
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, go, totals, name, &gi, &wi);
+        GroupQuant gq;
+        if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
         if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the build pass
@@ -1927,14 +1994,28 @@ int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_
             src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
         }
         return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
-                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name);
+                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr);
     });
 }
 
-int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
-                        uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines,
-                        const gx_batch_opts* opts) {
-    const std::string name = "gx_text_group_lines";
+int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                   uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals,
+                   const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_lines", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts, false, nullptr, 0, nullptr);
+}
+
+int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                       uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, uint32_t flags,
+                       const gx_group_out* out, gx_quantile_out* key_quantiles, gx_group_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_quantiles", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts, true, quantiles,
+                            n_quantiles, key_quantiles);
+}
+
+// gx_text_group_lines and, with quant, gx_text_group_quantiles
+static int text_group_call(const std::string& name, gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                           const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts,
+                           uint64_t* n_lines, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
+                           gx_quantile_out* key_quantiles) {
     return guarded([&]() -> int {
         if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -1943,6 +2024,8 @@ int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const 
         GroupImage gi;
         WhereImage wi;
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, go, totals, name, &gi, &wi);
+        GroupQuant gq;
+        if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
@@ -1962,7 +2045,7 @@ int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const 
         const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
         if (n_lines) *n_lines = tl.n;
         const int rc = group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
-                                  !o.device_pointers, totals, counts, stream, name);
+                                  !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr);
         // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
         // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
         // wait that delivered them was that already).
@@ -1973,6 +2056,19 @@ int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const 
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         return rc;
     });
+}
+
+int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
+                        uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                        const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_lines", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, false, nullptr, 0, nullptr);
+}
+
+int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
+                            uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, uint32_t flags, const gx_group_out* out,
+                            gx_quantile_out* key_quantiles, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_quantiles", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, true, quantiles,
+                           n_quantiles, key_quantiles);
 }
 
 // The parts of a gx_top_lines call as its keys pass reads them (gx_top.hpp: TopHead), checked against the handle.  Needs no device.

@@ -382,6 +382,33 @@ size_t quant_workspace_bytes(uint64_t n);
 hipError_t launch_quantiles(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
                             const void* quant_head, uint32_t n_quantiles, const QuantWs& w, hipStream_t stream);
 
+// The percentiles of a captured number per captured text (gx_group_quantile.hip; the rule: gx_group_quantile.hpp), behind
+// gx_group_lines' passes on the same stream.  The value's class and key are gx_top_lines': TopArgs whose image is a TopHead of the
+// parts that have a value group (smallest = 0; n_wanted is not looked at).
+struct GqPlan;
+struct GqWs {
+    uint8_t* head;                // GqDev (gx_group_quantile.hpp): class counts, the value keys' OR and AND, the candidates
+    uint64_t* masks;              // the compaction's workgroups' OR and AND
+    uint32_t* slab;               // the keys pass's counts, then a digit's counts, bin-major
+    uint64_t* bases;              // the digit's counts scanned
+    uint64_t* block_sums;         // the scans'
+    uint64_t* keys;               // [n] a line's value key
+    uint64_t* before;             // [n + 1] the candidates before line i
+    uint64_t* vkey[2];            // [n] the pairs' value keys, ping and pong (vkey[1] is keys)
+    uint32_t* knum[2];            // [n] the pairs' key numbers, ping and pong (knum[1]: the slots, until they are numbered)
+    uint8_t* cand;                // [n] the line is a candidate
+    size_t bytes;
+};
+GqWs gq_workspace(void* ws, uint64_t n);
+size_t gq_workspace_bytes(uint64_t n);
+bool gq_sorts_all_digits();       // the build sorts every value digit (-DGX_GQ_ALL_DIGITS)
+// n > 0, parts > 0; slot_of: launch_group_build's.  Behind it the host reads GqDev at w.head.
+hipError_t launch_gq_collect(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs& a,
+                             const uint32_t* slot_of, const GqWs& w, hipStream_t stream);
+// Behind launch_group_emit (keynum).  0 < m <= n candidates; rows: n_keys x n_q QuantOut on the device; quant_head: a QuantHead there.
+hipError_t launch_gq_sort_pick(const GqWs& w, uint64_t m, const GqPlan& plan, const uint32_t* keynum, uint32_t n_slots, const void* quant_head, uint32_t n_q,
+                               uint64_t n_keys, void* rows, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

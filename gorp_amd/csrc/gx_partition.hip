@@ -20,6 +20,7 @@
 
 #include "gx_device.hpp"
 #include "gx_outcome.hpp"
+#include "gx_radix_dev.hpp"
 #include "gx_scan.hpp"
 
 namespace gx {
@@ -41,25 +42,6 @@ __global__ void __launch_bounds__(256) k_part_keys(const void* __restrict__ ids,
         keys[i] = kept ? oc : 2u * K + 1u;
         klen[i] = kept ? static_cast<uint32_t>(len) : 0u;
     }
-}
-
-// The six ballots of a tile's digits.  bin_mask: the lanes whose digit is `mine` (a lane asks for its own digit: the lines it is
-// ranked among; or for its lane number: the lines of the bin it counts).
-struct DigitBallots {
-    uint64_t valid, bit[6];
-};
-__device__ __forceinline__ DigitBallots digit_ballots(uint32_t digit, bool valid) {
-    DigitBallots b;
-    b.valid = __ballot(valid);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) b.bit[q] = __ballot((digit >> q) & 1u);
-    return b;
-}
-__device__ __forceinline__ uint64_t bin_mask(const DigitBallots& b, uint32_t mine) {
-    uint64_t m = b.valid;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) m &= ((mine >> q) & 1u) ? b.bit[q] : ~b.bit[q];
-    return m;
 }
 
 // slab[bin * gridDim.x + workgroup] = the workgroup's lines whose digit is `bin`

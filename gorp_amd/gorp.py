@@ -1159,9 +1159,10 @@ class Gorp:
             _check(rc)
         return rc, self._group_totals(totals), counts, nl.value
 
-    def _group_host(self, call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap):
+    def _group_host(self, call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap, n_q=None):
         """Runs `call(out arrays..., max_keys, key_units_cap)` on host arrays; on GX_E_LIMIT once more with the sizes it reported when
-        they are exact, else with the number of lines (which may report exact sizes in turn).  Builds the result dict."""
+        they are exact, else with the number of lines (which may report exact sizes in turn).  Builds the result dict.  n_q (the
+        group_quantiles calls): `call` also takes max_keys x n_q gx_quantile_out rows, and the dict has "quantiles"."""
         max_keys = min(n_lines_cap, 1024) if max_keys is None else max_keys
         key_units_cap = 65536 if key_units_cap is None else key_units_cap
         for attempt in range(3):
@@ -1171,8 +1172,9 @@ class Gorp:
             lines = np.zeros(max(1, max_keys), np.uint64)
             stats = (N.gx_measure_stats * max(1, max_keys))() if parts.has_values else None
             line_key = np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32)
+            rows = None if n_q is None else (N.gx_quantile_out * max(1, max_keys * n_q))()
             got = call(units.ctypes.data, key_units_cap, koff.ctypes.data, first.ctypes.data, lines.ctypes.data, None if stats is None else C.addressof(stats),
-                       line_key.ctypes.data, max_keys)
+                       line_key.ctypes.data, max_keys, *(() if n_q is None else (C.addressof(rows),)))
             rc, totals = got[0], got[1]
             if rc == N.GX_OK:
                 break
@@ -1188,6 +1190,9 @@ class Gorp:
                "stats": None if stats is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
                                                       "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
                                                       "sum": (s.sum_hi << 64) + s.sum_lo} for s in stats[:k]]}
+        if n_q is not None:
+            res["quantiles"] = [[{"value": r.value if r.rank else None, "rank": r.rank, "below": r.below, "equal": r.equal}
+                                 for r in rows[j * n_q:(j + 1) * n_q]] for j in range(k)]
         if keys == "list":
             res["keys"] = [decode(units[int(koff[j]):int(koff[j + 1])]) for j in range(k)]
         elif keys != "csr":
@@ -1237,6 +1242,104 @@ class Gorp:
             return self.text_group_lines_device(raw.ctypes.data if raw.size else None, raw.size, parts, where, units, cap, koff, first, lines, stats, line_key, mk,
                                                 device_pointers=False, utf8=utf8)
         res, (counts, n_lines) = self._group_host(call, cap_lines, parts, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
+        res["line_key"] = res["line_key"][:n_lines]
+        return res, counts, n_lines
+
+    # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
+    def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
+                               key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,
+                               max_keys=0, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_group_quantiles on device pointers (ints): group_lines_device plus key_quantiles_ptr, room for max_keys x len(quantiles)
+        gx_quantile_out rows, key-major (optional).  quantiles: see quantile_asks.  Returns (rc, totals) as group_lines_device does."""
+        parts = self.group_parts(parts)
+        asks, n_q = self.quantile_asks(quantiles)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        totals = N.gx_group_totals()
+        rc = N.lib().gx_group_quantiles(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, asks, n_q,
+                                        N.GX_GROUP_WEAK_HASH if weak_hash else 0, C.byref(out), key_quantiles_ptr, C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._group_totals(totals)
+
+    def text_group_quantiles_device(self, text_ptr, size, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                                    key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None, max_keys=0,
+                                    offsets64=False, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_text_group_quantiles on a device buffer (int); outputs as group_quantiles_device takes them.  Returns (rc, totals, counts,
+        n_lines)."""
+        parts = self.group_parts(parts)
+        asks, n_q = self.quantile_asks(quantiles)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        totals = N.gx_group_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_quantiles(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, asks, n_q,
+                                             N.GX_GROUP_WEAK_HASH if weak_hash else 0, C.byref(out), key_quantiles_ptr, C.byref(totals), counts.ctypes.data,
+                                             C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._group_totals(totals), counts, nl.value
+
+    def group_quantiles(self, data, offsets, ids, rows, parts, quantiles, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None,
+                        weak_hash=False):
+        """gx_group_quantiles on host buffers: group_lines, and per key the nearest-rank quantiles of the numbers its lines captured
+        (the part's value extractor).  Returns group_lines' dict plus "quantiles": per key, in the keys' order, a list with a dict value
+        / rank / below / equal per quantile in input order (value None where the key has no numbers).  quantiles: see quantile_asks.
+        The retry on GX_E_LIMIT is group_lines'."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.group_parts(parts)
+        asks = self.quantile_asks(quantiles)
+        pairs = [(asks[0][q].num, asks[0][q].den) for q in range(asks[1])]
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk, kq):
+            return self.group_quantiles_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), parts, pairs, where, units, cap, koff, first, lines, stats,
+                                               line_key, kq, mk, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False,
+                                               utf8=bool(utf8), weak_hash=weak_hash)
+        res, _ = self._group_host(call, n, parts, data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap, n_q=len(pairs))
+        res["line_key"] = res["line_key"][:n]
+        return res
+
+    def text_group_quantiles(self, text, parts, quantiles, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None):
+        """gx_text_group_quantiles on a host buffer: raw text -> lines -> extraction -> group_quantiles.  Returns (the dict
+        group_quantiles returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.group_parts(parts)
+        asks = self.quantile_asks(quantiles)
+        pairs = [(asks[0][q].num, asks[0][q].den) for q in range(asks[1])]
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk, kq):
+            return self.text_group_quantiles_device(raw.ctypes.data if raw.size else None, raw.size, parts, pairs, where, units, cap, koff, first, lines, stats,
+                                                    line_key, kq, mk, device_pointers=False, utf8=utf8)
+        res, (counts, n_lines) = self._group_host(call, cap_lines, parts, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap, n_q=len(pairs))
         res["line_key"] = res["line_key"][:n_lines]
         return res, counts, n_lines
 

@@ -549,6 +549,46 @@ public:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         return q;
     }
+    // Percentiles of a captured number per captured text (gx_group_quantiles): groupLines plus, per key, the nearest-rank quantiles of
+    // the numbers its lines captured.  groupQuantiles(..., groupParts().of("GetRequest", "path", "timeTakenInMsec"), {{50, 100}, {95, 100},
+    // {99, 100}}) is the caller's byPath.computeIfAbsent(path, ...).add(timeTakenInMsec) and sorted(list)[ceil(q * size) - 1] per key
+    // (README.md:26,63-79).  A key without numbers has all-zero rows.
+    struct GroupQuantiles : Groups {
+        size_t nQuantiles = 0;
+        std::vector<gx_quantile_out> quantiles;   // keys.size() x nQuantiles rows, key-major
+        const gx_quantile_out& at(size_t key, size_t quantile) const { return quantiles[key * nQuantiles + quantile]; }
+    };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other layout)
+    GroupQuantiles groupQuantiles(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const GroupParts& parts,
+                                  const std::vector<gx_quantile>& quantiles, const Where* where = nullptr) const {
+        GroupQuantiles g;
+        g.nQuantiles = quantiles.size();
+        static_cast<Groups&>(g) = groupsOf(parts, where, &n, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                                  gx_group_totals* totals) {
+            return gx_group_quantiles(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, quantiles.data(), static_cast<uint32_t>(quantiles.size()), 0, out,
+                                      g.quantiles.empty() ? nullptr : g.quantiles.data(), totals, nullptr);
+        }, &g.quantiles, quantiles.size());
+        return g;
+    }
+    // Whole files: raw text in, the same result out (gx_text_group_quantiles).  counts (optional): lines per outcome index.
+    GroupQuantiles textGroupQuantiles(const std::string& text, const GroupParts& parts, const std::vector<gx_quantile>& quantiles, const Where* where = nullptr,
+                                      std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        GroupQuantiles g;
+        g.nQuantiles = quantiles.size();
+        static_cast<Groups&>(g) = groupsOf(parts, where, &lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                                      gx_group_totals* totals) {
+            return gx_text_group_quantiles(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, quantiles.data(),
+                                           static_cast<uint32_t>(quantiles.size()), 0, out, g.quantiles.empty() ? nullptr : g.quantiles.data(), totals,
+                                           counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        }, &g.quantiles, quantiles.size());
+        if (nLines) *nLines = lines;
+        return g;
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
@@ -617,7 +657,8 @@ private:
     // keys as lines, which always suffices -- then the call with exactly the sizes it reported.  *lines: the batch's lines (for a text:
     // what the call itself reports).
     template <typename Call>
-    Groups groupsOf(const GroupParts& parts, const Where* where, const uint64_t* lines, Call&& call) const {
+    Groups groupsOf(const GroupParts& parts, const Where* where, const uint64_t* lines, Call&& call, std::vector<gx_quantile_out>* rows = nullptr,
+                    size_t rowsPerKey = 0) const {
         const std::vector<gx_group_part>& p = parts.parts();
         const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
         const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
@@ -637,6 +678,7 @@ private:
         g.lines.assign(k, 0);
         if (parts.hasValues()) g.stats.assign(k, gx_measure_stats{});
         g.lineKey.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        if (rows) rows->assign(k * rowsPerKey, gx_quantile_out{});   // (groupQuantiles: its call delivers them from here on)
         gx_group_out out{};
         out.key_units = units.data();
         out.key_units_cap = g.totals.key_units;

@@ -620,6 +620,42 @@ int gx_text_capture_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, 
                               gx_quantile_out* out, gx_quantile_totals* totals, uint64_t* counts, uint64_t* n_lines,
                               const gx_batch_opts* opts);
 
+/* ---- percentiles of a captured number per captured text -------------------------------------------------------------------------
+ * The question an operator asks of a request log: p50 / p95 / p99 of timeTakenInMsec per path.  The reference's caller answers it
+ * right behind the extraction with a map of lists (README.md:26,63-79):
+ *     byPath.computeIfAbsent(r.asMap().get("path"), p -> new ArrayList<>()).add(Long.parseLong(r.asMap().get("timeTakenInMsec")));
+ *     ... sorted(list)[ceil(q * list.size()) - 1] per key
+ * gx_group_quantiles is gx_group_lines plus ONE output; nothing of gx_group_lines is reinterpreted.  Parts, terms, flags, out, totals,
+ * row formats, offsets64, utf16, utf8 = 1, staging or device_pointers, the stream, the size query, GX_E_LIMIT with nothing written and
+ * the overflowed table (exact = 0) are gx_group_lines'.  With n_quantiles == 0 the call delivers what gx_group_lines delivers, bit for
+ * bit, and key_quantiles is not touched.
+ * The quantiles are gx_quantile records with gx_capture_quantiles' rule (nearest rank in integers alone), at most GX_QUANTILE_MAX, in
+ * any order, repeats allowed.  Key j's POPULATION is the numbers among key j's lines whose part has a value_group: exactly the lines
+ * counted in key_stats[j].numbers.  A line whose key pair names no value belongs to no key; a part with value_group = -1 adds lines to
+ * its keys and nothing to their populations.
+ * key_quantiles (optional) holds n_keys x n_quantiles rows, key-major, the keys in gx_group_lines' order; its capacity is
+ * out->max_keys x n_quantiles rows (out == NULL: 0); device memory with device_pointers, else host, like the other per-key arrays.
+ * Row (j, q): value, the rank-th smallest number of key j; rank; below, the numbers of key j strictly below value; equal, those equal
+ * to it (below < rank <= below + equal <= key_stats[j].numbers).  A key without numbers gets all-zero rows.  Every result is exact
+ * and the same bits on every run.  key_quantiles == NULL with n_quantiles > 0 is legal: the size query, or the keys alone.
+ * GX_E_ARG, besides gx_group_lines': quantiles == NULL with n_quantiles > 0, den == 0, num > den.  GX_E_LIMIT, besides gx_group_lines':
+ * n_quantiles > GX_QUANTILE_MAX; key_quantiles given with n_keys > max_keys (nothing is written to any output, *totals is filled).
+ * All before the device is looked at: a host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).
+ * The call synchronises the stream once, where the host reads the totals and, in the same wait, what the sort's digit plan needs; with
+ * host outputs a second wait delivers them.  With device_pointers the remaining passes are left running on opts->stream; the handle's
+ * next gx_group_lines / gx_group_quantiles on another stream waits for them. */
+int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                       const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                       const gx_quantile* quantiles, uint32_t n_quantiles, uint32_t flags, const gx_group_out* out,
+                       gx_quantile_out* key_quantiles, gx_group_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the per-key quantiles at its end; counts, *n_lines, limits and options are
+ * gx_text_group_lines'.  Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                            const gx_where_term* terms, uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles,
+                            uint32_t flags, const gx_group_out* out, gx_quantile_out* key_quantiles, gx_group_totals* totals,
+                            uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
