@@ -52,8 +52,17 @@ def _check(rc):
 # ---------------------------------------------------------------------------
 # RegexHelper (core/util/RegexHelper.java) -- implemented in gx_host.cpp
 # ---------------------------------------------------------------------------
+def _c_text(text):
+    """A definition's text as the C ABI takes it: a C string, which would end at a U+0000 silently -- refused instead (the reference's
+    Strings may hold one)."""
+    if "\x00" in text:
+        raise DefinitionParseException(N.GX_E_UNSUPPORTED_CONSTRUCT, "a definition cannot hold U+0000: the library takes C strings "
+                                       "(the class [^\\u0001-\\uffff], its bounds written as characters, matches one)")
+    return text.encode("utf-8")
+
+
 def _string_call(fn, text):
-    raw = text.encode("utf-8")
+    raw = _c_text(text)
     cap = 8 * len(raw) + 64
     buf = C.create_string_buffer(cap)
     n = C.c_size_t(0)
@@ -336,10 +345,10 @@ def _create(autom, jdk, flags):
     L = N.lib()
     flags |= DEFAULT_CREATE_FLAGS
     n = len(autom)
-    A = (C.c_char_p * n)(*[s.encode("utf-8") for s in autom])
+    A = (C.c_char_p * n)(*[_c_text(s) for s in autom])
     J = None
     if jdk is not None:
-        J = (C.c_char_p * n)(*[s.encode("utf-8") for s in jdk])
+        J = (C.c_char_p * n)(*[_c_text(s) for s in jdk])
     h = C.c_void_p()
     rc = L.gx_create_from_patterns(A, J, n, flags, C.byref(h))
     if rc in (N.GX_E_REGEX_SYNTAX, N.GX_E_UNSUPPORTED_CONSTRUCT, N.GX_E_LIMIT):
@@ -1917,7 +1926,7 @@ def lines_to_csr(lines, offsets_dtype=np.uint32):
 def _definition_json(text, source_ref, stage):
     import json
     L = N.lib()
-    raw = text.encode("utf-8")
+    raw = _c_text(text)
     cap = 64 * len(raw) + 4096
     n = C.c_size_t(0)
     buf = C.create_string_buffer(cap)
@@ -1971,7 +1980,7 @@ class DefinitionReader:
         cooked = [CookedExtraction(i, x["name"], x["jdk_rx"], x["extractor_names"], x["append"])
                   for i, x in enumerate(d["extractions"])]
         hp = C.c_void_p()
-        rc = N.lib().gx_create_from_definition(self._text.encode("utf-8"), self._source_ref.encode("utf-8"),
+        rc = N.lib().gx_create_from_definition(_c_text(self._text), self._source_ref.encode("utf-8"),
                                                flags | DEFAULT_CREATE_FLAGS | (N.GX_CREATE_HOST_ONLY if host_only else 0), C.byref(hp))
         if rc in (N.GX_E_DEFINITION, N.GX_E_REGEX_SYNTAX, N.GX_E_UNSUPPORTED_CONSTRUCT, N.GX_E_LIMIT):
             raise DefinitionParseException(rc, N.last_error())
