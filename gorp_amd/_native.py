@@ -52,6 +52,7 @@ SYMBOLS = [
     "gx_top_lines", "gx_text_top_lines",
     "gx_capture_quantiles", "gx_text_capture_quantiles",
     "gx_group_quantiles", "gx_text_group_quantiles",
+    "gx_top_groups", "gx_text_top_groups",
 ]
 
 
@@ -95,6 +96,9 @@ GX_GROUP_WEAK_HASH = 1
 GX_TOP_SMALLEST = 1
 GX_TOP_MAX_LINES = 4096
 GX_QUANTILE_MAX = 16
+GX_RANK_LINES, GX_RANK_NUMBERS, GX_RANK_SUM, GX_RANK_MAX, GX_RANK_MIN = range(5)
+GX_TOP_GROUPS_SMALLEST = 2
+GX_TOP_GROUPS_MAX = 4096
 
 
 class gx_group_part(C.Structure):
@@ -130,6 +134,16 @@ class gx_group_out(C.Structure):
 class gx_group_totals(C.Structure):
     _fields_ = [("n_keys", C.c_uint64), ("key_units", C.c_uint64), ("lines", C.c_uint64), ("keyed", C.c_uint64), ("unset", C.c_uint64),
                 ("exact", C.c_uint64)]
+
+
+class gx_top_groups_out(C.Structure):
+    _fields_ = [("key_units", C.c_void_p), ("key_units_cap", C.c_uint64), ("key_offsets", C.c_void_p), ("key_number", C.c_void_p),
+                ("key_first_line", C.c_void_p), ("key_lines", C.c_void_p), ("key_stats", C.c_void_p), ("line_rank", C.c_void_p), ("cap_keys", C.c_uint64)]
+
+
+class gx_top_groups_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("candidates", C.c_uint64), ("n_top", C.c_uint64), ("units_top", C.c_uint64), ("last_lo", C.c_uint64),
+                ("last_hi", C.c_int64), ("ties_left", C.c_uint64)]
 
 
 class gx_device_shard(C.Structure):
@@ -324,6 +338,14 @@ def lib():
                                           C.POINTER(gx_quantile), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.c_void_p,
                                           C.POINTER(gx_group_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_quantiles.restype = C.c_int
+    L.gx_top_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32,
+                                C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(gx_top_groups_out),
+                                C.POINTER(gx_top_groups_totals), C.POINTER(gx_batch_opts)]
+    L.gx_top_groups.restype = C.c_int
+    L.gx_text_top_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(gx_top_groups_out), C.POINTER(gx_top_groups_totals),
+                                     C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_top_groups.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -22,6 +22,7 @@
 #include "gx_dsl.hpp"
 #include "gx_group.hpp"
 #include "gx_group_quantile.hpp"
+#include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
 #include "gx_slots.hpp"
@@ -275,6 +276,8 @@ struct gx_handle {
     // gx_group_quantiles behind them: its value parts, quantiles and terms (TopHead, QuantHead, WhereHead) and its workspace; they are
     // covered by group_event too
     GrowBuf gq_image, gq_ws;
+    // gx_top_groups behind gx_group_lines' build: its workspace (gx_top_groups.hip), covered by group_event too
+    GrowBuf tg_ws;
     Event group_event;
     bool group_pending = false;
     // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
@@ -1925,6 +1928,147 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     return GX_OK;
 }
 
+// gx_top_groups: what the call adds to gx_group_lines' arguments
+struct TopGroupsCall {
+    uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
+    gx_top_groups_out out{};
+    gx_top_groups_totals* totals = nullptr;
+};
+// what gx_top_groups adds to the refusals of gx_group_lines, behind them and before the look at the device
+static void tg_refusals(const GroupImage& gi, const TopGroupsCall& tg, const std::string& name) {
+    if (tg.rank_by >= TG_RANK_KINDS) throw GxError(GX_E_ARG, name + ": rank_by is not one of GX_RANK_LINES .. GX_RANK_MIN");
+    if (tg.rank_by != TG_RANK_LINES && !gi.values) throw GxError(GX_E_ARG, name + ": ranking by numbers, sum, max or min needs a part with a value_group");
+    if (tg.n_wanted > TG_MAX) throw GxError(GX_E_LIMIT, name + ": n_wanted above GX_TOP_GROUPS_MAX");
+}
+
+// gx_top_groups' passes on the handle's buffers (under h->mu): gx_group_lines' build, flags and scans, and the FIRST wait, where the
+// host reads gx_group_lines' totals (the keys, the status); then the keys pass, the select, the order and the scan of the chosen keys'
+// lengths, and the SECOND wait, where the host reads the candidates, the select's state, the ties and the chosen keys' units and checks
+// the capacities; then the emit over the chosen keys.  Host outputs are staged and a third wait delivers them; with device pointers the
+// emit is left running under group_event.
+static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
+                           const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, uint64_t max_keys, const TopGroupsCall& tg, bool out64,
+                           bool host_out, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    if (counts) {
+        if (h->select_pending) {
+            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
+            h->select_pending = false;
+        }
+        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
+        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
+        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    gx_top_groups_totals* totals = tg.totals;
+    *totals = gx_top_groups_totals{};
+    totals->group.exact = 1;
+    const gx_top_groups_out& out = tg.out;
+    const bool any_out = out.key_units || out.key_offsets || out.key_number || out.key_first_line || out.key_lines || out.key_stats || out.line_rank;
+    const uint64_t zero = 0;
+    // no keys: the offsets' one entry and every line's "none"
+    auto deliver_nothing = [&]() -> int {
+        if (out.key_offsets) {
+            if (host_out) memcpy(out.key_offsets, &zero, out64 ? 8 : 4);
+            else GX_HIP(hipMemsetAsync(out.key_offsets, 0, out64 ? 8 : 4, stream));
+        }
+        if (out.line_rank && n) {
+            if (host_out) memset(out.line_rank, 0xFF, n * 4);
+            else GX_HIP(hipMemsetAsync(out.line_rank, 0xFF, n * 4, stream));
+        }
+        return GX_OK;
+    };
+    if (n == 0 || gi.head.n_parts == 0) {
+        GX_HIP(hipStreamSynchronize(stream));
+        return deliver_nothing();
+    }
+    if (h->group_pending) {
+        GX_HIP(hipStreamWaitEvent(stream, h->group_event.get(), 0));
+        h->group_pending = false;
+    }
+    const uint32_t n_slots = group_slots(max_keys);
+    uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
+                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u};
+    const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
+    GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    // the first wait: gx_group_lines' totals
+    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
+    GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&key_units, w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got[2] & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be grouped");
+    totals->group.lines = got[0];
+    totals->group.unset = got[1];
+    totals->group.keyed = got[0] - got[1];
+    totals->group.n_keys = n_keys;
+    totals->group.key_units = key_units;
+    if (got[2] & 2u) {
+        totals->group.exact = 0;
+        totals->group.n_keys = static_cast<uint64_t>(n_slots) + 1u;
+        return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
+    }
+    if (n_keys == 0) return deliver_nothing();
+    if (n_keys > n) throw GxError(GX_E_ARG, "internal: " + name + ": more keys than lines");
+    // the keys pass, the select, the order; the second wait: what the select found
+    const TopGroupsWs tw = top_groups_workspace(h->tg_ws.get(top_groups_workspace_bytes(n, n_slots, n_keys)), n, n_slots, n_keys);
+    GX_HIP(launch_top_groups_select(n, a, w, n_keys, tg.rank_by, tg.smallest, tg.n_wanted, tw, stream));
+    TgDev head{};
+    uint64_t both = 0, units_top = 0;
+    GX_HIP(hipMemcpyAsync(&head, tw.head, offsetof(TgDev, hist), hipMemcpyDeviceToHost, stream));
+    if (tg.n_wanted) {
+        GX_HIP(hipMemcpyAsync(&both, tw.before + n_keys, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&units_top, tw.dst_off + tg.n_wanted, 8, hipMemcpyDeviceToHost, stream));
+    }
+    GX_HIP(hipStreamSynchronize(stream));
+    const uint32_t n_top = tg.n_wanted ? head.sel.n_top : 0u;
+    if (n_top > tg.n_wanted || n_top > head.candidates) throw GxError(GX_E_ARG, "internal: " + name + ": the select chose more keys than it may");
+    totals->candidates = head.candidates;
+    totals->n_top = n_top;
+    totals->units_top = units_top;
+    if (n_top) {
+        tg_value(head.sel.prefix, tg.smallest != 0u, &totals->last_hi, &totals->last_lo);
+        totals->ties_left = (both >> 32) - head.sel.remaining;
+    }
+    if (!any_out) return GX_OK;
+    const bool per_key = out.key_offsets || out.key_number || out.key_first_line || out.key_lines || out.key_stats;
+    if (per_key && n_top > out.cap_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_top) + " keys, cap_keys " + std::to_string(out.cap_keys));
+    if (out.key_units && units_top > out.key_units_cap)
+        return fail(GX_E_LIMIT, name + ": " + std::to_string(units_top) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
+    if (out.key_offsets && !out64 && units_top > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
+    const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
+    TopGroupsOut o{out.key_units, out.key_offsets, out.key_number, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_rank,
+                   out64 ? 1 : 0};
+    DevMem<> d_units, d_offs, d_num, d_first, d_lines, d_stats, d_lrank;
+    if (host_out) {
+        if (out.key_units) { d_units = dev_alloc(units_top * unit); o.key_units = d_units.get(); }
+        if (out.key_offsets) { d_offs = dev_alloc((n_top + 1) * off_w); o.key_offsets = d_offs.get(); }
+        if (out.key_number) { d_num = dev_alloc(n_top * 4); o.key_number = static_cast<uint32_t*>(d_num.get()); }
+        if (out.key_first_line) { d_first = dev_alloc(n_top * 4); o.key_first_line = static_cast<uint32_t*>(d_first.get()); }
+        if (out.key_lines) { d_lines = dev_alloc(n_top * 8); o.key_lines = static_cast<uint64_t*>(d_lines.get()); }
+        if (out.key_stats) { d_stats = dev_alloc(n_top * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
+        if (out.line_rank) { d_lrank = dev_alloc(n * 4); o.line_rank = static_cast<uint32_t*>(d_lrank.get()); }
+    }
+    GX_HIP(launch_top_groups_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, tw, o, n_top, units_top, stream));
+    if (host_out) {
+        if (out.key_units && units_top) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, units_top * unit, hipMemcpyDeviceToHost, stream));
+        if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_top + 1) * off_w, hipMemcpyDeviceToHost, stream));
+        if (out.key_number && n_top) GX_HIP(hipMemcpyAsync(out.key_number, o.key_number, n_top * 4, hipMemcpyDeviceToHost, stream));
+        if (out.key_first_line && n_top) GX_HIP(hipMemcpyAsync(out.key_first_line, o.key_first_line, n_top * 4, hipMemcpyDeviceToHost, stream));
+        if (out.key_lines && n_top) GX_HIP(hipMemcpyAsync(out.key_lines, o.key_lines, n_top * 8, hipMemcpyDeviceToHost, stream));
+        if (out.key_stats && n_top) GX_HIP(hipMemcpyAsync(out.key_stats, o.key_stats, n_top * 64, hipMemcpyDeviceToHost, stream));
+        if (out.line_rank) GX_HIP(hipMemcpyAsync(out.line_rank, o.line_rank, n * 4, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+    } else {
+        if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
+        GX_HIP(hipEventRecord(h->group_event.get(), stream));
+        h->group_pending = true;
+    }
+    return GX_OK;
+}
+
 // what gx_group_quantiles adds to the refusals of gx_group_lines, behind them and before the look at the device: the quantiles
 // (gx_capture_quantiles' rule), and the parts that have a value group as the keys pass reads them
 static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* rows, const std::string& name, GroupQuant* gq) {
@@ -1949,7 +2093,7 @@ static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint
 static int group_lines_call(const std::string& name, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
                             const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
                             gx_group_totals* totals, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                            gx_quantile_out* key_quantiles) {
+                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr) {
     return guarded([&]() -> int {
         if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -1962,6 +2106,7 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, go, totals, name, &gi, &wi);
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
+        if (tg) tg_refusals(gi, *tg, name);
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
         if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the build pass
@@ -1993,6 +2138,9 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
             }
             src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
         }
+        if (tg)
+            return top_groups_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi,
+                                   go.max_keys, *tg, o.offsets64 != 0, !o.device_pointers, nullptr, stream, name);
         return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
                           o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr);
     });
@@ -2015,7 +2163,7 @@ int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uin
 static int text_group_call(const std::string& name, gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
                            const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts,
                            uint64_t* n_lines, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                           gx_quantile_out* key_quantiles) {
+                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr) {
     return guarded([&]() -> int {
         if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2026,6 +2174,7 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, go, totals, name, &gi, &wi);
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
+        if (tg) tg_refusals(gi, *tg, name);
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
@@ -2044,8 +2193,10 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
         const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
         if (n_lines) *n_lines = tl.n;
-        const int rc = group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
-                                  !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr);
+        const int rc = tg ? top_groups_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go.max_keys, *tg,
+                                            o.offsets64 != 0, !o.device_pointers, counts, stream, name)
+                          : group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
+                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr);
         // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
         // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
         // wait that delivered them was that already).
@@ -2069,6 +2220,40 @@ int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, co
                             gx_quantile_out* key_quantiles, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_quantiles", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, true, quantiles,
                            n_quantiles, key_quantiles);
+}
+
+// gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST, a gx_group_out that holds
+// what gx_group_lines' refusals look at (key_stats, max_keys), and &totals->group.  Unknown flag bits stay in the flags and are refused there.
+static TopGroupsCall tg_call(uint32_t rank_by, uint32_t n_wanted, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals) {
+    TopGroupsCall tg;
+    tg.rank_by = rank_by;
+    tg.n_wanted = n_wanted;
+    tg.smallest = (flags & GX_TOP_GROUPS_SMALLEST) ? 1u : 0u;
+    if (out) tg.out = *out;
+    tg.totals = totals;
+    return tg;
+}
+
+int gx_top_groups(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                  uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t rank_by, uint32_t n_wanted, uint64_t max_keys, uint32_t flags,
+                  const gx_top_groups_out* out, gx_top_groups_totals* totals, const gx_batch_opts* opts) {
+    const TopGroupsCall tg = tg_call(rank_by, n_wanted, flags, out, totals);
+    gx_group_out go{};
+    go.key_stats = tg.out.key_stats;
+    go.max_keys = max_keys;
+    return group_lines_call("gx_top_groups", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_TOP_GROUPS_SMALLEST), &go,
+                            totals ? &totals->group : nullptr, opts, false, nullptr, 0, nullptr, &tg);
+}
+
+int gx_text_top_groups(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                       uint32_t rank_by, uint32_t n_wanted, uint64_t max_keys, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals,
+                       uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    const TopGroupsCall tg = tg_call(rank_by, n_wanted, flags, out, totals);
+    gx_group_out go{};
+    go.key_stats = tg.out.key_stats;
+    go.max_keys = max_keys;
+    return text_group_call("gx_text_top_groups", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_TOP_GROUPS_SMALLEST), &go,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, false, nullptr, 0, nullptr, &tg);
 }
 
 // The parts of a gx_top_lines call as its keys pass reads them (gx_top.hpp: TopHead), checked against the handle.  Needs no device.

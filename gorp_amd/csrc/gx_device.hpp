@@ -293,7 +293,7 @@ struct GroupWs {
     uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS]
     uint64_t* stats_words;        // [n_slots][GROUP_STATS_WORDS], with values
     uint64_t* totals;             // [8]: lines that count, lines without a key, status bits (1: a line of 4 G units, 2: the table is full)
-    uint32_t* keynum;             // [n_slots] the slot's key number, written by the emit pass
+    uint32_t* keynum;             // [n_slots] the slot's key number, written by the emit pass (gx_top_groups' emit: the rank of the slot's key)
     uint64_t* idx_off;            // [n + 1] first lines before line i; [n]: the keys
     uint64_t* dst_off;            // [n + 1] key units before line i's; [n]: all of them
     uint64_t *sums_a, *sums_b;    // the scans'
@@ -408,6 +408,48 @@ hipError_t launch_gq_collect(const void* ids, RowFormat fmt, uint32_t row_units,
 // Behind launch_group_emit (keynum).  0 < m <= n candidates; rows: n_keys x n_q QuantOut on the device; quant_head: a QuantHead there.
 hipError_t launch_gq_sort_pick(const GqWs& w, uint64_t m, const GqPlan& plan, const uint32_t* keynum, uint32_t n_slots, const void* quant_head, uint32_t n_q,
                                uint64_t n_keys, void* rows, hipStream_t stream);
+
+// The keys of a finished batch ranked by their lines or numbers (gx_top_groups.hip; the rule: gx_top_groups.hpp), behind
+// launch_group_build on the same stream and the host's look at its totals.  The passes' device workspace, cut out of one allocation of
+// top_groups_workspace_bytes(n, n_slots, n_keys) bytes; the columns are indexed by key number:
+struct TopGroupsWs {
+    uint8_t* head;                // TgDev (gx_top_groups.hpp): candidates, the keys' OR and AND, the select's state, a digit's histogram
+    uint8_t* slab;                // the keys pass's workgroups' partial reductions (64-bit), then their histograms (32-bit)
+    uint64_t* block_sums;         // the scans'
+    uint64_t *key_hi, *key_lo;    // [n_keys] the key's 128-bit key
+    uint64_t* col;                // [n_keys] 1: a candidate above the threshold, 2^32: one equal to it
+    uint64_t* before;             // [n_keys + 1] col scanned: both kinds before key j; [n_keys]: all of them
+    uint64_t *c_hi, *c_lo;        // [TG_MAX] the chosen candidates in key-number order: keys ...
+    uint64_t* dst_off;            // [n_wanted + 1] key units before rank r
+    uint32_t* first_of;           // [n_keys] the key's first line
+    uint32_t* slot_of_key;        // [n_keys] the key's slot
+    uint32_t* c_num;              // ... and key numbers
+    uint32_t *r_num, *r_first, *r_slot;   // [TG_MAX] per rank: the key's number, first line and slot
+    uint32_t* plen;               // [n_wanted] its key's units, 0 from n_top on
+    uint8_t* cand;                // [n_keys] the key is a candidate
+    size_t bytes;
+};
+// what the emit pass writes, each part optional (nullptr); all in rank order but line_rank
+struct TopGroupsOut {
+    void* key_units;
+    void* key_offsets;
+    uint32_t* key_number;
+    uint32_t* key_first_line;
+    uint64_t* key_lines;
+    uint64_t* key_stats;          // [n_top][8]: gx_measure_stats' fields
+    uint32_t* line_rank;          // [n]
+    int offsets64;                // key_offsets: uint64, else uint32
+};
+bool top_groups_by_slots(uint64_t n, uint32_t n_slots);   // the keys pass reaches the keys through the slots, not the flagged first lines
+TopGroupsWs top_groups_workspace(void* ws, uint64_t n, uint32_t n_slots, uint64_t n_keys);
+size_t top_groups_workspace_bytes(uint64_t n, uint32_t n_slots, uint64_t n_keys);
+// 0 < n_keys <= n, n_wanted <= TG_MAX.  Everything before the emit; behind it the host reads TgDev at w.head, w.before[n_keys] and
+// w.dst_off[n_wanted] (n_wanted > 0).
+hipError_t launch_top_groups_select(uint64_t n, const GroupArgs& a, const GroupWs& g, uint64_t n_keys, uint32_t rank_by, uint32_t smallest, uint32_t n_wanted,
+                                    const TopGroupsWs& w, hipStream_t stream);
+hipError_t launch_top_groups_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                                  const GroupWs& g, const TopGroupsWs& w, const TopGroupsOut& out, uint32_t n_top, uint64_t units_top,
+                                  hipStream_t stream);
 
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:

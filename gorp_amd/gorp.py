@@ -1352,6 +1352,161 @@ class Gorp:
         res["line_key"] = res["line_key"][:n_lines]
         return res, counts, n_lines
 
+    # -- keys ranked by their lines or numbers (gx_top_groups / gx_text_top_groups) ------------------------------------------------
+    RANK_BY = {"lines": N.GX_RANK_LINES, "numbers": N.GX_RANK_NUMBERS, "sum": N.GX_RANK_SUM, "max": N.GX_RANK_MAX, "min": N.GX_RANK_MIN}
+
+    @staticmethod
+    def _top_groups_totals(t):
+        return {"group": Gorp._group_totals(t.group), "candidates": t.candidates, "n_top": t.n_top, "units_top": t.units_top,
+                "last": (t.last_hi << 64) + t.last_lo if t.n_top else None, "ties_left": t.ties_left}
+
+    @staticmethod
+    def _rank_by(by):
+        if by not in Gorp.RANK_BY:
+            raise ValueError('by: "lines", "numbers", "sum", "max" or "min"')
+        return Gorp.RANK_BY[by]
+
+    def top_groups_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, n_wanted, by="lines", largest=True, where=None, key_units_ptr=None,
+                          key_units_cap=0, key_offsets_ptr=None, key_number_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None,
+                          line_rank_ptr=None, cap_keys=0, max_keys=0, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False,
+                          weak_hash=False):
+        """gx_top_groups on device pointers (ints); the outputs are the caller's buffers, each optional (none at all: the size query;
+        max_keys still sizes the table).  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says
+        what the outputs need (n_top, units_top; group.exact False: the table overflowed, max_keys = n always suffices); every other
+        error raises."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_top_groups_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_number_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_rank_ptr,
+                                  cap_keys)
+        totals = N.gx_top_groups_totals()
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (0 if largest else N.GX_TOP_GROUPS_SMALLEST)
+        rc = N.lib().gx_top_groups(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, self._rank_by(by),
+                                   n_wanted, max_keys, flags, C.byref(out), C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._top_groups_totals(totals)
+
+    def text_top_groups_device(self, text_ptr, size, parts, n_wanted, by="lines", largest=True, where=None, key_units_ptr=None, key_units_cap=0,
+                               key_offsets_ptr=None, key_number_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_rank_ptr=None,
+                               cap_keys=0, max_keys=0, offsets64=False, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_text_top_groups on a device buffer (int); outputs as top_groups_device takes them (line_rank: one entry per line of the
+        text).  Returns (rc, totals, counts, n_lines)."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out = N.gx_top_groups_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_number_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_rank_ptr,
+                                  cap_keys)
+        totals = N.gx_top_groups_totals()
+        nl = C.c_uint64(0)
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (0 if largest else N.GX_TOP_GROUPS_SMALLEST)
+        rc = N.lib().gx_text_top_groups(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, self._rank_by(by), n_wanted, max_keys, flags,
+                                        C.byref(out), C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._top_groups_totals(totals), counts, nl.value
+
+    def _top_groups_host(self, call, n_lines_cap, n_wanted, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, want_line_rank):
+        """Runs `call(out arrays..., cap_keys, max_keys)` on host arrays; on GX_E_LIMIT once more with the units it reported, or -- when
+        the table overflowed -- with max_keys = the number of lines: three calls at the most.  Builds the result dict."""
+        max_keys = min(n_lines_cap, 1024) if max_keys is None else max_keys
+        cap = max(1, n_wanted)
+        key_units_cap = 65536
+        for attempt in range(3):
+            units = np.zeros(max(1, key_units_cap), unit_dtype)
+            koff = np.zeros(cap + 1, offsets_dtype)
+            number = np.zeros(cap, np.uint32)
+            first = np.zeros(cap, np.uint32)
+            lines = np.zeros(cap, np.uint64)
+            stats = (N.gx_measure_stats * cap)() if parts.has_values else None
+            line_rank = np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32) if want_line_rank else None
+            got = call(units.ctypes.data, key_units_cap, koff.ctypes.data, number.ctypes.data, first.ctypes.data, lines.ctypes.data,
+                       None if stats is None else C.addressof(stats), None if line_rank is None else line_rank.ctypes.data, cap, max_keys)
+            rc, totals = got[0], got[1]
+            if rc == N.GX_OK:
+                break
+            if attempt == 2:
+                raise GorpError(rc, N.last_error())
+            if totals["group"]["exact"]:
+                key_units_cap = max(key_units_cap, totals["units_top"])
+            else:
+                max_keys = n_lines_cap
+        k = totals["n_top"]
+        koff, units = koff[:k + 1], units[:totals["units_top"]]
+        res = {"key_units": units, "key_offsets": koff, "key_number": number[:k], "first_line": first[:k], "lines": lines[:k], "totals": totals,
+               "stats": None if stats is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                                                      "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
+                                                      "sum": (s.sum_hi << 64) + s.sum_lo} for s in stats[:k]]}
+        if want_line_rank:
+            res["line_rank"] = line_rank
+        if keys == "list":
+            res["keys"] = [decode(units[int(koff[j]):int(koff[j + 1])]) for j in range(k)]
+        elif keys != "csr":
+            raise ValueError('keys: "list" or "csr"')
+        return res, got[2:]
+
+    def top_groups(self, data, offsets, ids, rows, parts, n, by="lines", largest=True, where=None, utf8=None, keys="list", max_keys=None, line_rank=False,
+                   weak_hash=False):
+        """gx_top_groups on host buffers: the n keys (at most 4096) that rank highest -- lowest with largest=False -- by their lines, or
+        by the numbers, sum, max or min of what the part's value extractor captured on their lines; ties go to the key that appeared
+        first.  data / offsets / ids / rows, parts, where and utf8 as group_lines takes them.  Returns group_lines' dict shape in RANK
+        order -- keys (keys="csr": left out), key_units / key_offsets, first_line, lines, stats -- plus key_number (the key's number
+        in group_lines' order), line_rank with line_rank=True (uint32 per input line, 0xFFFFFFFF: no key, or its key not delivered),
+        and totals: group (group_lines' totals), candidates, n_top, units_top, last (the rank value of the last delivered key as one
+        int, None without one) and ties_left."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.group_parts(parts)
+        n_lines = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, ucap, koff, number, first, lines, stats, lrank, cap, mk):
+            return self.top_groups_device(ptr(data), offsets.ctypes.data, n_lines, ptr(ids), ptr(caps), parts, n, by, largest, where, units, ucap, koff, number, first,
+                                          lines, stats, lrank, cap, mk, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact,
+                                          device_pointers=False, utf8=bool(utf8), weak_hash=weak_hash)
+        res, _ = self._top_groups_host(call, n_lines, n, parts, data.dtype, offsets.dtype, keys, decode, max_keys, line_rank)
+        if line_rank:
+            res["line_rank"] = res["line_rank"][:n_lines]
+        return res
+
+    def text_top_groups(self, text, parts, n, by="lines", largest=True, where=None, utf8=False, keys="list", max_keys=None, line_rank=False):
+        """gx_text_top_groups on a host buffer: raw text -> lines -> extraction -> top_groups.  Returns (the dict top_groups returns,
+        counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.group_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def call(units, ucap, koff, number, first, lines, stats, lrank, cap, mk):
+            return self.text_top_groups_device(raw.ctypes.data if raw.size else None, raw.size, parts, n, by, largest, where, units, ucap, koff, number, first, lines,
+                                               stats, lrank, cap, mk, device_pointers=False, utf8=utf8)
+        res, (counts, n_lines) = self._top_groups_host(call, cap_lines, n, parts, np.uint8, np.uint32, keys, decode, max_keys, line_rank)
+        if line_rank:
+            res["line_rank"] = res["line_rank"][:n_lines]
+        return res, counts, n_lines
+
     # -- lines ranked by a number they captured (gx_top_lines / gx_text_top_lines) ------------------------------------------------
     def top_parts(self, spec):
         """Resolves a list of (extraction, value extractor) into gx_top_part records: extraction is a name or an index, the extractor a

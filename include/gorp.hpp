@@ -589,6 +589,43 @@ public:
         if (nLines) *nLines = lines;
         return g;
     }
+    // Keys ranked by their lines or by the numbers their lines captured (gx_top_groups): "the ten most requested paths" is
+    // topGroups(..., groupParts().of("GetRequest", "path"), 10), "the ten clients that sent the most bytes" ranks with GX_RANK_SUM -- the
+    // caller's byPath.entrySet().stream().sorted(comparingByValue().reversed()).limit(10) (README.md:26,63-79).  Groups' fields in RANK
+    // order (ties: the key that appeared first), plus the keys' numbers in groupLines' order; lineKey stays empty, lineRank holds, when
+    // asked for, every input line's rank (0xFFFFFFFF: no key, or its key not delivered).
+    struct TopGroups : Groups {
+        std::vector<uint32_t> keyNumber;
+        std::vector<uint32_t> lineRank;
+        gx_top_groups_totals top{};   // top.group is Groups::totals
+    };
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other layout)
+    TopGroups topGroups(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const GroupParts& parts,
+                        uint32_t nWanted, uint32_t rankBy = GX_RANK_LINES, bool largest = true, const Where* where = nullptr, bool lineRank = false) const {
+        const uint32_t flags = largest ? 0u : GX_TOP_GROUPS_SMALLEST;
+        return topGroupsOf(parts, where, nWanted, lineRank, &n, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, uint64_t maxKeys,
+                                                                    const gx_top_groups_out* out, gx_top_groups_totals* totals) {
+            return gx_top_groups(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, rankBy, nWanted, maxKeys, flags, out, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same result out (gx_text_top_groups).  counts (optional): lines per outcome index.
+    TopGroups textTopGroups(const std::string& text, const GroupParts& parts, uint32_t nWanted, uint32_t rankBy = GX_RANK_LINES, bool largest = true,
+                            const Where* where = nullptr, bool lineRank = false, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr,
+                            bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        const uint32_t flags = largest ? 0u : GX_TOP_GROUPS_SMALLEST;
+        uint64_t lines = 0;
+        TopGroups g = topGroupsOf(parts, where, nWanted, lineRank, &lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt,
+                                                                               uint64_t maxKeys, const gx_top_groups_out* out, gx_top_groups_totals* totals) {
+            return gx_text_top_groups(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, rankBy, nWanted, maxKeys, flags, out, totals,
+                                      counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return g;
+    }
     // Whole files: raw text in, the text of the lines `want` names out (gx_text_select) -- with want(true, true) the
     // lines textToJsonl writes nothing for.  counts (optional): lines per outcome index.
     // utf8: the text is UTF-8 and outcomes are those of the decoded Strings (gx_batch_opts.utf8 = 1); the selected lines are their bytes
@@ -690,6 +727,45 @@ private:
         out.max_keys = g.totals.n_keys;   // (the arrays' capacity; a table of twice as many slots holds them all)
         rc = call(p.data(), np, terms.data(), nt, &out, &g.totals);
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
+        return g;
+    }
+    // groupsOf's scheme for topGroups: the size query with a table for a modest number of keys, once more with as many keys as lines if
+    // that table overflows, then the call with exactly the sizes it reported.
+    template <typename Call>
+    TopGroups topGroupsOf(const GroupParts& parts, const Where* where, uint32_t nWanted, bool lineRank, const uint64_t* lines, Call&& call) const {
+        const std::vector<gx_group_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
+        TopGroups g;
+        uint64_t maxKeys = 1024;
+        int rc = call(p.data(), np, terms.data(), nt, maxKeys, nullptr, &g.top);
+        if (rc == GX_E_LIMIT && g.top.group.n_keys != 0 && g.top.group.exact == 0) {
+            maxKeys = *lines;
+            rc = call(p.data(), np, terms.data(), nt, maxKeys, nullptr, &g.top);
+        }
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t k = static_cast<size_t>(g.top.n_top);
+        std::vector<uint8_t> units(static_cast<size_t>(g.top.units_top) + 1);
+        std::vector<uint32_t> offsets(k + 1, 0);
+        g.keyNumber.assign(k, 0);
+        g.firstLine.assign(k, 0);
+        g.lines.assign(k, 0);
+        if (parts.hasValues()) g.stats.assign(k, gx_measure_stats{});
+        if (lineRank) g.lineRank.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        gx_top_groups_out out{};
+        out.key_units = units.data();
+        out.key_units_cap = g.top.units_top;
+        out.key_offsets = offsets.data();
+        out.key_number = g.keyNumber.data();
+        out.key_first_line = g.firstLine.data();
+        out.key_lines = g.lines.data();
+        out.key_stats = parts.hasValues() ? g.stats.data() : nullptr;
+        out.line_rank = lineRank && !g.lineRank.empty() ? g.lineRank.data() : nullptr;
+        out.cap_keys = nWanted;
+        rc = call(p.data(), np, terms.data(), nt, maxKeys, &out, &g.top);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        g.totals = g.top.group;
         for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
         return g;
     }

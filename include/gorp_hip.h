@@ -656,6 +656,68 @@ int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, co
                             uint32_t flags, const gx_group_out* out, gx_quantile_out* key_quantiles, gx_group_totals* totals,
                             uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* Keys ranked by their lines or by the numbers their lines captured.  The reference caller's question "which keys are the biggest?"
+ * (README.md:26,63-79), on the map gx_group_lines builds:
+ *     byPath.merge(r.asMap().get("path"), 1L, Long::sum);          // or .record(Long.parseLong(timeTakenInMsec))
+ *     ... byPath.entrySet().stream().sorted(comparingByValue().reversed()).limit(10)
+ * Keys, parts, terms, which lines count, key equality, the one key space and the key numbers (order of first line) are gx_group_lines';
+ * nothing of that is reinterpreted.  Every key has a RANK VALUE, a signed 128-bit integer chosen by rank_by:
+ *     GX_RANK_LINES    key_lines[j]                        every key is a candidate
+ *     GX_RANK_NUMBERS  key_stats[j].numbers                every key
+ *     GX_RANK_SUM      the exact sum sum_hi : sum_lo       keys with numbers >= 1
+ *     GX_RANK_MAX      key_stats[j].max, sign-extended     keys with numbers >= 1
+ *     GX_RANK_MIN      key_stats[j].min, sign-extended     keys with numbers >= 1
+ * The result is the n_top = min(n_wanted, candidates) candidates ordered by (rank value descending, key number ascending) -- with
+ * GX_TOP_GROUPS_SMALLEST by (rank value ascending, key number ascending) -- so ties at the cut go to the keys that appeared first:
+ * gx_top_lines' tie rule, one level up.  Every output is exact and the same bits on every run; there is no floating point anywhere.
+ * Ranking by the mean or by a per-key quantile is not offered. */
+enum { GX_RANK_LINES = 0, GX_RANK_NUMBERS, GX_RANK_SUM, GX_RANK_MAX, GX_RANK_MIN };
+#define GX_TOP_GROUPS_SMALLEST 2u      /* GX_GROUP_WEAK_HASH (1u) is accepted in the same flags word; GX_TOP_SMALLEST is also 1u and is NOT used here */
+#define GX_TOP_GROUPS_MAX 4096u        /* the cap on n_wanted */
+
+typedef struct gx_top_groups_out {     /* every pointer optional; device memory with opts->device_pointers, else host; all in RANK order */
+    void*     key_units;  uint64_t key_units_cap;
+    void*     key_offsets;             /* n_top + 1, uint32 / uint64 as opts->offsets64 */
+    uint32_t* key_number;              /* the key's number in gx_group_lines' order (what gx_group_lines' line_key holds) */
+    uint32_t* key_first_line;
+    uint64_t* key_lines;
+    gx_measure_stats* key_stats;       /* NULL unless a part has a value_group */
+    uint32_t* line_rank;               /* n entries: the rank 0 .. n_top-1 of the line's key, 0xFFFFFFFF: no key, or key not delivered */
+    uint64_t  cap_keys;                /* capacity of the per-key arrays (key_offsets: cap_keys + 1); n_wanted always suffices */
+} gx_top_groups_out;
+
+typedef struct gx_top_groups_totals {  /* host, always */
+    gx_group_totals group;             /* exactly what gx_group_lines reports for the same call */
+    uint64_t candidates, n_top, units_top;
+    uint64_t last_lo; int64_t last_hi; /* rank value of the last delivered key, two's complement as sum_lo / sum_hi; 0 when n_top == 0 */
+    uint64_t ties_left;                /* candidates with that rank value that were not delivered */
+} gx_top_groups_totals;
+
+/* gx_top_groups: the batch is read exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16;
+ * utf8 = 1; staging or device_pointers; the stream).  max_keys sizes the hash table exactly as gx_group_out.max_keys does: the smallest
+ * power of two >= max(64, 2 * max_keys) slots, and n always suffices; an overflowed table is GX_E_LIMIT with group.exact = 0, and nothing
+ * is written.  With every output NULL, or out == NULL, the call is the size query: only *totals is delivered.  A per-key array with
+ * n_top > cap_keys, or key_units with units_top > key_units_cap, returns GX_E_LIMIT: every output stays untouched and *totals is filled.
+ * The host waits on the stream twice before any output is written -- for gx_group_lines' totals, then for what the select found -- and
+ * with host outputs a third wait delivers them; with device_pointers the emit over the chosen keys is left running on opts->stream
+ * when the call returns, and the handle's next group call on another stream waits for it.
+ * GX_E_ARG, besides every refusal gx_group_lines makes: rank_by out of range, rank_by != GX_RANK_LINES when no part has a value group,
+ * key_stats without a value group, unknown flag bits, totals == NULL, no_sync, utf8 = 2.  GX_E_LIMIT: n_wanted > GX_TOP_GROUPS_MAX, plus
+ * gx_group_lines' limits.  All of these come before the device is looked at (a host-only handle gives them, and GX_E_DEVICE after them:
+ * there is no CPU path), except what gx_group_lines itself can only see on the device.  n_parts == 0, n_wanted == 0 and n == 0 are
+ * legal; with n_wanted == 0 the totals are still filled. */
+int gx_top_groups(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                  const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t rank_by,
+                  uint32_t n_wanted, uint64_t max_keys, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals,
+                  const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the ranking at its end; counts and *n_lines are delivered as there, and
+ * out->line_rank has one entry per line of the text.  Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_top_groups(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                       const gx_where_term* terms, uint32_t n_terms, uint32_t rank_by, uint32_t n_wanted, uint64_t max_keys,
+                       uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                       const gx_batch_opts* opts);
+
 /* gx_partition_lines: every sink's lines at once.  Inputs, outputs, formats and options are exactly gx_select_lines'; the kept lines
  * -- those whose outcome index x <= 2K has want[x] != 0; want == NULL keeps every outcome 0 .. 2K -- leave ordered by (outcome index,
  * input line number): a stable partition.  The outcome-0 lines come first, then outcome 1's, and so on, in input order inside each
