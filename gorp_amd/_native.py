@@ -53,6 +53,7 @@ SYMBOLS = [
     "gx_capture_quantiles", "gx_text_capture_quantiles",
     "gx_group_quantiles", "gx_text_group_quantiles",
     "gx_top_groups", "gx_text_top_groups",
+    "gx_lines_by_key", "gx_text_lines_by_key",
 ]
 
 
@@ -99,6 +100,7 @@ GX_QUANTILE_MAX = 16
 GX_RANK_LINES, GX_RANK_NUMBERS, GX_RANK_SUM, GX_RANK_MAX, GX_RANK_MIN = range(5)
 GX_TOP_GROUPS_SMALLEST = 2
 GX_TOP_GROUPS_MAX = 4096
+GX_BY_KEY_ALL_DIGITS = 2
 
 
 class gx_group_part(C.Structure):
@@ -144,6 +146,15 @@ class gx_top_groups_out(C.Structure):
 class gx_top_groups_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("candidates", C.c_uint64), ("n_top", C.c_uint64), ("units_top", C.c_uint64), ("last_lo", C.c_uint64),
                 ("last_hi", C.c_int64), ("ties_left", C.c_uint64)]
+
+
+class gx_by_key_out(C.Structure):
+    _fields_ = [("out_index", C.c_void_p), ("out_bytes", C.c_void_p), ("out_offsets", C.c_void_p), ("out_ids", C.c_void_p), ("out_caps", C.c_void_p),
+                ("cap_lines", C.c_uint64), ("out_bytes_cap", C.c_uint64), ("key_out_lines", C.c_void_p), ("key_out_units", C.c_void_p)]
+
+
+class gx_by_key_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("keys_kept", C.c_uint64), ("lines_out", C.c_uint64), ("units_out", C.c_uint64)]
 
 
 class gx_device_shard(C.Structure):
@@ -346,6 +357,14 @@ def lib():
                                      C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(gx_top_groups_out), C.POINTER(gx_top_groups_totals),
                                      C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_top_groups.restype = C.c_int
+    L.gx_lines_by_key.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32,
+                                  C.POINTER(gx_where_term), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_by_key_out),
+                                  C.POINTER(gx_by_key_totals), C.POINTER(gx_batch_opts)]
+    L.gx_lines_by_key.restype = C.c_int
+    L.gx_text_lines_by_key.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                       C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(gx_group_out), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(gx_by_key_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_lines_by_key.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

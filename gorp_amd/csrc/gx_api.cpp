@@ -17,6 +17,7 @@
 #include <thread>
 #include <atomic>
 
+#include "gx_by_key.hpp"
 #include "gx_compile.hpp"
 #include "gx_device.hpp"
 #include "gx_dsl.hpp"
@@ -278,6 +279,8 @@ struct gx_handle {
     GrowBuf gq_image, gq_ws;
     // gx_top_groups behind gx_group_lines' build: its workspace (gx_top_groups.hip), covered by group_event too
     GrowBuf tg_ws;
+    // gx_lines_by_key behind gx_group_lines' build and emit: its workspace (gx_by_key.hip), covered by group_event too
+    GrowBuf by_key_ws;
     Event group_event;
     bool group_pending = false;
     // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
@@ -1804,10 +1807,23 @@ struct GroupQuant {
     gx_quantile_out* rows = nullptr;   // the caller's, device or host as the other per-key arrays; nullptr: not wanted
 };
 static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut), "the rows are copied as they are");
+// bk (gx_lines_by_key; nullptr: gx_group_lines as it is): before the read of the totals also the kept flags, their scan and the kept
+// lines, units and keys (launch_by_key_kept), read in the same wait; behind the emit, which numbers the slots, the compaction, the sort
+// by key number, the bounds (launch_by_key_sort) and the copy (launch_partition_copy).
+struct ByKeyCall {
+    uint64_t min_lines = 0, max_lines = 0;
+    bool all_digits = false;
+    gx_by_key_out out{};
+    gx_by_key_totals* totals = nullptr;   // (its group member is the gx_group_totals the pass fills)
+    bool per_line() const { return out.out_index || out.out_offsets || out.out_ids || out.out_caps; }
+    bool any() const { return per_line() || out.out_bytes || out.key_out_lines || out.key_out_units; }
+};
 static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
                       const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
-                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupQuant* gq = nullptr) {
+                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupQuant* gq = nullptr,
+                      const ByKeyCall* bk = nullptr) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    if (bk) *bk->totals = gx_by_key_totals{};
     if (counts) {
         if (h->select_pending) {
             GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
@@ -1822,7 +1838,8 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     const bool run = n != 0 && gi.head.n_parts != 0;
     gx_quantile_out* q_rows = gq && gq->qh.n_q ? gq->rows : nullptr;
     const uint32_t n_q = q_rows ? gq->qh.n_q : 0u;
-    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows;
+    const bool bk_out = bk && bk->any();
+    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out;
     if (!run) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -1834,6 +1851,15 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.line_key && n) {
             if (host_out) memset(out.line_key, 0xFF, n * 4);
             else GX_HIP(hipMemsetAsync(out.line_key, 0xFF, n * 4, stream));
+        }
+        if (bk_out) {   // no kept lines: the one entry of the offsets and of the two prefixes
+            void* const one[3] = {bk->out.out_offsets, bk->out.key_out_lines, bk->out.key_out_units};
+            const size_t width[3] = {off64 ? size_t(8) : size_t(4), 8, 8};
+            for (int q = 0; q < 3; ++q) {
+                if (!one[q]) continue;
+                if (host_out) memcpy(one[q], &zero, width[q]);
+                else GX_HIP(hipMemsetAsync(one[q], 0, width[q], stream));
+            }
         }
         return GX_OK;
     }
@@ -1866,6 +1892,14 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         GX_HIP(launch_gq_collect(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, ta, w.slot_of, qw, stream));
         GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, stream));
     }
+    // the kept lines of gx_lines_by_key, their units and their keys: from the slots' line counts, which the build has left complete
+    ByKeyWs bw{};
+    ByKeyDev bd{};
+    if (bk) {
+        bw = by_key_workspace(h->by_key_ws.get(by_key_workspace_bytes(n)), n);
+        GX_HIP(launch_by_key_kept(n, offsets, off64 ? 1 : 0, w, bk->min_lines, bk->max_lines, bw, stream));
+        GX_HIP(hipMemcpyAsync(&bd, bw.head, sizeof(ByKeyDev), hipMemcpyDeviceToHost, stream));
+    }
     uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
     GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
     GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -1882,6 +1916,12 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         totals->n_keys = static_cast<uint64_t>(n_slots) + 1u;
         return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
     }
+    if (bk) {
+        if (bd.lines_out > n || bd.keys_kept > n_keys) throw GxError(GX_E_ARG, "internal: " + name + ": more kept lines or keys than there are");
+        bk->totals->keys_kept = bd.keys_kept;
+        bk->totals->lines_out = bd.lines_out;
+        bk->totals->units_out = bd.units_out;
+    }
     if (!any_out) return GX_OK;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || q_rows;
     if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
@@ -1889,6 +1929,14 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         return fail(GX_E_LIMIT, name + ": " + std::to_string(key_units) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && key_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
     const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
+    if (bk_out) {
+        const gx_by_key_out& b = bk->out;
+        if (bk->per_line() && bd.lines_out > b.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
+        if (b.out_bytes && bd.units_out * unit > b.out_bytes_cap) return fail(GX_E_LIMIT, name + ": the kept text is larger than the capacity (see totals->units_out)");
+        if (b.out_offsets && !off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+        if ((b.key_out_lines || b.key_out_units) && n_keys > out.max_keys)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
+    }
     GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
     DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey, d_rows;
     void* rows = q_rows;
@@ -1903,6 +1951,40 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.line_key) { d_lkey = dev_alloc(n * 4); o.line_key = static_cast<uint32_t*>(d_lkey.get()); }
     }
     GX_HIP(launch_group_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
+    // gx_lines_by_key: the kept lines by (key number, line) as a new batch, and the keys' bounds in it
+    SelectOut so{};
+    DevMem<> b_index, b_bytes, b_off, b_ids, b_caps, b_kol, b_kou;
+    void *b_dst_ids = nullptr, *b_dst_caps = nullptr;
+    uint64_t *kol = nullptr, *kou = nullptr;
+    const uint64_t m = bd.lines_out;
+    const size_t in_off_w = off64 ? 8 : 4, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt), cap_slots = 2 * static_cast<size_t>(h->T.max_groups);
+    if (bk_out) {
+        const gx_by_key_out& b = bk->out;
+        so.index = b.out_index; so.bytes = b.out_bytes; so.offsets = b.out_offsets;
+        b_dst_ids = b.out_ids; b_dst_caps = b.out_caps;
+        kol = b.key_out_lines; kou = b.key_out_units;
+        if (host_out) {
+            if (b.out_index) { b_index = dev_alloc(m * 4); so.index = static_cast<uint32_t*>(b_index.get()); }
+            if (b.out_bytes) { b_bytes = dev_alloc(bd.units_out * unit); so.bytes = b_bytes.get(); }
+            if (b.out_offsets) { b_off = dev_alloc((m + 1) * in_off_w); so.offsets = b_off.get(); }
+            if (b.out_ids) { b_ids = dev_alloc(m * id_row); b_dst_ids = b_ids.get(); }
+            if (b.out_caps) { b_caps = dev_alloc(m * cap_slots * 4); b_dst_caps = b_caps.get(); }
+            if (kol) { b_kol = dev_alloc((n_keys + 1) * 8); kol = static_cast<uint64_t*>(b_kol.get()); }
+            if (kou) { b_kou = dev_alloc((n_keys + 1) * 8); kou = static_cast<uint64_t*>(b_kou.get()); }
+        }
+        if (b.out_ids) { so.col_src[0] = ids; so.col_dst[0] = b_dst_ids; so.col_width[0] = row_units; so.col_unit_bytes[0] = row_unit_bytes(fmt); }
+        if (b.out_caps) { so.col_src[1] = caps; so.col_dst[1] = b_dst_caps; so.col_width[1] = static_cast<uint32_t>(cap_slots); so.col_unit_bytes[1] = 4; }
+        if (m == 0) {
+            if (so.offsets) GX_HIP(hipMemsetAsync(so.offsets, 0, in_off_w, stream));
+            if (kol) GX_HIP(hipMemsetAsync(kol, 0, (n_keys + 1) * 8, stream));
+            if (kou) GX_HIP(hipMemsetAsync(kou, 0, (n_keys + 1) * 8, stream));
+        } else {
+            PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
+            GX_HIP(launch_by_key_sort(n, m, n_keys, by_key_passes(n_keys, bk->all_digits), w, bw, kol, kou, &pw.perm_sorted, stream));
+            pw.dst_off = bw.dst_off;
+            GX_HIP(launch_partition_copy(so, data, offsets, off64 ? 1 : 0, wide ? 1 : 0, n, m, pw, stream));
+        }
+    }
     if (rows_bytes) {
         if (sort && qd.candidates != 0) {
             const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, n_keys, gq_sorts_all_digits());
@@ -1919,6 +2001,16 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.key_lines && n_keys) GX_HIP(hipMemcpyAsync(out.key_lines, o.key_lines, n_keys * 8, hipMemcpyDeviceToHost, stream));
         if (out.key_stats && n_keys) GX_HIP(hipMemcpyAsync(out.key_stats, o.key_stats, n_keys * 64, hipMemcpyDeviceToHost, stream));
         if (out.line_key) GX_HIP(hipMemcpyAsync(out.line_key, o.line_key, n * 4, hipMemcpyDeviceToHost, stream));
+        if (bk_out) {
+            const gx_by_key_out& b = bk->out;
+            if (b.out_index && m) GX_HIP(hipMemcpyAsync(b.out_index, so.index, m * 4, hipMemcpyDeviceToHost, stream));
+            if (b.out_bytes && bd.units_out) GX_HIP(hipMemcpyAsync(b.out_bytes, so.bytes, bd.units_out * unit, hipMemcpyDeviceToHost, stream));
+            if (b.out_offsets) GX_HIP(hipMemcpyAsync(b.out_offsets, so.offsets, (m + 1) * in_off_w, hipMemcpyDeviceToHost, stream));
+            if (b.out_ids && m) GX_HIP(hipMemcpyAsync(b.out_ids, b_dst_ids, m * id_row, hipMemcpyDeviceToHost, stream));
+            if (b.out_caps && m) GX_HIP(hipMemcpyAsync(b.out_caps, b_dst_caps, m * cap_slots * 4, hipMemcpyDeviceToHost, stream));
+            if (b.key_out_lines) GX_HIP(hipMemcpyAsync(b.key_out_lines, kol, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
+            if (b.key_out_units) GX_HIP(hipMemcpyAsync(b.key_out_units, kou, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
+        }
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
@@ -1926,6 +2018,26 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         h->group_pending = true;
     }
     return GX_OK;
+}
+
+// what gx_lines_by_key adds to the refusals of gx_group_lines, behind them and before the look at the device
+static bool ranges_meet(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    if (!a || !b || !a_bytes || !b_bytes) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    // (a capacity may be "large enough": an end beyond the address space is the address space's)
+    const uintptr_t a1 = a_bytes > UINTPTR_MAX - a0 ? UINTPTR_MAX : a0 + static_cast<uintptr_t>(a_bytes);
+    const uintptr_t b1 = b_bytes > UINTPTR_MAX - b0 ? UINTPTR_MAX : b0 + static_cast<uintptr_t>(b_bytes);
+    return a0 < b1 && b0 < a1;
+}
+static void by_key_refusals(const ByKeyCall& bk, const std::string& name) {
+    if (bk.max_lines != 0 && bk.min_lines > bk.max_lines) throw GxError(GX_E_ARG, name + ": min_lines is above max_lines");
+}
+// outputs (pointer, capacity in bytes) against inputs (pointer, bytes known before the device is looked at)
+static void by_key_overlaps(const std::pair<const void*, uint64_t>* outs, size_t n_outs, const std::pair<const void*, uint64_t>* ins, size_t n_ins,
+                            const std::string& name) {
+    for (size_t a = 0; a < n_outs; ++a)
+        for (size_t b = 0; b < n_ins; ++b)
+            if (ranges_meet(outs[a].first, outs[a].second, ins[b].first, ins[b].second)) throw GxError(GX_E_ARG, name + ": an output overlaps an input");
 }
 
 // gx_top_groups: what the call adds to gx_group_lines' arguments
@@ -2093,7 +2205,7 @@ static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint
 static int group_lines_call(const std::string& name, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
                             const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
                             gx_group_totals* totals, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr) {
+                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr) {
     return guarded([&]() -> int {
         if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2107,6 +2219,12 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if (tg) tg_refusals(gi, *tg, name);
+        ByKeyCall bk;
+        if (by_key) {
+            bk = *by_key;
+            by_key_refusals(bk, name);
+            if (bk.out.out_caps && fmt != ROWS_DENSE) return fail(GX_E_ARG, name + ": out_caps on compact rows (out_ids holds whole rows)");
+        }
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
         if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the build pass
@@ -2114,8 +2232,22 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
             for (uint64_t i = 0; i < n; ++i)
                 if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be grouped");
         }
-        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (by_key) {
+            if (bk.out.out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
+            if (!slots) bk.out.out_caps = nullptr;
+            const uint64_t ow = o.offsets64 ? 8 : 4, un = o.utf16 ? 2 : 1, idr = static_cast<uint64_t>(row_units) * row_unit_bytes(fmt);
+            const uint64_t in_units = o.device_pointers ? (n ? 1u : 0u) : HostOffsets{offsets, o.offsets64 != 0, n}[n];
+            const gx_by_key_out& b = bk.out;
+            const uint64_t cap = std::min<uint64_t>(b.cap_lines, n);   // (no more than n lines leave, whatever the capacity says: n < 2^32, no product wraps)
+            const std::pair<const void*, uint64_t> outs[7] = {{b.out_index, cap * 4}, {b.out_bytes, b.out_bytes_cap}, {b.out_offsets, (cap + 1) * ow},
+                                                              {b.out_ids, cap * idr}, {b.out_caps, cap * slots * 4},
+                                                              {b.key_out_lines, (go.max_keys + 1) * 8}, {b.key_out_units, (go.max_keys + 1) * 8}};
+            const std::pair<const void*, uint64_t> ins[4] = {{bytes, in_units * un}, {offsets, (n + 1) * ow}, {ids, n * idr},
+                                                             {fmt == ROWS_DENSE ? caps : nullptr, n * slots * 4}};
+            by_key_overlaps(outs, 7, ins, 4, name);
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         if (fmt != ROWS_DENSE) caps = nullptr;
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
@@ -2142,7 +2274,7 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
             return top_groups_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi,
                                    go.max_keys, *tg, o.offsets64 != 0, !o.device_pointers, nullptr, stream, name);
         return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
-                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr);
+                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr, by_key ? &bk : nullptr);
     });
 }
 
@@ -2163,7 +2295,7 @@ int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uin
 static int text_group_call(const std::string& name, gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
                            const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts,
                            uint64_t* n_lines, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr) {
+                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr) {
     return guarded([&]() -> int {
         if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2175,6 +2307,14 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if (tg) tg_refusals(gi, *tg, name);
+        if (by_key) {
+            by_key_refusals(*by_key, name);
+            const gx_by_key_out& b = by_key->out;
+            const std::pair<const void*, uint64_t> outs[5] = {{b.out_bytes, b.out_bytes_cap}, {b.out_offsets, 4}, {b.out_index, 4}, {b.key_out_lines, (go.max_keys + 1) * 8},
+                                                              {b.key_out_units, (go.max_keys + 1) * 8}};
+            const std::pair<const void*, uint64_t> ins[1] = {{text, size}};
+            by_key_overlaps(outs, 5, ins, 1, name);
+        }
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
@@ -2196,7 +2336,7 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         const int rc = tg ? top_groups_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go.max_keys, *tg,
                                             o.offsets64 != 0, !o.device_pointers, counts, stream, name)
                           : group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
-                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr);
+                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr, by_key);
         // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
         // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
         // wait that delivered them was that already).
@@ -2220,6 +2360,40 @@ int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, co
                             gx_quantile_out* key_quantiles, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_quantiles", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, true, quantiles,
                            n_quantiles, key_quantiles);
+}
+
+// gx_lines_by_key's own arguments as gx_group_lines' callers take them: the flags without GX_BY_KEY_ALL_DIGITS (unknown bits stay in the
+// flags and are refused there), and &totals->group.
+static ByKeyCall by_key_call(uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_by_key_out* out, gx_by_key_totals* totals) {
+    ByKeyCall bk;
+    bk.min_lines = min_lines;
+    bk.max_lines = max_lines;
+    bk.all_digits = (flags & GX_BY_KEY_ALL_DIGITS) != 0u;
+    if (out) bk.out = *out;
+    bk.totals = totals;
+    return bk;
+}
+
+int gx_lines_by_key(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                    uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_group_out* keys,
+                    const gx_by_key_out* out, gx_by_key_totals* totals, const gx_batch_opts* opts) {
+    const ByKeyCall bk = by_key_call(min_lines, max_lines, flags, out, totals);
+    return group_lines_call("gx_lines_by_key", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
+                            totals ? &totals->group : nullptr, opts, false, nullptr, 0, nullptr, nullptr, &bk);
+}
+
+int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                         uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_group_out* keys, uint8_t* out, uint64_t out_cap, void* out_offsets,
+                         uint32_t* out_index, uint64_t* key_out_lines, uint64_t* key_out_units, gx_by_key_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                         const gx_batch_opts* opts) {
+    gx_by_key_out bo{};
+    bo.out_index = out_index; bo.out_bytes = out; bo.out_offsets = out_offsets;
+    bo.cap_lines = ~0ull;   // (sized by the size query: the header)
+    bo.out_bytes_cap = out_cap;
+    bo.key_out_lines = key_out_lines; bo.key_out_units = key_out_units;
+    const ByKeyCall bk = by_key_call(min_lines, max_lines, flags, &bo, totals);
+    return text_group_call("gx_text_lines_by_key", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, false, nullptr, 0, nullptr, nullptr, &bk);
 }
 
 // gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST, a gx_group_out that holds

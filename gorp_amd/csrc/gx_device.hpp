@@ -451,6 +451,33 @@ hipError_t launch_top_groups_emit(const void* ids, RowFormat fmt, uint32_t row_u
                                   const GroupWs& g, const TopGroupsWs& w, const TopGroupsOut& out, uint32_t n_top, uint64_t units_top,
                                   hipStream_t stream);
 
+// Every key's lines together (gx_by_key.hip; the rule: gx_by_key.hpp), behind gx_group_lines' passes on the same stream.  The passes'
+// device workspace, cut out of one allocation of by_key_workspace_bytes(n) bytes:
+struct ByKeyWs {
+    uint8_t* head;                // ByKeyDev (gx_by_key.hpp): the kept lines, their units, the kept keys
+    uint64_t* sums;               // the kept pass's workgroups' units and keys
+    uint32_t* slab;               // a digit's counts, bin-major
+    uint64_t* bases;              // ... scanned
+    uint64_t* block_sums;         // the scans'
+    uint64_t* before;             // [n + 1] the kept lines before line i; [n]: all of them
+    uint64_t* dst_off;            // [m + 1] code units before output line j (the same memory as `before`, behind the compaction)
+    uint32_t* knum[2];            // [n] the entries' key numbers, ping and pong
+    uint32_t* line[2];            // [n] their line numbers, likewise
+    uint32_t* len;                // [n] every line's code units
+    uint32_t* plen;               // [m] the same in output order
+    uint8_t* kept;                // [n] the line is kept
+    size_t bytes;
+};
+ByKeyWs by_key_workspace(void* ws, uint64_t n);
+size_t by_key_workspace_bytes(uint64_t n);
+// n > 0; g: launch_group_build's, behind it.  Behind this the host reads ByKeyDev at w.head.
+hipError_t launch_by_key_kept(uint64_t n, const void* offsets, int offsets64, const GroupWs& g, uint64_t min_lines, uint64_t max_lines, const ByKeyWs& w,
+                              hipStream_t stream);
+// Behind launch_group_emit (g.keynum).  0 < m <= n kept lines; key_out_lines / key_out_units: n_keys + 1 each on the device, optional.
+// Behind it the copy is launch_partition_copy with *perm and w.dst_off.
+hipError_t launch_by_key_sort(uint64_t n, uint64_t m, uint64_t n_keys, uint32_t n_passes, const GroupWs& g, const ByKeyWs& w, uint64_t* key_out_lines,
+                              uint64_t* key_out_units, uint32_t** perm, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

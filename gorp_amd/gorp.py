@@ -1254,6 +1254,139 @@ class Gorp:
         res["line_key"] = res["line_key"][:n_lines]
         return res, counts, n_lines
 
+    # -- every key's lines together (gx_lines_by_key / gx_text_lines_by_key) ------------------------------------------------------
+    @staticmethod
+    def _by_key_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(keys_kept=t.keys_kept, lines_out=t.lines_out, units_out=t.units_out)
+        return d
+
+    def lines_by_key_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, min_lines=1, max_lines=None, where=None, key_units_ptr=None,
+                            key_units_cap=0, key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0,
+                            out_index_ptr=None, out_data_ptr=None, out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0,
+                            key_out_lines_ptr=None, key_out_units_ptr=None, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True,
+                            utf8=False, weak_hash=False, all_digits=False):
+        """gx_lines_by_key on device pointers (ints): the lines whose key has min_lines .. max_lines lines (max_lines None: no upper
+        bound), ordered by (key number, input line), as a new CSR batch in the caller's buffers, each optional (none of the out_* and
+        key_out_*: the size query); the key_* / line_key / max_keys arguments are group_lines_device's and deliver what it would.
+        Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says what the outputs need (n_keys,
+        key_units, lines_out, units_out; exact False: the table overflowed, max_keys = n always suffices); every other error raises."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_by_key_out(out_index_ptr, out_data_ptr, out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap, key_out_lines_ptr, key_out_units_ptr)
+        totals = N.gx_by_key_totals()
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (N.GX_BY_KEY_ALL_DIGITS if all_digits else 0)
+        rc = N.lib().gx_lines_by_key(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, int(min_lines),
+                                     0 if max_lines is None else int(max_lines), flags, C.byref(keys), C.byref(out), C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._by_key_totals(totals)
+
+    def text_lines_by_key_device(self, text_ptr, size, parts, min_lines=1, max_lines=None, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                                 key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, out_ptr=None, out_cap=0,
+                                 out_offsets_ptr=None, out_index_ptr=None, key_out_lines_ptr=None, key_out_units_ptr=None, offsets64=False, stream=None,
+                                 device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_text_lines_by_key on a device buffer (int); outputs as lines_by_key_device takes them (out_offsets: uint32, out_index: line
+        numbers of the text, both sized by the size query).  Returns (rc, totals, counts, n_lines)."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        totals = N.gx_by_key_totals()
+        nl = C.c_uint64(0)
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (N.GX_BY_KEY_ALL_DIGITS if all_digits else 0)
+        rc = N.lib().gx_text_lines_by_key(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, int(min_lines),
+                                          0 if max_lines is None else int(max_lines), flags, C.byref(keys), out_ptr, out_cap, out_offsets_ptr, out_index_ptr,
+                                          key_out_lines_ptr, key_out_units_ptr, C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._by_key_totals(totals), counts, nl.value
+
+    def lines_by_key(self, data, offsets, match_id, caps, parts, min_lines=1, max_lines=None, where=None, utf8=None, keys="list", max_keys=None,
+                     key_units_cap=None, weak_hash=False, all_digits=False):
+        """gx_lines_by_key on host buffers: every kept key's lines together -- keys in order of their first line, lines in input order
+        inside each (Collectors.groupingBy on a captured text, insertion-ordered).  data / offsets / match_id (ids or compact rows) /
+        caps, parts, where, utf8, keys, max_keys as group_lines takes them; a key is kept when it has min_lines .. max_lines lines
+        (max_lines None: no upper bound; min_lines=1, max_lines=1: the keys with one line).  Returns group_lines' dict -- every key, kept
+        or not -- plus index (input line of every output line), data / offsets (the kept lines as a CSR batch), ids and caps (their ids
+        or whole rows; caps None for compact rows or without caps), key_out_lines / key_out_units (uint64[n_keys + 1]: key j's lines are
+        output lines key_out_lines[j] .. key_out_lines[j + 1]) and totals with keys_kept, lines_out, units_out besides group_lines'."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(match_id)
+        compact = self._ids_format(ids)
+        rows = None if caps is None or compact else np.ascontiguousarray(caps, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.group_parts(parts)
+        n = len(offsets) - 1
+        total = int(offsets[n] - offsets[0]) if n else 0
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+        got = {}
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            # no regrouping is larger than its input; the two prefixes are per key
+            got.update(index=np.zeros(n, np.uint32), data=np.zeros(total, data.dtype), offsets=np.zeros(n + 1, offsets.dtype), ids=np.zeros(ids.shape, ids.dtype),
+                       caps=None if rows is None else np.zeros((n, 2 * self.max_groups), np.int32), key_out_lines=np.zeros(mk + 1, np.uint64),
+                       key_out_units=np.zeros(mk + 1, np.uint64))
+            return self.lines_by_key_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(rows), parts, min_lines, max_lines, where, units, cap, koff, first, lines,
+                                            stats, line_key, mk, out_index_ptr=got["index"].ctypes.data, out_data_ptr=got["data"].ctypes.data,
+                                            out_offsets_ptr=got["offsets"].ctypes.data, out_ids_ptr=got["ids"].ctypes.data,
+                                            out_caps_ptr=None if got["caps"] is None else got["caps"].ctypes.data, cap_lines=n,
+                                            out_bytes_cap=total * data.itemsize, key_out_lines_ptr=got["key_out_lines"].ctypes.data,
+                                            key_out_units_ptr=got["key_out_units"].ctypes.data, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact,
+                                            device_pointers=False, utf8=bool(utf8), weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._group_host(call, n, parts, data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap)
+        res["line_key"] = res["line_key"][:n]
+        m, k = res["totals"]["lines_out"], res["totals"]["n_keys"]
+        res.update(index=got["index"][:m], data=got["data"][:res["totals"]["units_out"]], offsets=got["offsets"][:m + 1], ids=got["ids"][:m],
+                   caps=None if got["caps"] is None else got["caps"][:m], key_out_lines=got["key_out_lines"][:k + 1], key_out_units=got["key_out_units"][:k + 1])
+        return res
+
+    def text_lines_by_key(self, text, parts, min_lines=1, max_lines=None, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None):
+        """gx_text_lines_by_key on a host buffer: raw text -> lines -> extraction -> lines_by_key.  Returns (the dict lines_by_key returns
+        without ids and caps: data holds the kept lines' original bytes, offsets (uint32) delimits them, index holds line numbers of
+        the text; counts uint64[2K + 2] of outcomes; n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.group_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+        got = {}
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            got.update(index=np.zeros(cap_lines, np.uint32), data=np.zeros(raw.size, np.uint8), offsets=np.zeros(cap_lines + 1, np.uint32),
+                       key_out_lines=np.zeros(mk + 1, np.uint64), key_out_units=np.zeros(mk + 1, np.uint64))
+            return self.text_lines_by_key_device(raw.ctypes.data if raw.size else None, raw.size, parts, min_lines, max_lines, where, units, cap, koff, first, lines,
+                                                 stats, line_key, mk, out_ptr=got["data"].ctypes.data if raw.size else None, out_cap=raw.size,
+                                                 out_offsets_ptr=got["offsets"].ctypes.data, out_index_ptr=got["index"].ctypes.data,
+                                                 key_out_lines_ptr=got["key_out_lines"].ctypes.data, key_out_units_ptr=got["key_out_units"].ctypes.data,
+                                                 device_pointers=False, utf8=utf8)
+        res, (counts, n_lines) = self._group_host(call, cap_lines, parts, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
+        res["line_key"] = res["line_key"][:n_lines]
+        m, k = res["totals"]["lines_out"], res["totals"]["n_keys"]
+        res.update(index=got["index"][:m], data=got["data"][:res["totals"]["units_out"]], offsets=got["offsets"][:m + 1],
+                   key_out_lines=got["key_out_lines"][:k + 1], key_out_units=got["key_out_units"][:k + 1])
+        return res, counts, n_lines
+
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
     def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
                                key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,

@@ -447,6 +447,81 @@ public:
         if (nLines) *nLines = lines;
         return g;
     }
+    // Every key's lines together (gx_lines_by_key): the caller's byRequest.computeIfAbsent(r.asMap().get("requestId"), k -> new
+    // ArrayList<>()).add(line) (README.md:26,63-79).  groupLines' result for every key, kept or not, plus the lines of the keys that have
+    // minLines .. maxLines lines (maxLines 0: no upper bound; 1, 1: the keys with a single line) as a new batch ordered by (key number,
+    // input line): key j's lines are the output lines keyOutLines[j] .. keyOutLines[j + 1], its bytes bytes[keyOutUnits[j] ..
+    // keyOutUnits[j + 1]).  ids / caps: the kept lines' match ids and capture rows (textLinesByKey: empty; index holds lines of the text).
+    struct LinesByKey : Groups {
+        std::vector<uint32_t> index;
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> offsets;
+        std::vector<int32_t> ids, caps;
+        std::vector<uint64_t> keyOutLines, keyOutUnits;
+        gx_by_key_totals byKey{};
+    };
+    LinesByKey linesByKey(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const GroupParts& parts,
+                          uint64_t minLines = 1, uint64_t maxLines = 0, const Where* where = nullptr) const {
+        LinesByKey r;
+        const size_t slots = 2 * static_cast<size_t>(gx_max_groups(h_));
+        Groups g = groupsOf(parts, where, &n, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out, gx_group_totals* totals) {
+            gx_by_key_out b{};
+            const bool deliver = out->key_offsets != nullptr;   // (the size query before it left the sizes in r.byKey)
+            if (deliver) {
+                const size_t m = static_cast<size_t>(r.byKey.lines_out);
+                r.index.assign(m, 0);
+                r.bytes.assign(static_cast<size_t>(r.byKey.units_out) + 1, 0);
+                r.offsets.assign(m + 1, 0);
+                r.ids.assign(m, 0);
+                r.caps.assign(m * slots + 1, 0);
+                r.keyOutLines.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+                r.keyOutUnits.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+                b.out_index = r.index.data(); b.out_bytes = r.bytes.data(); b.out_offsets = r.offsets.data(); b.out_ids = r.ids.data();
+                b.out_caps = caps && slots ? r.caps.data() : nullptr;
+                b.cap_lines = m; b.out_bytes_cap = r.byKey.units_out;
+                b.key_out_lines = r.keyOutLines.data(); b.key_out_units = r.keyOutUnits.data();
+            }
+            const int rc = gx_lines_by_key(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, minLines, maxLines, 0, out, deliver ? &b : nullptr, &r.byKey, nullptr);
+            *totals = r.byKey.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        r.bytes.resize(static_cast<size_t>(r.byKey.units_out));
+        r.caps.resize(caps ? r.index.size() * slots : 0);
+        return r;
+    }
+    // Whole files: raw text in, the same regrouping out (gx_text_lines_by_key); bytes holds the kept lines' original bytes, cut at offsets.
+    LinesByKey textLinesByKey(const std::string& text, const GroupParts& parts, uint64_t minLines = 1, uint64_t maxLines = 0, const Where* where = nullptr,
+                              std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        LinesByKey r;
+        Groups g = groupsOf(parts, where, &lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                      gx_group_totals* totals) {
+            const bool deliver = out->key_offsets != nullptr;
+            if (deliver) {
+                r.index.assign(static_cast<size_t>(r.byKey.lines_out), 0);
+                r.bytes.assign(static_cast<size_t>(r.byKey.units_out) + 1, 0);
+                r.offsets.assign(static_cast<size_t>(r.byKey.lines_out) + 1, 0);
+                r.keyOutLines.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+                r.keyOutUnits.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+            }
+            const uint64_t cap = r.byKey.units_out;
+            const int rc = gx_text_lines_by_key(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, minLines, maxLines, 0, out,
+                                                deliver ? r.bytes.data() : nullptr, cap, deliver ? r.offsets.data() : nullptr, deliver ? r.index.data() : nullptr,
+                                                deliver ? r.keyOutLines.data() : nullptr, deliver ? r.keyOutUnits.data() : nullptr, &r.byKey,
+                                                counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+            *totals = r.byKey.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        r.bytes.resize(static_cast<size_t>(r.byKey.units_out));
+        if (nLines) *nLines = lines;
+        return r;
+    }
     // Lines ranked by a number they captured (gx_top_lines): the parts of a call, built by name.  topParts().of("GetRequest",
     // "timeTakenInMsec").of("OtherRequest", "timeTakenInMsec") with topLines(..., 10) is the caller's "which requests were the slowest?",
     // sorted(results, by timeTakenInMsec).take(10) (README.md:26,63-79).  Names resolve as Where's do; one part per extraction; all

@@ -743,6 +743,84 @@ int gx_partition_lines(gx_handle* h, const void* bytes, const void* offsets, uin
                        uint64_t cap_lines, uint64_t out_bytes_cap, uint64_t* group_lines, uint64_t* group_units, uint64_t* n_out,
                        uint64_t* bytes_out, const gx_batch_opts* opts);
 
+/* Every key's lines together.  The reference caller's remaining everyday move on a captured text (README.md:26,63-79) is
+ *     r = gorp.extract(line);
+ *     if (r != null) byRequest.computeIfAbsent(r.asMap().get("requestId"), k -> new ArrayList<>()).add(line);
+ * -- Collectors.groupingBy on a captured text: every request's, session's or trace's lines together, in the order they were logged; the
+ * keys with exactly one line are the requests that have a start line and no end line.  gx_group_lines gets as far as line_key; this call
+ * does the regrouping on the device, as gx_partition_lines does it by outcome.
+ * INHERITED from gx_group_lines, and nothing of it is reinterpreted: keys, parts and terms, which lines count, key equality and the one
+ * key space, the key numbers (order of first line), max_keys sizing the table.  `keys` is gx_group_lines' own output struct and delivers
+ * exactly what that call would, for every key, kept or not.
+ * KEPT: key j is kept when max(min_lines, 1) <= key_lines[j], and either max_lines == 0 or key_lines[j] <= max_lines.  A line is kept when
+ * it has a key and that key is kept.
+ * ORDER: the kept lines leave ordered by (key number, input line number) -- sessions in order of their first line, lines in input order
+ * inside each: what a LinkedHashMap<String, List<String>> filled line by line holds.  A key that is not kept is an empty range in the two
+ * prefix arrays; key_out_lines[n_keys] == lines_out.
+ * COPIES: each line is copied as gx_select_lines copies one: units exactly, terminator included.  out_ids and out_caps hold the lines'
+ * ids or whole result rows in the input's format, so the result is an ordinary batch for every other call.
+ * EXACT: every output is exact and the same bits on every run: ranks come from ballots and scans, and no output depends on wave timing. */
+#define GX_BY_KEY_ALL_DIGITS 2u   /* test hook, accepted beside GX_GROUP_WEAK_HASH (1u): sort all five key-number digits whatever n_keys is;
+                                     results identical, only slower */
+
+typedef struct gx_by_key_out {    /* every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* out_index;          /* gx_partition_lines' five outputs, same meaning, same formats: the kept lines as a new CSR batch */
+    void*     out_bytes;
+    void*     out_offsets;
+    void*     out_ids;
+    int32_t*  out_caps;
+    uint64_t  cap_lines, out_bytes_cap;
+    uint64_t* key_out_lines;      /* keys->max_keys + 1: exclusive prefix; key j's lines are output lines [key_out_lines[j], key_out_lines[j+1]) */
+    uint64_t* key_out_units;      /* the same in code units of out_bytes (out_offsets read at those lines) */
+} gx_by_key_out;
+
+typedef struct gx_by_key_totals { /* host, always */
+    gx_group_totals group;        /* exactly what gx_group_lines reports for the same call */
+    uint64_t keys_kept, lines_out, units_out;
+} gx_by_key_totals;
+
+/* gx_lines_by_key: the batch is read exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16;
+ * utf8 = 1; staging or device_pointers; the stream).  cap_lines is the capacity of out_index, out_ids, out_caps (lines) and out_offsets
+ * (cap_lines + 1, the width of the input's offsets); out_bytes_cap is in BYTES, with utf16 too.  key_out_lines and key_out_units hold
+ * n_keys + 1 entries each and are sized by keys->max_keys + 1 (keys == NULL: max_keys 0).
+ * HOST WAITS: ONE host wait before any output -- the wait in which gx_group_lines reads its totals also reads keys_kept, lines_out and
+ * units_out, computed by a pass behind the build on the same stream from the per-slot line counts of the table and the lengths in the
+ * offsets.  With host outputs a second wait delivers them.  With device_pointers the passes (compaction, a stable radix sort of the kept
+ * lines by key number with ceil(bits(n_keys - 1) / 6) six-bit digits -- none for one key, five for 2^30 keys --, scan, copy) are left
+ * running on opts->stream when the call returns, as gx_group_lines leaves its emit; the handle's next group call on another stream
+ * waits for them, and the batch must stay unchanged until they have run.
+ * SIZE QUERY: all of out's pointers NULL, or out == NULL: only *totals is delivered, and with `keys` whatever gx_group_lines would
+ * deliver.
+ * GX_E_LIMIT: cap_lines < lines_out (with any per-line output), out_bytes_cap too small, key_out_lines / key_out_units with n_keys >
+ * keys->max_keys, 32-bit out_offsets with 2^32 units and more: no output of out and none of keys is written, and *totals is filled;
+ * and gx_group_lines' own limits, including the overflowed table with group.exact = 0.
+ * GX_E_ARG: every refusal gx_group_lines makes; max_lines != 0 && min_lines > max_lines; unknown flag bits; totals == NULL; no_sync;
+ * utf8 = 2; out_caps on compact rows; an output overlapping an input (an output's capacity in bytes -- of at most n lines, whatever cap_lines says -- against bytes, offsets, ids and
+ * caps; of device bytes only the first unit is known before the device is looked at).  All of these come before the device is looked
+ * at: a host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).  n == 0 and n_parts == 0 are legal and give all
+ * zeros (out_offsets and the two prefix arrays: their one entry).  With lines_out == 0 out_offsets[0] = 0, the two prefix arrays are all
+ * zeros and nothing else is written.
+ * The device workspace stays on the handle, a buffer of its own beside gx_group_lines': 33 bytes per INPUT line (the scan of the kept
+ * flags, later the destination offsets 8; two key-number and two line-number arrays of the sort 16; the lengths by line and in output
+ * order 8; the flags 1) plus 768 bytes of counts per 2 048 lines, until gx_destroy. */
+int gx_lines_by_key(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                    const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint64_t min_lines,
+                    uint64_t max_lines, uint32_t flags, const gx_group_out* keys, const gx_by_key_out* out, gx_by_key_totals* totals,
+                    const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the regrouping at its end: raw text -> lines -> the match-and-extract path ->
+ * the regrouping.  out (out_cap bytes) receives the kept lines' original bytes one behind the other, as gx_text_select writes them;
+ * out_offsets (optional, lines_out + 1 entries, uint32 whatever opts->offsets64 says: the text is below 4 GiB) delimits them -- a last line of the text without a
+ * terminator is copied as it is and may now lie in the middle, so the output is cut at out_offsets, not at line ends; out_index
+ * (optional, lines_out entries) holds line numbers of the text.  out_offsets and out_index are sized by the size query (out, out_offsets,
+ * out_index, key_out_lines and key_out_units all NULL); *n_lines entries (+ 1) always suffice.  counts and *n_lines as
+ * gx_text_group_lines delivers them.  Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                         const gx_where_term* terms, uint32_t n_terms, uint64_t min_lines, uint64_t max_lines, uint32_t flags,
+                         const gx_group_out* keys, uint8_t* out, uint64_t out_cap, void* out_offsets, uint32_t* out_index,
+                         uint64_t* key_out_lines, uint64_t* key_out_units, gx_by_key_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                         const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
