@@ -54,6 +54,7 @@ SYMBOLS = [
     "gx_group_quantiles", "gx_text_group_quantiles",
     "gx_top_groups", "gx_text_top_groups",
     "gx_lines_by_key", "gx_text_lines_by_key",
+    "gx_group_pairs", "gx_text_group_pairs",
 ]
 
 
@@ -155,6 +156,16 @@ class gx_by_key_out(C.Structure):
 
 class gx_by_key_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("keys_kept", C.c_uint64), ("lines_out", C.c_uint64), ("units_out", C.c_uint64)]
+
+
+class gx_pairs_out(C.Structure):
+    _fields_ = [("pair_units", C.c_void_p), ("pair_units_cap", C.c_uint64), ("pair_offsets", C.c_void_p), ("pair_key", C.c_void_p),
+                ("pair_first_line", C.c_void_p), ("pair_lines", C.c_void_p), ("key_pairs", C.c_void_p), ("line_pair", C.c_void_p), ("max_pairs", C.c_uint64)]
+
+
+class gx_pairs_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("n_pairs", C.c_uint64), ("pair_units", C.c_uint64), ("paired", C.c_uint64), ("unpaired", C.c_uint64),
+                ("pairs_exact", C.c_uint64)]
 
 
 class gx_device_shard(C.Structure):
@@ -365,6 +376,14 @@ def lib():
                                        C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(gx_group_out), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(gx_by_key_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_lines_by_key.restype = C.c_int
+    L.gx_group_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
+                                 C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_pairs_out), C.POINTER(gx_pairs_totals),
+                                 C.POINTER(gx_batch_opts)]
+    L.gx_group_pairs.restype = C.c_int
+    L.gx_text_group_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(gx_where_term),
+                                      C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_pairs_out), C.POINTER(gx_pairs_totals), C.c_void_p,
+                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_pairs.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -23,6 +23,7 @@
 #include "gx_dsl.hpp"
 #include "gx_group.hpp"
 #include "gx_group_quantile.hpp"
+#include "gx_pairs.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
@@ -281,6 +282,9 @@ struct gx_handle {
     GrowBuf tg_ws;
     // gx_lines_by_key behind gx_group_lines' build and emit: its workspace (gx_by_key.hip), covered by group_event too
     GrowBuf by_key_ws;
+    // gx_group_pairs behind gx_group_lines' build: its second groups (PairsHead, gx_pairs.hpp), the pair slots' words and the per-line
+    // arrays (gx_pairs.hip), covered by group_event too
+    GrowBuf pairs_image, pairs_table, pairs_lines;
     Event group_event;
     bool group_pending = false;
     // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
@@ -1818,12 +1822,26 @@ struct ByKeyCall {
     bool per_line() const { return out.out_index || out.out_offsets || out.out_ids || out.out_caps; }
     bool any() const { return per_line() || out.out_bytes || out.key_out_lines || out.key_out_units; }
 };
+// pc (gx_group_pairs; nullptr: gx_group_lines as it is): behind the build the pair table's build, flags and scans (launch_pairs_build),
+// whose totals, pairs and units are read in the same wait; behind the emit, which numbers the key slots, the pair emit.
+struct PairsCall {
+    PairsHead head{};                  // the second group per entry of GroupHead::ext[]
+    bool any_second = false;
+    gx_pairs_out out{};
+    gx_pairs_totals* totals = nullptr;   // (its group member is the gx_group_totals the pass fills)
+    bool per_pair() const { return out.pair_offsets || out.pair_key || out.pair_first_line || out.pair_lines; }
+    bool any() const { return per_pair() || out.pair_units || out.key_pairs || out.line_pair; }
+};
 static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
                       const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
                       gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupQuant* gq = nullptr,
-                      const ByKeyCall* bk = nullptr) {
+                      const ByKeyCall* bk = nullptr, const PairsCall* pc = nullptr) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
     if (bk) *bk->totals = gx_by_key_totals{};
+    if (pc) {
+        *pc->totals = gx_pairs_totals{};
+        pc->totals->pairs_exact = 1;
+    }
     if (counts) {
         if (h->select_pending) {
             GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
@@ -1839,7 +1857,8 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     gx_quantile_out* q_rows = gq && gq->qh.n_q ? gq->rows : nullptr;
     const uint32_t n_q = q_rows ? gq->qh.n_q : 0u;
     const bool bk_out = bk && bk->any();
-    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out;
+    const bool pc_out = pc && pc->any();
+    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out || pc_out;
     if (!run) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -1859,6 +1878,16 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
                 if (!one[q]) continue;
                 if (host_out) memcpy(one[q], &zero, width[q]);
                 else GX_HIP(hipMemsetAsync(one[q], 0, width[q], stream));
+            }
+        }
+        if (pc_out) {   // no pairs: the offsets' one entry and every line's "none"
+            if (pc->out.pair_offsets) {
+                if (host_out) memcpy(pc->out.pair_offsets, &zero, out64 ? 8 : 4);
+                else GX_HIP(hipMemsetAsync(pc->out.pair_offsets, 0, out64 ? 8 : 4, stream));
+            }
+            if (pc->out.line_pair && n) {
+                if (host_out) memset(pc->out.line_pair, 0xFF, n * 4);
+                else GX_HIP(hipMemsetAsync(pc->out.line_pair, 0xFF, n * 4, stream));
             }
         }
         return GX_OK;
@@ -1900,6 +1929,21 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         GX_HIP(launch_by_key_kept(n, offsets, off64 ? 1 : 0, w, bk->min_lines, bk->max_lines, bw, stream));
         GX_HIP(hipMemcpyAsync(&bd, bw.head, sizeof(ByKeyDev), hipMemcpyDeviceToHost, stream));
     }
+    // the pairs of gx_group_pairs: a second table keyed by (key slot, second text), behind the build that has left slot_of[] complete
+    PairsWs pw{};
+    PairsDev pd{};
+    uint64_t n_pairs = 0, pair_units = 0;
+    uint8_t* d_pimg = nullptr;
+    if (pc) {
+        const uint32_t p_slots = group_slots(pc->out.max_pairs);
+        d_pimg = static_cast<uint8_t*>(h->pairs_image.get(sizeof(PairsHead)));
+        GX_HIP(hipMemcpyAsync(d_pimg, &pc->head, sizeof(PairsHead), hipMemcpyHostToDevice, stream));
+        pw = pairs_workspace(h->pairs_table.get(pairs_table_bytes(p_slots, n_slots)), h->pairs_lines.get(pairs_lines_bytes(n)), n, p_slots, n_slots);
+        GX_HIP(launch_pairs_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_pimg, w, pw, stream));
+        GX_HIP(hipMemcpyAsync(&pd, pw.totals, sizeof(PairsDev), hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&n_pairs, pw.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&pair_units, pw.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    }
     uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
     GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
     GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -1922,6 +1966,18 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         bk->totals->lines_out = bd.lines_out;
         bk->totals->units_out = bd.units_out;
     }
+    if (pc) {
+        if (pd.paired + pd.unpaired != totals->keyed) throw GxError(GX_E_ARG, "internal: " + name + ": paired and unpaired lines do not add up to the keyed lines");
+        pc->totals->paired = pd.paired;
+        pc->totals->unpaired = pd.unpaired;
+        pc->totals->n_pairs = n_pairs;
+        pc->totals->pair_units = pair_units;
+        if (pd.status & 2u) {
+            pc->totals->pairs_exact = 0;
+            pc->totals->n_pairs = static_cast<uint64_t>(pw.n_slots) + 1u;
+            return fail(GX_E_LIMIT, name + ": the pair table of " + std::to_string(pw.n_slots) + " slots is full; the number of lines is always a sufficient max_pairs");
+        }
+    }
     if (!any_out) return GX_OK;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || q_rows;
     if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
@@ -1936,6 +1992,14 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (b.out_offsets && !off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
         if ((b.key_out_lines || b.key_out_units) && n_keys > out.max_keys)
             return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
+    }
+    if (pc_out) {
+        const gx_pairs_out& b = pc->out;
+        if (pc->per_pair() && n_pairs > b.max_pairs) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_pairs) + " pairs, max_pairs " + std::to_string(b.max_pairs));
+        if (b.pair_units && pair_units > b.pair_units_cap)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(pair_units) + " pair units, pair_units_cap " + std::to_string(b.pair_units_cap));
+        if (b.pair_offsets && !out64 && pair_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G pair units and more need offsets64");
+        if (b.key_pairs && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
     }
     GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
     DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey, d_rows;
@@ -1985,6 +2049,23 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
             GX_HIP(launch_partition_copy(so, data, offsets, off64 ? 1 : 0, wide ? 1 : 0, n, m, pw, stream));
         }
     }
+    // gx_group_pairs: the pairs' rows, their seconds, the keys' pairs and the lines' pair numbers
+    PairsOut po{};
+    DevMem<> p_units, p_offs, p_key, p_first, p_lines, p_kp, p_lp;
+    if (pc_out) {
+        const gx_pairs_out& b = pc->out;
+        po = PairsOut{b.pair_units, b.pair_offsets, b.pair_key, b.pair_first_line, b.pair_lines, b.key_pairs, b.line_pair, out64 ? 1 : 0};
+        if (host_out) {
+            if (b.pair_units) { p_units = dev_alloc(pair_units * unit); po.pair_units = p_units.get(); }
+            if (b.pair_offsets) { p_offs = dev_alloc((n_pairs + 1) * off_w); po.pair_offsets = p_offs.get(); }
+            if (b.pair_key) { p_key = dev_alloc(n_pairs * 4); po.pair_key = static_cast<uint32_t*>(p_key.get()); }
+            if (b.pair_first_line) { p_first = dev_alloc(n_pairs * 4); po.pair_first_line = static_cast<uint32_t*>(p_first.get()); }
+            if (b.pair_lines) { p_lines = dev_alloc(n_pairs * 8); po.pair_lines = static_cast<uint64_t*>(p_lines.get()); }
+            if (b.key_pairs) { p_kp = dev_alloc(n_keys * 8); po.key_pairs = static_cast<uint64_t*>(p_kp.get()); }
+            if (b.line_pair) { p_lp = dev_alloc(n * 4); po.line_pair = static_cast<uint32_t*>(p_lp.get()); }
+        }
+        GX_HIP(launch_pairs_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_pimg, w, pw, po, n_pairs, pair_units, n_keys, stream));
+    }
     if (rows_bytes) {
         if (sort && qd.candidates != 0) {
             const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, n_keys, gq_sorts_all_digits());
@@ -2011,6 +2092,16 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
             if (b.key_out_lines) GX_HIP(hipMemcpyAsync(b.key_out_lines, kol, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
             if (b.key_out_units) GX_HIP(hipMemcpyAsync(b.key_out_units, kou, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
         }
+        if (pc_out) {
+            const gx_pairs_out& b = pc->out;
+            if (b.pair_units && pair_units) GX_HIP(hipMemcpyAsync(b.pair_units, po.pair_units, pair_units * unit, hipMemcpyDeviceToHost, stream));
+            if (b.pair_offsets) GX_HIP(hipMemcpyAsync(b.pair_offsets, po.pair_offsets, (n_pairs + 1) * off_w, hipMemcpyDeviceToHost, stream));
+            if (b.pair_key && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_key, po.pair_key, n_pairs * 4, hipMemcpyDeviceToHost, stream));
+            if (b.pair_first_line && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_first_line, po.pair_first_line, n_pairs * 4, hipMemcpyDeviceToHost, stream));
+            if (b.pair_lines && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_lines, po.pair_lines, n_pairs * 8, hipMemcpyDeviceToHost, stream));
+            if (b.key_pairs && n_keys) GX_HIP(hipMemcpyAsync(b.key_pairs, po.key_pairs, n_keys * 8, hipMemcpyDeviceToHost, stream));
+            if (b.line_pair) GX_HIP(hipMemcpyAsync(b.line_pair, po.line_pair, n * 4, hipMemcpyDeviceToHost, stream));
+        }
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
@@ -2018,6 +2109,25 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         h->group_pending = true;
     }
     return GX_OK;
+}
+
+// what gx_group_pairs adds to the refusals of gx_group_lines, behind them and before the look at the device: the second groups, checked
+// against the handle and laid out by GroupHead::ext[] (gi: group_refusals')
+static void pairs_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const int32_t* second_groups,
+                           const gx_pairs_out* out, const std::string& name, PairsCall* pc) {
+    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) pc->head.second[q] = PAIRS_NO_SECOND;
+    if (out) pc->out = *out;
+    if (n_parts && !second_groups) throw GxError(GX_E_ARG, name + ": second_groups is NULL");
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const int32_t sg = second_groups[t];
+        if (sg < -1 || sg >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's second group is neither -1 nor one of its extraction's");
+        if (sg < 0) continue;
+        pc->any_second = true;
+        for (uint32_t q = 0; q < gi.head.n_parts; ++q)
+            if (gi.head.ext[q] == static_cast<uint32_t>(parts[t].extraction)) pc->head.second[q] = sg;
+    }
+    if (n_parts && !pc->any_second && pc->any()) throw GxError(GX_E_ARG, name + ": pair outputs while every part's second group is -1");
+    if (pc->out.max_pairs > PAIRS_MAX_PAIRS) throw GxError(GX_E_LIMIT, name + ": max_pairs above 2^30");
 }
 
 // what gx_lines_by_key adds to the refusals of gx_group_lines, behind them and before the look at the device
@@ -2205,7 +2315,8 @@ static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint
 static int group_lines_call(const std::string& name, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
                             const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
                             gx_group_totals* totals, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr) {
+                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr, PairsCall* pairs = nullptr,
+                            const int32_t* second_groups = nullptr, const gx_pairs_out* pairs_out = nullptr) {
     return guarded([&]() -> int {
         if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2219,6 +2330,7 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if (tg) tg_refusals(gi, *tg, name);
+        if (pairs) pairs_refusals(h, gi, parts, n_parts, second_groups, pairs_out, name, pairs);
         ByKeyCall bk;
         if (by_key) {
             bk = *by_key;
@@ -2274,7 +2386,7 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
             return top_groups_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi,
                                    go.max_keys, *tg, o.offsets64 != 0, !o.device_pointers, nullptr, stream, name);
         return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
-                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr, by_key ? &bk : nullptr);
+                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr, by_key ? &bk : nullptr, pairs_out ? pairs : nullptr);
     });
 }
 
@@ -2295,7 +2407,8 @@ int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uin
 static int text_group_call(const std::string& name, gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
                            const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts,
                            uint64_t* n_lines, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr) {
+                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr, PairsCall* pairs = nullptr,
+                           const int32_t* second_groups = nullptr, const gx_pairs_out* pairs_out = nullptr) {
     return guarded([&]() -> int {
         if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2307,6 +2420,7 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         GroupQuant gq;
         if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
         if (tg) tg_refusals(gi, *tg, name);
+        if (pairs) pairs_refusals(h, gi, parts, n_parts, second_groups, pairs_out, name, pairs);
         if (by_key) {
             by_key_refusals(*by_key, name);
             const gx_by_key_out& b = by_key->out;
@@ -2336,7 +2450,7 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         const int rc = tg ? top_groups_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go.max_keys, *tg,
                                             o.offsets64 != 0, !o.device_pointers, counts, stream, name)
                           : group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
-                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr, by_key);
+                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr, by_key, pairs_out ? pairs : nullptr);
         // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
         // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
         // wait that delivered them was that already).
@@ -2394,6 +2508,33 @@ int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const
     const ByKeyCall bk = by_key_call(min_lines, max_lines, flags, &bo, totals);
     return text_group_call("gx_text_lines_by_key", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
                            totals ? &totals->group : nullptr, counts, n_lines, opts, false, nullptr, 0, nullptr, nullptr, &bk);
+}
+
+// gx_group_pairs: gx_group_lines' call with the pairs behind it.  totals == NULL is refused as gx_group_lines refuses it.
+int gx_group_pairs(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                   uint32_t n_parts, const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
+                   const gx_pairs_out* pairs, gx_pairs_totals* totals, const gx_batch_opts* opts) {
+    PairsCall pc;
+    pc.totals = totals;
+    if (totals) {
+        *totals = gx_pairs_totals{};
+        totals->pairs_exact = 1;
+    }
+    return group_lines_call("gx_group_pairs", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, opts, false,
+                            nullptr, 0, nullptr, nullptr, nullptr, &pc, second_groups, pairs);
+}
+
+int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* second_groups,
+                        const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_pairs_out* pairs, gx_pairs_totals* totals,
+                        uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    PairsCall pc;
+    pc.totals = totals;
+    if (totals) {
+        *totals = gx_pairs_totals{};
+        totals->pairs_exact = 1;
+    }
+    return text_group_call("gx_text_group_pairs", h, text, size, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, counts, n_lines, opts,
+                           false, nullptr, 0, nullptr, nullptr, nullptr, &pc, second_groups, pairs);
 }
 
 // gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST, a gx_group_out that holds

@@ -321,6 +321,49 @@ hipError_t launch_group_build(const void* ids, RowFormat fmt, uint32_t row_units
 hipError_t launch_group_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
                              const GroupWs& w, const GroupOut& out, uint64_t n_keys, uint64_t key_units, hipStream_t stream);
 
+// The lines of a finished batch grouped by TWO captured texts (gx_pairs.hip; the rule: gx_pairs.hpp), behind gx_group_lines' passes on
+// the same stream: a second table keyed by (key slot, second text).  The passes' device workspace: the pair slots' words
+// (pairs_table_bytes) and the per-line arrays (pairs_lines_bytes).
+struct PairsWs {
+    uint32_t n_slots;             // pair slots, a power of two
+    uint32_t n_key_slots;         // GroupWs::n_slots
+    uint64_t* table;              // [n_slots] the pair slot words
+    uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS]: lines, first line
+    uint64_t* kpairs;             // [n_key_slots] the pairs of the key slot
+    uint64_t* totals;             // [8] PairsDev
+    uint32_t* pairnum;            // [n_slots] the pair slot's pair number, written by the emit pass
+    uint64_t* idx_off;            // [n + 1] first-of-pair lines before line i; [n]: the pairs
+    uint64_t* dst_off;            // [n + 1] second units before line i's; [n]: all of them
+    uint64_t *sums_a, *sums_b;    // the scans'
+    uint32_t* pslot_of;           // [n] the line's pair slot, GROUP_NONE: it is not paired
+    uint32_t* plen;               // [n] the second's units where the line is its pair's first, else 0
+    uint8_t* flags;               // [n] the line is its pair's first
+};
+// what the pair emit writes, each part optional (nullptr)
+struct PairsOut {
+    void* pair_units;
+    void* pair_offsets;
+    uint32_t* pair_key;
+    uint32_t* pair_first_line;
+    uint64_t* pair_lines;
+    uint64_t* key_pairs;
+    uint32_t* line_pair;
+    int offsets64;                // pair_offsets: uint64, else uint32
+};
+size_t pairs_table_zero_bytes(uint32_t n_slots, uint32_t n_key_slots);
+size_t pairs_table_bytes(uint32_t n_slots, uint32_t n_key_slots);
+size_t pairs_lines_bytes(uint64_t n);
+PairsWs pairs_workspace(void* table_mem, void* lines_mem, uint64_t n, uint32_t n_slots, uint32_t n_key_slots);
+// n > 0, parts > 0, behind launch_group_build (g.slot_of); pairs_image: a PairsHead on the device, 16-byte aligned.  Build, flags and
+// the two scans; behind them the host reads w.totals, w.idx_off[n], w.dst_off[n].
+hipError_t launch_pairs_build(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                              const void* pairs_image, const GroupWs& g, const PairsWs& w, hipStream_t stream);
+// Behind launch_group_emit (g.keynum) and the host's check of the capacities: n_pairs <= the per-pair arrays' capacity, pair_units <=
+// pair_units' capacity, n_keys <= key_pairs' capacity.
+hipError_t launch_pairs_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                             const void* pairs_image, const GroupWs& g, const PairsWs& w, const PairsOut& out, uint64_t n_pairs, uint64_t pair_units,
+                             uint64_t n_keys, hipStream_t stream);
+
 // The lines of a finished batch ranked by a number they captured (gx_top.hip; the rule: gx_top.hpp): the n_wanted largest (or smallest)
 // numbers' lines, ordered by (value, input line).
 struct TopArgs {

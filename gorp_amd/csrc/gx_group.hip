@@ -64,31 +64,6 @@ __device__ __forceinline__ void group_add(u64* head, u64* stats, bool values, co
     }
 }
 
-// The entry of `slot` in the workgroup's LDS table (keys[GROUP_LDS_ENTRIES], GROUP_NONE: free), inserted if it is new and the table
-// still takes keys; GROUP_NONE: the table is full, add to global memory.  At most GROUP_LDS_KEYS entries are ever claimed (a claim is
-// reserved in *used first), so a free entry ends every probe sequence and the loop is bounded by the table besides.
-__device__ __forceinline__ uint32_t group_lds_entry(uint32_t* keys, uint32_t* used, uint32_t slot) {
-    uint32_t e = (slot * 0x9E3779B1u) >> (32u - GROUP_LDS_BITS);
-    bool reserved = false;
-    for (uint32_t probe = 0; probe < GROUP_LDS_ENTRIES; ++probe) {
-        uint32_t k = __hip_atomic_load(keys + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == slot) return e;
-        if (k == GROUP_NONE) {
-            if (!reserved) {
-                if (__hip_atomic_load(used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= GROUP_LDS_KEYS) return GROUP_NONE;
-                if (atomicAdd(used, 1u) >= GROUP_LDS_KEYS) return GROUP_NONE;
-                reserved = true;
-            }
-            k = atomicCAS(keys + e, GROUP_NONE, slot);
-            // (k == slot: another wave claimed this very slot's entry meanwhile.  The reservation is not handed back, so the table may
-            // refuse new slots a little before it holds GROUP_LDS_KEYS; those add to global memory directly -- capacity, never results.)
-            if (k == GROUP_NONE || k == slot) return e;
-        }
-        e = (e + 1u) & (GROUP_LDS_ENTRIES - 1u);
-    }
-    return GROUP_NONE;
-}
-
 // LDS: GroupHead, the term image (wimage_bytes, 0: no terms), then keys[GROUP_LDS_ENTRIES], 4 words (used, spare), 4 totals (64-bit),
 // and GROUP_LDS_ENTRIES x (GROUP_HEAD_WORDS + GROUP_STATS_WORDS) 64-bit words.
 // totals[0..3]: lines that count, lines whose key pair names no value, status bits (1: a line of 4 G units, 2: the table is full).

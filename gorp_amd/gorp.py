@@ -1387,6 +1387,158 @@ class Gorp:
                    key_out_lines=got["key_out_lines"][:k + 1], key_out_units=got["key_out_units"][:k + 1])
         return res, counts, n_lines
 
+    # -- lines grouped by two captured texts (gx_group_pairs / gx_text_group_pairs) ----------------------------------------------
+    def pair_parts(self, spec):
+        """Resolves a list of (extraction, key extractor, second extractor[, value extractor]) into (GroupParts, int32 second groups):
+        the first, second and optional fourth entry as group_parts takes a part, the third the extractor whose value is the line's
+        SECOND (None: the part's lines have a key and no second).  A (GroupParts, seconds) tuple passes through."""
+        if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], GroupParts):
+            return spec
+        spec = [tuple(item) for item in spec]
+        for item in spec:
+            if len(item) not in (3, 4):
+                raise ValueError("a part is (extraction, key extractor, second extractor[, value extractor])")
+        parts = self.group_parts([(item[0], item[1]) + tuple(item[3:]) for item in spec])
+        seconds = (C.c_int32 * max(1, len(spec)))()
+        for t, item in enumerate(spec):
+            seconds[t] = -1 if item[2] is None else self._extraction_and_group(parts.array[t].extraction, item[2])[1]
+        return parts, seconds
+
+    @staticmethod
+    def _pairs_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(n_pairs=t.n_pairs, pair_units=t.pair_units, paired=t.paired, unpaired=t.unpaired, pairs_exact=bool(t.pairs_exact))
+        return d
+
+    def group_pairs_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                           key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, pair_units_ptr=None, pair_units_cap=0,
+                           pair_offsets_ptr=None, pair_key_ptr=None, pair_first_line_ptr=None, pair_lines_ptr=None, key_pairs_ptr=None, line_pair_ptr=None,
+                           max_pairs=0, pairs=True, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_group_pairs on device pointers (ints): group_lines_device's keys, plus the pairs (key, second text) in the caller's
+        buffers, each optional (none at all: the size query; max_keys and max_pairs still size the tables).  pairs=False passes
+        pairs == NULL: the call is gx_group_lines.  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and
+        totals says what the outputs need (n_keys, key_units, n_pairs, pair_units; exact / pairs_exact False: that table overflowed,
+        the number of lines always suffices); every other error raises."""
+        parts, seconds = self.pair_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_pairs_out(pair_units_ptr, pair_units_cap, pair_offsets_ptr, pair_key_ptr, pair_first_line_ptr, pair_lines_ptr, key_pairs_ptr, line_pair_ptr, max_pairs)
+        totals = N.gx_pairs_totals()
+        rc = N.lib().gx_group_pairs(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, seconds, terms.array, terms.n,
+                                    N.GX_GROUP_WEAK_HASH if weak_hash else 0, C.byref(keys), C.byref(out) if pairs else None, C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._pairs_totals(totals)
+
+    def text_group_pairs_device(self, text_ptr, size, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None, key_first_line_ptr=None,
+                                key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, pair_units_ptr=None, pair_units_cap=0, pair_offsets_ptr=None,
+                                pair_key_ptr=None, pair_first_line_ptr=None, pair_lines_ptr=None, key_pairs_ptr=None, line_pair_ptr=None, max_pairs=0, pairs=True,
+                                offsets64=False, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_text_group_pairs on a device buffer (int); outputs as group_pairs_device takes them (line_key and line_pair: one entry per
+        line of the text).  Returns (rc, totals, counts, n_lines)."""
+        parts, seconds = self.pair_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_pairs_out(pair_units_ptr, pair_units_cap, pair_offsets_ptr, pair_key_ptr, pair_first_line_ptr, pair_lines_ptr, key_pairs_ptr, line_pair_ptr, max_pairs)
+        totals = N.gx_pairs_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_pairs(self._h.ptr, text_ptr, size, parts.array, parts.n, seconds, terms.array, terms.n, N.GX_GROUP_WEAK_HASH if weak_hash else 0,
+                                         C.byref(keys), C.byref(out) if pairs else None, C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._pairs_totals(totals), counts, nl.value
+
+    def _pairs_host(self, device_call, n_lines_cap, units_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap, max_pairs, pair_units_cap):
+        """_group_host with the pair arrays beside the key arrays.  max_pairs defaults to the number of lines and pair_units_cap to the
+        batch's units, which always suffice (no more pairs than lines, and a pair's second is a part of its first line); smaller ones
+        are raised to what a GX_E_LIMIT reports."""
+        size = {"max_pairs": n_lines_cap if max_pairs is None else max_pairs, "pair_units_cap": units_cap if pair_units_cap is None else pair_units_cap}
+        got = {}
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            mp, pc = size["max_pairs"], size["pair_units_cap"]
+            got.update(pair_units=np.zeros(max(1, pc), unit_dtype), pair_offsets=np.zeros(mp + 1, offsets_dtype), pair_key=np.zeros(max(1, mp), np.uint32),
+                       pair_first_line=np.zeros(max(1, mp), np.uint32), pair_lines=np.zeros(max(1, mp), np.uint64), key_pairs=np.zeros(max(1, mk), np.uint64),
+                       line_pair=np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32))
+            r = device_call(units, cap, koff, first, lines, stats, line_key, mk, got["pair_units"].ctypes.data, pc, got["pair_offsets"].ctypes.data,
+                            got["pair_key"].ctypes.data, got["pair_first_line"].ctypes.data, got["pair_lines"].ctypes.data, got["key_pairs"].ctypes.data,
+                            got["line_pair"].ctypes.data, mp)
+            if r[0] == N.GX_E_LIMIT and r[1]["exact"]:
+                if r[1]["pairs_exact"]:
+                    size.update(max_pairs=max(mp, r[1]["n_pairs"]), pair_units_cap=max(pc, r[1]["pair_units"]))
+                else:
+                    size["max_pairs"] = n_lines_cap
+            return r
+        res, rest = self._group_host(call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap)
+        p, k = res["totals"]["n_pairs"], res["totals"]["n_keys"]
+        poff, punits = got["pair_offsets"][:p + 1], got["pair_units"][:res["totals"]["pair_units"]]
+        res.update(pair_units=punits, pair_offsets=poff, pair_key=got["pair_key"][:p], pair_first_line=got["pair_first_line"][:p], pair_lines=got["pair_lines"][:p],
+                   key_pairs=got["key_pairs"][:k], line_pair=got["line_pair"])
+        if keys == "list":
+            res["pairs"] = [(int(got["pair_key"][j]), decode(punits[int(poff[j]):int(poff[j + 1])])) for j in range(p)]
+        return res, rest
+
+    def group_pairs(self, data, offsets, ids, rows, parts, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None, max_pairs=None,
+                    pair_units_cap=None, weak_hash=False):
+        """gx_group_pairs on host buffers: group_lines' keys, and the lines grouped by (key, second text) -- GROUP BY a, b and
+        COUNT(DISTINCT b) GROUP BY a.  parts: (extraction, key extractor, second extractor[, value extractor]) each (pair_parts);
+        everything else as group_lines takes it.  Returns group_lines' dict plus pairs (a list of (key number, second) in order of
+        first appearance; keys="csr": pair_units / pair_offsets / pair_key alone, which are always there), pair_lines, pair_first_line
+        (per pair), key_pairs (per key: its distinct seconds), line_pair (uint32 per input line, 0xFFFFFFFF: none) and the pair totals
+        (n_pairs, pair_units, paired, unpaired, pairs_exact) in totals.  max_pairs defaults to the number of lines."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        both = self.pair_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.group_pairs_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), both, where, *outs, offsets64=offsets.dtype == np.uint64,
+                                           utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8), weak_hash=weak_hash)
+        res, _ = self._pairs_host(device_call, n, int(offsets[n] - offsets[0]) if n else 0, both[0], data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap,
+                                  max_pairs, pair_units_cap)
+        res["line_key"], res["line_pair"] = res["line_key"][:n], res["line_pair"][:n]
+        return res
+
+    def text_group_pairs(self, text, parts, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None, max_pairs=None, pair_units_cap=None):
+        """gx_text_group_pairs on a host buffer: raw text -> lines -> extraction -> group_pairs.  Returns (the dict group_pairs returns,
+        counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        both = self.pair_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.text_group_pairs_device(raw.ctypes.data if raw.size else None, raw.size, both, where, *outs, device_pointers=False, utf8=utf8)
+        res, (counts, n_lines) = self._pairs_host(device_call, cap_lines, raw.size, both[0], np.uint8, np.uint32, keys, decode, max_keys, key_units_cap, max_pairs,
+                                                  pair_units_cap)
+        res["line_key"], res["line_pair"] = res["line_key"][:n_lines], res["line_pair"][:n_lines]
+        return res, counts, n_lines
+
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
     def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
                                key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,

@@ -522,6 +522,75 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Lines grouped by TWO captured texts (gx_group_pairs): the caller's seen.computeIfAbsent(r.asMap().get("verb"), v -> new
+    // HashSet<>()).add(r.asMap().get("path")) and byBoth.merge(List.of(verb, path), 1L, Long::sum) (README.md:26,63-79).  The parts of a
+    // call are groupParts' plus a SECOND extractor per part (an empty name, or -1: the part's lines have a key and no second):
+    // pairParts().of("GetRequest", "verb", "path").of("OtherRequest", "verb", "path").
+    class PairParts {
+    public:
+        explicit PairParts(const Gorp* g) : g_(g), keys_(g) {}
+        PairParts& of(const std::string& extraction, const std::string& key, const std::string& second, const std::string& value = std::string()) {
+            int32_t s = -1;
+            if (!second.empty()) {
+                Where at(g_);
+                at.on(extraction, second).isSet();
+                s = at.terms()[0].group;
+            }
+            keys_.of(extraction, key, value);
+            seconds_.push_back(s);
+            return *this;
+        }
+        PairParts& of(size_t extraction, size_t keyGroup, int32_t secondGroup, int32_t valueGroup = -1) {
+            if (secondGroup < -1 || (extraction < g_->extractions_.size() && secondGroup >= 0 &&
+                                     static_cast<size_t>(secondGroup) >= g_->extractions_[extraction].extractorNames.size()))
+                throw std::invalid_argument("no such extraction or group");
+            keys_.of(extraction, keyGroup, valueGroup);
+            seconds_.push_back(secondGroup);
+            return *this;
+        }
+        const GroupParts& keys() const { return keys_; }
+        const std::vector<int32_t>& seconds() const { return seconds_; }
+
+    private:
+        const Gorp* g_;
+        GroupParts keys_;
+        std::vector<int32_t> seconds_;
+    };
+    PairParts pairParts() const { return PairParts(this); }
+    // groupLines' result, plus the distinct pairs (key, second) in the order of their first line: per pair its key's number, its second,
+    // its first line and its lines; per key its pairs (its distinct seconds); per input line its pair's number (0xFFFFFFFF: none).
+    struct Pairs : Groups {
+        std::vector<uint32_t> pairKey;
+        std::vector<std::string> seconds;
+        std::vector<uint32_t> pairFirstLine;
+        std::vector<uint64_t> pairLines, keyPairs;
+        std::vector<uint32_t> linePair;
+        gx_pairs_totals pairs{};
+    };
+    Pairs groupPairs(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const PairParts& parts,
+                     const Where* where = nullptr) const {
+        return pairsOf(parts, where, &n, n, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                const gx_pairs_out* po, gx_pairs_totals* totals) {
+            return gx_group_pairs(h_, bytes, offsets, n, match_id, caps, p, np, s, t, nt, 0, out, po, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same pairs out (gx_text_group_pairs).  counts (optional): lines per outcome index.
+    Pairs textGroupPairs(const std::string& text, const PairParts& parts, const Where* where = nullptr, std::vector<uint64_t>* counts = nullptr,
+                         uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0, ends = 1;   // (no more lines than line ends, plus the last)
+        for (const char c : text) ends += (c == '\n' || c == '\r') ? 1u : 0u;
+        Pairs r = pairsOf(parts, where, &lines, ends, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt,
+                                                         const gx_group_out* out, const gx_pairs_out* po, gx_pairs_totals* totals) {
+            return gx_text_group_pairs(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, s, t, nt, 0, out, po, totals,
+                                       counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return r;
+    }
     // Lines ranked by a number they captured (gx_top_lines): the parts of a call, built by name.  topParts().of("GetRequest",
     // "timeTakenInMsec").of("OtherRequest", "timeTakenInMsec") with topLines(..., 10) is the caller's "which requests were the slowest?",
     // sorted(results, by timeTakenInMsec).take(10) (README.md:26,63-79).  Names resolve as Where's do; one part per extraction; all
@@ -804,6 +873,47 @@ private:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
         return g;
+    }
+    // groupsOf with the pairs beside the keys: the size queries ask with a pair table for maxLines lines, which always suffices; the call
+    // with exactly the sizes they reported delivers both.  Pair outputs are asked for only where a part has a second (the C call refuses
+    // them otherwise: there is nothing they could hold).
+    template <typename Call>
+    Pairs pairsOf(const PairParts& parts, const Where* where, const uint64_t* lines, uint64_t maxLines, Call&& call) const {
+        Pairs r;
+        const int32_t none = -1;
+        const std::vector<int32_t>& seconds = parts.seconds();
+        bool wanted = seconds.empty();
+        for (const int32_t s : seconds) wanted = wanted || s >= 0;
+        std::vector<uint8_t> units;
+        std::vector<uint32_t> offsets;
+        Groups g = groupsOf(parts.keys(), where, lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                            gx_group_totals* totals) {
+            gx_pairs_out po{};
+            po.max_pairs = maxLines < (1ull << 30) ? maxLines : (1ull << 30);
+            if (out->key_offsets != nullptr && wanted) {   // (the size query before it left the sizes in r.pairs)
+                const size_t m = static_cast<size_t>(r.pairs.n_pairs);
+                units.assign(static_cast<size_t>(r.pairs.pair_units) + 1, 0);
+                offsets.assign(m + 1, 0);
+                r.pairKey.assign(m, 0);
+                r.pairFirstLine.assign(m, 0);
+                r.pairLines.assign(m, 0);
+                r.keyPairs.assign(static_cast<size_t>(out->max_keys), 0);
+                r.linePair.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+                po.pair_units = units.data(); po.pair_units_cap = r.pairs.pair_units; po.pair_offsets = offsets.data(); po.pair_key = r.pairKey.data();
+                po.pair_first_line = r.pairFirstLine.data(); po.pair_lines = r.pairLines.data(); po.key_pairs = r.keyPairs.data(); po.line_pair = r.linePair.data();
+                po.max_pairs = r.pairs.n_pairs;   // (the arrays' capacity; a table of twice as many slots holds them all)
+            }
+            const int rc = call(p, np, seconds.empty() ? &none : seconds.data(), t, nt, out, &po, &r.pairs);
+            *totals = r.pairs.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        if (!wanted) {
+            r.keyPairs.assign(r.keys.size(), 0);
+            r.linePair.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        }
+        for (size_t j = 0; j < r.pairKey.size(); ++j) r.seconds.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
+        return r;
     }
     // groupsOf's scheme for topGroups: the size query with a table for a modest number of keys, once more with as many keys as lines if
     // that table overflows, then the call with exactly the sizes it reported.

@@ -821,6 +821,74 @@ int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const
                          uint64_t* key_out_lines, uint64_t* key_out_units, gx_by_key_totals* totals, uint64_t* counts, uint64_t* n_lines,
                          const gx_batch_opts* opts);
 
+/* ---- Lines grouped by TWO captured texts, on the device (gx_group_pairs) ----
+ * The reference's caller keys on two captured texts at once right behind the extraction (README.md:26,63-79):
+ *     r = gorp.extract(line);
+ *     if (r != null) seen.computeIfAbsent(r.asMap().get("verb"), v -> new HashSet<>()).add(r.asMap().get("path"));   // distinct paths per verb
+ *     if (r != null) byBoth.merge(List.of(r.asMap().get("verb"), r.asMap().get("path")), 1L, Long::sum);              // lines per (verb, path)
+ * -- COUNT(DISTINCT b) GROUP BY a and GROUP BY a, b.  Neither is a gx_group_lines call: it keys on one group, and two values one
+ * behind the other are no key (("ab","c") and ("a","bc") differ).
+ * PARTS: gx_group_lines' parts, plus second_groups[n_parts]: per part the group whose value is the line's SECOND, in
+ * [0, gx_num_groups(h, extraction)), or -1: the part's lines have a key and no second.
+ * THE RULE: a line counts, is keyed or adds to `unset` exactly as in gx_group_lines; nothing of that call is reinterpreted.  A keyed line
+ * is PAIRED when its part's second group is >= 0 and that group's capture names a value (the rule of gx_where_term: an unset group,
+ * begin < 0 <= end, end < begin or an end beyond the line is never dereferenced); every other keyed line is UNPAIRED: keyed == paired +
+ * unpaired.  The empty second is a value like any other.  Two paired lines hold the same PAIR when they have the same key and their
+ * seconds have the same number of code units and the same units; the seconds of different parts live in one space, as the keys do.
+ * ORDER: pairs leave ordered by the first input line that holds them (pair_first_line ascends).
+ * EXACT: every output is exact and the same bits on every run; all merges are unsigned integer adds and maxima.
+ * NOT IN SCOPE: stats per pair, quantiles per pair, ranking pairs, more than two texts. */
+typedef struct gx_pairs_out {      /* every pointer optional; device memory with opts->device_pointers, else host */
+    void*     pair_units;          /* the pairs' SECOND values, one behind the other, in the batch's code units */
+    uint64_t  pair_units_cap;      /* in code units */
+    void*     pair_offsets;        /* n_pairs + 1, uint32 or uint64 as opts->offsets64 */
+    uint32_t* pair_key;            /* the key number (gx_group_out's order) of pair p */
+    uint32_t* pair_first_line;     /* pairs are ORDERED by it */
+    uint64_t* pair_lines;
+    uint64_t* key_pairs;           /* per KEY: its distinct seconds = its pairs; capacity keys->max_keys (keys == NULL: 0) */
+    uint32_t* line_pair;           /* n entries, 0xFFFFFFFF: none */
+    uint64_t  max_pairs;           /* capacity of the per-pair arrays, and the pair table's size; read in the size query too; <= 2^30 */
+} gx_pairs_out;
+
+typedef struct gx_pairs_totals {   /* host, always */
+    gx_group_totals group;         /* exactly what gx_group_lines reports for the same call */
+    uint64_t n_pairs, pair_units, paired, unpaired, pairs_exact;
+} gx_pairs_totals;
+
+/* gx_group_pairs: everything gx_group_lines delivers through `keys` and totals->group is delivered bit for bit, and the batch is read
+ * exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging or device_pointers; the
+ * stream; GX_GROUP_WEAK_HASH applies to both tables).  With pairs == NULL the call IS gx_group_lines: the pair passes do not run, and the
+ * pair totals are zero with pairs_exact = 1.
+ * THE PAIR TABLE has the smallest power of two >= max(64, 2 * max_pairs) slots; the number of lines is always a sufficient max_pairs.
+ * HOST WAITS: ONE host wait before any output -- the wait in which gx_group_lines reads its totals also reads n_pairs, pair_units,
+ * paired, unpaired and the pair table's state, computed behind the build on the same stream.  With host outputs a second wait delivers
+ * them.  With device_pointers the emits are left running on opts->stream when the call returns, as gx_group_lines leaves its emit; the
+ * handle's next group call on another stream waits for them, and the batch must stay unchanged until they have run.
+ * SIZE QUERY: every output of `keys` and `pairs` NULL: only *totals is filled; keys->max_keys and pairs->max_pairs are still read as
+ * the tables' sizes.
+ * GX_E_LIMIT: a per-pair array (pair_offsets, pair_key, pair_first_line, pair_lines) with n_pairs > max_pairs; pair_units with
+ * pair_units > pair_units_cap; key_pairs with n_keys > keys->max_keys; pair_offsets without offsets64 and 4 G units or more; max_pairs >
+ * 2^30; a full pair table (pairs_exact = 0 and n_pairs = slots + 1, while group.exact stays 1); and gx_group_lines' own limits.  In
+ * every one of these cases nothing is written to ANY output, the key outputs included, and *totals is filled (after the overflow of
+ * the KEY table the pair totals are zero).
+ * GX_E_ARG: every refusal gx_group_lines makes; second_groups == NULL with n_parts > 0; a second group that is neither -1 nor one of
+ * its part's extraction's; an output of `pairs` given while n_parts > 0 and every second group is -1 (there is nothing they could
+ * hold: ask gx_group_lines).  All refusals that need no device come before the device is looked at: a host-only handle gives them, and
+ * GX_E_DEVICE after them (there is no CPU path).  n == 0 and n_parts == 0 are legal and give all zeros (pair_offsets: its one entry;
+ * line_pair: all none).
+ * The device workspace stays on the handle beside gx_group_lines', two buffers of their own: 28 bytes per pair slot plus 8 per key slot,
+ * and 25 bytes per input line plus 16 per 2 048 lines, until gx_destroy. */
+int gx_group_pairs(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                   const gx_group_part* parts, uint32_t n_parts, const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms,
+                   uint32_t flags, const gx_group_out* keys, const gx_pairs_out* pairs, gx_pairs_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the pairs at its end: raw text -> lines -> the match-and-extract path -> the keys
+ * and the pairs.  counts and *n_lines as gx_text_group_lines delivers them; line_pair holds one entry per line of the text.  Like every
+ * gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                        const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
+                        const gx_pairs_out* pairs, gx_pairs_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
