@@ -890,6 +890,11 @@ int64_t gx_stat(const gx_handle* h, int32_t which) {
     case 23: return I.hop[1].ok ? static_cast<int64_t>(I.hop[1].img.full.n_hot) : 0; // ... whose records are in LDS
     case 19: { GxLds L; return plan_hop_slice_launch(I, &L) ? static_cast<int64_t>(L.nwaves) : 0; }  // ... of the hop slice kernel
     case 9: return !I.tile_ok ? 0 : !I.has_mo ? gx_stat(h, 7) : I.dense[1].L.tier == 3 ? 4 : I.dense[1].L.tier == 2 ? 3 : I.dense[1].L.tier == 1 ? 2 : 1;
+    // what the table images were built from (read-only, for tests that must know how near an image is to a limit of its format)
+    case 36: return I.tile_ok ? static_cast<int64_t>(I.dense[0].records) : 0;                    // range records of the batch image (0: dense rows)
+    case 37: return I.tile_ok ? static_cast<int64_t>(I.dense[I.dense_of(true)].records) : 0;     // ... of the image match-only batches walk
+    case 38: return I.tile_ok ? static_cast<int64_t>(I.dense[0].rows) : 0;                       // automaton rows (states) the batch image covers
+    case 39: return I.tile_ok && I.dense[0].fused ? 1 : 0;                                       // 1: its capture side is the fused automaton
     default: return -1;
     }
 }

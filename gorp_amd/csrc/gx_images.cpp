@@ -48,7 +48,7 @@ constexpr uint32_t REC_MORE = 0x80u << 24, REC_HDR = 2u << 24, REC_IDC = 254u, R
 
 bool records_from_dense(const Tables& T, const std::vector<uint32_t>& at, size_t rows, uint32_t cols, const std::vector<uint32_t>& dead_of_row,
                         const std::vector<std::array<uint64_t, 2>>& loop_set, bool simple, Image& img, GxLds& L, std::vector<uint32_t>& c_rule,
-                        std::vector<uint32_t>* items_global) {
+                        std::vector<uint32_t>* items_global, uint32_t* n_records) {
     const int ncls = T.ncls;
     const uint32_t ACC = ncls + 1, INFO = ncls + 2;
     auto has = [](const ClassSet& s, int c) { return (s[c >> 6] >> (c & 63)) & 1ull; };
@@ -132,6 +132,7 @@ bool records_from_dense(const Tables& T, const std::vector<uint32_t>& at, size_t
         }
     const bool wide = items_global != nullptr;  // records in global memory: 22-bit successors
     if (n_items > (wide ? 0x3FFFFFu : 65535u)) return false;
+    *n_records = static_cast<uint32_t>(n_items);
     auto pack_w1 = [&](uint32_t target, uint32_t op, bool more, bool hdr) {
         return wide ? (target | op << 22 | (hdr ? 1u << 30 : 0u) | (more ? 1u << 31 : 0u)) : (target | op << 16 | (hdr ? REC_HDR : 0u) | (more ? REC_MORE : 0u));
     };
@@ -449,10 +450,11 @@ bool build_tile_image(TileImages& I, const Tables& T, uint32_t flags, int tier, 
     // tier 3: one global image per handle: [capture-side records + final records][match-only records]; GxLds::rec_g /
     // fin_tags are byte offsets into it
     const size_t g_base = I.l2.size();
+    uint32_t n_records = 0;
     if (tier >= 2) {
         img.bytes.clear();  // the record tiers have their own class map (classes renumbered so that sets become ranges)
         std::vector<uint32_t> items_g;
-        if (!records_from_dense(T, at, rows, cols, dead_of_row, loop_set, simple, img, L, c_rule, tier == 3 ? &items_g : nullptr)) return false;
+        if (!records_from_dense(T, at, rows, cols, dead_of_row, loop_set, simple, img, L, c_rule, tier == 3 ? &items_g : nullptr, &n_records)) return false;
         if (tier == 2 && img.bytes.size() + T.ops_off.size() * 4 + T.ops.size() * 2 + fin_rec.size() * 2 + 1024 > LDS_TABLE_BUDGET) return false;
         if (tier == 3) {
             L.c_base = static_cast<uint32_t>(g_base);  // (byte offset of this image's records in the global image)
@@ -492,6 +494,9 @@ bool build_tile_image(TileImages& I, const Tables& T, uint32_t flags, int tier, 
     DenseImage& D = I.dense[part == 2 ? 1 : 0];
     D.L = L;
     D.bytes.swap(img.bytes);
+    D.rows = static_cast<uint32_t>(rows);
+    D.records = n_records;
+    D.fused = part != 2 && fused && T.has_capture;
     (part == 2 ? I.has_mo : I.tile_ok) = true;
     return true;
 }

@@ -23,7 +23,9 @@ struct Image {
 };
 
 // An image that a batch kernel copies into LDS: its layout (GxLds::tier 0-3) and its bytes.
-struct DenseImage { GxLds L{}; std::vector<uint8_t> bytes; };
+// rows / records / fused: what the image was built from, for gx_stat alone -- the automaton rows it covers, the range records they
+// became (0: dense rows), whether its capture side is the fused automaton.
+struct DenseImage { GxLds L{}; std::vector<uint8_t> bytes; uint32_t rows = 0, records = 0; bool fused = false; };
 // The hop tier of one automaton (gx_hop.hpp), laid out for the tile kernel (full) and for the hop slice kernel (small).
 struct HopTier { bool ok = false; HopImage img; GxLds full{}, small{}; };
 

@@ -130,7 +130,11 @@ int32_t gx_max_groups(const gx_handle* h);
  * handle has none); 33 / 34 = for the most recent gx_batch_opts.utf8 batch (gx_extract_batch, gx_text_to_jsonl, gx_text_select): the lines that
  * held a byte >= 0x80 and were walked again as Strings, and the UTF-16 code units made for them;
  * 35 = the workgroups of 256 lanes a per-line launch of this handle is kept within, every lane that may run a program having its own
- * thread lists (-1: the handle has no extraction that runs as a program) */
+ * thread lists (-1: the handle has no extraction that runs as a program);
+ * what the batch kernels' table image was built from (read-only, for tests that must know how near an image is to a limit of its
+ * format): 36 / 37 = the range records of the batch image / of the image match-only batches walk (0: dense rows, or no image),
+ * 38 = the automaton rows (states) the batch image covers, 39 = 1 when its capture side is the fused automaton (0: one capture
+ * automaton per extraction -- the two-pass layout --, no capture regexps, or no image) */
 int64_t gx_stat(const gx_handle* h, int32_t which);
 
 typedef struct gx_batch_opts {
