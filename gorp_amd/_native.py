@@ -55,6 +55,7 @@ SYMBOLS = [
     "gx_top_groups", "gx_text_top_groups",
     "gx_lines_by_key", "gx_text_lines_by_key",
     "gx_group_pairs", "gx_text_group_pairs",
+    "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
 
 
@@ -92,6 +93,13 @@ class gx_measure(C.Structure):
 class gx_measure_stats(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64),
                 ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64)]
+
+
+GX_NUMBER_LONG, GX_NUMBER_DECIMAL, GX_NUMBER_ISO8601, GX_NUMBER_CLF = range(4)
+
+
+class gx_number_format(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("scale", C.c_uint32)]
 
 
 GX_GROUP_WEAK_HASH = 1
@@ -303,6 +311,12 @@ def lib():
     L.gx_results_to_jsonl.restype = C.c_int
     L.gx_set_extraction_meta.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p]
     L.gx_set_extraction_meta.restype = C.c_int
+    L.gx_set_number_format.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(gx_number_format)]
+    L.gx_set_number_format.restype = C.c_int
+    L.gx_get_number_format.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(gx_number_format)]
+    L.gx_get_number_format.restype = C.c_int
+    L.gx_parse_number.argtypes = [C.POINTER(gx_number_format), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.gx_parse_number.restype = C.c_int
     L.gx_text_to_jsonl.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_to_jsonl.restype = C.c_int

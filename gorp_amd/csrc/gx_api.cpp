@@ -27,6 +27,7 @@
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
+#include "gx_number.hpp"
 #include "gx_slots.hpp"
 #include "gx_stats.hpp"
 #include "gx_quantile.hpp"
@@ -199,6 +200,13 @@ struct gx_handle {
     DevMem<> d_img[IMG_COUNT];
     int num_cus = 256;
     std::vector<dsl::Extraction> meta;  // names / extractor names / append (from definition text or gx_set_extraction_meta)
+    // gx_set_number_format: per extraction and group the packed format (gx_number.hpp: number_pack); an extraction without an entry,
+    // and every group of a new handle, is LONG.  Not part of the blob.
+    std::vector<std::vector<uint8_t>> number_formats;
+    uint8_t number_format_of(int32_t k, int32_t g) const {
+        if (static_cast<size_t>(k) >= number_formats.size() || static_cast<size_t>(g) >= number_formats[k].size()) return 0;
+        return number_formats[k][g];
+    }
     // scratch of the one-String entry points: device, and its pinned host mirror (one_line)
     struct OneScratch {
         DevMem<uint8_t> dev;
@@ -1289,6 +1297,7 @@ struct Selected {
 // code units), checked against the handle; `none` when the call has no terms.  Needs no device.
 struct WhereImage {
     std::vector<uint8_t> bytes;   // empty: no terms
+    bool formats = false;         // an integer term reads a group whose format is not LONG (gx_set_number_format)
     bool none() const { return bytes.empty(); }
 };
 static WhereImage where_image(const gx_handle* h, const gx_where_term* terms, uint32_t n_terms, bool wide, const std::string& name) {
@@ -1330,12 +1339,15 @@ static WhereImage where_image(const gx_handle* h, const gx_where_term* terms, ui
         d.op = static_cast<uint8_t>(m.op);
         d.negate = m.negate ? 1 : 0;
         d.number = m.number;
+        if (m.op >= WHERE_INT_EQ) head.fmt[q] = h->number_format_of(m.extraction, m.group);   // (nothing else sees the format)
+        if (head.fmt[q]) head.formats = 1u;
         d.lit_at = static_cast<uint16_t>(at);
         d.lit_len = text_op ? static_cast<uint16_t>(m.text_units) : 0;
         if (d.lit_len) memcpy(lits + at * unit, m.text, d.lit_len * unit);
         at += d.lit_len;
     }
     head.first[head.n_ext] = static_cast<uint8_t>(n_terms);
+    img.formats = head.formats != 0u;
     memcpy(img.bytes.data(), &head, sizeof(head));
     return img;
 }
@@ -1361,7 +1373,8 @@ static Selected select_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32
         const std::vector<uint8_t>& img = where->image->bytes;
         void* d_img = h->where_image.get(img.size());
         GX_HIP(hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, stream));
-        const WhereArgs a{where->data, where->wide ? 1 : 0, where->caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(img.size())};
+        const WhereArgs a{where->data, where->wide ? 1 : 0, where->caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(img.size()),
+                              where->image->formats ? 1u : 0u};
         GX_HIP(launch_where_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, counts != nullptr, s.w, stream));
     } else {
         GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
@@ -1570,6 +1583,7 @@ struct StatsImage {
     std::vector<uint8_t> bytes;
     std::vector<uint32_t> order;
     uint32_t n_bins = 0;
+    bool formats = false;   // a measure reads a group whose format is not LONG (gx_set_number_format)
 };
 static StatsImage stats_image(const gx_handle* h, const gx_measure* measures, uint32_t n_measures, const std::string& name) {
     StatsImage img;
@@ -1612,7 +1626,9 @@ static StatsImage stats_image(const gx_handle* h, const gx_measure* measures, ui
         }
         StatsMeasure& d = head.m[q];
         d.group = static_cast<uint16_t>(m.group);
-        d.n_edges = static_cast<uint16_t>(m.n_edges);
+        d.n_edges = static_cast<uint8_t>(m.n_edges);   // (<= STATS_MAX_EDGES)
+        d.fmt = h->number_format_of(m.extraction, m.group);
+        if (d.fmt) img.formats = true;
         d.edge_at = static_cast<uint16_t>(at);
         d.hist_at = static_cast<uint16_t>(hist_at[img.order[q]]);
         if (m.n_edges) memcpy(edges + at * 8, m.edges, static_cast<size_t>(m.n_edges) * 8);
@@ -1646,7 +1662,8 @@ static void stats_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t ro
         GX_HIP(hipMemcpyAsync(d_img, si.bytes.data(), si.bytes.size(), hipMemcpyHostToDevice, stream));
         if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + si.bytes.size(), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
         const StatsArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(si.bytes.size()),
-                          wi.none() ? nullptr : d_img + si.bytes.size(), static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins};
+                          wi.none() ? nullptr : d_img + si.bytes.size(), static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins,
+                          (si.formats || wi.formats) ? 1u : 0u};
         void* ws = h->stats_ws.get(stats_workspace_bytes(n, n_measures, si.n_bins));
         GX_HIP(launch_capture_stats(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, ws, stream));
         GX_HIP(hipMemcpyAsync(got.data(), ws, (total + 2) * 8, hipMemcpyDeviceToHost, stream));
@@ -1785,6 +1802,8 @@ static GroupImage group_image(const gx_handle* h, const gx_group_part* parts, ui
         img.head.ext[q] = static_cast<uint32_t>(p.extraction);
         img.head.part[q].key_group = static_cast<uint16_t>(p.key_group);
         img.head.part[q].value_group = p.value_group < 0 ? static_cast<uint16_t>(GROUP_NO_VALUE) : static_cast<uint16_t>(p.value_group);
+        if (p.value_group >= 0) img.head.fmt[q] = h->number_format_of(p.extraction, p.value_group);
+        if (img.head.fmt[q]) img.head.formats = 1u;
     }
     img.head.n_parts = n_parts;
     img.head.has_values = img.values ? 1u : 0u;
@@ -1906,7 +1925,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
     const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
-                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u};
+                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
     const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
     GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
     // the quantiles' candidates: only where rows are wanted and a part has a value (else every population is empty)
@@ -1921,7 +1940,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         GX_HIP(hipMemcpyAsync(d_qimg + sizeof(TopHead), &gq->qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
         if (!wi.none()) GX_HIP(hipMemcpyAsync(d_qimg + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
         const TopArgs ta{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_qimg, wi.none() ? nullptr : d_qimg + at_terms,
-                         static_cast<uint32_t>(wi.bytes.size()), 0u, 0u};
+                         static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
         qw = gq_workspace(h->gq_ws.get(gq_workspace_bytes(n)), n);
         GX_HIP(launch_gq_collect(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, ta, w.slot_of, qw, stream));
         GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, stream));
@@ -2217,7 +2236,7 @@ static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_
     GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
     const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
-                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u};
+                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
     const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
     GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
     // the first wait: gx_group_lines' totals
@@ -2311,6 +2330,7 @@ static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint
     for (uint32_t e = 0; e < gi.head.n_parts; ++e) {   // (ascending by extraction already)
         if (gi.head.part[e].value_group == GROUP_NO_VALUE) continue;
         gq->ti.ext[gq->ti.n_parts] = gi.head.ext[e];
+        gq->ti.fmt[gq->ti.n_parts] = gi.head.fmt[e];
         gq->ti.group[gq->ti.n_parts++] = gi.head.part[e].value_group;
     }
     gq->rows = rows;
@@ -2599,6 +2619,8 @@ static TopHead top_image(const gx_handle* h, const gx_top_part* parts, uint32_t 
         if (q && parts[order[q - 1]].extraction == p.extraction) throw GxError(GX_E_ARG, name + ": two parts for one extraction");
         head.ext[q] = static_cast<uint32_t>(p.extraction);
         head.group[q] = static_cast<uint16_t>(p.value_group);
+        head.fmt[q] = h->number_format_of(p.extraction, p.value_group);
+        if (head.fmt[q]) head.formats = 1u;
     }
     head.n_parts = n_parts;
     return head;
@@ -2663,7 +2685,7 @@ static int top_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_u
     GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
     const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + sizeof(TopHead),
-                    static_cast<uint32_t>(wi.bytes.size()), ti.smallest, n_wanted};
+                    static_cast<uint32_t>(wi.bytes.size()), ti.smallest, n_wanted, (ti.formats || wi.formats) ? 1u : 0u};
     const TopWs w = top_workspace(h->top_ws.get(top_workspace_bytes(n)), n);
     GX_HIP(launch_top_select(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
     struct { uint32_t counts[TOP_COUNTS]; TopSelect sel; } got{};
@@ -2872,7 +2894,7 @@ static int quant_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), &qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
     const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + at_terms,
-                    static_cast<uint32_t>(wi.bytes.size()), 0u, 0u};
+                    static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (ti.formats || wi.formats) ? 1u : 0u};
     const QuantWs w = quant_workspace(h->quant_ws.get(quant_workspace_bytes(n)), n);
     GX_HIP(launch_quantiles(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_img + sizeof(TopHead), qh.n_q, w, stream));
     struct { uint32_t counts[TOP_COUNTS]; QuantOut out[QUANT_MAX]; } got{};
@@ -3233,6 +3255,39 @@ int gx_set_extraction_meta(gx_handle* h, int32_t k, const char* name, const char
         h->append_entries.clear();
         return GX_OK;
     });
+}
+
+int gx_set_number_format(gx_handle* h, int32_t k, int32_t g, const gx_number_format* f) {
+    if (!h || k < 0 || k >= h->T.n_rules || g < 0 || g >= h->T.rules[k].n_groups) return fail(GX_E_ARG, "gx_set_number_format: bad argument");
+    if (f && !number_format_ok(f->kind, f->scale)) return fail(GX_E_ARG, "gx_set_number_format: an unknown kind, or a scale the kind does not take");
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> lock(h->mu);
+        if (static_cast<int>(h->number_formats.size()) != h->T.n_rules) h->number_formats.resize(h->T.n_rules);
+        std::vector<uint8_t>& row = h->number_formats[k];
+        if (static_cast<int>(row.size()) != h->T.rules[k].n_groups) row.assign(h->T.rules[k].n_groups, 0);
+        row[g] = f ? number_pack(f->kind, f->scale) : 0;
+        return GX_OK;
+    });
+}
+
+int gx_get_number_format(const gx_handle* h, int32_t k, int32_t g, gx_number_format* out) {
+    if (!h || !out || k < 0 || k >= h->T.n_rules || g < 0 || g >= h->T.rules[k].n_groups) return fail(GX_E_ARG, "gx_get_number_format: bad argument");
+    const uint8_t packed = h->number_format_of(k, g);
+    out->kind = number_kind(packed);
+    out->scale = number_scale(packed);
+    return GX_OK;
+}
+
+int gx_parse_number(const gx_number_format* f, const void* units, uint32_t n_units, uint32_t utf16, int64_t* value, int32_t* is_number) {
+    if (!value || !is_number || (n_units && !units)) return fail(GX_E_ARG, "gx_parse_number: bad argument");
+    const uint32_t kind = f ? f->kind : static_cast<uint32_t>(NUMBER_LONG), scale = f ? f->scale : 0u;
+    if (!number_format_ok(kind, scale)) return fail(GX_E_ARG, "gx_parse_number: an unknown kind, or a scale the kind does not take");
+    int64_t v = 0;
+    const bool ok = utf16 ? number_parse(kind, scale, static_cast<const uint16_t*>(units), n_units, &v)
+                          : number_parse(kind, scale, static_cast<const uint8_t*>(units), n_units, &v);
+    *is_number = ok ? 1 : 0;
+    if (ok) *value = v;
+    return GX_OK;
 }
 
 // One host-pointer batch through the workers of gx_handle::host_slot.  `proto` carries the batch's modes (wide,

@@ -248,6 +248,7 @@ struct WhereArgs {
     uint32_t slots;        // 2 * max_groups
     const void* image;     // WhereHead + the literals, on the device, 16-byte aligned
     uint32_t image_bytes;  // a multiple of 16
+    uint32_t formats;      // WhereHead::formats: a term's group has a number format other than LONG
 };
 // counts: also the histogram of outcomes in w.counts
 hipError_t launch_where_flags(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64,
@@ -265,6 +266,7 @@ struct StatsArgs {
     const void* where_image;     // WhereHead + the literals, or nullptr: no terms
     uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
     uint32_t n_measures, n_bins;
+    uint32_t formats;            // a measure's or a term's group has a number format other than LONG
 };
 uint32_t stats_blocks(uint64_t n);
 size_t stats_workspace_bytes(uint64_t n, uint32_t n_measures, uint32_t n_bins);
@@ -285,6 +287,7 @@ struct GroupArgs {
     const void* where_image;     // WhereHead + the literals, or nullptr: no terms
     uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
     uint32_t has_values;         // a part has a value group: the slots have stats words
+    uint32_t formats;            // a value group's or a term's group has a number format other than LONG
 };
 // The passes' device workspace: the slots' words (group_table_bytes) and the per-line arrays (group_lines_bytes).
 struct GroupWs {
@@ -376,6 +379,7 @@ struct TopArgs {
     uint32_t where_image_bytes;  // a multiple of 16; 0: no terms
     uint32_t smallest;           // GX_TOP_SMALLEST
     uint32_t n_wanted;           // <= TOP_MAX_LINES
+    uint32_t formats;            // a value group's or a term's group has a number format other than LONG
 };
 // The passes' device workspace, cut out of one allocation of top_workspace_bytes(n) bytes:
 struct TopWs {

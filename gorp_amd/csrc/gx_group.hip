@@ -67,7 +67,7 @@ __device__ __forceinline__ void group_add(u64* head, u64* stats, bool values, co
 // LDS: GroupHead, the term image (wimage_bytes, 0: no terms), then keys[GROUP_LDS_ENTRIES], 4 words (used, spare), 4 totals (64-bit),
 // and GROUP_LDS_ENTRIES x (GROUP_HEAD_WORDS + GROUP_STATS_WORDS) 64-bit words.
 // totals[0..3]: lines that count, lines whose key pair names no value, status bits (1: a line of 4 G units, 2: the table is full).
-template <typename OFF, RowFormat F, typename UNIT>
+template <typename OFF, RowFormat F, typename UNIT, bool NUM>
 __global__ void __launch_bounds__(256) k_group_build(const void* __restrict__ ids, const int32_t* __restrict__ caps, uint32_t row_units, uint32_t slots, uint32_t K,
                                                      uint64_t n, const OFF* __restrict__ off, const UNIT* __restrict__ data, const uint4* __restrict__ gimage,
                                                      const uint4* __restrict__ wimage, uint32_t wimage_bytes, u64* __restrict__ table, uint32_t n_slots,
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(256) k_group_build(const void* __restrict__ id
             line_units = len > 0xFFFFFFFFull ? 0u : len;    // (no value is looked at in a line that is refused anyway)
             if (oc >= ext_lo && oc <= ext_hi) {             // (oc <= ext_hi < K: a matched extraction)
                 e = where_find(gh->ext, n_ext, oc);
-                if (e < n_ext && terms && !where_line_holds<F, UNIT>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_ext;
+                if (e < n_ext && terms && !where_line_holds<F, UNIT, NUM>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_ext;
             }
         }
         uint32_t slot = GROUP_NONE, kn = 0;
@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(256) k_group_build(const void* __restrict__ id
                 else if (part.value_group != GROUP_NO_VALUE) {
                     pair_of<F>(ids, caps, i, row_units, slots, part.value_group, pb, pe);
                     if (!where_pair_set(pb, pe, line_units)) cls = 1u;
-                    else cls = where_parse_int64(data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
+                    else cls = number_parse_packed<NUM>(NUM ? gh->fmt[e] : 0u, data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
                 }
             }
         }
@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) k_group_line_key(uint64_t n, const uint32
     }
 }
 
-template <typename OFF, typename UNIT>
+template <typename OFF, typename UNIT, bool NUM>
 void launch_build_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t stream, const void* ids, uint32_t row_units, uint32_t K, uint64_t n, const void* off,
                      const GroupArgs& a, const GroupWs& w) {
     const OFF* o = static_cast<const OFF*>(off);
@@ -324,13 +324,13 @@ void launch_build_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t s
     u64 *table = reinterpret_cast<u64*>(w.table), *gw = reinterpret_cast<u64*>(w.head_words), *gs = reinterpret_cast<u64*>(w.stats_words),
         *totals = reinterpret_cast<u64*>(w.totals);
     if (fmt == ROWS_U8)
-        hipLaunchKernelGGL((k_group_build<OFF, ROWS_U8, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
+        hipLaunchKernelGGL((k_group_build<OFF, ROWS_U8, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
                            a.where_image_bytes, table, w.n_slots, gw, gs, w.slot_of, w.klen, totals);
     else if (fmt == ROWS_U16)
-        hipLaunchKernelGGL((k_group_build<OFF, ROWS_U16, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
+        hipLaunchKernelGGL((k_group_build<OFF, ROWS_U16, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
                            a.where_image_bytes, table, w.n_slots, gw, gs, w.slot_of, w.klen, totals);
     else
-        hipLaunchKernelGGL((k_group_build<OFF, ROWS_DENSE, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
+        hipLaunchKernelGGL((k_group_build<OFF, ROWS_DENSE, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, gi, wi,
                            a.where_image_bytes, table, w.n_slots, gw, gs, w.slot_of, w.klen, totals);
 }
 
@@ -401,12 +401,19 @@ hipError_t launch_group_build(const void* ids, RowFormat fmt, uint32_t row_units
                          GROUP_LDS_ENTRIES * (GROUP_HEAD_WORDS + GROUP_STATS_WORDS) * 8u;
     if (lds > 64u * 1024u) return hipErrorInvalidValue;   // (64 terms of 255 two-byte units: 34 KiB; GroupHead and the LDS table: 11.1 KiB)
     const unsigned blocks = group_blocks(n);
+    // (a.formats: a value group or a term reads a group under another number format than LONG -- the instantiation with the wider parser)
+    auto go = [&](auto off_t, auto unit_t) {
+        using OFF = decltype(off_t);
+        using UNIT = decltype(unit_t);
+        if (a.formats) launch_build_as<OFF, UNIT, true>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
+        else launch_build_as<OFF, UNIT, false>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
+    };
     if (a.wide) {
-        if (offsets64) launch_build_as<uint64_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
-        else launch_build_as<uint32_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
+        if (offsets64) go(uint64_t{}, uint16_t{});
+        else go(uint32_t{}, uint16_t{});
     } else {
-        if (offsets64) launch_build_as<uint64_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
-        else launch_build_as<uint32_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, w);
+        if (offsets64) go(uint64_t{}, uint8_t{});
+        else go(uint32_t{}, uint8_t{});
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;

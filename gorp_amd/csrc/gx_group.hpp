@@ -103,9 +103,11 @@ struct GroupPart {
     uint16_t value_group;   // GROUP_NO_VALUE: count only
 };
 struct GroupHead {
-    uint32_t n_parts, flags, has_values, pad;
+    uint32_t n_parts, flags, has_values;
+    uint32_t formats;                // != 0: some fmt[] is not LONG -- the host launches the build pass's instantiation that reads them
     uint32_t ext[GROUP_MAX_PARTS];
     GroupPart part[GROUP_MAX_PARTS];
+    uint8_t fmt[GROUP_MAX_PARTS];    // part[e].value_group's packed number format (gx_number.hpp), 0 = LONG
 };
 static_assert(sizeof(GroupPart) == 4 && sizeof(GroupHead) % 16 == 0, "the head is copied in 16-byte words");
 

@@ -28,7 +28,7 @@ __device__ __forceinline__ uint64_t wave_xor64(uint64_t v, int d) { return stati
 
 // LDS: the measure image (simage_bytes), the term image (wimage_bytes, 0: no terms), n_measures x STATS_WORDS 64-bit words, n_bins
 // 32-bit bins.  slab[blockIdx.x][n_measures * STATS_WORDS + n_bins], 64-bit.
-template <typename OFF, RowFormat F, typename UNIT>
+template <typename OFF, RowFormat F, typename UNIT, bool NUM>
 __global__ void __launch_bounds__(256) k_capture_stats(const void* __restrict__ ids, const int32_t* __restrict__ caps, uint32_t row_units, uint32_t slots,
                                                        uint32_t K, uint64_t n, const OFF* __restrict__ off, const UNIT* __restrict__ data,
                                                        const uint4* __restrict__ simage, uint32_t simage_bytes, const uint4* __restrict__ wimage,
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256) k_capture_stats(const void* __restrict__ 
             line_units = len > 0xFFFFFFFFull ? 0u : len;     // (no value is looked at in a line that is refused anyway)
             if (oc >= ext_lo && oc <= ext_hi) {              // (oc <= ext_hi < K: a matched extraction)
                 e = where_find(sh->ext, n_ext, oc);
-                if (e < n_ext && terms && !where_line_holds<F, UNIT>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_ext;
+                if (e < n_ext && terms && !where_line_holds<F, UNIT, NUM>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_ext;
             }
         }
         // the distinct extractions among the wave's 64 lines that have measures (mostly none or one)
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256) k_capture_stats(const void* __restrict__ 
                     int32_t pb, pe;
                     pair_of<F>(ids, caps, i, row_units, slots, m.group, pb, pe);
                     if (!where_pair_set(pb, pe, line_units)) cls = 1u;
-                    else cls = where_parse_int64(data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
+                    else cls = number_parse_packed<NUM>(m.fmt, data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
                 }
                 unsigned long long* a = acc + q * STATS_WORDS;
 #ifdef GX_STATS_PER_LANE
@@ -167,20 +167,20 @@ __global__ void __launch_bounds__(256) k_stats_sum(const unsigned long long* __r
     if (threadIdx.x == 0) out[w] = fold(fold(part[0], part[1]), fold(part[2], part[3]));
 }
 
-template <typename OFF, typename UNIT>
+template <typename OFF, typename UNIT, bool NUM>
 void launch_stats_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t stream, const void* ids, uint32_t row_units, uint32_t K, uint64_t n, const void* off,
                      const StatsArgs& a, unsigned long long* slab, uint32_t* status) {
     const OFF* o = static_cast<const OFF*>(off);
     const UNIT* d = static_cast<const UNIT*>(a.data);
     const uint4 *si = static_cast<const uint4*>(a.image), *wi = static_cast<const uint4*>(a.where_image);
     if (fmt == ROWS_U8)
-        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_U8, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
+        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_U8, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
                            wi, a.where_image_bytes, slab, status);
     else if (fmt == ROWS_U16)
-        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_U16, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
+        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_U16, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
                            wi, a.where_image_bytes, slab, status);
     else
-        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_DENSE, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
+        hipLaunchKernelGGL((k_capture_stats<OFF, ROWS_DENSE, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, si, a.image_bytes,
                            wi, a.where_image_bytes, slab, status);
 }
 
@@ -207,12 +207,19 @@ hipError_t launch_capture_stats(const void* ids, RowFormat fmt, uint32_t row_uni
     const uint32_t lds = a.image_bytes + a.where_image_bytes + words * 8u + a.n_bins * 4u;
     if (lds > 64u * 1024u) return hipErrorInvalidValue;   // (64 measures, 1 024 edges, 64 terms of 255 two-byte units: 53 KiB)
     const unsigned blocks = stats_blocks(n);
+    // (a.formats: a measure or a term reads a group under another number format than LONG -- the instantiation with the wider parser)
+    auto go = [&](auto off_t, auto unit_t) {
+        using OFF = decltype(off_t);
+        using UNIT = decltype(unit_t);
+        if (a.formats) launch_stats_as<OFF, UNIT, true>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
+        else launch_stats_as<OFF, UNIT, false>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
+    };
     if (a.wide) {
-        if (offsets64) launch_stats_as<uint64_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
-        else launch_stats_as<uint32_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
+        if (offsets64) go(uint64_t{}, uint16_t{});
+        else go(uint32_t{}, uint16_t{});
     } else {
-        if (offsets64) launch_stats_as<uint64_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
-        else launch_stats_as<uint32_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, slab, status);
+        if (offsets64) go(uint64_t{}, uint8_t{});
+        else go(uint32_t{}, uint8_t{});
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;

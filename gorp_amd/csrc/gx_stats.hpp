@@ -16,7 +16,7 @@
 namespace gx {
 
 constexpr uint32_t STATS_MAX_MEASURES = 64;
-constexpr uint32_t STATS_MAX_EDGES = 64;          // of one measure
+constexpr uint32_t STATS_MAX_EDGES = 64;          // of one measure (StatsMeasure::n_edges is a byte)
 constexpr uint32_t STATS_MAX_EDGES_TOTAL = 1024;  // of a call
 constexpr int64_t STATS_INT64_MAX = 0x7FFFFFFFFFFFFFFFll, STATS_INT64_MIN = -STATS_INT64_MAX - 1;
 
@@ -95,7 +95,8 @@ GX_WHERE_HD uint32_t stats_add(StatsAcc& a, bool pair_set, VP value, uint32_t un
 // where_find).  hist_at: the measure's first bin among the call's bins, which lie in the caller's order.
 struct StatsMeasure {
     uint16_t group;
-    uint16_t n_edges;
+    uint8_t n_edges;    // <= STATS_MAX_EDGES
+    uint8_t fmt;        // the group's packed number format (gx_number.hpp), 0 = LONG
     uint16_t edge_at;   // first edge among the edges
     uint16_t hist_at;   // first of its n_edges + 1 bins
 };

@@ -35,7 +35,7 @@ constexpr uint32_t SWEEP_LINES = 4;   // lines a lane of a sweep takes per trip
 static_assert(TOP_MAX_LINES * 8u <= 64u * 1024u, "a workgroup of the order pass keeps every chosen key in LDS");
 
 // LDS: the part image (TopHead), the term image (wimage_bytes, 0: no terms).  slab[blockIdx.x][TOP_COUNTS].
-template <typename OFF, RowFormat F, typename UNIT>
+template <typename OFF, RowFormat F, typename UNIT, bool NUM>
 __global__ void __launch_bounds__(256) k_top_keys(const void* __restrict__ ids, const int32_t* __restrict__ caps, uint32_t row_units, uint32_t slots, uint32_t K,
                                                   uint64_t n, const OFF* __restrict__ off, const UNIT* __restrict__ data, const uint4* __restrict__ timage,
                                                   const uint4* __restrict__ wimage, uint32_t wimage_bytes, uint64_t* __restrict__ keys,
@@ -70,14 +70,14 @@ __global__ void __launch_bounds__(256) k_top_keys(const void* __restrict__ ids, 
             uint32_t e = n_parts;
             if (oc >= ext_lo && oc <= ext_hi) {                    // (oc <= ext_hi < K: a matched extraction)
                 e = where_find(th->ext, n_parts, oc);
-                if (e < n_parts && terms && !where_line_holds<F, UNIT>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_parts;
+                if (e < n_parts && terms && !where_line_holds<F, UNIT, NUM>(wh, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units)) e = n_parts;
             }
             if (e < n_parts) {
                 int32_t pb, pe;
                 int64_t v = 0;
                 pair_of<F>(ids, caps, i, row_units, slots, th->group[e], pb, pe);
                 if (!where_pair_set(pb, pe, line_units)) cls = 1u;
-                else cls = where_parse_int64(data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
+                else cls = number_parse_packed<NUM>(NUM ? th->fmt[e] : 0u, data + o0 + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), &v) ? 0u : 2u;
                 if (cls == 0u) keys[i] = top_key(v, smallest);
             }
             cand[i] = cls == 0u ? 1 : 0;
@@ -231,20 +231,20 @@ __global__ void __launch_bounds__(ORDER_THREADS) k_top_order(const uint64_t* __r
     if (at >= m && at < n_wanted) plen[at] = 0u;
 }
 
-template <typename OFF, typename UNIT>
+template <typename OFF, typename UNIT, bool NUM>
 void launch_keys_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t stream, const void* ids, uint32_t row_units, uint32_t K, uint64_t n, const void* off,
                     const TopArgs& a, const TopWs& w) {
     const OFF* o = static_cast<const OFF*>(off);
     const UNIT* d = static_cast<const UNIT*>(a.data);
     const uint4 *ti = static_cast<const uint4*>(a.image), *wi = static_cast<const uint4*>(a.where_image);
     if (fmt == ROWS_U8)
-        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_U8, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
+        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_U8, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
                            a.where_image_bytes, w.keys, w.cand, w.slab);
     else if (fmt == ROWS_U16)
-        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_U16, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
+        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_U16, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
                            a.where_image_bytes, w.keys, w.cand, w.slab);
     else
-        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_DENSE, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
+        hipLaunchKernelGGL((k_top_keys<OFF, ROWS_DENSE, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, ti, wi,
                            a.where_image_bytes, w.keys, w.cand, w.slab);
 }
 
@@ -285,12 +285,19 @@ hipError_t launch_top_keys(const void* ids, RowFormat fmt, uint32_t row_units, u
     const uint32_t lds = static_cast<uint32_t>(sizeof(TopHead)) + a.where_image_bytes;
     if (lds > 60u * 1024u) return hipErrorInvalidValue;   // (64 terms of 255 two-byte units: 35 KiB)
     const unsigned kb = keys_blocks(n);
+    // (a.formats: a value group or a term reads a group under another number format than LONG -- the instantiation with the wider parser)
+    auto go = [&](auto off_t, auto unit_t) {
+        using OFF = decltype(off_t);
+        using UNIT = decltype(unit_t);
+        if (a.formats) launch_keys_as<OFF, UNIT, true>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
+        else launch_keys_as<OFF, UNIT, false>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
+    };
     if (a.wide) {
-        if (offsets64) launch_keys_as<uint64_t, uint16_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
-        else launch_keys_as<uint32_t, uint16_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
+        if (offsets64) go(uint64_t{}, uint16_t{});
+        else go(uint32_t{}, uint16_t{});
     } else {
-        if (offsets64) launch_keys_as<uint64_t, uint8_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
-        else launch_keys_as<uint32_t, uint8_t>(fmt, kb, lds, stream, ids, row_units, K, n, offsets, a, w);
+        if (offsets64) go(uint64_t{}, uint8_t{});
+        else go(uint32_t{}, uint8_t{});
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

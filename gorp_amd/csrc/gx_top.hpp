@@ -93,9 +93,12 @@ GX_WHERE_HD bool top_chosen(const TopSelect& s, uint64_t key, uint64_t eq_rank) 
 // The parts as the keys pass reads them, built by the host (gx_api.cpp: top_image) and copied to LDS by every workgroup: the
 // extractions that have a part, ascending (searched with where_find), and each one's value group.
 struct TopHead {
-    uint32_t n_parts, smallest, pad[2];
+    uint32_t n_parts, smallest;
+    uint32_t formats;                // != 0: some fmt[] is not LONG -- the host launches the keys pass's instantiation that reads them
+    uint32_t pad;
     uint32_t ext[TOP_MAX_PARTS];
     uint16_t group[TOP_MAX_PARTS];
+    uint8_t fmt[TOP_MAX_PARTS];      // group[e]'s packed number format (gx_number.hpp), 0 = LONG
 };
 static_assert(sizeof(TopHead) % 16 == 0, "the head is copied in 16-byte words");
 

@@ -25,7 +25,7 @@ namespace {
 extern __shared__ __attribute__((aligned(16))) uint32_t where_smem[];
 
 // image: WhereHead + literals (image_bytes, a multiple of 16).  want_lds != 0: the mask's 2K + 1 bytes go to LDS behind them.
-template <typename OFF, RowFormat F, typename UNIT>
+template <typename OFF, RowFormat F, typename UNIT, bool NUM>
 __global__ void __launch_bounds__(256) k_where_flags(const void* __restrict__ ids, const int32_t* __restrict__ caps, uint32_t row_units, uint32_t slots,
                                                      uint32_t K, uint64_t n, const OFF* __restrict__ off, const UNIT* __restrict__ data,
                                                      const uint8_t* __restrict__ want, const uint4* __restrict__ image, uint32_t image_bytes,
@@ -53,27 +53,27 @@ __global__ void __launch_bounds__(256) k_where_flags(const void* __restrict__ id
         if (len > 0xFFFFFFFFull) atomicOr(status, 1u);   // (a line of 4 G code units, or offsets that go backwards: refused by the host)
         if (kept && oc >= ext_lo && oc <= ext_hi) {   // (oc <= ext_hi < K: a matched extraction)
             const uint64_t line_units = len > 0xFFFFFFFFull ? 0u : len;   // (no value is looked at in a line that is refused anyway)
-            kept = where_line_holds<F, UNIT>(head, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units);
+            kept = where_line_holds<F, UNIT, NUM>(head, lits, oc, ids, caps, i, row_units, slots, data + o0, line_units);
         }
         flags[i] = kept ? 1 : 0;
         klen[i] = kept ? static_cast<uint32_t>(len) : 0u;
     }
 }
 
-template <typename OFF, typename UNIT>
+template <typename OFF, typename UNIT, bool NUM>
 void launch_where_as(RowFormat fmt, unsigned blocks, uint32_t lds, hipStream_t stream, const void* ids, uint32_t row_units, uint32_t K, uint64_t n, const void* off,
                      const WhereArgs& a, uint32_t want_lds, const SelectWs& w) {
     const OFF* o = static_cast<const OFF*>(off);
     const UNIT* d = static_cast<const UNIT*>(a.data);
     const uint4* img = static_cast<const uint4*>(a.image);
     if (fmt == ROWS_U8)
-        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_U8, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
+        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_U8, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
                            a.image_bytes, want_lds, w.flags, w.klen, w.status);
     else if (fmt == ROWS_U16)
-        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_U16, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
+        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_U16, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
                            a.image_bytes, want_lds, w.flags, w.klen, w.status);
     else
-        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_DENSE, UNIT>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
+        hipLaunchKernelGGL((k_where_flags<OFF, ROWS_DENSE, UNIT, NUM>), dim3(blocks), dim3(256), lds, stream, ids, a.caps, row_units, a.slots, K, n, o, d, w.want, img,
                            a.image_bytes, want_lds, w.flags, w.klen, w.status);
 }
 
@@ -92,12 +92,19 @@ hipError_t launch_where_flags(const void* ids, RowFormat fmt, uint32_t row_units
         const uint32_t want_lds = bins <= SELECT_LDS_BINS ? 1u : 0u;
         const uint32_t lds = a.image_bytes + (want_lds ? ((bins + 15u) & ~15u) : 0u);
         const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((n + 255) / 256, 2048));
+        // (a.formats: a term reads a group under another number format than LONG -- the instantiation with the wider parser)
+        auto go = [&](auto off_t, auto unit_t) {
+            using OFF = decltype(off_t);
+            using UNIT = decltype(unit_t);
+            if (a.formats) launch_where_as<OFF, UNIT, true>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
+            else launch_where_as<OFF, UNIT, false>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
+        };
         if (a.wide) {
-            if (offsets64) launch_where_as<uint64_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
-            else launch_where_as<uint32_t, uint16_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
+            if (offsets64) go(uint64_t{}, uint16_t{});
+            else go(uint32_t{}, uint16_t{});
         } else {
-            if (offsets64) launch_where_as<uint64_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
-            else launch_where_as<uint32_t, uint8_t>(fmt, blocks, lds, stream, ids, row_units, K, n, offsets, a, want_lds, w);
+            if (offsets64) go(uint64_t{}, uint8_t{});
+            else go(uint32_t{}, uint8_t{});
         }
         e = hipGetLastError();
         if (e != hipSuccess) return e;

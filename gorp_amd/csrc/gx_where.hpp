@@ -6,8 +6,9 @@
 // A TERM is one such test on one group of one extraction: test(value) XOR negate.  The value is the code units
 // line[begin, end) that the group's capture offsets name; a group that is unset (Matcher.group(g) == null), or whose offsets do not
 // lie inside the line (where_pair_set), fails every test.  Text tests compare code units -- bytes, or 16-bit units of a utf16 batch --
-// with a literal; integer tests parse the value as Long.parseLong does for ASCII input (where_parse_int64).  Every loop is bounded by
-// the value's length or the literal's, and nothing outside [value, value + length) is read.
+// with a literal; integer tests parse the value as Long.parseLong does for ASCII input (where_parse_int64) -- or, where the group has
+// a number format of its own (gx_set_number_format), as gx_number.hpp's number_where_test does.  Every loop is bounded by the value's
+// length or the literal's, and nothing outside [value, value + length) is read.
 #pragma once
 #include <cstdint>
 
@@ -112,9 +113,11 @@ struct WhereTerm {
     int64_t number;
 };
 struct WhereHead {
-    uint32_t n_terms, n_ext, lit_units, pad;
+    uint32_t n_terms, n_ext, lit_units;
+    uint32_t formats;                      // != 0: some fmt[] is not LONG -- the host launches the pass's instantiation that reads them
     uint32_t ext[WHERE_MAX_TERMS];
     uint8_t first[WHERE_MAX_TERMS + 16];   // n_ext + 1 entries
+    uint8_t fmt[WHERE_MAX_TERMS];          // term[t]'s group as a number: its packed format (gx_number.hpp), 0 = LONG; integer terms only
     WhereTerm term[WHERE_MAX_TERMS];
 };
 static_assert(sizeof(WhereTerm) == 16 && sizeof(WhereHead) % 16 == 0, "the head is copied in 16-byte words");

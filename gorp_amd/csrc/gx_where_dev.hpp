@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gx_layout.hpp"
+#include "gx_number.hpp"
 #include "gx_where.hpp"
 
 namespace gx {
@@ -32,8 +33,9 @@ __device__ __forceinline__ void pair_of(const void* ids, const int32_t* caps, ui
 // Line i, whose outcome oc is a matched extraction: does every term of that extraction hold?  head / lits: the term image (WhereHead,
 // then the literals) in LDS; line: the line's first code unit; line_units: its length (0 for a line the call refuses anyway -- then no
 // value is looked at).  An extraction without terms holds.  The terms are tested in the caller's order and a line leaves at its first
-// term that fails; a pair that names no value (where_pair_set) is never dereferenced.
-template <RowFormat F, typename UNIT>
+// term that fails; a pair that names no value (where_pair_set) is never dereferenced.  NUM: an integer term parses its value under
+// the format beside it (WhereHead::fmt); without it every one is Long.parseLong's, the code of a call that names LONG groups alone.
+template <RowFormat F, typename UNIT, bool NUM>
 __device__ __forceinline__ bool where_line_holds(const WhereHead* head, const UNIT* lits, uint32_t oc, const void* ids, const int32_t* caps, uint64_t i,
                                                  uint32_t row_units, uint32_t slots, const UNIT* line, uint64_t line_units) {
     const uint32_t n_ext = head->n_ext;
@@ -47,7 +49,8 @@ __device__ __forceinline__ bool where_line_holds(const WhereHead* head, const UN
         pair_of<F>(ids, caps, i, row_units, slots, m.group, pb, pe);
         bool holds = false;
         if (where_pair_set(pb, pe, line_units))
-            holds = where_test(m.op, line + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), lits + m.lit_at, m.lit_len, m.number);
+            holds = number_where_test<NUM>(NUM ? head->fmt[t] : 0u, m.op, line + static_cast<uint32_t>(pb), static_cast<uint32_t>(pe - pb), lits + m.lit_at,
+                                           m.lit_len, m.number);
         kept = kept && (holds != (m.negate != 0));
     }
     return kept;

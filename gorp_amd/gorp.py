@@ -793,8 +793,10 @@ class Gorp:
         """Resolves a list of (extraction, extractor, op, value) -- value may be left out for "set" / "unset" -- into gx_where_term
         records: extraction is a name or an index, extractor a name or a group index (a name two groups of the extraction share is a
         ValueError), op one of "set", "unset", "==", "!=", "startswith", "endswith", "contains", "not contains", "<", "<=", ">",
-        ">=".  An int value selects the integer form of == / != (Long.parseLong's rule for ASCII input); a str is encoded to the
-        batch's code units (units: "latin-1" bytes, "utf-8" bytes or "utf-16" units), bytes are taken as they are.  Returns
+        ">=".  An int value selects the integer form of == / != (the group's number format: set_number_format; Long.parseLong's
+        rule for ASCII input by default); a str is encoded to the batch's code units (units: "latin-1" bytes, "utf-8" bytes or
+        "utf-16" units), bytes are taken as they are.  The number of "<", "<=", ">", ">=" may be a str where the group has a number
+        format other than "long": it is converted by parse_number under that format (GorpError if it is no number).  Returns
         (ctypes array, number of terms, what keeps the literals alive); a WhereTerms passes through."""
         if isinstance(spec, WhereTerms):
             return spec
@@ -846,6 +848,13 @@ class Gorp:
                 if not -2 ** 63 <= int(value) < 2 ** 63:
                     raise ValueError("a number must fit int64")
                 m.number = int(value)
+            elif isinstance(value, str) and code >= N.GX_WHERE_INT_EQ and self.number_format(k, g)[0] != "long":
+                # (a group with a number format of its own: the str is a number in that format, "2026-01-03T00:00:00Z")
+                kind, scale = self.number_format(k, g)
+                number = parse_number(kind, scale, value)
+                if number is None:
+                    raise GorpError(N.GX_E_ARG, "%r is no number under %s(%d), the format of %r group %d" % (value, kind, scale, names[k], g))
+                m.number = number
             elif isinstance(value, (str, bytes, bytearray)):
                 if code >= N.GX_WHERE_INT_EQ:
                     raise ValueError("%r takes an int" % op)
@@ -979,6 +988,28 @@ class Gorp:
         if groups.count(group) > 1:
             raise ValueError("extractor name %r is shared by %d groups of %r: name the group by its index" % (group, groups.count(group), names[k]))
         raise ValueError("extraction %r has no extractor %r" % (names[k], group))
+
+    # -- how a group is read as a number (gx_set_number_format) ----------------------------------------------------------
+    def set_number_format(self, extraction, group, kind, scale=0):
+        """gx_set_number_format: from now on every call that parses this group as a number -- where_terms' integer comparisons,
+        capture_stats, the value group of group_lines / group_quantiles / top_groups / top_lines / capture_quantiles -- reads it as
+        kind "long" (Long.parseLong, the default), "decimal" (scale 0 .. 18: the value times 10^scale, cut toward zero), "iso8601" or
+        "clf" (scale 0, 3, 6 or 9: the instant in 10^-scale seconds since the epoch).  extraction and group are resolved as
+        where_terms resolves them.  Needs no device; not kept in the blob."""
+        k, g = self._extraction_and_group(extraction, group)
+        if kind not in NUMBER_KINDS:
+            raise ValueError("kind: long, decimal, iso8601 or clf")
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 0 <= int(scale) < 2 ** 32:
+            raise ValueError("scale: a non-negative int")
+        f = N.gx_number_format(NUMBER_KINDS.index(kind), int(scale))
+        _check(N.lib().gx_set_number_format(self._h.ptr, k, g, C.byref(f)))
+
+    def number_format(self, extraction, group):
+        """(kind, scale) of the group: gx_get_number_format."""
+        k, g = self._extraction_and_group(extraction, group)
+        f = N.gx_number_format()
+        _check(N.lib().gx_get_number_format(self._h.ptr, k, g, C.byref(f)))
+        return NUMBER_KINDS[f.kind], int(f.scale)
 
     def measures(self, spec):
         """Resolves a list of (extraction, extractor) or (extraction, extractor, edges) into gx_measure records: extraction is a name or
@@ -2155,6 +2186,26 @@ class Gorp:
                     r._input = line
                 out.append(r)
         return out
+
+
+NUMBER_KINDS = ("long", "decimal", "iso8601", "clf")
+
+
+def parse_number(kind, scale, text):
+    """gx_parse_number: text (str, or bytes) as a number under the format (kind, scale) -- the rule the device applies to a captured
+    value (set_number_format) -- or None when it is no number.  parse_number("iso8601", 3, "2026-01-03T00:00:00Z") is a term's
+    number for a group read as epoch milliseconds."""
+    if kind not in NUMBER_KINDS:
+        raise ValueError("kind: long, decimal, iso8601 or clf")
+    f = N.gx_number_format(NUMBER_KINDS.index(kind), int(scale))
+    if isinstance(text, str):
+        units = np.frombuffer(text.encode("utf-16-le"), dtype=np.uint16).copy()
+    else:
+        units = np.frombuffer(bytes(text), dtype=np.uint8).copy()
+    value, is_number = C.c_int64(0), C.c_int32(0)
+    _check(N.lib().gx_parse_number(C.byref(f), units.ctypes.data if units.size else None, units.size, 1 if units.dtype == np.uint16 else 0,
+                                   C.byref(value), C.byref(is_number)))
+    return int(value.value) if is_number.value else None
 
 
 class _ByteSlices:

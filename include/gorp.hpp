@@ -296,6 +296,23 @@ public:
         s.offsets.resize(static_cast<size_t>(k) + 1);
         return s;
     }
+    // How a group is read as a number (gx_set_number_format): setNumberFormat("Syslog", "ts", {GX_NUMBER_ISO8601, 3}) makes every
+    // integer term, measure and value group on it the caller's Instant.parse(r.asMap().get("ts")).toEpochMilli().  Names resolve as
+    // Where's do.  Not thread-safe against calls on the same Gorp.
+    void setNumberFormat(const std::string& extraction, const std::string& extractor, gx_number_format format) {
+        Where at(this);
+        at.on(extraction, extractor).isSet();
+        const gx_where_term t = at.terms()[0];
+        if (gx_set_number_format(h_, t.extraction, t.group, &format) != GX_OK) throw GorpError(GX_E_ARG, gx_last_error());
+    }
+    gx_number_format numberFormat(const std::string& extraction, const std::string& extractor) const {
+        Where at(this);
+        at.on(extraction, extractor).isSet();
+        const gx_where_term t = at.terms()[0];
+        gx_number_format f{};
+        if (gx_get_number_format(h_, t.extraction, t.group, &f) != GX_OK) throw GorpError(GX_E_ARG, gx_last_error());
+        return f;
+    }
     // Captured numbers, summarised (gx_capture_stats): the measures of a call, built by name.  measures().of("GetRequest",
     // "timeTakenInMsec", {10, 100, 500, 1000}) is the caller's metrics.record(Long.parseLong(r.asMap().get("timeTakenInMsec")))
     // (README.md:26,63-79) with a latency histogram.  Names resolve as Where's do; edges are strictly ascending, at most 64.

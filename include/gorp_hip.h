@@ -922,6 +922,38 @@ int gx_unpack_results8(const uint8_t* rows, uint64_t n, int32_t slots, int32_t* 
 int gx_set_extraction_meta(gx_handle* h, int32_t k, const char* name, const char* const* extractor_names, int32_t n_names,
                            const char* append_json);
 
+/* How a captured value is read as a number.  The reference's caller does not only Long.parseLong what a line captured
+ * (README.md:26,63-79): its next line is as often Instant.parse(r.asMap().get("ts")).toEpochMilli() or
+ * new BigDecimal(r.asMap().get("request_time")).  A FORMAT {kind, scale} is a property of group g of extraction k, kept on the
+ * handle like the names of gx_set_extraction_meta.  Wherever a call parses that group as a number -- the GX_WHERE_INT_* terms of
+ * gx_select_lines_where, a measure of gx_capture_stats, the value group of gx_group_lines / gx_group_quantiles / gx_top_groups /
+ * gx_top_lines / gx_capture_quantiles, and their gx_text_* forms -- it parses it under the group's format, and a term's `number`,
+ * a measure's `edges` and every min / max / sum / quantile / ranked value are in the format's unit.  Nothing else sees the format:
+ * text terms, keys, the extraction itself and JSON Lines read the value as text.  The rule: gorp_amd/csrc/gx_number.hpp.
+ *   GX_NUMBER_LONG     scale 0: Long.parseLong on ASCII.  The default of every group.
+ *   GX_NUMBER_DECIMAL  scale 0 .. 18: [+-]? ( digits+ ( '.' digits* )? | '.' digits+ ), the value times 10^scale with further
+ *                      fraction digits dropped toward zero: new BigDecimal(t).setScale(scale, RoundingMode.DOWN).unscaledValue()
+ *                      .longValueExact().  No exponent, no grouping.  "-0.0004" at scale 3 is 0; "12.7" at scale 0 is 12.
+ *   GX_NUMBER_ISO8601  scale 0, 3, 6 or 9: YYYY-MM-DD, 'T' / 't' / one space, hh:mm:ss, an optional '.' or ',' and 1 .. 9 digits,
+ *                      an optional zone: 'Z', 'z', +hh:mm, +hhmm, +hh (either sign, at most 18:00); none is UTC.  The value is the
+ *                      instant in 10^-scale seconds since the epoch, further digits dropped (toEpochMilli's floor): scale 3 of
+ *                      "1969-12-31T23:59:59.999Z" is -1.  Years 0001 .. 9999; year 0000, ":60", "24:00:00", date-only, week and
+ *                      ordinal dates are no numbers, and at scale 9 neither is an instant outside int64 nanoseconds.
+ *   GX_NUMBER_CLF      scale 0, 3, 6 or 9: the access-log stamp "dd/Mon/yyyy:HH:mm:ss +hhmm", exactly
+ *                      (DateTimeFormatter.ofPattern("dd/MMM/yyyy:HH:mm:ss Z", Locale.ENGLISH)).
+ * Whatever fits no grammar or lies outside int64 is "not a number", as today.  RFC 3164 stamps carry no year: out of scope.
+ * The setters need no device (a host-only handle takes them) and must not run concurrently with a call on the handle.  The format
+ * is not part of the blob: gx_blob_copy gives the same bytes before and after, and a handle from a blob -- each handle of
+ * gx_create_on_devices too -- starts with LONG everywhere.  GX_E_ARG: h / k / g out of range, an unknown kind, a scale the kind does
+ * not take.  f == NULL sets the group back to LONG.
+ * gx_parse_number is the rule on the host: units[0, n_units) (bytes, or 16-bit units with utf16 != 0) under *f (NULL: LONG);
+ * *is_number = 0 / 1, and *value when it is 1.  It is how a caller turns "2026-01-03T00:00:00Z" into a term's `number`. */
+enum { GX_NUMBER_LONG = 0, GX_NUMBER_DECIMAL, GX_NUMBER_ISO8601, GX_NUMBER_CLF };
+typedef struct gx_number_format { uint32_t kind, scale; } gx_number_format;
+int gx_set_number_format(gx_handle* h, int32_t k, int32_t g, const gx_number_format* f);
+int gx_get_number_format(const gx_handle* h, int32_t k, int32_t g, gx_number_format* out);
+int gx_parse_number(const gx_number_format* f, const void* units, uint32_t n_units, uint32_t utf16, int64_t* value, int32_t* is_number);
+
 /* Replaces one Gorp.extract(String) call (core/Gorp.java:145-147): s is the
  * String's UTF-16 code units.  Runs on the GPU like the batch path.
  * caps has 2*gx_max_groups(h) slots. */
