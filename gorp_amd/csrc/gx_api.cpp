@@ -1095,6 +1095,39 @@ static const GxJsonl& jsonl_templates(gx_handle* h, const char* id_as) {
     return h->jsonl.emplace(key, std::move(ji)).first->second.dev;
 }
 
+// What a pass over a batch's results reads, all of it in device memory: the ids (dense, or compact rows of row_units units), the
+// n + 1 line offsets, the text in 8- or 16-bit units (wide), and the dense capture rows (nullptr: none, or compact rows hold them).
+struct BatchView {
+    const void* ids;
+    RowFormat fmt;
+    uint32_t row_units;
+    uint64_t n;
+    const void* offsets;
+    bool off64;
+    const void* data;
+    const int32_t* caps;
+    bool wide;
+};
+// A whole-file call's text on the device: the caller's own pointer (device_pointers; refused unless 16-byte aligned), or a copy that
+// lives as long as this object.
+namespace {
+struct StagedText {
+    DevMem<uint8_t> copy;
+    const uint8_t* src;
+};
+}  // namespace
+static StagedText stage_text(const uint8_t* text, uint64_t size, const gx_batch_opts& o, hipStream_t stream, const char* name) {
+    StagedText t{{}, text};
+    if (!o.device_pointers) {
+        t.copy = dev_alloc<uint8_t>(size);
+        if (size) GX_HIP(hipMemcpyAsync(t.copy.get(), text, size, hipMemcpyHostToDevice, stream));
+        t.src = t.copy.get();
+    } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
+        throw GxError(GX_E_ARG, std::string(name) + ": device text must be 16-byte aligned");
+    }
+    return t;
+}
+
 // Steps 1 and 2 of the whole-file calls (gx_text_to_jsonl, gx_text_select), under h->mu: raw text on the device -> line offsets
 // (gx_split_lines semantics, 32-bit) -> the match-and-extract path, enqueued on `stream`.  Everything lives in the handle's scratch:
 // 2 split workspace, 3 offsets, 4 ids, 5 captures (dense rows; unset for a handle without capture regexps).  The line count is read
@@ -1104,6 +1137,8 @@ struct TextLines {
     GxBatch b;
     uint32_t mean_in;
     bool no_control_bytes;   // with esc_bits: no byte of the text takes five more bytes inside a JSON string
+    // what the passes behind the path read: dense ids, 32-bit offsets, the text's bytes, dense capture rows
+    BatchView view() const { return {b.match_id, ROWS_DENSE, 1, n, b.offsets, false, b.data, b.caps, false}; }
 };
 // utf8 (gx_batch_opts.utf8 = 1; not with esc_bits: the split pass's first kernel makes EITHER the escape bits or the masks of the bytes
 // >= 0x80 that the line flags come from -- launch_split_lines refuses both at once -- so a utf8 text's JSON sizes are taken from the text
@@ -1150,6 +1185,18 @@ static TextLines text_lines(gx_handle* h, const uint8_t* src, uint64_t size, siz
     if (utf8) utf8_fixup(h, b, 1, d_flags, stream);
     if (!h->T.has_capture && n && slots) GX_HIP(hipMemsetAsync(d_caps, 0xFF, n * slots * 4, stream));
     b.caps = static_cast<int32_t*>(d_caps);
+    return t;
+}
+// A whole-file reduction's batch: the text staged, split and extracted (no escape bits), and the view of what that left (v.n: the text's lines).
+namespace {
+struct TextBatch {
+    StagedText text;
+    BatchView v;
+};
+}  // namespace
+static TextBatch stage_text_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_batch_opts& o, hipStream_t stream, const char* name) {
+    TextBatch t{stage_text(text, size, o, stream, name), {}};
+    t.v = text_lines(h, t.text.src, size, 2 * static_cast<size_t>(h->T.max_groups), stream, nullptr, 0, o.utf8 != 0).view();
     return t;
 }
 
@@ -1226,22 +1273,16 @@ int gx_text_to_jsonl(gx_handle* h, const uint8_t* text, uint64_t size, const cha
         std::lock_guard<std::mutex> lock(h->mu);
         const GxJsonl& tm = jsonl_templates(h, id_as);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text, d_out;   // (host buffers only; everything between lives in the handle's scratch: 2 split workspace, 3 offsets, 4 ids, 5 captures, 6 counts)
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, "gx_text_to_jsonl: device text must be 16-byte aligned");
-        }
+        // (host buffers only; everything between lives in the handle's scratch: 2 split workspace, 3 offsets, 4 ids, 5 captures, 6 counts)
+        const StagedText st = stage_text(text, size, o, stream, "gx_text_to_jsonl");
+        DevMem<uint8_t> d_out;
         // 1. lines, 2. the path
         // (the split pass also leaves a bit per byte that takes one more byte inside a JSON string, and says whether some byte takes five
         // more -- a control character --: without one, the sizes pass below does not read the text again)
         // (utf8: the split pass makes line flags in their place)
         uint16_t* esc_bits = o.utf8 ? nullptr : static_cast<uint16_t*>(h->scratch[7].get(((size + 32767) / 32768) * 4096 + 64));   // (written in whole blocks of 32 KiB of text)
         const int passthrough = (o.utf8_passthrough || o.utf8) ? 1 : 0;   // (utf8 implies it)
-        const TextLines tl = text_lines(h, src, size, slots, stream, esc_bits, passthrough, o.utf8 != 0);
+        const TextLines tl = text_lines(h, st.src, size, slots, stream, esc_bits, passthrough, o.utf8 != 0);
         const uint64_t n = tl.n;
         const GxBatch& b = tl.b;
         const uint32_t mean_in = tl.mean_in;
@@ -1284,11 +1325,121 @@ static RowFormat id_format(const gx_handle* h, const gx_batch_opts& o, uint32_t*
     return f;
 }
 
-// The flags pass and, with offsets, the two scans behind it, on the handle's workspace (under h->mu); then the host reads what
-// it must know before anything is written -- the number of kept lines and of kept code units, and whether a line was too long
-// to count -- and the histogram if the caller wants it: ONE small synchronisation of the stream, as gx_pack_results has
-// (before it the want mask goes to the device: a second small transfer per call, from pageable memory, which the runtime stages).
-// ids / offsets / want: device pointers, except want (host, uint8_t[2K + 1]; nullptr with offsets == nullptr: counts alone).
+// A "lines" call's batch on the device.  With device_pointers the view is of the caller's own pointers; host buffers are copied to
+// device memory that lives as long as this object, and the view is of the copies.
+namespace {
+struct StagedLines {
+    BatchView v;
+    DevMem<> bytes, offsets, ids, caps;
+};
+}  // namespace
+// what of a host batch a call's passes read besides the ids and the offsets (device pointers travel nowhere)
+struct Travels {
+    bool text, caps;
+};
+static StagedLines stage_lines(const gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_batch_opts& o,
+                               RowFormat fmt, uint32_t row_units, Travels travels, hipStream_t stream, const char* name) {
+    StagedLines s{{ids, fmt, row_units, n, offsets, o.offsets64 != 0, bytes, caps, o.utf16 != 0}, {}, {}, {}, {}};
+    if (o.device_pointers) return s;
+    const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    const size_t in_bytes = static_cast<size_t>(HostOffsets{offsets, o.offsets64 != 0, n}[n]) * unit;
+    if (in_bytes && !bytes) throw GxError(GX_E_ARG, std::string(name) + ": bytes is NULL");
+    if (travels.text) s.bytes = dev_alloc(in_bytes);
+    s.offsets = dev_alloc((n + 1) * off_w);
+    s.ids = dev_alloc(n * id_row);
+    if (travels.text && in_bytes) GX_HIP(hipMemcpyAsync(s.bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
+    GX_HIP(hipMemcpyAsync(s.offsets.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
+    if (n) GX_HIP(hipMemcpyAsync(s.ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
+    if (travels.caps && n && slots) {
+        s.caps = dev_alloc(n * slots * 4);
+        GX_HIP(hipMemcpyAsync(s.caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
+    }
+    s.v.data = s.bytes.get(); s.v.offsets = s.offsets.get(); s.v.ids = s.ids.get(); s.v.caps = static_cast<const int32_t*>(s.caps.get());
+    return s;
+}
+
+// Host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the call's first pass.
+static void refuse_long_host_lines(const HostOffsets& off, const std::string& name, const char* verb) {
+    for (uint64_t i = 0; i < off.n; ++i)
+        if (off[i + 1] - off[i] > 0xFFFFFFFFull) throw GxError(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be " + verb);
+}
+
+// A pass left running on a caller's stream still reads one of the handle's workspaces (select_event, group_event, top_event): it
+// records the event, and the workspace's next user makes its stream wait for it first.
+static void leave_pending(Event& event, bool& pending, hipStream_t stream) {
+    if (!event) GX_HIP(hipEventCreateWithFlags(event.out(), hipEventDisableTiming));
+    GX_HIP(hipEventRecord(event.get(), stream));
+    pending = true;
+}
+static void wait_pending(const Event& event, bool& pending, hipStream_t stream) {
+    if (!pending) return;
+    GX_HIP(hipStreamWaitEvent(stream, event.get(), 0));
+    pending = false;
+}
+
+// Where selected lines go: the caller's pointers, each nullptr when not wanted.
+struct LinesOut {
+    uint32_t* index;
+    void* bytes;
+    void* offsets;
+    void* ids;
+    int32_t* caps;
+    bool per_line() const { return index || offsets || ids || caps; }
+    bool any() const { return per_line() || bytes; }
+};
+// What the copy pass (launch_select_copy, launch_partition_copy) writes for `lines` lines of `units` code units: straight to the
+// caller's device pointers, or -- host buffers -- to device twins that live as long as this object and that deliver() copies back.
+namespace {
+struct StagedLinesOut {
+    SelectOut dev{};
+    DevMem<> index, bytes, offsets, ids, caps;
+};
+}  // namespace
+static StagedLinesOut stage_lines_out(const gx_handle* h, const BatchView& v, const LinesOut& out, bool host, uint64_t lines, uint64_t units) {
+    const size_t off_w = v.off64 ? 8 : 4, unit = v.wide ? 2 : 1, id_row = static_cast<size_t>(v.row_units) * row_unit_bytes(v.fmt);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    StagedLinesOut s;
+    s.dev.index = out.index; s.dev.bytes = out.bytes; s.dev.offsets = out.offsets;
+    void *dst_ids = out.ids, *dst_caps = out.caps;
+    if (host) {
+        if (out.index) { s.index = dev_alloc(lines * 4); s.dev.index = static_cast<uint32_t*>(s.index.get()); }
+        if (out.bytes) { s.bytes = dev_alloc(units * unit); s.dev.bytes = s.bytes.get(); }
+        if (out.offsets) { s.offsets = dev_alloc((lines + 1) * off_w); s.dev.offsets = s.offsets.get(); }
+        if (out.ids) { s.ids = dev_alloc(lines * id_row); dst_ids = s.ids.get(); }
+        if (out.caps) { s.caps = dev_alloc(lines * slots * 4); dst_caps = s.caps.get(); }
+    }
+    if (out.ids) { s.dev.col_src[0] = v.ids; s.dev.col_dst[0] = dst_ids; s.dev.col_width[0] = v.row_units; s.dev.col_unit_bytes[0] = row_unit_bytes(v.fmt); }
+    if (out.caps) { s.dev.col_src[1] = v.caps; s.dev.col_dst[1] = dst_caps; s.dev.col_width[1] = static_cast<uint32_t>(slots); s.dev.col_unit_bytes[1] = 4; }
+    return s;
+}
+// behind the copy pass, host buffers only: the twins back to the caller's buffers
+static void deliver_lines_out(const gx_handle* h, const BatchView& v, const LinesOut& out, const StagedLinesOut& s, uint64_t lines, uint64_t units,
+                              hipStream_t stream) {
+    const size_t off_w = v.off64 ? 8 : 4, unit = v.wide ? 2 : 1, id_row = static_cast<size_t>(v.row_units) * row_unit_bytes(v.fmt);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    if (out.index && lines) GX_HIP(hipMemcpyAsync(out.index, s.dev.index, lines * 4, hipMemcpyDeviceToHost, stream));
+    if (out.bytes && units) GX_HIP(hipMemcpyAsync(out.bytes, s.dev.bytes, units * unit, hipMemcpyDeviceToHost, stream));
+    if (out.offsets) GX_HIP(hipMemcpyAsync(out.offsets, s.dev.offsets, (lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
+    if (out.ids && lines) GX_HIP(hipMemcpyAsync(out.ids, s.dev.col_dst[0], lines * id_row, hipMemcpyDeviceToHost, stream));
+    if (out.caps && lines) GX_HIP(hipMemcpyAsync(out.caps, s.dev.col_dst[1], lines * slots * 4, hipMemcpyDeviceToHost, stream));
+}
+
+// The histogram of a batch's outcomes beside a reduction of it (k_select_flags' counting form, on the handle's select workspace, under
+// h->mu): enqueued on `stream`, and in counts[2K + 2] once the caller's next wait for the stream is over.  Only v's ids are read.
+static void counts_beside(gx_handle* h, const BatchView& v, uint64_t* counts, hipStream_t stream) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    wait_pending(h->select_event, h->select_pending, stream);
+    const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(v.n, K, false)), v.n, K, false);
+    GX_HIP(launch_select_flags(v.ids, v.fmt, v.row_units, K, v.n, nullptr, 0, w, stream));
+    GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+}
+
+// The flags pass and the two scans behind it, on the handle's workspace (under h->mu); then the host reads what it must know
+// before anything is written -- the number of kept lines and of kept code units, and whether a line was too long to count -- and
+// the histogram if the caller wants it: ONE small synchronisation of the stream, as gx_pack_results has (before it the want mask
+// goes to the device: a second small transfer per call, from pageable memory, which the runtime stages).
+// want: host, uint8_t[2K + 1].
 struct Selected {
     SelectWs w;
     uint64_t lines = 0, units = 0;
@@ -1351,40 +1502,27 @@ static WhereImage where_image(const gx_handle* h, const gx_where_term* terms, ui
     memcpy(img.bytes.data(), &head, sizeof(head));
     return img;
 }
-// what a flags pass with terms reads besides the ids and offsets (device pointers; caps: dense capture rows or nullptr)
-struct WhereBatch {
-    const WhereImage* image;
-    const void* data;
-    const int32_t* caps;
-    bool wide;
-};
-static Selected select_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const uint8_t* want,
-                     uint64_t* counts, hipStream_t stream, const WhereBatch* where = nullptr) {
+static Selected select_pass(gx_handle* h, const BatchView& v, const uint8_t* want, const WhereImage& where, uint64_t* counts, hipStream_t stream) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
-    if (h->select_pending) {
-        GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-        h->select_pending = false;
-    }
+    const uint64_t n = v.n;
+    wait_pending(h->select_event, h->select_pending, stream);
     Selected s;
-    s.w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, offsets != nullptr)), n, K, offsets != nullptr);
-    if (offsets) GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
-    if (where && !where->image->none()) {
+    s.w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, true)), n, K, true);
+    GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
+    if (!where.none()) {
         // (the terms and literals go beside the mask, the same way: a small transfer from pageable memory)
-        const std::vector<uint8_t>& img = where->image->bytes;
-        void* d_img = h->where_image.get(img.size());
-        GX_HIP(hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, stream));
-        const WhereArgs a{where->data, where->wide ? 1 : 0, where->caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(img.size()),
-                              where->image->formats ? 1u : 0u};
-        GX_HIP(launch_where_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, counts != nullptr, s.w, stream));
+        void* d_img = h->where_image.get(where.bytes.size());
+        GX_HIP(hipMemcpyAsync(d_img, where.bytes.data(), where.bytes.size(), hipMemcpyHostToDevice, stream));
+        const WhereArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(where.bytes.size()),
+                          where.formats ? 1u : 0u};
+        GX_HIP(launch_where_flags(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, counts != nullptr, s.w, stream));
     } else {
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+        GX_HIP(launch_select_flags(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, s.w, stream));
     }
     uint32_t status = 0;
-    if (offsets) {
-        GX_HIP(hipMemcpyAsync(&s.lines, s.w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&s.units, s.w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&status, s.w.status, 4, hipMemcpyDeviceToHost, stream));
-    }
+    GX_HIP(hipMemcpyAsync(&s.lines, s.w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&s.units, s.w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&status, s.w.status, 4, hipMemcpyDeviceToHost, stream));
     if (counts) GX_HIP(hipMemcpyAsync(counts, s.w.counts, static_cast<size_t>(bins) * 8, hipMemcpyDeviceToHost, stream));
     GX_HIP(hipStreamSynchronize(stream));
     if (status) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be selected");
@@ -1408,7 +1546,8 @@ int gx_count_outcomes(gx_handle* h, const void* ids, uint64_t n, uint64_t* count
             if (bytes) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, bytes, hipMemcpyHostToDevice, stream));
             ids = d_ids.get();
         }
-        select_pass(h, ids, fmt, row_units, n, nullptr, false, nullptr, counts, stream);
+        counts_beside(h, BatchView{ids, fmt, row_units, n, nullptr, false, nullptr, nullptr, false}, counts, stream);
+        GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });
 }
@@ -1443,63 +1582,26 @@ static int select_lines_call(const char* fn, bool where, gx_handle* h, const voi
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        const size_t unit = o.utf16 ? 2 : 1;
         const bool host = !o.device_pointers;
-        // host buffers are staged to the device and back; the passes are the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps, d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (host) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
-            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if ((out_caps || (caps && !image.none())) && n && slots) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        const WhereBatch wb{&image, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0};
-        const Selected s = select_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, nullptr, stream, &wb);
+        // (the capture rows travel only if they are asked for, or read by terms)
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, out_caps || (caps && !image.none())}, stream, name.c_str());
+        const BatchView& v = in.v;
+        const Selected s = select_pass(h, v, want, image, nullptr, stream);
         *n_selected = s.lines;
         *bytes_selected = s.units * unit;
-        if (!out_bytes && !out_index && !out_offsets && !out_ids && !out_caps) return GX_OK;   // size query
-        if ((out_index || out_offsets || out_ids || out_caps) && s.lines > cap_lines)
-            return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the selection (see *n_selected)");
+        const LinesOut lo{out_index, out_bytes, out_offsets, out_ids, out_caps};
+        if (!lo.any()) return GX_OK;   // size query
+        if (lo.per_line() && s.lines > cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the selection (see *n_selected)");
         if (out_bytes && s.units * unit > out_bytes_cap)
             return fail(GX_E_LIMIT, name + ": out_bytes_cap is smaller than the selected text (see *bytes_selected)");
-        SelectOut out{};
-        out.index = out_index; out.bytes = out_bytes; out.offsets = out_offsets;
-        void *dst_ids = out_ids, *dst_caps = out_caps;
-        if (host) {
-            if (out_index) { d_oindex = dev_alloc(s.lines * 4); out.index = static_cast<uint32_t*>(d_oindex.get()); }
-            if (out_bytes) { d_obytes = dev_alloc(s.units * unit); out.bytes = d_obytes.get(); }
-            if (out_offsets) { d_ooff = dev_alloc((s.lines + 1) * off_w); out.offsets = d_ooff.get(); }
-            if (out_ids) { d_oids = dev_alloc(s.lines * id_row); dst_ids = d_oids.get(); }
-            if (out_caps) { d_ocaps = dev_alloc(s.lines * slots * 4); dst_caps = d_ocaps.get(); }
-        }
-        if (out_ids) { out.col_src[0] = src_ids; out.col_dst[0] = dst_ids; out.col_width[0] = row_units; out.col_unit_bytes[0] = row_unit_bytes(fmt); }
-        if (out_caps) { out.col_src[1] = src_caps; out.col_dst[1] = dst_caps; out.col_width[1] = static_cast<uint32_t>(slots); out.col_unit_bytes[1] = 4; }
-        if (out.offsets && n == 0) GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
-        GX_HIP(launch_select_copy(out, src, src_off, o.offsets64 ? 1 : 0, o.utf16 ? 1 : 0, n, s.w, stream));
-        if (host) {
-            if (out_index && s.lines) GX_HIP(hipMemcpyAsync(out_index, out.index, s.lines * 4, hipMemcpyDeviceToHost, stream));
-            if (out_bytes && s.units) GX_HIP(hipMemcpyAsync(out_bytes, out.bytes, s.units * unit, hipMemcpyDeviceToHost, stream));
-            if (out_offsets) GX_HIP(hipMemcpyAsync(out_offsets, out.offsets, (s.lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
-            if (out_ids && s.lines) GX_HIP(hipMemcpyAsync(out_ids, dst_ids, s.lines * id_row, hipMemcpyDeviceToHost, stream));
-            if (out_caps && s.lines) GX_HIP(hipMemcpyAsync(out_caps, dst_caps, s.lines * slots * 4, hipMemcpyDeviceToHost, stream));
-        }
-        if (o.no_sync) {
-            // (the copy pass still reads the workspace: whoever uses it next waits for this)
-            if (!h->select_event) GX_HIP(hipEventCreateWithFlags(h->select_event.out(), hipEventDisableTiming));
-            GX_HIP(hipEventRecord(h->select_event.get(), stream));
-            h->select_pending = true;
-            return GX_OK;
-        }
-        GX_HIP(hipStreamSynchronize(stream));
+        const StagedLinesOut out = stage_lines_out(h, v, lo, host, s.lines, s.units);
+        if (out.dev.offsets && n == 0) GX_HIP(hipMemsetAsync(out.dev.offsets, 0, v.off64 ? 8 : 4, stream));
+        GX_HIP(launch_select_copy(out.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, s.w, stream));
+        if (host) deliver_lines_out(h, v, lo, out, s.lines, s.units, stream);
+        // (no_sync: the copy pass still reads the workspace: whoever uses it next waits for this)
+        if (o.no_sync) leave_pending(h->select_event, h->select_pending, stream);
+        else GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });
 }
@@ -1538,20 +1640,12 @@ static int text_select_call(const char* fn, bool where, gx_handle* h, const uint
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text, d_out;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
-        }
-        // lines and the path as in gx_text_to_jsonl; then the selection's passes over the ids and offsets they left on the device
+        const StagedText st = stage_text(text, size, o, stream, name.c_str());
+        DevMem<uint8_t> d_out;
         if (o.utf8 == 2) return fail(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (lines are selected by their bytes)");
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        const WhereBatch wb{&image, src, tl.b.caps, false};
-        const Selected s = select_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, want, counts, stream, &wb);
+        // the lines and the path; then the selection's passes over the ids and offsets they left on the device
+        const TextLines tl = text_lines(h, st.src, size, slots, stream, nullptr, 0, o.utf8 != 0);
+        const Selected s = select_pass(h, tl.view(), want, image, counts, stream);
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         *out_size = s.units;
         if (n_lines) *n_lines = tl.n;
@@ -1560,7 +1654,7 @@ static int text_select_call(const char* fn, bool where, gx_handle* h, const uint
         SelectOut sel{};
         sel.bytes = out;
         if (!o.device_pointers) { d_out = dev_alloc<uint8_t>(s.units); sel.bytes = d_out.get(); }
-        GX_HIP(launch_select_copy(sel, src, tl.b.offsets, 0, 0, tl.n, s.w, stream));
+        GX_HIP(launch_select_copy(sel, st.src, tl.b.offsets, 0, 0, tl.n, s.w, stream));
         if (!o.device_pointers && s.units) GX_HIP(hipMemcpyAsync(out, sel.bytes, s.units, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
@@ -1640,20 +1734,12 @@ static StatsImage stats_image(const gx_handle* h, const gx_measure* measures, ui
 }
 
 // The reduction on the handle's buffers (under h->mu) and, with counts, the histogram of outcomes beside it (k_select_flags' counting
-// form); then ONE synchronisation of the stream, where the host reads the summed words.  ids / offsets / data / caps: device pointers.
-static void stats_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
-                       const int32_t* caps, bool wide, const StatsImage& si, const WhereImage& wi, uint32_t n_measures, gx_measure_stats* stats, uint64_t* hist,
+// form); then ONE synchronisation of the stream, where the host reads the summed words.
+static void stats_pass(gx_handle* h, const BatchView& v, const StatsImage& si, const WhereImage& wi, uint32_t n_measures, gx_measure_stats* stats, uint64_t* hist,
                        uint64_t* counts, hipStream_t stream) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
-    if (counts) {
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
-        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
-        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
-    }
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
     const size_t words = static_cast<size_t>(n_measures) * STATS_WORDS, total = words + si.n_bins;
     std::vector<uint64_t> got(total + 2, 0);   // (the words, the bins, the status word)
     const bool run = n != 0 && n_measures != 0;
@@ -1661,11 +1747,11 @@ static void stats_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t ro
         uint8_t* d_img = static_cast<uint8_t*>(h->stats_image.get(si.bytes.size() + wi.bytes.size()));
         GX_HIP(hipMemcpyAsync(d_img, si.bytes.data(), si.bytes.size(), hipMemcpyHostToDevice, stream));
         if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + si.bytes.size(), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-        const StatsArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(si.bytes.size()),
+        const StatsArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(si.bytes.size()),
                           wi.none() ? nullptr : d_img + si.bytes.size(), static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins,
                           (si.formats || wi.formats) ? 1u : 0u};
         void* ws = h->stats_ws.get(stats_workspace_bytes(n, n_measures, si.n_bins));
-        GX_HIP(launch_capture_stats(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, ws, stream));
+        GX_HIP(launch_capture_stats(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, ws, stream));
         GX_HIP(hipMemcpyAsync(got.data(), ws, (total + 2) * 8, hipMemcpyDeviceToHost, stream));
     }
     GX_HIP(hipStreamSynchronize(stream));
@@ -1709,31 +1795,12 @@ int gx_capture_stats(gx_handle* h, const void* bytes, const void* offsets, uint6
         if ((n_measures || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": measures and terms on dense ids need caps");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         if (n >= (1ull << 32)) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 4 G lines and more");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         if (fmt != ROWS_DENSE) caps = nullptr;
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
-        // host buffers are staged to the device; the pass is the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (!o.device_pointers) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
-            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (caps && n && slots) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        stats_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, si, wi, n_measures, stats,
-                   hist, nullptr, stream);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        stats_pass(h, in.v, si, wi, n_measures, stats, hist, nullptr, stream);
         return GX_OK;
     });
 }
@@ -1749,24 +1816,14 @@ int gx_text_capture_stats(gx_handle* h, const uint8_t* text, uint64_t size, cons
         stats_refusals(h, o, measures, n_measures, terms, n_terms, false, stats, name, &si, &wi);
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
-        }
-        // lines and the path as in gx_text_select_where; then the reduction over the ids, offsets and capture rows they left on the device
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        stats_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, si, wi, n_measures, stats, hist, counts, stream);
+        // the text's lines and the path; then the reduction over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        stats_pass(h, tb.v, si, wi, n_measures, stats, hist, counts, stream);
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
-        if (n_lines) *n_lines = tl.n;
+        if (n_lines) *n_lines = tb.v.n;
         return GX_OK;
     });
 }
@@ -1824,15 +1881,17 @@ static void group_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_
 }
 
 // The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
-// totals and checks the capacities; then the emit.  ids / offsets / data / caps: device pointers; out: the caller's, device or host
+// totals and checks the capacities; then the emit.  out: the caller's, device or host
 // (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes (gx_text_group_lines).
 // gq (gx_group_quantiles; nullptr or n_q == 0: gx_group_lines as it is): before the read of the totals also the candidates' pairs, their
 // number and the OR and AND of their value keys (launch_gq_collect), read in the same wait; behind the emit the sort by the digit
 // plan made from them and the pick.
 struct GroupQuant {
-    TopHead ti{};                 // the parts that have a value group
-    QuantHead qh{};
+    const gx_quantile* quantiles = nullptr;
+    uint32_t n_quantiles = 0;
     gx_quantile_out* rows = nullptr;   // the caller's, device or host as the other per-key arrays; nullptr: not wanted
+    TopHead ti{};                 // (gq_refusals) the parts that have a value group
+    QuantHead qh{};
 };
 static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut), "the rows are copied as they are");
 // bk (gx_lines_by_key; nullptr: gx_group_lines as it is): before the read of the totals also the kept flags, their scan and the kept
@@ -1849,32 +1908,41 @@ struct ByKeyCall {
 // pc (gx_group_pairs; nullptr: gx_group_lines as it is): behind the build the pair table's build, flags and scans (launch_pairs_build),
 // whose totals, pairs and units are read in the same wait; behind the emit, which numbers the key slots, the pair emit.
 struct PairsCall {
-    PairsHead head{};                  // the second group per entry of GroupHead::ext[]
+    const int32_t* second_groups = nullptr;
+    const gx_pairs_out* asked = nullptr;   // the caller's; nullptr: the keys alone, no pair table
+    gx_pairs_totals* totals = nullptr;     // (its group member is the gx_group_totals the pass fills)
+    PairsHead head{};                      // (pairs_refusals) the second group per entry of GroupHead::ext[]
     bool any_second = false;
     gx_pairs_out out{};
-    gx_pairs_totals* totals = nullptr;   // (its group member is the gx_group_totals the pass fills)
     bool per_pair() const { return out.pair_offsets || out.pair_key || out.pair_first_line || out.pair_lines; }
     bool any() const { return per_pair() || out.pair_units || out.key_pairs || out.line_pair; }
 };
-static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
-                      const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
-                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupQuant* gq = nullptr,
-                      const ByKeyCall* bk = nullptr, const PairsCall* pc = nullptr) {
+// gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
+struct TopGroupsCall {
+    uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
+    gx_top_groups_out out{};
+    gx_top_groups_totals* totals = nullptr;
+};
+// What the calls built on gx_group_lines add to it, each absent by default.
+struct GroupExtras {
+    std::optional<GroupQuant> quant;
+    std::optional<TopGroupsCall> top;
+    std::optional<ByKeyCall> by_key;
+    std::optional<PairsCall> pairs;
+};
+static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
+                      gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupExtras& x) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const GroupQuant* gq = x.quant ? &*x.quant : nullptr;
+    const ByKeyCall* bk = x.by_key ? &*x.by_key : nullptr;
+    const PairsCall* pc = x.pairs && x.pairs->asked ? &*x.pairs : nullptr;
+    const uint64_t n = v.n;
     if (bk) *bk->totals = gx_by_key_totals{};
     if (pc) {
         *pc->totals = gx_pairs_totals{};
         pc->totals->pairs_exact = 1;
     }
-    if (counts) {
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
-        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
-        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
-    }
+    if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
     totals->exact = 1;
     const bool run = n != 0 && gi.head.n_parts != 0;
@@ -1897,7 +1965,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         }
         if (bk_out) {   // no kept lines: the one entry of the offsets and of the two prefixes
             void* const one[3] = {bk->out.out_offsets, bk->out.key_out_lines, bk->out.key_out_units};
-            const size_t width[3] = {off64 ? size_t(8) : size_t(4), 8, 8};
+            const size_t width[3] = {v.off64 ? size_t(8) : size_t(4), 8, 8};
             for (int q = 0; q < 3; ++q) {
                 if (!one[q]) continue;
                 if (host_out) memcpy(one[q], &zero, width[q]);
@@ -1916,18 +1984,15 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         }
         return GX_OK;
     }
-    if (h->group_pending) {
-        GX_HIP(hipStreamWaitEvent(stream, h->group_event.get(), 0));
-        h->group_pending = false;
-    }
+    wait_pending(h->group_event, h->group_pending, stream);
     const uint32_t n_slots = group_slots(out.max_keys);
     uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
     GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
+    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
                       static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
     const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
-    GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    GX_HIP(launch_group_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
     // the quantiles' candidates: only where rows are wanted and a part has a value (else every population is empty)
     const bool sort = q_rows && gq->ti.n_parts != 0;
     GqWs qw{};
@@ -1939,10 +2004,10 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         GX_HIP(hipMemcpyAsync(d_qimg, &gq->ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
         GX_HIP(hipMemcpyAsync(d_qimg + sizeof(TopHead), &gq->qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
         if (!wi.none()) GX_HIP(hipMemcpyAsync(d_qimg + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-        const TopArgs ta{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_qimg, wi.none() ? nullptr : d_qimg + at_terms,
+        const TopArgs ta{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_qimg, wi.none() ? nullptr : d_qimg + at_terms,
                          static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
         qw = gq_workspace(h->gq_ws.get(gq_workspace_bytes(n)), n);
-        GX_HIP(launch_gq_collect(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, ta, w.slot_of, qw, stream));
+        GX_HIP(launch_gq_collect(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, ta, w.slot_of, qw, stream));
         GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, stream));
     }
     // the kept lines of gx_lines_by_key, their units and their keys: from the slots' line counts, which the build has left complete
@@ -1950,7 +2015,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     ByKeyDev bd{};
     if (bk) {
         bw = by_key_workspace(h->by_key_ws.get(by_key_workspace_bytes(n)), n);
-        GX_HIP(launch_by_key_kept(n, offsets, off64 ? 1 : 0, w, bk->min_lines, bk->max_lines, bw, stream));
+        GX_HIP(launch_by_key_kept(n, v.offsets, v.off64 ? 1 : 0, w, bk->min_lines, bk->max_lines, bw, stream));
         GX_HIP(hipMemcpyAsync(&bd, bw.head, sizeof(ByKeyDev), hipMemcpyDeviceToHost, stream));
     }
     // the pairs of gx_group_pairs: a second table keyed by (key slot, second text), behind the build that has left slot_of[] complete
@@ -1963,7 +2028,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         d_pimg = static_cast<uint8_t*>(h->pairs_image.get(sizeof(PairsHead)));
         GX_HIP(hipMemcpyAsync(d_pimg, &pc->head, sizeof(PairsHead), hipMemcpyHostToDevice, stream));
         pw = pairs_workspace(h->pairs_table.get(pairs_table_bytes(p_slots, n_slots)), h->pairs_lines.get(pairs_lines_bytes(n)), n, p_slots, n_slots);
-        GX_HIP(launch_pairs_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_pimg, w, pw, stream));
+        GX_HIP(launch_pairs_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_pimg, w, pw, stream));
         GX_HIP(hipMemcpyAsync(&pd, pw.totals, sizeof(PairsDev), hipMemcpyDeviceToHost, stream));
         GX_HIP(hipMemcpyAsync(&n_pairs, pw.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipMemcpyAsync(&pair_units, pw.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -2008,12 +2073,12 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     if (out.key_units && key_units > out.key_units_cap)
         return fail(GX_E_LIMIT, name + ": " + std::to_string(key_units) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && key_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
-    const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
+    const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
     if (bk_out) {
         const gx_by_key_out& b = bk->out;
         if (bk->per_line() && bd.lines_out > b.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
         if (b.out_bytes && bd.units_out * unit > b.out_bytes_cap) return fail(GX_E_LIMIT, name + ": the kept text is larger than the capacity (see totals->units_out)");
-        if (b.out_offsets && !off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+        if (b.out_offsets && !v.off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
         if ((b.key_out_lines || b.key_out_units) && n_keys > out.max_keys)
             return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
     }
@@ -2038,39 +2103,31 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.key_stats) { d_stats = dev_alloc(n_keys * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
         if (out.line_key) { d_lkey = dev_alloc(n * 4); o.line_key = static_cast<uint32_t*>(d_lkey.get()); }
     }
-    GX_HIP(launch_group_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
+    GX_HIP(launch_group_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
     // gx_lines_by_key: the kept lines by (key number, line) as a new batch, and the keys' bounds in it
-    SelectOut so{};
-    DevMem<> b_index, b_bytes, b_off, b_ids, b_caps, b_kol, b_kou;
-    void *b_dst_ids = nullptr, *b_dst_caps = nullptr;
+    LinesOut bo{};
+    StagedLinesOut so;
+    DevMem<> b_kol, b_kou;
     uint64_t *kol = nullptr, *kou = nullptr;
     const uint64_t m = bd.lines_out;
-    const size_t in_off_w = off64 ? 8 : 4, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt), cap_slots = 2 * static_cast<size_t>(h->T.max_groups);
     if (bk_out) {
         const gx_by_key_out& b = bk->out;
-        so.index = b.out_index; so.bytes = b.out_bytes; so.offsets = b.out_offsets;
-        b_dst_ids = b.out_ids; b_dst_caps = b.out_caps;
+        bo = LinesOut{b.out_index, b.out_bytes, b.out_offsets, b.out_ids, b.out_caps};
+        so = stage_lines_out(h, v, bo, host_out, m, bd.units_out);
         kol = b.key_out_lines; kou = b.key_out_units;
         if (host_out) {
-            if (b.out_index) { b_index = dev_alloc(m * 4); so.index = static_cast<uint32_t*>(b_index.get()); }
-            if (b.out_bytes) { b_bytes = dev_alloc(bd.units_out * unit); so.bytes = b_bytes.get(); }
-            if (b.out_offsets) { b_off = dev_alloc((m + 1) * in_off_w); so.offsets = b_off.get(); }
-            if (b.out_ids) { b_ids = dev_alloc(m * id_row); b_dst_ids = b_ids.get(); }
-            if (b.out_caps) { b_caps = dev_alloc(m * cap_slots * 4); b_dst_caps = b_caps.get(); }
             if (kol) { b_kol = dev_alloc((n_keys + 1) * 8); kol = static_cast<uint64_t*>(b_kol.get()); }
             if (kou) { b_kou = dev_alloc((n_keys + 1) * 8); kou = static_cast<uint64_t*>(b_kou.get()); }
         }
-        if (b.out_ids) { so.col_src[0] = ids; so.col_dst[0] = b_dst_ids; so.col_width[0] = row_units; so.col_unit_bytes[0] = row_unit_bytes(fmt); }
-        if (b.out_caps) { so.col_src[1] = caps; so.col_dst[1] = b_dst_caps; so.col_width[1] = static_cast<uint32_t>(cap_slots); so.col_unit_bytes[1] = 4; }
         if (m == 0) {
-            if (so.offsets) GX_HIP(hipMemsetAsync(so.offsets, 0, in_off_w, stream));
+            if (so.dev.offsets) GX_HIP(hipMemsetAsync(so.dev.offsets, 0, v.off64 ? 8 : 4, stream));
             if (kol) GX_HIP(hipMemsetAsync(kol, 0, (n_keys + 1) * 8, stream));
             if (kou) GX_HIP(hipMemsetAsync(kou, 0, (n_keys + 1) * 8, stream));
         } else {
             PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
             GX_HIP(launch_by_key_sort(n, m, n_keys, by_key_passes(n_keys, bk->all_digits), w, bw, kol, kou, &pw.perm_sorted, stream));
             pw.dst_off = bw.dst_off;
-            GX_HIP(launch_partition_copy(so, data, offsets, off64 ? 1 : 0, wide ? 1 : 0, n, m, pw, stream));
+            GX_HIP(launch_partition_copy(so.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, m, pw, stream));
         }
     }
     // gx_group_pairs: the pairs' rows, their seconds, the keys' pairs and the lines' pair numbers
@@ -2088,7 +2145,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
             if (b.key_pairs) { p_kp = dev_alloc(n_keys * 8); po.key_pairs = static_cast<uint64_t*>(p_kp.get()); }
             if (b.line_pair) { p_lp = dev_alloc(n * 4); po.line_pair = static_cast<uint32_t*>(p_lp.get()); }
         }
-        GX_HIP(launch_pairs_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_pimg, w, pw, po, n_pairs, pair_units, n_keys, stream));
+        GX_HIP(launch_pairs_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_pimg, w, pw, po, n_pairs, pair_units, n_keys, stream));
     }
     if (rows_bytes) {
         if (sort && qd.candidates != 0) {
@@ -2108,11 +2165,7 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         if (out.line_key) GX_HIP(hipMemcpyAsync(out.line_key, o.line_key, n * 4, hipMemcpyDeviceToHost, stream));
         if (bk_out) {
             const gx_by_key_out& b = bk->out;
-            if (b.out_index && m) GX_HIP(hipMemcpyAsync(b.out_index, so.index, m * 4, hipMemcpyDeviceToHost, stream));
-            if (b.out_bytes && bd.units_out) GX_HIP(hipMemcpyAsync(b.out_bytes, so.bytes, bd.units_out * unit, hipMemcpyDeviceToHost, stream));
-            if (b.out_offsets) GX_HIP(hipMemcpyAsync(b.out_offsets, so.offsets, (m + 1) * in_off_w, hipMemcpyDeviceToHost, stream));
-            if (b.out_ids && m) GX_HIP(hipMemcpyAsync(b.out_ids, b_dst_ids, m * id_row, hipMemcpyDeviceToHost, stream));
-            if (b.out_caps && m) GX_HIP(hipMemcpyAsync(b.out_caps, b_dst_caps, m * cap_slots * 4, hipMemcpyDeviceToHost, stream));
+            deliver_lines_out(h, v, bo, so, m, bd.units_out, stream);
             if (b.key_out_lines) GX_HIP(hipMemcpyAsync(b.key_out_lines, kol, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
             if (b.key_out_units) GX_HIP(hipMemcpyAsync(b.key_out_units, kou, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
         }
@@ -2128,22 +2181,19 @@ static int group_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
         }
         GX_HIP(hipStreamSynchronize(stream));
     } else {
-        if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
-        GX_HIP(hipEventRecord(h->group_event.get(), stream));
-        h->group_pending = true;
+        leave_pending(h->group_event, h->group_pending, stream);
     }
     return GX_OK;
 }
 
 // what gx_group_pairs adds to the refusals of gx_group_lines, behind them and before the look at the device: the second groups, checked
 // against the handle and laid out by GroupHead::ext[] (gi: group_refusals')
-static void pairs_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const int32_t* second_groups,
-                           const gx_pairs_out* out, const std::string& name, PairsCall* pc) {
+static void pairs_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, PairsCall* pc) {
     for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) pc->head.second[q] = PAIRS_NO_SECOND;
-    if (out) pc->out = *out;
-    if (n_parts && !second_groups) throw GxError(GX_E_ARG, name + ": second_groups is NULL");
+    if (pc->asked) pc->out = *pc->asked;
+    if (n_parts && !pc->second_groups) throw GxError(GX_E_ARG, name + ": second_groups is NULL");
     for (uint32_t t = 0; t < n_parts; ++t) {
-        const int32_t sg = second_groups[t];
+        const int32_t sg = pc->second_groups[t];
         if (sg < -1 || sg >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's second group is neither -1 nor one of its extraction's");
         if (sg < 0) continue;
         pc->any_second = true;
@@ -2174,12 +2224,6 @@ static void by_key_overlaps(const std::pair<const void*, uint64_t>* outs, size_t
             if (ranges_meet(outs[a].first, outs[a].second, ins[b].first, ins[b].second)) throw GxError(GX_E_ARG, name + ": an output overlaps an input");
 }
 
-// gx_top_groups: what the call adds to gx_group_lines' arguments
-struct TopGroupsCall {
-    uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
-    gx_top_groups_out out{};
-    gx_top_groups_totals* totals = nullptr;
-};
 // what gx_top_groups adds to the refusals of gx_group_lines, behind them and before the look at the device
 static void tg_refusals(const GroupImage& gi, const TopGroupsCall& tg, const std::string& name) {
     if (tg.rank_by >= TG_RANK_KINDS) throw GxError(GX_E_ARG, name + ": rank_by is not one of GX_RANK_LINES .. GX_RANK_MIN");
@@ -2192,19 +2236,11 @@ static void tg_refusals(const GroupImage& gi, const TopGroupsCall& tg, const std
 // lengths, and the SECOND wait, where the host reads the candidates, the select's state, the ties and the chosen keys' units and checks
 // the capacities; then the emit over the chosen keys.  Host outputs are staged and a third wait delivers them; with device pointers the
 // emit is left running under group_event.
-static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
-                           const int32_t* caps, bool wide, const GroupImage& gi, const WhereImage& wi, uint64_t max_keys, const TopGroupsCall& tg, bool out64,
+static int top_groups_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, uint64_t max_keys, const TopGroupsCall& tg, bool out64,
                            bool host_out, uint64_t* counts, hipStream_t stream, const std::string& name) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
-    if (counts) {
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
-        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
-        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
-    }
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
     gx_top_groups_totals* totals = tg.totals;
     *totals = gx_top_groups_totals{};
     totals->group.exact = 1;
@@ -2227,18 +2263,15 @@ static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_
         GX_HIP(hipStreamSynchronize(stream));
         return deliver_nothing();
     }
-    if (h->group_pending) {
-        GX_HIP(hipStreamWaitEvent(stream, h->group_event.get(), 0));
-        h->group_pending = false;
-    }
+    wait_pending(h->group_event, h->group_pending, stream);
     const uint32_t n_slots = group_slots(max_keys);
     uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
     GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const GroupArgs a{data, wide ? 1 : 0, caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
+    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
                       static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
     const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
-    GX_HIP(launch_group_build(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    GX_HIP(launch_group_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
     // the first wait: gx_group_lines' totals
     uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
     GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
@@ -2284,7 +2317,7 @@ static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_
     if (out.key_units && units_top > out.key_units_cap)
         return fail(GX_E_LIMIT, name + ": " + std::to_string(units_top) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && units_top > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
-    const size_t unit = wide ? 2 : 1, off_w = out64 ? 8 : 4;
+    const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
     TopGroupsOut o{out.key_units, out.key_offsets, out.key_number, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_rank,
                    out64 ? 1 : 0};
     DevMem<> d_units, d_offs, d_num, d_first, d_lines, d_stats, d_lrank;
@@ -2297,7 +2330,7 @@ static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_
         if (out.key_stats) { d_stats = dev_alloc(n_top * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
         if (out.line_rank) { d_lrank = dev_alloc(n * 4); o.line_rank = static_cast<uint32_t*>(d_lrank.get()); }
     }
-    GX_HIP(launch_top_groups_emit(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, tw, o, n_top, units_top, stream));
+    GX_HIP(launch_top_groups_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, tw, o, n_top, units_top, stream));
     if (host_out) {
         if (out.key_units && units_top) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, units_top * unit, hipMemcpyDeviceToHost, stream));
         if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_top + 1) * off_w, hipMemcpyDeviceToHost, stream));
@@ -2308,19 +2341,18 @@ static int top_groups_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_
         if (out.line_rank) GX_HIP(hipMemcpyAsync(out.line_rank, o.line_rank, n * 4, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipStreamSynchronize(stream));
     } else {
-        if (!h->group_event) GX_HIP(hipEventCreateWithFlags(h->group_event.out(), hipEventDisableTiming));
-        GX_HIP(hipEventRecord(h->group_event.get(), stream));
-        h->group_pending = true;
+        leave_pending(h->group_event, h->group_pending, stream);
     }
     return GX_OK;
 }
 
 // what gx_group_quantiles adds to the refusals of gx_group_lines, behind them and before the look at the device: the quantiles
 // (gx_capture_quantiles' rule), and the parts that have a value group as the keys pass reads them
-static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint32_t n_quantiles, gx_quantile_out* rows, const std::string& name, GroupQuant* gq) {
+static void gq_refusals(const GroupImage& gi, const std::string& name, GroupQuant* gq) {
+    const gx_quantile* quantiles = gq->quantiles;
+    const uint32_t n_quantiles = gq->n_quantiles;
     if (n_quantiles && !quantiles) throw GxError(GX_E_ARG, name + ": quantiles is NULL");
     if (n_quantiles > GX_QUANTILE_MAX) throw GxError(GX_E_LIMIT, name + ": n_quantiles above GX_QUANTILE_MAX");
-    *gq = GroupQuant{};
     gq->qh.n_q = n_quantiles;
     for (uint32_t q = 0; q < n_quantiles; ++q) {
         if (quantiles[q].den == 0) throw GxError(GX_E_ARG, name + ": a quantile's den is 0");
@@ -2333,15 +2365,20 @@ static void gq_refusals(const GroupImage& gi, const gx_quantile* quantiles, uint
         gq->ti.fmt[gq->ti.n_parts] = gi.head.fmt[e];
         gq->ti.group[gq->ti.n_parts++] = gi.head.part[e].value_group;
     }
-    gq->rows = rows;
 }
 
-// gx_group_lines and, with quant, gx_group_quantiles
+// what the extras add to the refusals of gx_group_lines, behind them (gi: group_refusals') and before the look at the device
+static void extras_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, GroupExtras* x) {
+    if (x->quant) gq_refusals(gi, name, &*x->quant);
+    if (x->top) tg_refusals(gi, *x->top, name);
+    if (x->pairs) pairs_refusals(h, gi, parts, n_parts, name, &*x->pairs);
+    if (x->by_key) by_key_refusals(*x->by_key, name);
+}
+
+// gx_group_lines and, with extras, the calls built on it
 static int group_lines_call(const std::string& name, gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
                             const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out,
-                            gx_group_totals* totals, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                            gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr, PairsCall* pairs = nullptr,
-                            const int32_t* second_groups = nullptr, const gx_pairs_out* pairs_out = nullptr) {
+                            gx_group_totals* totals, const gx_batch_opts* opts, GroupExtras x = {}) {
     return guarded([&]() -> int {
         if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2352,30 +2389,18 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
         GroupImage gi;
         WhereImage wi;
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, go, totals, name, &gi, &wi);
-        GroupQuant gq;
-        if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
-        if (tg) tg_refusals(gi, *tg, name);
-        if (pairs) pairs_refusals(h, gi, parts, n_parts, second_groups, pairs_out, name, pairs);
-        ByKeyCall bk;
-        if (by_key) {
-            bk = *by_key;
-            by_key_refusals(bk, name);
-            if (bk.out.out_caps && fmt != ROWS_DENSE) return fail(GX_E_ARG, name + ": out_caps on compact rows (out_ids holds whole rows)");
-        }
+        extras_refusals(h, gi, parts, n_parts, name, &x);
+        if (x.by_key && x.by_key->out.out_caps && fmt != ROWS_DENSE) return fail(GX_E_ARG, name + ": out_caps on compact rows (out_ids holds whole rows)");
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
-        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the build pass
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            for (uint64_t i = 0; i < n; ++i)
-                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be grouped");
-        }
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-        if (by_key) {
-            if (bk.out.out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
-            if (!slots) bk.out.out_caps = nullptr;
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "grouped");
+        if (x.by_key) {
+            const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+            gx_by_key_out& b = x.by_key->out;
+            if (b.out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
+            if (!slots) b.out_caps = nullptr;
             const uint64_t ow = o.offsets64 ? 8 : 4, un = o.utf16 ? 2 : 1, idr = static_cast<uint64_t>(row_units) * row_unit_bytes(fmt);
             const uint64_t in_units = o.device_pointers ? (n ? 1u : 0u) : HostOffsets{offsets, o.offsets64 != 0, n}[n];
-            const gx_by_key_out& b = bk.out;
             const uint64_t cap = std::min<uint64_t>(b.cap_lines, n);   // (no more than n lines leave, whatever the capacity says: n < 2^32, no product wraps)
             const std::pair<const void*, uint64_t> outs[7] = {{b.out_index, cap * 4}, {b.out_bytes, b.out_bytes_cap}, {b.out_offsets, (cap + 1) * ow},
                                                               {b.out_ids, cap * idr}, {b.out_caps, cap * slots * 4},
@@ -2389,51 +2414,30 @@ static int group_lines_call(const std::string& name, gx_handle* h, const void* b
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
-        // host buffers are staged to the device; the passes are the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (!o.device_pointers) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
-            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (caps && n && slots) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        if (tg)
-            return top_groups_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi,
-                                   go.max_keys, *tg, o.offsets64 != 0, !o.device_pointers, nullptr, stream, name);
-        return group_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, gi, wi, go,
-                          o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, quant ? &gq : nullptr, by_key ? &bk : nullptr, pairs_out ? pairs : nullptr);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        if (x.top) return top_groups_pass(h, in.v, gi, wi, go.max_keys, *x.top, o.offsets64 != 0, !o.device_pointers, nullptr, stream, name);
+        return group_pass(h, in.v, gi, wi, go, o.offsets64 != 0, !o.device_pointers, totals, nullptr, stream, name, x);
     });
 }
 
 int gx_group_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
                    uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals,
                    const gx_batch_opts* opts) {
-    return group_lines_call("gx_group_lines", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts, false, nullptr, 0, nullptr);
+    return group_lines_call("gx_group_lines", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts);
 }
 
 int gx_group_quantiles(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
                        uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, uint32_t flags,
                        const gx_group_out* out, gx_quantile_out* key_quantiles, gx_group_totals* totals, const gx_batch_opts* opts) {
-    return group_lines_call("gx_group_quantiles", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts, true, quantiles,
-                            n_quantiles, key_quantiles);
+    GroupExtras x;
+    x.quant = GroupQuant{quantiles, n_quantiles, key_quantiles};
+    return group_lines_call("gx_group_quantiles", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, out, totals, opts, x);
 }
 
-// gx_text_group_lines and, with quant, gx_text_group_quantiles
+// gx_text_group_lines and, with extras, the calls built on it
 static int text_group_call(const std::string& name, gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
                            const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts,
-                           uint64_t* n_lines, const gx_batch_opts* opts, bool quant, const gx_quantile* quantiles, uint32_t n_quantiles,
-                           gx_quantile_out* key_quantiles, const TopGroupsCall* tg = nullptr, const ByKeyCall* by_key = nullptr, PairsCall* pairs = nullptr,
-                           const int32_t* second_groups = nullptr, const gx_pairs_out* pairs_out = nullptr) {
+                           uint64_t* n_lines, const gx_batch_opts* opts, GroupExtras x = {}) {
     return guarded([&]() -> int {
         if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
         const gx_batch_opts o = read_opts(opts);
@@ -2442,13 +2446,9 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         GroupImage gi;
         WhereImage wi;
         group_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, go, totals, name, &gi, &wi);
-        GroupQuant gq;
-        if (quant) gq_refusals(gi, quantiles, n_quantiles, key_quantiles, name, &gq);
-        if (tg) tg_refusals(gi, *tg, name);
-        if (pairs) pairs_refusals(h, gi, parts, n_parts, second_groups, pairs_out, name, pairs);
-        if (by_key) {
-            by_key_refusals(*by_key, name);
-            const gx_by_key_out& b = by_key->out;
+        extras_refusals(h, gi, parts, n_parts, name, &x);
+        if (x.by_key) {
+            const gx_by_key_out& b = x.by_key->out;
             const std::pair<const void*, uint64_t> outs[5] = {{b.out_bytes, b.out_bytes_cap}, {b.out_offsets, 4}, {b.out_index, 4}, {b.key_out_lines, (go.max_keys + 1) * 8},
                                                               {b.key_out_units, (go.max_keys + 1) * 8}};
             const std::pair<const void*, uint64_t> ins[1] = {{text, size}};
@@ -2456,26 +2456,14 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
         }
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
-        }
-        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        if (n_lines) *n_lines = tl.n;
-        const int rc = tg ? top_groups_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go.max_keys, *tg,
-                                            o.offsets64 != 0, !o.device_pointers, counts, stream, name)
-                          : group_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, gi, wi, go, o.offsets64 != 0,
-                                       !o.device_pointers, totals, counts, stream, name, quant ? &gq : nullptr, by_key, pairs_out ? pairs : nullptr);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        const int rc = x.top ? top_groups_pass(h, tb.v, gi, wi, go.max_keys, *x.top, o.offsets64 != 0, !o.device_pointers, counts, stream, name)
+                             : group_pass(h, tb.v, gi, wi, go, o.offsets64 != 0, !o.device_pointers, totals, counts, stream, name, x);
         // The emit pass reads the offsets, ids and capture rows that text_lines left in the handle's scratch buffers, which the next
         // whole-file call on any stream overwrites: like every gx_text_* call this one returns with its work done (host outputs: the
         // wait that delivered them was that already).
@@ -2491,34 +2479,36 @@ static int text_group_call(const std::string& name, gx_handle* h, const uint8_t*
 int gx_text_group_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
                         uint32_t n_terms, uint32_t flags, const gx_group_out* out, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines,
                         const gx_batch_opts* opts) {
-    return text_group_call("gx_text_group_lines", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, false, nullptr, 0, nullptr);
+    return text_group_call("gx_text_group_lines", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts);
 }
 
 int gx_text_group_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms,
                             uint32_t n_terms, const gx_quantile* quantiles, uint32_t n_quantiles, uint32_t flags, const gx_group_out* out,
                             gx_quantile_out* key_quantiles, gx_group_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
-    return text_group_call("gx_text_group_quantiles", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, true, quantiles,
-                           n_quantiles, key_quantiles);
+    GroupExtras x;
+    x.quant = GroupQuant{quantiles, n_quantiles, key_quantiles};
+    return text_group_call("gx_text_group_quantiles", h, text, size, parts, n_parts, terms, n_terms, flags, out, totals, counts, n_lines, opts, x);
 }
 
 // gx_lines_by_key's own arguments as gx_group_lines' callers take them: the flags without GX_BY_KEY_ALL_DIGITS (unknown bits stay in the
 // flags and are refused there), and &totals->group.
-static ByKeyCall by_key_call(uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_by_key_out* out, gx_by_key_totals* totals) {
+static GroupExtras by_key_extras(uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_by_key_out* out, gx_by_key_totals* totals) {
     ByKeyCall bk;
     bk.min_lines = min_lines;
     bk.max_lines = max_lines;
     bk.all_digits = (flags & GX_BY_KEY_ALL_DIGITS) != 0u;
     if (out) bk.out = *out;
     bk.totals = totals;
-    return bk;
+    GroupExtras x;
+    x.by_key = bk;
+    return x;
 }
 
 int gx_lines_by_key(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
                     uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint64_t min_lines, uint64_t max_lines, uint32_t flags, const gx_group_out* keys,
                     const gx_by_key_out* out, gx_by_key_totals* totals, const gx_batch_opts* opts) {
-    const ByKeyCall bk = by_key_call(min_lines, max_lines, flags, out, totals);
     return group_lines_call("gx_lines_by_key", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
-                            totals ? &totals->group : nullptr, opts, false, nullptr, 0, nullptr, nullptr, &bk);
+                            totals ? &totals->group : nullptr, opts, by_key_extras(min_lines, max_lines, flags, out, totals));
 }
 
 int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
@@ -2530,70 +2520,69 @@ int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const
     bo.cap_lines = ~0ull;   // (sized by the size query: the header)
     bo.out_bytes_cap = out_cap;
     bo.key_out_lines = key_out_lines; bo.key_out_units = key_out_units;
-    const ByKeyCall bk = by_key_call(min_lines, max_lines, flags, &bo, totals);
     return text_group_call("gx_text_lines_by_key", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
-                           totals ? &totals->group : nullptr, counts, n_lines, opts, false, nullptr, 0, nullptr, nullptr, &bk);
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, by_key_extras(min_lines, max_lines, flags, &bo, totals));
 }
 
 // gx_group_pairs: gx_group_lines' call with the pairs behind it.  totals == NULL is refused as gx_group_lines refuses it.
-int gx_group_pairs(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
-                   uint32_t n_parts, const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
-                   const gx_pairs_out* pairs, gx_pairs_totals* totals, const gx_batch_opts* opts) {
-    PairsCall pc;
-    pc.totals = totals;
+static GroupExtras pairs_extras(const int32_t* second_groups, const gx_pairs_out* pairs, gx_pairs_totals* totals) {
     if (totals) {
         *totals = gx_pairs_totals{};
         totals->pairs_exact = 1;
     }
-    return group_lines_call("gx_group_pairs", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, opts, false,
-                            nullptr, 0, nullptr, nullptr, nullptr, &pc, second_groups, pairs);
+    GroupExtras x;
+    x.pairs = PairsCall{second_groups, pairs, totals};
+    return x;
+}
+
+int gx_group_pairs(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                   uint32_t n_parts, const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
+                   const gx_pairs_out* pairs, gx_pairs_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_pairs", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, opts,
+                            pairs_extras(second_groups, pairs, totals));
 }
 
 int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* second_groups,
                         const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_pairs_out* pairs, gx_pairs_totals* totals,
                         uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
-    PairsCall pc;
-    pc.totals = totals;
-    if (totals) {
-        *totals = gx_pairs_totals{};
-        totals->pairs_exact = 1;
-    }
     return text_group_call("gx_text_group_pairs", h, text, size, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, counts, n_lines, opts,
-                           false, nullptr, 0, nullptr, nullptr, nullptr, &pc, second_groups, pairs);
+                           pairs_extras(second_groups, pairs, totals));
 }
 
-// gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST, a gx_group_out that holds
-// what gx_group_lines' refusals look at (key_stats, max_keys), and &totals->group.  Unknown flag bits stay in the flags and are refused there.
-static TopGroupsCall tg_call(uint32_t rank_by, uint32_t n_wanted, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals) {
+// gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST and &totals->group (unknown
+// flag bits stay in the flags and are refused there), and a gx_group_out that holds what gx_group_lines' refusals look at.
+static GroupExtras top_groups_extras(uint32_t rank_by, uint32_t n_wanted, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals) {
     TopGroupsCall tg;
     tg.rank_by = rank_by;
     tg.n_wanted = n_wanted;
     tg.smallest = (flags & GX_TOP_GROUPS_SMALLEST) ? 1u : 0u;
     if (out) tg.out = *out;
     tg.totals = totals;
-    return tg;
+    GroupExtras x;
+    x.top = tg;
+    return x;
+}
+static gx_group_out top_groups_keys(const gx_top_groups_out* out, uint64_t max_keys) {
+    gx_group_out go{};
+    go.key_stats = out ? out->key_stats : nullptr;
+    go.max_keys = max_keys;
+    return go;
 }
 
 int gx_top_groups(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
                   uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t rank_by, uint32_t n_wanted, uint64_t max_keys, uint32_t flags,
                   const gx_top_groups_out* out, gx_top_groups_totals* totals, const gx_batch_opts* opts) {
-    const TopGroupsCall tg = tg_call(rank_by, n_wanted, flags, out, totals);
-    gx_group_out go{};
-    go.key_stats = tg.out.key_stats;
-    go.max_keys = max_keys;
+    const gx_group_out go = top_groups_keys(out, max_keys);
     return group_lines_call("gx_top_groups", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_TOP_GROUPS_SMALLEST), &go,
-                            totals ? &totals->group : nullptr, opts, false, nullptr, 0, nullptr, &tg);
+                            totals ? &totals->group : nullptr, opts, top_groups_extras(rank_by, n_wanted, flags, out, totals));
 }
 
 int gx_text_top_groups(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
                        uint32_t rank_by, uint32_t n_wanted, uint64_t max_keys, uint32_t flags, const gx_top_groups_out* out, gx_top_groups_totals* totals,
                        uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
-    const TopGroupsCall tg = tg_call(rank_by, n_wanted, flags, out, totals);
-    gx_group_out go{};
-    go.key_stats = tg.out.key_stats;
-    go.max_keys = max_keys;
+    const gx_group_out go = top_groups_keys(out, max_keys);
     return text_group_call("gx_text_top_groups", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_TOP_GROUPS_SMALLEST), &go,
-                           totals ? &totals->group : nullptr, counts, n_lines, opts, false, nullptr, 0, nullptr, &tg);
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, top_groups_extras(rank_by, n_wanted, flags, out, totals));
 }
 
 // The parts of a gx_top_lines call as its keys pass reads them (gx_top.hpp: TopHead), checked against the handle.  Needs no device.
@@ -2639,55 +2628,40 @@ static void top_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_to
 
 // where the delivered lines go: the caller's pointers, device or host (host_out: staged, and a second wait delivers them)
 struct TopOut {
-    uint32_t* index;
+    LinesOut lines;
     int64_t* values;
-    void* bytes;
-    void* offsets;
-    void* ids;
-    int32_t* caps;
     uint64_t cap_lines, bytes_cap;
-    bool any() const { return index || values || bytes || offsets || ids || caps; }
+    bool any() const { return lines.any() || values; }
 };
 
 // The passes on the handle's workspace (under h->mu): keys, select, choose and order; ONE synchronisation of the stream, where the host
-// reads the totals and checks the capacities; then the emit (launch_partition_copy).  ids / offsets / data / caps: device pointers.
-// counts: also the histogram of outcomes (gx_text_top_lines).
-static int top_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
-                    const int32_t* caps, bool wide, const TopHead& ti, const WhereImage& wi, uint32_t n_wanted, const TopOut& out, bool host_out,
+// reads the totals and checks the capacities; then the emit (launch_partition_copy).  counts: also the histogram of outcomes
+// (gx_text_top_lines).
+static int top_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const WhereImage& wi, uint32_t n_wanted, const TopOut& out, bool host_out,
                     gx_top_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
     const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    if (counts) {
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
-        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
-        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
-    }
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_top_totals{};
-    const size_t unit = wide ? 2 : 1, off_w = off64 ? 8 : 4, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+    const size_t unit = v.wide ? 2 : 1, off_w = v.off64 ? 8 : 4;
     const uint64_t zero = 0;
     if (n == 0 || ti.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
-        if (out.offsets) {   // no lines: the offsets' one entry
-            if (host_out) memcpy(out.offsets, &zero, off_w);
-            else GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
+        if (out.lines.offsets) {   // no lines: the offsets' one entry
+            if (host_out) memcpy(out.lines.offsets, &zero, off_w);
+            else GX_HIP(hipMemsetAsync(out.lines.offsets, 0, off_w, stream));
         }
         return GX_OK;
     }
-    if (h->top_pending) {
-        GX_HIP(hipStreamWaitEvent(stream, h->top_event.get(), 0));
-        h->top_pending = false;
-    }
+    wait_pending(h->top_event, h->top_pending, stream);
     uint8_t* d_img = static_cast<uint8_t*>(h->top_image.get(sizeof(TopHead) + wi.bytes.size()));
     GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + sizeof(TopHead),
+    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + sizeof(TopHead),
                     static_cast<uint32_t>(wi.bytes.size()), ti.smallest, n_wanted, (ti.formats || wi.formats) ? 1u : 0u};
     const TopWs w = top_workspace(h->top_ws.get(top_workspace_bytes(n)), n);
-    GX_HIP(launch_top_select(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, w, stream));
+    GX_HIP(launch_top_select(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
     struct { uint32_t counts[TOP_COUNTS]; TopSelect sel; } got{};
     static_assert(sizeof(got) == offsetof(TopDev, spare), "the head's first words");
     uint64_t both = 0, units = 0;
@@ -2711,40 +2685,22 @@ static int top_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_u
         totals->ties_left = (both >> 32) - got.sel.remaining;
     }
     if (!out.any()) return GX_OK;   // size query
-    if ((out.index || out.values || out.offsets || out.ids || out.caps) && n_top > out.cap_lines)
-        return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->n_top)");
-    if (out.bytes && units * unit > out.bytes_cap) return fail(GX_E_LIMIT, name + ": the delivered text is larger than the capacity (see totals->units_top)");
-    if (out.offsets && !off64 && units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
-    SelectOut so{};
-    so.index = out.index; so.bytes = out.bytes; so.offsets = out.offsets;
-    void *dst_ids = out.ids, *dst_caps = out.caps;
-    DevMem<> d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
-    if (host_out) {
-        if (out.index) { d_oindex = dev_alloc(n_top * 4); so.index = static_cast<uint32_t*>(d_oindex.get()); }
-        if (out.bytes) { d_obytes = dev_alloc(units * unit); so.bytes = d_obytes.get(); }
-        if (out.offsets) { d_ooff = dev_alloc((n_top + 1) * off_w); so.offsets = d_ooff.get(); }
-        if (out.ids) { d_oids = dev_alloc(n_top * id_row); dst_ids = d_oids.get(); }
-        if (out.caps) { d_ocaps = dev_alloc(n_top * slots * 4); dst_caps = d_ocaps.get(); }
-    }
-    if (out.ids) { so.col_src[0] = ids; so.col_dst[0] = dst_ids; so.col_width[0] = row_units; so.col_unit_bytes[0] = row_unit_bytes(fmt); }
-    if (out.caps) { so.col_src[1] = caps; so.col_dst[1] = dst_caps; so.col_width[1] = static_cast<uint32_t>(slots); so.col_unit_bytes[1] = 4; }
-    if (so.offsets && n_top == 0) GX_HIP(hipMemsetAsync(so.offsets, 0, off_w, stream));
+    if ((out.lines.per_line() || out.values) && n_top > out.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->n_top)");
+    if (out.lines.bytes && units * unit > out.bytes_cap)
+        return fail(GX_E_LIMIT, name + ": the delivered text is larger than the capacity (see totals->units_top)");
+    if (out.lines.offsets && !v.off64 && units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+    const StagedLinesOut so = stage_lines_out(h, v, out.lines, host_out, n_top, units);
+    if (so.dev.offsets && n_top == 0) GX_HIP(hipMemsetAsync(so.dev.offsets, 0, off_w, stream));
     PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
     pw.perm_sorted = w.perm;
     pw.dst_off = w.dst_off;
-    GX_HIP(launch_partition_copy(so, data, offsets, off64 ? 1 : 0, wide ? 1 : 0, n, n_top, pw, stream));
+    GX_HIP(launch_partition_copy(so.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, n_top, pw, stream));
     if (out.values && n_top) GX_HIP(hipMemcpyAsync(out.values, w.values, n_top * 8, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
     if (host_out) {
-        if (out.index && n_top) GX_HIP(hipMemcpyAsync(out.index, so.index, n_top * 4, hipMemcpyDeviceToHost, stream));
-        if (out.bytes && units) GX_HIP(hipMemcpyAsync(out.bytes, so.bytes, units * unit, hipMemcpyDeviceToHost, stream));
-        if (out.offsets) GX_HIP(hipMemcpyAsync(out.offsets, so.offsets, (n_top + 1) * off_w, hipMemcpyDeviceToHost, stream));
-        if (out.ids && n_top) GX_HIP(hipMemcpyAsync(out.ids, dst_ids, n_top * id_row, hipMemcpyDeviceToHost, stream));
-        if (out.caps && n_top) GX_HIP(hipMemcpyAsync(out.caps, dst_caps, n_top * slots * 4, hipMemcpyDeviceToHost, stream));
+        deliver_lines_out(h, v, out.lines, so, n_top, units, stream);
         GX_HIP(hipStreamSynchronize(stream));
     } else {
-        if (!h->top_event) GX_HIP(hipEventCreateWithFlags(h->top_event.out(), hipEventDisableTiming));
-        GX_HIP(hipEventRecord(h->top_event.get(), stream));
-        h->top_pending = true;
+        leave_pending(h->top_event, h->top_pending, stream);
     }
     return GX_OK;
 }
@@ -2764,11 +2720,7 @@ int gx_top_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t 
         top_refusals(h, o, parts, n_parts, terms, n_terms, n_wanted, flags, o.utf16 != 0, totals, name, &ti, &wi);
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 2^32 - 1 lines and more");
-        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the keys pass
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            for (uint64_t i = 0; i < n; ++i)
-                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be ranked");
-        }
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "ranked");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
         const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         if (fmt != ROWS_DENSE) { caps = nullptr; out_caps = nullptr; }
@@ -2777,27 +2729,9 @@ int gx_top_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t 
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
-        // host buffers are staged to the device; the passes are the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (!o.device_pointers) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
-            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (caps && n && slots) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        const TopOut out{out_index, out_values, out_bytes, out_offsets, out_ids, out_caps, cap_lines, out_bytes_cap};
-        return top_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, ti, wi, n_wanted, out,
-                        !o.device_pointers, totals, nullptr, stream, name);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        const TopOut out{{out_index, out_bytes, out_offsets, out_ids, out_caps}, out_values, cap_lines, out_bytes_cap};
+        return top_pass(h, in.v, ti, wi, n_wanted, out, !o.device_pointers, totals, nullptr, stream, name);
     });
 }
 
@@ -2813,25 +2747,14 @@ int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx
         top_refusals(h, o, parts, n_parts, terms, n_terms, n_wanted, flags, false, totals, name, &ti, &wi);
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
-        }
-        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        if (n_lines) *n_lines = tl.n;
-        const TopOut to{out_index, out_values, out, nullptr, nullptr, nullptr, n_wanted, out_cap};
-        const int rc = top_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, ti, wi, n_wanted, to, !o.device_pointers,
-                                totals, counts, stream, name);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        const TopOut to{{out_index, out, nullptr, nullptr, nullptr}, out_values, n_wanted, out_cap};
+        const int rc = top_pass(h, tb.v, ti, wi, n_wanted, to, !o.device_pointers, totals, counts, stream, name);
         if (out_size) *out_size = totals->units_top;
         // The emit pass reads the offsets that text_lines left in the handle's scratch buffers, which the next whole-file call on any
         // stream overwrites: like every gx_text_* call this one returns with its work done.
@@ -2865,22 +2788,14 @@ static void quant_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_
 }
 
 // The passes on the handle's workspace (under h->mu) and ONE synchronisation of the stream, where the host reads the counts and the
-// result rows.  ids / offsets / data / caps: device pointers.  counts: also the histogram of outcomes (gx_text_capture_quantiles).
+// result rows.  counts: also the histogram of outcomes (gx_text_capture_quantiles).
 static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut) && offsetof(gx_quantile_out, below) == offsetof(QuantOut, below), "the rows are copied as they are");
-static int quant_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64, const void* data,
-                      const int32_t* caps, bool wide, const TopHead& ti, const QuantHead& qh, const WhereImage& wi, gx_quantile_out* out,
+static int quant_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const QuantHead& qh, const WhereImage& wi, gx_quantile_out* out,
                       gx_quantile_totals* totals, uint64_t* counts, hipStream_t stream) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
     const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    if (counts) {
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
-        const SelectWs w = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, false)), n, K, false);
-        GX_HIP(launch_select_flags(ids, fmt, row_units, K, n, nullptr, 0, w, stream));
-        GX_HIP(hipMemcpyAsync(counts, w.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
-    }
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_quantile_totals{};
     for (uint32_t q = 0; q < qh.n_q; ++q) out[q] = gx_quantile_out{};
     if (n == 0 || ti.n_parts == 0) {
@@ -2893,10 +2808,10 @@ static int quant_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row
     GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
     GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), &qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
     if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const TopArgs a{data, wide ? 1 : 0, caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + at_terms,
+    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + at_terms,
                     static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (ti.formats || wi.formats) ? 1u : 0u};
     const QuantWs w = quant_workspace(h->quant_ws.get(quant_workspace_bytes(n)), n);
-    GX_HIP(launch_quantiles(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, a, d_img + sizeof(TopHead), qh.n_q, w, stream));
+    GX_HIP(launch_quantiles(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_img + sizeof(TopHead), qh.n_q, w, stream));
     struct { uint32_t counts[TOP_COUNTS]; QuantOut out[QUANT_MAX]; } got{};
     static_assert(sizeof(got) == offsetof(QuantDev, sel), "the head's first words");
     GX_HIP(hipMemcpyAsync(&got, w.head, sizeof(got), hipMemcpyDeviceToHost, stream));
@@ -2925,37 +2840,14 @@ int gx_capture_quantiles(gx_handle* h, const void* bytes, const void* offsets, u
         quant_refusals(h, o, parts, n_parts, terms, n_terms, quantiles, n_quantiles, out, o.utf16 != 0, totals, name, &ti, &qh, &wi);
         if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
         if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits; split batches of 2^32 - 1 lines and more");
-        if (!o.device_pointers) {   // host offsets: a line of 4 G code units (or offsets that go backwards) is found here; device offsets by the keys pass
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            for (uint64_t i = 0; i < n; ++i)
-                if (off[i + 1] - off[i] > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": a line of 4 G code units or more cannot be measured");
-        }
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "measured");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         if (fmt != ROWS_DENSE) caps = nullptr;
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
-        // host buffers are staged to the device; the passes are the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (!o.device_pointers) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, name + ": bytes is NULL");
-            d_bytes = dev_alloc(in_bytes); d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (caps && n && slots) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        return quant_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, src, static_cast<const int32_t*>(src_caps), o.utf16 != 0, ti, qh, wi, out, totals,
-                          nullptr, stream);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        return quant_pass(h, in.v, ti, qh, wi, out, totals, nullptr, stream);
     });
 }
 
@@ -2972,23 +2864,13 @@ int gx_text_capture_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, 
         quant_refusals(h, o, parts, n_parts, terms, n_terms, quantiles, n_quantiles, out, false, totals, name, &ti, &qh, &wi);
         if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
         if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
-        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, name + ": device text must be 16-byte aligned");
-        }
-        // lines and the path as in gx_text_capture_stats; then the passes over the ids, offsets and capture rows they left on the device
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        if (n_lines) *n_lines = tl.n;
-        const int rc = quant_pass(h, tl.b.match_id, ROWS_DENSE, 1, tl.n, tl.b.offsets, false, src, tl.b.caps, false, ti, qh, wi, out, totals, counts, stream);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        const int rc = quant_pass(h, tb.v, ti, qh, wi, out, totals, counts, stream);
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         return rc;
     });
@@ -2997,26 +2879,22 @@ int gx_text_capture_quantiles(gx_handle* h, const uint8_t* text, uint64_t size, 
 // Keys, sort, scan and the groups on the handle's workspace (under h->mu); then the host reads what it must know before anything is
 // written -- the groups' boundaries, whose last entries are the number of kept lines and of kept code units, and whether a line was
 // too long to count: ONE small synchronisation of the stream (before it the want mask goes to the device, as select_pass sends it).
-// ids / offsets: device pointers; want: host, uint8_t[2K + 1], or nullptr = every outcome 0 .. 2K.  front: bytes at the head of the
+// want: host, uint8_t[2K + 1], or nullptr = every outcome 0 .. 2K.  front: bytes at the head of the
 // workspace that the caller keeps for itself.
 struct Partitioned {
     PartWs w;
     std::vector<uint64_t> groups;   // [2K + 3] lines, then [2K + 3] code units
     uint64_t lines = 0, units = 0;
 };
-static Partitioned partition_pass(gx_handle* h, const void* ids, RowFormat fmt, uint32_t row_units, uint64_t n, const void* offsets, bool off64,
-                                  const uint8_t* want, size_t front, hipStream_t stream) {
+static Partitioned partition_pass(gx_handle* h, const BatchView& v, const uint8_t* want, size_t front, hipStream_t stream) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
-    if (h->select_pending) {
-        GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-        h->select_pending = false;
-    }
+    wait_pending(h->select_event, h->select_pending, stream);
     Partitioned s;
-    uint8_t* ws = static_cast<uint8_t*>(h->select_ws.get(front + partition_workspace_bytes(n, K)));
-    s.w = partition_workspace(ws + front, n, K);
+    uint8_t* ws = static_cast<uint8_t*>(h->select_ws.get(front + partition_workspace_bytes(v.n, K)));
+    s.w = partition_workspace(ws + front, v.n, K);
     if (want) GX_HIP(hipMemcpyAsync(s.w.want, want, bins - 1u, hipMemcpyHostToDevice, stream));
     else GX_HIP(hipMemsetAsync(s.w.want, 1, bins - 1u, stream));
-    GX_HIP(launch_partition_sort(ids, fmt, row_units, K, n, offsets, off64 ? 1 : 0, s.w, stream));
+    GX_HIP(launch_partition_sort(v.ids, v.fmt, v.row_units, K, v.n, v.offsets, v.off64 ? 1 : 0, s.w, stream));
     s.groups.assign(2 * static_cast<size_t>(bins + 1), 0);
     uint32_t status = 0;
     GX_HIP(hipMemcpyAsync(s.groups.data(), s.w.groups, s.groups.size() * 8, hipMemcpyDeviceToHost, stream));
@@ -3047,69 +2925,30 @@ int gx_partition_lines(gx_handle* h, const void* bytes, const void* offsets, uin
         GX_HIP(hipSetDevice(h->device));
         std::lock_guard<std::mutex> lock(h->mu);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        const size_t off_w = o.offsets64 ? 8 : 4, unit = o.utf16 ? 2 : 1, id_row = static_cast<size_t>(row_units) * row_unit_bytes(fmt);
+        const size_t unit = o.utf16 ? 2 : 1;
         const size_t bins = 2 * static_cast<size_t>(h->T.n_rules) + 2;
         const bool host = !o.device_pointers;
-        // host buffers are staged to the device and back; the passes are the same
-        DevMem<> d_bytes, d_off, d_ids, d_caps, d_oindex, d_obytes, d_ooff, d_oids, d_ocaps;
-        const void *src = bytes, *src_off = offsets, *src_ids = ids, *src_caps = caps;
-        if (host) {
-            const HostOffsets off{offsets, o.offsets64 != 0, n};
-            const size_t in_bytes = static_cast<size_t>(off[n]) * unit;
-            if (in_bytes && !bytes) return fail(GX_E_ARG, "gx_partition_lines: bytes is NULL");
-            d_off = dev_alloc((n + 1) * off_w); d_ids = dev_alloc(n * id_row);
-            // (the sizes and the groups depend on the ids and the offsets alone: the text travels only if it is asked for)
-            if (out_bytes) {
-                d_bytes = dev_alloc(in_bytes);
-                if (in_bytes) GX_HIP(hipMemcpyAsync(d_bytes.get(), bytes, in_bytes, hipMemcpyHostToDevice, stream));
-            }
-            GX_HIP(hipMemcpyAsync(d_off.get(), offsets, (n + 1) * off_w, hipMemcpyHostToDevice, stream));
-            if (n) GX_HIP(hipMemcpyAsync(d_ids.get(), ids, n * id_row, hipMemcpyHostToDevice, stream));
-            if (out_caps && n) {
-                d_caps = dev_alloc(n * slots * 4);
-                GX_HIP(hipMemcpyAsync(d_caps.get(), caps, n * slots * 4, hipMemcpyHostToDevice, stream));
-            }
-            src = d_bytes.get(); src_off = d_off.get(); src_ids = d_ids.get(); src_caps = d_caps.get();
-        }
-        const Partitioned s = partition_pass(h, src_ids, fmt, row_units, n, src_off, o.offsets64 != 0, want, 0, stream);
+        // (the sizes and the groups depend on the ids and the offsets alone: the text and the capture rows travel only if they are asked for)
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{out_bytes != nullptr, out_caps != nullptr}, stream,
+                                           "gx_partition_lines");
+        const BatchView& v = in.v;
+        const Partitioned s = partition_pass(h, v, want, 0, stream);
         *n_out = s.lines;
         *bytes_out = s.units * unit;
         if (group_lines) std::copy(s.groups.begin(), s.groups.begin() + bins + 1, group_lines);
         if (group_units) std::copy(s.groups.begin() + bins + 1, s.groups.end(), group_units);
-        if (!out_bytes && !out_index && !out_offsets && !out_ids && !out_caps) return GX_OK;   // size query
-        if ((out_index || out_offsets || out_ids || out_caps) && s.lines > cap_lines)
-            return fail(GX_E_LIMIT, "gx_partition_lines: cap_lines is smaller than the partition (see *n_out)");
+        const LinesOut lo{out_index, out_bytes, out_offsets, out_ids, out_caps};
+        if (!lo.any()) return GX_OK;   // size query
+        if (lo.per_line() && s.lines > cap_lines) return fail(GX_E_LIMIT, "gx_partition_lines: cap_lines is smaller than the partition (see *n_out)");
         if (out_bytes && s.units * unit > out_bytes_cap)
             return fail(GX_E_LIMIT, "gx_partition_lines: out_bytes_cap is smaller than the kept text (see *bytes_out)");
-        SelectOut out{};
-        out.index = out_index; out.bytes = out_bytes; out.offsets = out_offsets;
-        void *dst_ids = out_ids, *dst_caps = out_caps;
-        if (host) {
-            if (out_index) { d_oindex = dev_alloc(s.lines * 4); out.index = static_cast<uint32_t*>(d_oindex.get()); }
-            if (out_bytes) { d_obytes = dev_alloc(s.units * unit); out.bytes = d_obytes.get(); }
-            if (out_offsets) { d_ooff = dev_alloc((s.lines + 1) * off_w); out.offsets = d_ooff.get(); }
-            if (out_ids) { d_oids = dev_alloc(s.lines * id_row); dst_ids = d_oids.get(); }
-            if (out_caps) { d_ocaps = dev_alloc(s.lines * slots * 4); dst_caps = d_ocaps.get(); }
-        }
-        if (out_ids) { out.col_src[0] = src_ids; out.col_dst[0] = dst_ids; out.col_width[0] = row_units; out.col_unit_bytes[0] = row_unit_bytes(fmt); }
-        if (out_caps) { out.col_src[1] = src_caps; out.col_dst[1] = dst_caps; out.col_width[1] = static_cast<uint32_t>(slots); out.col_unit_bytes[1] = 4; }
-        if (out.offsets && s.lines == 0) GX_HIP(hipMemsetAsync(out.offsets, 0, off_w, stream));
-        GX_HIP(launch_partition_copy(out, src, src_off, o.offsets64 ? 1 : 0, o.utf16 ? 1 : 0, n, s.lines, s.w, stream));
-        if (host) {
-            if (out_index && s.lines) GX_HIP(hipMemcpyAsync(out_index, out.index, s.lines * 4, hipMemcpyDeviceToHost, stream));
-            if (out_bytes && s.units) GX_HIP(hipMemcpyAsync(out_bytes, out.bytes, s.units * unit, hipMemcpyDeviceToHost, stream));
-            if (out_offsets) GX_HIP(hipMemcpyAsync(out_offsets, out.offsets, (s.lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
-            if (out_ids && s.lines) GX_HIP(hipMemcpyAsync(out_ids, dst_ids, s.lines * id_row, hipMemcpyDeviceToHost, stream));
-            if (out_caps && s.lines) GX_HIP(hipMemcpyAsync(out_caps, dst_caps, s.lines * slots * 4, hipMemcpyDeviceToHost, stream));
-        }
-        if (o.no_sync) {
-            // (the copy pass still reads the workspace: whoever uses it next waits for this)
-            if (!h->select_event) GX_HIP(hipEventCreateWithFlags(h->select_event.out(), hipEventDisableTiming));
-            GX_HIP(hipEventRecord(h->select_event.get(), stream));
-            h->select_pending = true;
-            return GX_OK;
-        }
-        GX_HIP(hipStreamSynchronize(stream));
+        const StagedLinesOut out = stage_lines_out(h, v, lo, host, s.lines, s.units);
+        if (out.dev.offsets && s.lines == 0) GX_HIP(hipMemsetAsync(out.dev.offsets, 0, v.off64 ? 8 : 4, stream));
+        GX_HIP(launch_partition_copy(out.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, s.lines, s.w, stream));
+        if (host) deliver_lines_out(h, v, lo, out, s.lines, s.units, stream);
+        // (no_sync: the copy pass still reads the workspace: whoever uses it next waits for this)
+        if (o.no_sync) leave_pending(h->select_event, h->select_pending, stream);
+        else GX_HIP(hipStreamSynchronize(stream));
         return GX_OK;
     });
 }
@@ -3128,35 +2967,21 @@ int gx_text_to_jsonl_by_extraction(gx_handle* h, const uint8_t* text, uint64_t s
         std::lock_guard<std::mutex> lock(h->mu);
         const GxJsonl& tm = jsonl_templates(h, id_as);
         hipStream_t stream = static_cast<hipStream_t>(o.stream);
-        DevMem<uint8_t> d_text, d_out;
-        const uint8_t* src = text;
-        if (!o.device_pointers) {
-            d_text = dev_alloc<uint8_t>(size);
-            if (size) GX_HIP(hipMemcpyAsync(d_text.get(), text, size, hipMemcpyHostToDevice, stream));
-            src = d_text.get();
-        } else if (reinterpret_cast<uintptr_t>(text) & 15u) {
-            return fail(GX_E_ARG, "gx_text_to_jsonl_by_extraction: device text must be 16-byte aligned");
-        }
+        DevMem<uint8_t> d_out;
         const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
         const int passthrough = (o.utf8_passthrough || o.utf8) ? 1 : 0;   // (utf8 implies it)
         // 1. lines, 2. the path (no escape bits: they would belong to the original text, and the JSON passes read the partitioned one)
-        const TextLines tl = text_lines(h, src, size, slots, stream, nullptr, 0, o.utf8 != 0);
-        const uint64_t n = tl.n;
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, "gx_text_to_jsonl_by_extraction");
+        const BatchView& v = tb.v;
+        const uint64_t n = v.n;
         // 3. the histogram (the head of the workspace) and the partition of the matched lines, outcomes 0 .. K - 1
         const size_t front = counts ? select_workspace_bytes(n, K, false) : 0;
         std::vector<uint8_t> want(bins - 1u, 0);
         std::fill(want.begin(), want.begin() + K, 1);
-        if (h->select_pending) {
-            GX_HIP(hipStreamWaitEvent(stream, h->select_event.get(), 0));
-            h->select_pending = false;
-        }
+        wait_pending(h->select_event, h->select_pending, stream);
         (void)h->select_ws.get(front + partition_workspace_bytes(n, K));   // (grown once: the histogram's part stays where it is)
-        if (counts) {
-            const SelectWs cw = select_workspace(h->select_ws.get(front), n, K, false);
-            GX_HIP(launch_select_flags(tl.b.match_id, ROWS_DENSE, 1, K, n, nullptr, 0, cw, stream));
-            GX_HIP(hipMemcpyAsync(counts, cw.counts, static_cast<size_t>(bins) * 8, hipMemcpyDeviceToHost, stream));
-        }
-        const Partitioned s = partition_pass(h, tl.b.match_id, ROWS_DENSE, 1, n, tl.b.offsets, false, want.data(), front, stream);
+        if (counts) counts_beside(h, v, counts, stream);
+        const Partitioned s = partition_pass(h, v, want.data(), front, stream);
         // (the extraction ran on the split pass's own longest line; a kernel that met a longer one after all left rows unwritten)
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: gx_text_to_jsonl_by_extraction: a line longer than the split pass reported");
         const uint64_t m = s.lines;
@@ -3169,10 +2994,10 @@ int gx_text_to_jsonl_by_extraction(gx_handle* h, const uint8_t* text, uint64_t s
         b.strip_eol = 1;
         SelectOut part{};
         part.bytes = const_cast<void*>(b.data); part.offsets = const_cast<void*>(b.offsets);
-        part.col_src[0] = tl.b.match_id; part.col_dst[0] = b.match_id; part.col_width[0] = 1; part.col_unit_bytes[0] = 4;
-        if (slots) { part.col_src[1] = tl.b.caps; part.col_dst[1] = b.caps; part.col_width[1] = static_cast<uint32_t>(slots); part.col_unit_bytes[1] = 4; }
+        part.col_src[0] = v.ids; part.col_dst[0] = b.match_id; part.col_width[0] = 1; part.col_unit_bytes[0] = 4;
+        if (slots) { part.col_src[1] = v.caps; part.col_dst[1] = b.caps; part.col_width[1] = static_cast<uint32_t>(slots); part.col_unit_bytes[1] = 4; }
         if (m == 0) GX_HIP(hipMemsetAsync(part.offsets, 0, 4, stream));
-        GX_HIP(launch_partition_copy(part, src, tl.b.offsets, 0, 0, n, m, s.w, stream));
+        GX_HIP(launch_partition_copy(part, v.data, v.offsets, 0, 0, n, m, s.w, stream));
         // 4. the text, from the partitioned batch
         void* ws_json = h->scratch[0].get(jsonl_workspace_bytes(m));
         uint64_t* loff = static_cast<uint64_t*>(h->scratch[1].get((m + 1) * 8 + (static_cast<size_t>(K) + 1) * 8));

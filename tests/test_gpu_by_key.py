@@ -451,3 +451,83 @@ def test_text_form_equals_the_batch_form_of_its_lines(last_newline):
         if parts is BY_PATH and lo == 2 and not last_newline:
             j = got["index"].tolist().index(n - 1)
             assert j + 1 < len(got["index"]) and got["data"][got["offsets"][j + 1] - 1] != 10      # the unterminated line, now in the middle
+
+
+# ---------------------------------------------------------------------------
+# the same batch from host buffers and from device pointers
+# ---------------------------------------------------------------------------
+def twin_batch(n, offsets_dtype):
+    """n lines of seven keys; among 65 lines one is empty (its key group unset) and one is unmatched"""
+    names, lengths, ids = [i % 7 for i in range(n)], [5 + i % 11 for i in range(n)], [i % 3 for i in range(n)]
+    if n > 9:
+        names[5], lengths[5] = -1, 0
+        names[9], ids[9] = -1, -1
+    return named(names, lengths=lengths, ids=ids, offsets_dtype=offsets_dtype)
+
+
+@pytest.mark.parametrize("offsets_dtype", [np.uint32, np.uint64])
+@pytest.mark.parametrize("compact", [0, 1])
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_host_buffers_and_device_pointers_leave_the_same_bytes(n, compact, offsets_dtype):
+    from twin_buffers import twins
+    gorp = trivial_handle(3)
+    data, offsets, ids, caps = twin_batch(n, offsets_dtype)
+    if compact:
+        ids, caps = pack(ids, caps, np.uint16) if n else np.zeros((0, 5), np.uint16), None
+    id_row = ids.itemsize * (ids.shape[1] if ids.ndim == 2 else 1)
+    off_w = np.dtype(offsets_dtype).itemsize
+    parts = [(0, 0), (1, 0), (2, 0)]
+    opts = dict(offsets64=off_w == 8, compact=compact)
+
+    def size_query(b, device_pointers):
+        rc, totals = gorp.lines_by_key_device(b.put(data), b.put(offsets), n, b.put(ids), b.put(caps), parts, 2, None, max_keys=n, device_pointers=device_pointers, **opts)
+        return rc, totals
+    (rc, t), _ = twins(size_query)
+    assert rc == N.GX_OK and t["lines_out"] == (n - 2 if n > 9 else 0) and t["n_keys"] == min(n, 7)
+    m, units, k = t["lines_out"], t["units_out"], t["n_keys"]
+
+    def call(b, device_pointers):
+        rc, totals = gorp.lines_by_key_device(
+            b.put(data), b.put(offsets), n, b.put(ids), b.put(caps), parts, 2, None, key_lines_ptr=b.room("lines", k * 8), line_key_ptr=b.room("line_key", n * 4),
+            max_keys=n, out_index_ptr=b.room("index", m * 4), out_data_ptr=b.room("data", units), out_offsets_ptr=b.room("offsets", (m + 1) * off_w),
+            out_ids_ptr=b.room("ids", m * id_row), out_caps_ptr=None if compact else b.room("caps", m * 16), cap_lines=m, out_bytes_cap=units,
+            key_out_lines_ptr=b.room("kol", (k + 1) * 8), key_out_units_ptr=b.room("kou", (k + 1) * 8), device_pointers=device_pointers, **opts)
+        return rc, totals
+    (rc, totals), rooms = twins(call)
+    assert rc == N.GX_OK and totals == t
+    index = np.frombuffer(rooms["index"], np.uint32)[:m]
+    kept = [i for i in range(n) if n > 9 and i not in (5, 9)]
+    first = {}
+    for i in kept:
+        first.setdefault(i % 7, i)                                     # keys are numbered by their first line
+    assert index.tolist() == [i for key in sorted(first, key=first.get) for i in kept if i % 7 == key]
+    assert np.frombuffer(rooms["offsets"][:(m + 1) * off_w], offsets_dtype)[m] == units
+
+
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_form_from_host_buffers_and_device_pointers(n):
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+
+    def size_query(b, device_pointers):
+        rc, totals, counts, n_lines = gorp.text_lines_by_key_device(b.put(text16), text.size, BY_PATH, 2, None, max_keys=n, device_pointers=device_pointers)
+        return rc, totals, counts.tolist(), n_lines
+    (rc, t, counts, n_lines), _ = twins(size_query)
+    assert rc == N.GX_OK and n_lines == n and sum(counts) == n and t["lines_out"] == (n - 2 if n > 9 else 0)
+    m, units, k = t["lines_out"], t["units_out"], t["n_keys"]
+
+    def call(b, device_pointers):
+        rc, totals, counts, n_lines = gorp.text_lines_by_key_device(
+            b.put(text16), text.size, BY_PATH, 2, None, key_lines_ptr=b.room("lines", k * 8), line_key_ptr=b.room("line_key", n * 4), max_keys=n,
+            out_ptr=b.room("data", units), out_cap=units, out_offsets_ptr=b.room("offsets", (m + 1) * 4), out_index_ptr=b.room("index", m * 4),
+            key_out_lines_ptr=b.room("kol", (k + 1) * 8), key_out_units_ptr=b.room("kou", (k + 1) * 8), device_pointers=device_pointers)
+        return rc, totals, counts.tolist(), n_lines
+    (rc, totals, counts2, _), rooms = twins(call)
+    assert rc == N.GX_OK and totals == t and counts2 == counts
+    assert len(set(np.frombuffer(rooms["index"], np.uint32)[:m].tolist())) == m and np.frombuffer(rooms["offsets"], np.uint32)[m] == units

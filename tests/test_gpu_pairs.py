@@ -490,3 +490,73 @@ def test_text_form_equals_the_batch_form_of_its_lines(last_newline):
             assert got[name].dtype == want[name].dtype and np.array_equal(got[name], want[name]), name
     listed, _, _ = gorp.text_group_pairs(text, VERB_PATH)
     assert listed["pairs"][0] == (0, lines[0].split()[3].encode()) and len(listed["pairs"]) == listed["totals"]["n_pairs"]
+
+
+# ---------------------------------------------------------------------------
+# the same batch from host buffers and from device pointers
+# ---------------------------------------------------------------------------
+def pair_rooms(b, n, t, unit, off_w):
+    """every output of a group_pairs_device / text_group_pairs_device call, sized by the totals of its size query"""
+    k, ku, p, pu = t["n_keys"], t["key_units"], t["n_pairs"], t["pair_units"]
+    return dict(key_units_ptr=b.room("key_units", ku * unit), key_units_cap=ku, key_offsets_ptr=b.room("key_offsets", (k + 1) * off_w),
+                key_first_line_ptr=b.room("first_line", k * 4), key_lines_ptr=b.room("lines", k * 8), line_key_ptr=b.room("line_key", n * 4), max_keys=max(k, 1),
+                pair_units_ptr=b.room("pair_units", pu * unit), pair_units_cap=pu, pair_offsets_ptr=b.room("pair_offsets", (p + 1) * off_w),
+                pair_key_ptr=b.room("pair_key", p * 4), pair_first_line_ptr=b.room("pair_first_line", p * 4), pair_lines_ptr=b.room("pair_lines", p * 8),
+                key_pairs_ptr=b.room("key_pairs", k * 8), line_pair_ptr=b.room("line_pair", n * 4), max_pairs=max(p, 1))
+
+
+@pytest.mark.parametrize("offsets_dtype", [np.uint32, np.uint64])
+@pytest.mark.parametrize("compact", [0, 1])
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_host_buffers_and_device_pointers_leave_the_same_bytes(n, compact, offsets_dtype):
+    from twin_buffers import twins
+    gorp = trivial_handle(3)
+    kn, sn, lengths, ids = [i % 7 for i in range(n)], [i % 3 for i in range(n)], [6 + i % 11 for i in range(n)], [i % 3 for i in range(n)]
+    if n > 9:
+        kn[5], sn[5], lengths[5] = -1, -1, 0                           # an empty line: neither group set
+        kn[9], sn[9], ids[9] = -1, -1, -1                              # an unmatched line
+    data, offsets, ids, caps = named(kn, sn, lengths=lengths, ids=ids, offsets_dtype=offsets_dtype)
+    if compact:
+        ids, caps = pack(ids, caps, np.uint16) if n else np.zeros((0, 5), np.uint16), None
+    off_w = np.dtype(offsets_dtype).itemsize
+    parts = [(0, 0, 1), (1, 0, 1), (2, 0, 1)]
+    opts = dict(offsets64=off_w == 8, compact=compact)
+
+    def size_query(b, device_pointers):
+        return gorp.group_pairs_device(b.put(data), b.put(offsets), n, b.put(ids), b.put(caps), parts, max_keys=max(n, 1), max_pairs=max(n, 1),
+                                       device_pointers=device_pointers, **opts)
+    (rc, t), _ = twins(size_query)
+    assert rc == N.GX_OK and t["n_keys"] == min(n, 7) and t["n_pairs"] == min(n, 21) and t["paired"] == (n - 2 if n > 9 else n)
+
+    def call(b, device_pointers):
+        return gorp.group_pairs_device(b.put(data), b.put(offsets), n, b.put(ids), b.put(caps), parts, device_pointers=device_pointers,
+                                       **pair_rooms(b, n, t, 1, off_w), **opts)
+    (rc, totals), rooms = twins(call)
+    assert rc == N.GX_OK and totals == t
+    assert int(np.frombuffer(rooms["pair_lines"], np.uint64)[:t["n_pairs"]].sum()) == t["paired"]
+
+
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_form_from_host_buffers_and_device_pointers(n):
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+
+    def size_query(b, device_pointers):
+        rc, totals, counts, n_lines = gorp.text_group_pairs_device(b.put(text16), text.size, VERB_PATH, max_keys=max(n, 1), max_pairs=max(n, 1),
+                                                                   device_pointers=device_pointers)
+        return rc, totals, counts.tolist(), n_lines
+    (rc, t, counts, n_lines), _ = twins(size_query)
+    assert rc == N.GX_OK and n_lines == n and sum(counts) == n and t["paired"] == (n - 2 if n > 9 else n) and t["n_pairs"] == min(n, 21)
+
+    def call(b, device_pointers):
+        rc, totals, counts, n_lines = gorp.text_group_pairs_device(b.put(text16), text.size, VERB_PATH, device_pointers=device_pointers, **pair_rooms(b, n, t, 1, 4))
+        return rc, totals, counts.tolist(), n_lines
+    (rc, totals, counts2, _), rooms = twins(call)
+    assert rc == N.GX_OK and totals == t and counts2 == counts
+    assert int(np.frombuffer(rooms["pair_lines"], np.uint64)[:t["n_pairs"]].sum()) == t["paired"]

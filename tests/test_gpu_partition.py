@@ -568,3 +568,35 @@ def test_text_to_jsonl_by_extraction_utf8(three):
     assert "中".encode("utf-8") in text and "é".encode("utf-8") in text
     got, group_out, counts = check_by_extraction(gorp, text, ["ab", "cee", "dee"], utf8=True)
     assert "中".encode("utf-8") in got and (np.diff(group_out.astype(np.int64)) > 0).all()
+
+
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_to_jsonl_by_extraction_from_host_buffers_and_device_pointers(n):
+    """the same text once from a host buffer and once from a device pointer: equal sizes, groups, counts, line count and bytes; every
+    matched line's object lies in its extraction's group (among 65 lines one is empty and one matches nothing)"""
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+
+    def size_query(b, device_pointers):
+        size, group_out, counts, n_lines = gorp.text_to_jsonl_by_extraction_device(b.put(text16), text.size, None, 0, id_as="rule", device_pointers=device_pointers)
+        return size, group_out.tolist(), counts.tolist(), n_lines
+    (size, group_out, counts, n_lines), _ = twins(size_query)
+    matched = n - 2 if n > 9 else n
+    assert n_lines == n and sum(counts) == n and sum(counts[:3]) == matched and group_out[0] == 0 and group_out[-1] == size
+
+    def call(b, device_pointers):
+        got, g, c, nl = gorp.text_to_jsonl_by_extraction_device(b.put(text16), text.size, b.room("out", size), size, id_as="rule", device_pointers=device_pointers)
+        return got, g.tolist(), c.tolist(), nl
+    (got, group_out2, counts2, _), rooms = twins(call)
+    assert got == size and group_out2 == group_out and counts2 == counts
+    objects = rooms["out"][:size].split(b"\n")[:-1] if size else []
+    assert len(objects) == matched
+    for k in range(3):
+        part = rooms["out"][group_out[k]:group_out[k + 1]]
+        assert part.count(b"\n") == counts[k] and all(b'"rule"' in o for o in part.split(b"\n")[:-1])

@@ -521,6 +521,32 @@ def test_text_capture_stats_is_split_extract_stats(utf8):
     assert n_lines == 0 and counts.sum() == 0 and all(s["lines"] == 0 and s["min"] is None and s["sum"] == 0 for s in got)
 
 
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_form_from_host_buffers_and_device_pointers(n):
+    """the same text once from a host buffer and once from a device pointer: equal stats, histogram, counts and line count, and the
+    stats are those of the GET lines (every third line; among 65 lines one is empty and one matches nothing)"""
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+    v = np.array([10 * i for i in range(n) if i % 3 == 0 and i != 9], np.int64)     # (no value lies on an edge)
+    for where, keep in ((None, v), ([("GetRequest", "timeTakenInMsec", ">=", 300)], v[v >= 300])):
+        def call(b, device_pointers):
+            stats, counts, n_lines = gorp.text_capture_stats_device(b.put(text16), text.size, README_MEASURES, where, device_pointers=device_pointers)
+            return plain(stats), counts.tolist(), n_lines
+        (stats, counts, n_lines), _ = twins(call)
+        assert n_lines == n and sum(counts) == n and counts[gorp.num_extractions] == (2 if n > 9 else 0)      # (unmatched: the empty line and "nothing here")
+        get = stats[0]
+        assert get["lines"] == get["numbers"] == len(keep) and get["unset"] == get["not_numbers"] == 0 and get["sum"] == int(keep.sum())
+        assert (get["min"], get["max"]) == ((int(keep.min()), int(keep.max())) if len(keep) else (None, None))
+        assert get["hist"] == np.bincount(np.searchsorted(EDGES, keep), minlength=len(EDGES) + 1).tolist()
+        assert stats[2]["lines"] == len(keep) and stats[2]["numbers"] == 0 and stats[2]["not_numbers"] == len(keep)   # ("GET" is no number)
+
+
 # ---------------------------------------------------------------------------
 # a batch that lives on the device, against torch's integer reductions
 # ---------------------------------------------------------------------------

@@ -619,3 +619,36 @@ def test_200k_lines_on_the_device_against_torch_sort():
             assert torch.equal(index.to(torch.int64), lines[order[:want]]) and torch.equal(values, v[order[:want]])
             assert torch.equal(out.view(want, L), data.view(n, L)[lines[order[:want]]])
             assert totals["last_value"] == int(values[-1]) and totals["ties_left"] == int((v == values[-1]).sum() - (values == values[-1]).sum())
+
+
+# ---------------------------------------------------------------------------
+# the whole-file call from host buffers and from device pointers
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_form_from_host_buffers_and_device_pointers(n):
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+    gets = [i for i in range(n) if i % 3 == 0 and i != 9][::-1][:4]     # the four slowest GET lines, slowest first
+
+    def size_query(b, device_pointers):
+        rc, totals, size, counts, n_lines = gorp.text_top_lines_device(b.put(text16), text.size, BY_TIME, 4, device_pointers=device_pointers)
+        return rc, totals, size, counts.tolist(), n_lines
+    (rc, t, size, counts, n_lines), _ = twins(size_query)
+    assert rc == N.GX_OK and n_lines == n and sum(counts) == n and t["n_top"] == len(gets) and size == sum(len(lines[i]) + 1 for i in gets)
+
+    def call(b, device_pointers):
+        rc, totals, out_size, c, nl = gorp.text_top_lines_device(b.put(text16), text.size, BY_TIME, 4, out_index_ptr=b.room("index", 4 * 4),
+                                                                 out_values_ptr=b.room("values", 4 * 8), out_ptr=b.room("out", size), out_cap=size,
+                                                                 device_pointers=device_pointers)
+        return rc, totals, out_size, c.tolist(), nl
+    (rc, totals, out_size, counts2, _), rooms = twins(call)
+    assert rc == N.GX_OK and totals == t and out_size == size and counts2 == counts
+    assert np.frombuffer(rooms["index"], np.uint32)[:len(gets)].tolist() == gets
+    assert np.frombuffer(rooms["values"], np.int64)[:len(gets)].tolist() == [10 * i for i in gets]
+    assert rooms["out"][:size] == "".join(lines[i] + "\n" for i in gets).encode()

@@ -580,3 +580,32 @@ def test_200k_lines_on_the_device():
         assert torch.equal(out, data.view(n, L)[t_keep].reshape(-1))
         assert torch.equal(o_off, (torch.arange(k + 1, device="cuda") * L).to(torch.int32))
         assert torch.equal(o_ids, ids[t_keep]) and torch.equal(o_caps, caps[t_keep])
+
+
+# ---------------------------------------------------------------------------
+# the whole-file call from host buffers and from device pointers
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_text_form_from_host_buffers_and_device_pointers(n):
+    from twin_buffers import twins
+    gorp = Gorp.construct(W.readme3_definition())
+    lines = ["[%d]: %s %dms /p/%d" % (i, ("GET", "PUT", "POST")[i % 3], 10 * i, i % 7) for i in range(n)]
+    if n > 9:
+        lines[5], lines[9] = "", "nothing here"
+    text = np.frombuffer("".join(l + "\n" for l in lines).encode(), np.uint8)
+    text16 = np.zeros((text.size + 15) // 16 * 16 + 16, np.uint8)       # (a device text is 16-byte aligned: torch's allocations are)
+    text16[:text.size] = text
+    kept = [l for i, l in enumerate(lines) if i % 3 == 0 and 10 * i >= 300 and i != 9]
+    for where, want, expect in (([("GetRequest", "timeTakenInMsec", ">=", 300)], "matched-by-terms", "".join(l + "\n" for l in kept).encode()),
+                                ([], ("unmatched", "exceptions"), b"\nnothing here\n" if n > 9 else b"")):
+        def size_query(b, device_pointers):
+            size, counts, n_lines = gorp.text_select_where_device(b.put(text16), text.size, want, where, None, 0, device_pointers=device_pointers)
+            return size, counts.tolist(), n_lines
+        (size, counts, n_lines), _ = twins(size_query)
+        assert size == len(expect) and n_lines == n and sum(counts) == n
+
+        def call(b, device_pointers):
+            got, c, nl = gorp.text_select_where_device(b.put(text16), text.size, want, where, b.room("out", size), size, device_pointers=device_pointers)
+            return got, c.tolist(), nl
+        (got, counts2, _), rooms = twins(call)
+        assert got == size and counts2 == counts and rooms["out"][:size] == expect
