@@ -55,6 +55,7 @@ SYMBOLS = [
     "gx_top_groups", "gx_text_top_groups",
     "gx_lines_by_key", "gx_text_lines_by_key",
     "gx_group_pairs", "gx_text_group_pairs",
+    "gx_bucket_lines", "gx_text_bucket_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
 
@@ -110,6 +111,7 @@ GX_RANK_LINES, GX_RANK_NUMBERS, GX_RANK_SUM, GX_RANK_MAX, GX_RANK_MIN = range(5)
 GX_TOP_GROUPS_SMALLEST = 2
 GX_TOP_GROUPS_MAX = 4096
 GX_BY_KEY_ALL_DIGITS = 2
+GX_BUCKET_ALL_DIGITS = 2
 
 
 class gx_group_part(C.Structure):
@@ -174,6 +176,20 @@ class gx_pairs_out(C.Structure):
 class gx_pairs_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("n_pairs", C.c_uint64), ("pair_units", C.c_uint64), ("paired", C.c_uint64), ("unpaired", C.c_uint64),
                 ("pairs_exact", C.c_uint64)]
+
+
+class gx_bucket_part(C.Structure):
+    _fields_ = [("extraction", C.c_int32), ("number_group", C.c_int32), ("value_group", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class gx_bucket_out(C.Structure):
+    _fields_ = [("bucket_number", C.c_void_p), ("bucket_first_line", C.c_void_p), ("bucket_lines", C.c_void_p), ("bucket_stats", C.c_void_p),
+                ("line_bucket", C.c_void_p), ("max_buckets", C.c_uint64)]
+
+
+class gx_bucket_totals(C.Structure):
+    _fields_ = [("n_buckets", C.c_uint64), ("lines", C.c_uint64), ("bucketed", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64),
+                ("out_of_range", C.c_uint64), ("exact", C.c_uint64), ("first_bucket", C.c_int64), ("last_bucket", C.c_int64)]
 
 
 class gx_device_shard(C.Structure):
@@ -398,6 +414,13 @@ def lib():
                                       C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_pairs_out), C.POINTER(gx_pairs_totals), C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_pairs.restype = C.c_int
+    L.gx_bucket_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_bucket_part), C.c_uint32, C.c_int64, C.c_int64,
+                                  C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.POINTER(gx_batch_opts)]
+    L.gx_bucket_lines.restype = C.c_int
+    L.gx_text_bucket_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_bucket_part), C.c_uint32, C.c_int64, C.c_int64, C.POINTER(gx_where_term),
+                                       C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.c_void_p, C.POINTER(C.c_uint64),
+                                       C.POINTER(gx_batch_opts)]
+    L.gx_text_bucket_lines.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

@@ -24,6 +24,7 @@
 #include "gx_group.hpp"
 #include "gx_group_quantile.hpp"
 #include "gx_pairs.hpp"
+#include "gx_bucket.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
@@ -295,6 +296,12 @@ struct gx_handle {
     GrowBuf pairs_image, pairs_table, pairs_lines;
     Event group_event;
     bool group_pending = false;
+    // gx_bucket_lines: its parts and terms on the device (BucketHead, gx_bucket.hpp; WhereHead behind it), the slots' words and arrays,
+    // the lines' slots and the sort's workspace (gx_bucket.hip).  Used under `mu`.  With device pointers the sort and the emit are left
+    // running on the caller's stream: the next call's stream waits for bucket_event first.
+    GrowBuf bucket_image, bucket_table, bucket_lines, bucket_sort;
+    Event bucket_event;
+    bool bucket_pending = false;
     // gx_top_lines: its parts and terms on the device (TopHead, gx_top.hpp; WhereHead behind it) and the passes' workspace (gx_top.hip:
     // TopWs).  Used under `mu`.  With device pointers the emit pass is left running on the caller's stream and still reads the
     // workspace: the next call's stream waits for top_event first (gx_partition_lines' rule for its no_sync copy pass).
@@ -2547,6 +2554,209 @@ int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_pairs", h, text, size, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, counts, n_lines, opts,
                            pairs_extras(second_groups, pairs, totals));
+}
+
+// The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.
+struct BucketImage {
+    BucketHead head{};
+    bool values = false;
+};
+static BucketImage bucket_image(const gx_handle* h, const gx_bucket_part* parts, uint32_t n_parts, int64_t origin, int64_t width, uint32_t flags,
+                                const std::string& name) {
+    BucketImage img;
+    if (flags & ~static_cast<uint32_t>(GX_GROUP_WEAK_HASH | GX_BUCKET_ALL_DIGITS)) throw GxError(GX_E_ARG, name + ": unknown flag bits");
+    if (width < 1) throw GxError(GX_E_ARG, name + ": width below 1");
+    img.head.flags = flags;
+    img.head.origin = origin;
+    img.head.width = static_cast<uint64_t>(width);
+    if (n_parts == 0) return img;
+    if (!parts) throw GxError(GX_E_ARG, name + ": parts is NULL");
+    if (n_parts > BUCKET_MAX_PARTS) throw GxError(GX_E_LIMIT, name + ": more than 64 parts");
+    const int32_t K = static_cast<int32_t>(h->T.n_rules);
+    std::vector<uint32_t> order(n_parts);
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const gx_bucket_part& p = parts[t];
+        order[t] = t;
+        if (p.extraction < 0 || p.extraction >= K) throw GxError(GX_E_ARG, name + ": a part's extraction is not in [0, K)");
+        const int32_t groups = gx_num_groups(h, p.extraction);
+        if (p.number_group < 0 || p.number_group >= groups) throw GxError(GX_E_ARG, name + ": a part's number_group is not one of its extraction's");
+        if (p.value_group < -1 || p.value_group >= groups) throw GxError(GX_E_ARG, name + ": a part's value_group is neither -1 nor one of its extraction's");
+        if (p.reserved != 0) throw GxError(GX_E_ARG, name + ": a part's reserved is not 0");
+        if (p.value_group >= 0) img.values = true;
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return parts[a].extraction < parts[b].extraction; });
+    for (uint32_t q = 0; q < n_parts; ++q) {
+        const gx_bucket_part& p = parts[order[q]];
+        if (q && parts[order[q - 1]].extraction == p.extraction) throw GxError(GX_E_ARG, name + ": two parts for one extraction");
+        img.head.ext[q] = static_cast<uint32_t>(p.extraction);
+        img.head.part[q].key_group = static_cast<uint16_t>(p.number_group);
+        img.head.part[q].value_group = p.value_group < 0 ? static_cast<uint16_t>(GROUP_NO_VALUE) : static_cast<uint16_t>(p.value_group);
+        img.head.nfmt[q] = h->number_format_of(p.extraction, p.number_group);
+        if (p.value_group >= 0) img.head.vfmt[q] = h->number_format_of(p.extraction, p.value_group);
+        if (img.head.nfmt[q] || img.head.vfmt[q]) img.head.formats = 1u;
+    }
+    img.head.n_parts = n_parts;
+    img.head.has_values = img.values ? 1u : 0u;
+    return img;
+}
+
+// what both bucket calls refuse before they look at the device: group_refusals' list in its order, with the width behind the flags
+static void bucket_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_bucket_part* parts, uint32_t n_parts, int64_t origin, int64_t width,
+                            const gx_where_term* terms, uint32_t n_terms, uint32_t flags, bool wide, const gx_bucket_out& out, const gx_bucket_totals* totals,
+                            const std::string& name, BucketImage* bi, WhereImage* wi) {
+    if (!totals) throw GxError(GX_E_ARG, name + ": totals is NULL");
+    *bi = bucket_image(h, parts, n_parts, origin, width, flags, name);
+    if (out.bucket_stats && !bi->values) throw GxError(GX_E_ARG, name + ": bucket_stats without a value_group");
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the totals are host values");
+    if (out.max_buckets > BUCKET_MAX_BUCKETS) throw GxError(GX_E_LIMIT, name + ": max_buckets above 2^30");
+}
+
+// The passes on the handle's buffers (under h->mu): build, flags and the scan; ONE synchronisation of the stream, where the host reads
+// the totals, the buckets and the range of their words and checks the capacity; then the pairs, the sort and the emits.  out: the
+// caller's, device or host (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes
+// (gx_text_bucket_lines).
+static int bucket_pass(gx_handle* h, const BatchView& v, const BucketImage& bi, const WhereImage& wi, const gx_bucket_out& out, bool host_out,
+                       gx_bucket_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
+    *totals = gx_bucket_totals{};
+    totals->exact = 1;
+    const bool per_bucket = out.bucket_number || out.bucket_first_line || out.bucket_lines || out.bucket_stats;
+    const bool any_out = per_bucket || out.line_bucket;
+    auto no_line_has_one = [&]() {
+        if (!out.line_bucket || !n) return;
+        if (host_out) memset(out.line_bucket, 0xFF, n * 4);
+        else GX_HIP(hipMemsetAsync(out.line_bucket, 0xFF, n * 4, stream));
+    };
+    if (n == 0 || bi.head.n_parts == 0) {
+        GX_HIP(hipStreamSynchronize(stream));
+        no_line_has_one();
+        return GX_OK;
+    }
+    wait_pending(h->bucket_event, h->bucket_pending, stream);
+    const uint32_t n_slots = group_slots(out.max_buckets);
+    uint8_t* d_img = static_cast<uint8_t*>(h->bucket_image.get(sizeof(BucketHead) + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d_img, &bi.head, sizeof(BucketHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(BucketHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(BucketHead),
+                      static_cast<uint32_t>(wi.bytes.size()), bi.values ? 1u : 0u, (bi.head.formats || wi.formats) ? 1u : 0u};
+    const BucketWs w = bucket_workspace(h->bucket_table.get(bucket_table_bytes(n_slots, bi.values)), h->bucket_lines.get(bucket_lines_bytes(n)), n, n_slots, bi.values);
+    GX_HIP(launch_bucket_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
+    BucketDev got{};
+    uint64_t n_buckets = 0;
+    GX_HIP(hipMemcpyAsync(&got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipMemcpyAsync(&n_buckets, w.before + n_slots, 8, hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got.status & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be bucketed");
+    if (got.unset + got.not_numbers + got.out_of_range > got.lines) throw GxError(GX_E_ARG, "internal: " + name + ": the classes exceed the lines that count");
+    totals->lines = got.lines;
+    totals->unset = got.unset;
+    totals->not_numbers = got.not_numbers;
+    totals->out_of_range = got.out_of_range;
+    totals->bucketed = got.lines - got.unset - got.not_numbers - got.out_of_range;
+    totals->n_buckets = n_buckets;
+    const uint64_t min_word = ~got.min_inv, max_word = got.max_word;
+    if (n_buckets) {
+        totals->first_bucket = bucket_number(min_word);
+        totals->last_bucket = bucket_number(max_word);
+    }
+    if (got.status & 2u) {
+        totals->exact = 0;
+        totals->n_buckets = static_cast<uint64_t>(n_slots) + 1u;
+        return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_buckets");
+    }
+    if (!any_out) return GX_OK;
+    if (per_bucket && n_buckets > out.max_buckets)
+        return fail(GX_E_LIMIT, name + ": " + std::to_string(n_buckets) + " buckets, max_buckets " + std::to_string(out.max_buckets));
+    if (n_buckets == 0) {   // lines, and none of them bucketed
+        no_line_has_one();
+        return GX_OK;
+    }
+    BucketOut o{out.bucket_number, out.bucket_first_line, out.bucket_lines, reinterpret_cast<uint64_t*>(out.bucket_stats), out.line_bucket};
+    DevMem<> d_num, d_first, d_lines, d_stats, d_lb;
+    if (host_out) {
+        if (out.bucket_number) { d_num = dev_alloc(n_buckets * 8); o.bucket_number = static_cast<int64_t*>(d_num.get()); }
+        if (out.bucket_first_line) { d_first = dev_alloc(n_buckets * 4); o.bucket_first_line = static_cast<uint32_t*>(d_first.get()); }
+        if (out.bucket_lines) { d_lines = dev_alloc(n_buckets * 8); o.bucket_lines = static_cast<uint64_t*>(d_lines.get()); }
+        if (out.bucket_stats) { d_stats = dev_alloc(n_buckets * 64); o.bucket_stats = static_cast<uint64_t*>(d_stats.get()); }
+        if (out.line_bucket) { d_lb = dev_alloc(n * 4); o.line_bucket = static_cast<uint32_t*>(d_lb.get()); }
+    }
+    const uint32_t n_digits = (bi.head.flags & BUCKET_ALL_DIGITS) ? BUCKET_MAX_DIGITS : bucket_digits(min_word, max_word);
+    const BucketSortWs sw = bucket_sort_workspace(h->bucket_sort.get(bucket_sort_workspace_bytes(n_buckets)), n_buckets);
+    GX_HIP(launch_bucket_emit(n, n_buckets, n_digits, w, sw, o, stream));
+    if (host_out) {
+        if (out.bucket_number) GX_HIP(hipMemcpyAsync(out.bucket_number, o.bucket_number, n_buckets * 8, hipMemcpyDeviceToHost, stream));
+        if (out.bucket_first_line) GX_HIP(hipMemcpyAsync(out.bucket_first_line, o.bucket_first_line, n_buckets * 4, hipMemcpyDeviceToHost, stream));
+        if (out.bucket_lines) GX_HIP(hipMemcpyAsync(out.bucket_lines, o.bucket_lines, n_buckets * 8, hipMemcpyDeviceToHost, stream));
+        if (out.bucket_stats) GX_HIP(hipMemcpyAsync(out.bucket_stats, o.bucket_stats, n_buckets * 64, hipMemcpyDeviceToHost, stream));
+        if (out.line_bucket) GX_HIP(hipMemcpyAsync(out.line_bucket, o.line_bucket, n * 4, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipStreamSynchronize(stream));
+    } else {
+        leave_pending(h->bucket_event, h->bucket_pending, stream);
+    }
+    return GX_OK;
+}
+static_assert(sizeof(gx_bucket_out) == 48 && sizeof(gx_bucket_totals) == 72 && sizeof(gx_bucket_part) == 16, "include/gorp_hip.h states these sizes");
+
+int gx_bucket_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_bucket_part* parts,
+                    uint32_t n_parts, int64_t origin, int64_t width, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_bucket_out* out,
+                    gx_bucket_totals* totals, const gx_batch_opts* opts) {
+    const std::string name = "gx_bucket_lines";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        const gx_bucket_out none{};
+        const gx_bucket_out& bo = out ? *out : none;
+        BucketImage bi;
+        WhereImage wi;
+        bucket_refusals(h, o, parts, n_parts, origin, width, terms, n_terms, flags, o.utf16 != 0, bo, totals, name, &bi, &wi);
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and one is kept for \"none\"; split batches of 2^32 - 1 lines and more");
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "bucketed");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        return bucket_pass(h, in.v, bi, wi, bo, !o.device_pointers, totals, nullptr, stream, name);
+    });
+}
+
+int gx_text_bucket_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_bucket_part* parts, uint32_t n_parts, int64_t origin, int64_t width,
+                         const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_bucket_out* out, gx_bucket_totals* totals, uint64_t* counts,
+                         uint64_t* n_lines, const gx_batch_opts* opts) {
+    const std::string name = "gx_text_bucket_lines";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        const gx_bucket_out none{};
+        const gx_bucket_out& bo = out ? *out : none;
+        BucketImage bi;
+        WhereImage wi;
+        bucket_refusals(h, o, parts, n_parts, origin, width, terms, n_terms, flags, false, bo, totals, name, &bi, &wi);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        const int rc = bucket_pass(h, tb.v, bi, wi, bo, !o.device_pointers, totals, counts, stream, name);
+        // (gx_text_group_lines' reason: the emit reads what text_lines left in the handle's scratch buffers)
+        if (h->bucket_pending) {
+            GX_HIP(hipStreamSynchronize(stream));
+            h->bucket_pending = false;
+        }
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
+    });
 }
 
 // gx_top_groups' own arguments as gx_group_lines' callers take them: the flags without GX_TOP_GROUPS_SMALLEST and &totals->group (unknown

@@ -367,6 +367,50 @@ hipError_t launch_pairs_emit(const void* ids, RowFormat fmt, uint32_t row_units,
                              const void* pairs_image, const GroupWs& g, const PairsWs& w, const PairsOut& out, uint64_t n_pairs, uint64_t pair_units,
                              uint64_t n_keys, hipStream_t stream);
 
+// The lines of a finished batch counted and measured per interval of a number they captured (gx_bucket.hip; the rule: gx_bucket.hpp): a
+// hash table of the distinct bucket numbers with gx_group_lines' per-slot words, the buckets sorted by their number.  GroupArgs::image is
+// a BucketHead here.  The passes' device workspace: the slots' words and arrays (bucket_table_bytes), the lines' slots
+// (bucket_lines_bytes) and, sized by the buckets the host has read, the sort's (bucket_sort_workspace_bytes).
+struct BucketWs {
+    uint32_t n_slots;             // a power of two
+    uint64_t* table;              // [n_slots] the slot words: group_max_word(bucket), 0 = empty
+    uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS]
+    uint64_t* stats_words;        // [n_slots][GROUP_STATS_WORDS], with values
+    uint64_t* totals;             // [8] BucketDev
+    uint64_t* before;             // [n_slots + 1] occupied slots before slot s; [n_slots]: the buckets
+    uint64_t* sums;               // the scan's
+    uint32_t* rank_of_slot;       // [n_slots] the rank of the slot's bucket, written by the emit pass
+    uint8_t* occupied;            // [n_slots]
+    uint32_t* slot_of;            // [n] the line's slot, GROUP_NONE: it has no bucket
+};
+struct BucketSortWs {
+    uint64_t* word[2];            // [m] the buckets' words, ping and pong
+    uint32_t* slot[2];            // [m] their slots
+    uint32_t* slab;               // the sort's counts, bin-major
+    uint64_t* bases;              // their scan
+    uint64_t* block_sums;
+    size_t bytes;
+};
+// what the emit passes write, each part optional (nullptr)
+struct BucketOut {
+    int64_t* bucket_number;
+    uint32_t* bucket_first_line;
+    uint64_t* bucket_lines;
+    uint64_t* bucket_stats;       // [n_buckets][8]: gx_measure_stats' fields
+    uint32_t* line_bucket;
+};
+size_t bucket_table_zero_bytes(uint32_t n_slots, bool values);
+size_t bucket_table_bytes(uint32_t n_slots, bool values);
+size_t bucket_lines_bytes(uint64_t n);
+BucketWs bucket_workspace(void* table_mem, void* lines_mem, uint64_t n, uint32_t n_slots, bool values);
+size_t bucket_sort_workspace_bytes(uint64_t m);
+BucketSortWs bucket_sort_workspace(void* ws, uint64_t m);
+// n > 0, parts > 0.  Build, flags and the scan; then -- behind the host's look at w.totals and w.before[n_slots] -- the pairs, the sort
+// over n_digits digits and the emits.
+hipError_t launch_bucket_build(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                               const BucketWs& w, hipStream_t stream);
+hipError_t launch_bucket_emit(uint64_t n, uint64_t m, uint32_t n_digits, const BucketWs& w, const BucketSortWs& s, const BucketOut& out, hipStream_t stream);
+
 // The lines of a finished batch ranked by a number they captured (gx_top.hip; the rule: gx_top.hpp): the n_wanted largest (or smallest)
 // numbers' lines, ordered by (value, input line).
 struct TopArgs {

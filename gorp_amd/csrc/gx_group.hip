@@ -44,25 +44,7 @@ struct GroupDevTable {
     __device__ __forceinline__ uint64_t claim(uint32_t slot, uint64_t word) { return atomicCAS(words + slot, 0ull, static_cast<u64>(word)); }
 };
 
-// what one slot receives: GROUP_HEAD_WORDS words at `head`, GROUP_STATS_WORDS at `stats` (with values); zeros are not sent
-struct GroupAdd {
-    uint64_t lines, first, numbers, unset, not_numbers, mn, mx, lo, hi;
-};
-__device__ __forceinline__ void group_add(u64* head, u64* stats, bool values, const GroupAdd& a) {
-    atomicAdd(head + GROUP_W_LINES, static_cast<u64>(a.lines));
-    atomicMax(head + GROUP_W_FIRST, static_cast<u64>(a.first));
-    if (values) {
-        if (a.unset) atomicAdd(stats + GROUP_S_UNSET, static_cast<u64>(a.unset));
-        if (a.not_numbers) atomicAdd(stats + GROUP_S_NOT_NUMBERS, static_cast<u64>(a.not_numbers));
-        if (a.numbers) {
-            atomicAdd(stats + GROUP_S_NUMBERS, static_cast<u64>(a.numbers));
-            atomicAdd(stats + GROUP_S_LO, static_cast<u64>(a.lo));
-            atomicAdd(stats + GROUP_S_HI, static_cast<u64>(a.hi));
-            atomicMax(stats + GROUP_S_MIN, static_cast<u64>(a.mn));
-            atomicMax(stats + GROUP_S_MAX, static_cast<u64>(a.mx));
-        }
-    }
-}
+// (what one slot receives: GroupAdd and group_add of gx_group_dev.hpp)
 
 // LDS: GroupHead, the term image (wimage_bytes, 0: no terms), then keys[GROUP_LDS_ENTRIES], 4 words (used, spare), 4 totals (64-bit),
 // and GROUP_LDS_ENTRIES x (GROUP_HEAD_WORDS + GROUP_STATS_WORDS) 64-bit words.

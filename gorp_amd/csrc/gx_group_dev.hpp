@@ -31,6 +31,28 @@ struct GroupBatch {
     }
 };
 
+// what one slot receives: GROUP_HEAD_WORDS words at `head`, GROUP_STATS_WORDS at `stats` (with values); zeros are not sent.  The build
+// passes of gx_group.hip and gx_bucket.hip add it to a workgroup's LDS entry or to the slot's words in global memory.
+struct GroupAdd {
+    uint64_t lines, first, numbers, unset, not_numbers, mn, mx, lo, hi;
+};
+__device__ __forceinline__ void group_add(unsigned long long* head, unsigned long long* stats, bool values, const GroupAdd& a) {
+    typedef unsigned long long u64;
+    atomicAdd(head + GROUP_W_LINES, static_cast<u64>(a.lines));
+    atomicMax(head + GROUP_W_FIRST, static_cast<u64>(a.first));
+    if (values) {
+        if (a.unset) atomicAdd(stats + GROUP_S_UNSET, static_cast<u64>(a.unset));
+        if (a.not_numbers) atomicAdd(stats + GROUP_S_NOT_NUMBERS, static_cast<u64>(a.not_numbers));
+        if (a.numbers) {
+            atomicAdd(stats + GROUP_S_NUMBERS, static_cast<u64>(a.numbers));
+            atomicAdd(stats + GROUP_S_LO, static_cast<u64>(a.lo));
+            atomicAdd(stats + GROUP_S_HI, static_cast<u64>(a.hi));
+            atomicMax(stats + GROUP_S_MIN, static_cast<u64>(a.mn));
+            atomicMax(stats + GROUP_S_MAX, static_cast<u64>(a.mx));
+        }
+    }
+}
+
 // The entry of `slot` in the workgroup's LDS table (keys[GROUP_LDS_ENTRIES], GROUP_NONE: free), inserted if it is new and the table
 // still takes keys; GROUP_NONE: the table is full, add to global memory.  At most GROUP_LDS_KEYS entries are ever claimed (a claim is
 // reserved in *used first), so a free entry ends every probe sequence and the loop is bounded by the table besides.

@@ -1,4 +1,4 @@
-// gx_radix_dev.hpp -- what the stable LSD radix sorts of gx_partition.hip, gx_group_quantile.hip and gx_by_key.hip share: six bits a digit, 64 bins,
+// gx_radix_dev.hpp -- what the stable LSD radix sorts of gx_partition.hip, gx_group_quantile.hip, gx_by_key.hip and gx_bucket.hip share: six bits a digit, 64 bins,
 // one per lane of a wave, and a line's rank among the lines of its bin from ballots alone -- no atomics, so the order of the output
 // is the order of the input whatever the waves' timing.  Device code only.
 #pragma once

@@ -308,6 +308,17 @@ class GroupParts:
         return any(self.array[t].value_group >= 0 for t in range(self.n))
 
 
+class BucketParts:
+    """Gorp.bucket_parts' result: the gx_bucket_part array of a call."""
+
+    def __init__(self, array, n):
+        self.array, self.n = array, n
+
+    @property
+    def has_values(self):
+        return any(self.array[t].value_group >= 0 for t in range(self.n))
+
+
 class TopParts:
     """Parts for top_lines (Gorp.top_parts)."""
 
@@ -992,7 +1003,8 @@ class Gorp:
     # -- how a group is read as a number (gx_set_number_format) ----------------------------------------------------------
     def set_number_format(self, extraction, group, kind, scale=0):
         """gx_set_number_format: from now on every call that parses this group as a number -- where_terms' integer comparisons,
-        capture_stats, the value group of group_lines / group_quantiles / top_groups / top_lines / capture_quantiles -- reads it as
+        capture_stats, the value group of group_lines / group_quantiles / top_groups / top_lines / capture_quantiles, both groups of
+        bucket_lines -- reads it as
         kind "long" (Long.parseLong, the default), "decimal" (scale 0 .. 18: the value times 10^scale, cut toward zero), "iso8601" or
         "clf" (scale 0, 3, 6 or 9: the instant in 10^-scale seconds since the epoch).  extraction and group are resolved as
         where_terms resolves them.  Needs no device; not kept in the blob."""
@@ -1568,6 +1580,170 @@ class Gorp:
         res, (counts, n_lines) = self._pairs_host(device_call, cap_lines, raw.size, both[0], np.uint8, np.uint32, keys, decode, max_keys, key_units_cap, max_pairs,
                                                   pair_units_cap)
         res["line_key"], res["line_pair"] = res["line_key"][:n_lines], res["line_pair"][:n_lines]
+        return res, counts, n_lines
+
+    # -- lines per interval of a captured number (gx_bucket_lines / gx_text_bucket_lines) ------------------------------------------
+    def bucket_parts(self, spec):
+        """Resolves a list of (extraction, number extractor) or (extraction, number extractor, value extractor) into gx_bucket_part
+        records, names and indices as group_parts takes them: ("Syslog", "ts") or ("GetRequest", "ts", "timeTakenInMsec").  At most
+        one part per extraction, at most 64 parts.  Returns a BucketParts; a BucketParts passes through."""
+        if isinstance(spec, BucketParts):
+            return spec
+        spec = list(spec)
+        if len(spec) > 64:
+            raise ValueError("at most 64 parts")
+        arr = (N.gx_bucket_part * max(1, len(spec)))()
+        seen = set()
+        for t, item in enumerate(spec):
+            item = tuple(item)
+            if len(item) == 2:
+                item = item + (None,)
+            if len(item) != 3:
+                raise ValueError("a part is (extraction, number extractor[, value extractor])")
+            k, g = self._extraction_and_group(item[0], item[1])
+            if k in seen:
+                raise ValueError("two parts for extraction %r" % (item[0],))
+            seen.add(k)
+            arr[t].extraction, arr[t].number_group, arr[t].value_group = k, g, -1 if item[2] is None else self._extraction_and_group(k, item[2])[1]
+        return BucketParts(arr, len(spec))
+
+    def _bucket_origin(self, parts, origin):
+        """origin as an int; a str or bytes is read with parse_number under the first part's number format."""
+        if isinstance(origin, (str, bytes, bytearray)):
+            if not parts.n:
+                raise ValueError("a text origin needs a part: it is read under the first part's number format")
+            kind, scale = self.number_format(parts.array[0].extraction, parts.array[0].number_group)
+            value = parse_number(kind, scale, origin)
+            if value is None:
+                raise ValueError("origin %r is no number under the format (%s, %d)" % (origin, kind, scale))
+            return value
+        if isinstance(origin, bool) or not isinstance(origin, (int, np.integer)) or not -2 ** 63 <= int(origin) < 2 ** 63:
+            raise ValueError("origin: an int64, or a text read under the first part's number format")
+        return int(origin)
+
+    @staticmethod
+    def _bucket_totals(t):
+        return {"n_buckets": t.n_buckets, "lines": t.lines, "bucketed": t.bucketed, "unset": t.unset, "not_numbers": t.not_numbers,
+                "out_of_range": t.out_of_range, "exact": bool(t.exact), "first_bucket": t.first_bucket, "last_bucket": t.last_bucket}
+
+    @staticmethod
+    def _bucket_flags(weak_hash, all_digits):
+        return (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (N.GX_BUCKET_ALL_DIGITS if all_digits else 0)
+
+    def bucket_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, width, origin=0, where=None, bucket_number_ptr=None,
+                            bucket_first_line_ptr=None, bucket_lines_ptr=None, bucket_stats_ptr=None, line_bucket_ptr=None, max_buckets=0, offsets64=False,
+                            utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_bucket_lines on device pointers (ints); the outputs are the caller's buffers, each optional (none at all: the size query;
+        max_buckets still sizes the table).  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals
+        says what the outputs need (n_buckets; exact False: the table overflowed, max_buckets = n always suffices); every other error
+        raises."""
+        parts = self.bucket_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_bucket_out(bucket_number_ptr, bucket_first_line_ptr, bucket_lines_ptr, bucket_stats_ptr, line_bucket_ptr, max_buckets)
+        totals = N.gx_bucket_totals()
+        rc = N.lib().gx_bucket_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, self._bucket_origin(parts, origin), int(width),
+                                     terms.array, terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(out), C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_buckets):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._bucket_totals(totals)
+
+    def text_bucket_lines_device(self, text_ptr, size, parts, width, origin=0, where=None, bucket_number_ptr=None, bucket_first_line_ptr=None,
+                                 bucket_lines_ptr=None, bucket_stats_ptr=None, line_bucket_ptr=None, max_buckets=0, stream=None, device_pointers=True, utf8=False,
+                                 weak_hash=False, all_digits=False):
+        """gx_text_bucket_lines on a device buffer (int); outputs as bucket_lines_device takes them (line_bucket: one entry per line of
+        the text).  Returns (rc, totals, counts, n_lines)."""
+        parts = self.bucket_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        out = N.gx_bucket_out(bucket_number_ptr, bucket_first_line_ptr, bucket_lines_ptr, bucket_stats_ptr, line_bucket_ptr, max_buckets)
+        totals = N.gx_bucket_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_bucket_lines(self._h.ptr, text_ptr, size, parts.array, parts.n, self._bucket_origin(parts, origin), int(width), terms.array, terms.n,
+                                          self._bucket_flags(weak_hash, all_digits), C.byref(out), C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.n_buckets):
+            _check(rc)
+        return rc, self._bucket_totals(totals), counts, nl.value
+
+    def _bucket_host(self, call, n_lines_cap, parts, max_buckets):
+        """Runs `call(out arrays..., max_buckets)` on host arrays; on GX_E_LIMIT once more with the size it reported when it is exact,
+        else with the number of lines (which may report an exact size in turn): three calls at the most.  Builds the result dict."""
+        max_buckets = min(n_lines_cap, 1024) if max_buckets is None else max_buckets
+        for attempt in range(3):
+            number = np.zeros(max(1, max_buckets), np.int64)
+            first = np.zeros(max(1, max_buckets), np.uint32)
+            lines = np.zeros(max(1, max_buckets), np.uint64)
+            stats = (N.gx_measure_stats * max(1, max_buckets))() if parts.has_values else None
+            line_bucket = np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32)
+            got = call(number.ctypes.data, first.ctypes.data, lines.ctypes.data, None if stats is None else C.addressof(stats), line_bucket.ctypes.data, max_buckets)
+            rc, totals = got[0], got[1]
+            if rc == N.GX_OK:
+                break
+            if attempt == 2:
+                raise GorpError(rc, N.last_error())
+            max_buckets = max(max_buckets, totals["n_buckets"]) if totals["exact"] else n_lines_cap
+        k = totals["n_buckets"]
+        res = {"bucket_number": number[:k], "first_line": first[:k], "lines": lines[:k], "totals": totals, "line_bucket": line_bucket,
+               "stats": None if stats is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                                                      "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
+                                                      "sum": (s.sum_hi << 64) + s.sum_lo} for s in stats[:k]]}
+        return res, got[2:]
+
+    def bucket_lines(self, data, offsets, match_id, caps, parts, width, origin=0, where=None, max_buckets=None, utf8=None, weak_hash=False, all_digits=False):
+        """gx_bucket_lines on host buffers: the lines counted -- and, with a value extractor, measured -- per interval
+        floor((number - origin) / width) of the number the part of their extraction names (parts: Gorp.bucket_parts or its input), of
+        the lines on which every term of `where` holds.  The number is read under its group's number format (set_number_format), so
+        with ("Syslog", "ts") read as iso8601 at scale 3 and width 60_000 the buckets are minutes; origin is an int in the format's
+        unit, or a text read under the first part's format.  data / offsets / match_id / caps and utf8 as group_lines takes them.
+        Returns a dict: bucket_number (int64, ascending; only occupied buckets), first_line, lines (per bucket), stats (per bucket, as
+        group_lines gives them per key; None when no part has a value extractor), line_bucket (uint32 per input line: the index of its
+        bucket in bucket_number, 0xFFFFFFFF: none) and totals."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(match_id)
+        compact = self._ids_format(ids)
+        rows = None if caps is None or compact else np.ascontiguousarray(caps, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.bucket_parts(parts)
+        n = len(offsets) - 1
+
+        def call(number, first, lines, stats, line_bucket, mb):
+            return self.bucket_lines_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(rows), parts, width, origin, where, number, first, lines, stats,
+                                            line_bucket, mb, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False,
+                                            utf8=bool(utf8), weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._bucket_host(call, n, parts, max_buckets)
+        res["line_bucket"] = res["line_bucket"][:n]
+        return res
+
+    def text_bucket_lines(self, text, parts, width, origin=0, where=None, max_buckets=None, utf8=False, weak_hash=False, all_digits=False):
+        """gx_text_bucket_lines on a host buffer: raw text -> lines -> extraction -> bucket_lines.  Returns (the dict bucket_lines
+        returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.bucket_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+
+        def call(number, first, lines, stats, line_bucket, mb):
+            return self.text_bucket_lines_device(raw.ctypes.data if raw.size else None, raw.size, parts, width, origin, where, number, first, lines, stats, line_bucket,
+                                                 mb, device_pointers=False, utf8=utf8, weak_hash=weak_hash, all_digits=all_digits)
+        res, (counts, n_lines) = self._bucket_host(call, cap_lines, parts, max_buckets)
+        res["line_bucket"] = res["line_bucket"][:n_lines]
         return res, counts, n_lines
 
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------

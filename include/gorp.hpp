@@ -608,6 +608,67 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Lines counted and measured per interval of a captured number (gx_bucket_lines): the caller's
+    //     long b = Math.floorDiv(Instant.parse(r.asMap().get("ts")).toEpochMilli() - origin, 60_000L);
+    //     perMinute.merge(b, 1L, Long::sum); latency.computeIfAbsent(b, x -> new Stats()).record(Long.parseLong(...));
+    // (README.md:26,63-79, with a timestamp field).  The parts of a call, built by name: bucketParts().of("Syslog", "ts") or
+    // .of("GetRequest", "ts", "timeTakenInMsec"), which also measures a number per bucket.  The number is read under its group's number
+    // format (gx_set_number_format).  Names resolve as Where's do; one part per extraction; all parts share one bucket space.
+    class BucketParts {
+    public:
+        explicit BucketParts(const Gorp* g) : groups_(g) {}
+        BucketParts& of(const std::string& extraction, const std::string& number, const std::string& value = std::string()) {
+            groups_.of(extraction, number, value);
+            return *this;
+        }
+        BucketParts& of(size_t extraction, size_t numberGroup, int32_t valueGroup = -1) {
+            groups_.of(extraction, numberGroup, valueGroup);
+            return *this;
+        }
+        std::vector<gx_bucket_part> parts() const {
+            std::vector<gx_bucket_part> out;
+            for (const gx_group_part& p : groups_.parts()) out.push_back(gx_bucket_part{p.extraction, p.key_group, p.value_group, 0});
+            return out;
+        }
+        bool hasValues() const { return groups_.hasValues(); }
+
+    private:
+        GroupParts groups_;
+    };
+    BucketParts bucketParts() const { return BucketParts(this); }
+    // The occupied buckets b = floor((number - origin) / width) in ascending order: per bucket its number, its first line, its lines and --
+    // when a part has a value -- its gx_measure_stats; per input line the index of its bucket (0xFFFFFFFF: none).
+    struct Buckets {
+        std::vector<int64_t> bucketNumber;
+        std::vector<uint32_t> firstLine;
+        std::vector<uint64_t> lines;
+        std::vector<gx_measure_stats> stats;   // empty when no part has a value
+        std::vector<uint32_t> lineBucket;
+        gx_bucket_totals totals{};
+    };
+    Buckets bucketLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const BucketParts& parts,
+                        int64_t width, int64_t origin = 0, const Where* where = nullptr) const {
+        return bucketsOf(parts, where, &n, [&](const gx_bucket_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_bucket_out* out,
+                                               gx_bucket_totals* totals) {
+            return gx_bucket_lines(h_, bytes, offsets, n, match_id, caps, p, np, origin, width, t, nt, 0, out, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same buckets out (gx_text_bucket_lines).  counts (optional): lines per outcome index.
+    Buckets textBucketLines(const std::string& text, const BucketParts& parts, int64_t width, int64_t origin = 0, const Where* where = nullptr,
+                            std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        Buckets b = bucketsOf(parts, where, &lines, [&](const gx_bucket_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_bucket_out* out,
+                                                        gx_bucket_totals* totals) {
+            return gx_text_bucket_lines(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, origin, width, t, nt, 0, out, totals,
+                                        counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return b;
+    }
     // Lines ranked by a number they captured (gx_top_lines): the parts of a call, built by name.  topParts().of("GetRequest",
     // "timeTakenInMsec").of("OtherRequest", "timeTakenInMsec") with topLines(..., 10) is the caller's "which requests were the slowest?",
     // sorted(results, by timeTakenInMsec).take(10) (README.md:26,63-79).  Names resolve as Where's do; one part per extraction; all
@@ -890,6 +951,39 @@ private:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
         return g;
+    }
+    // groupsOf's scheme for bucketLines: the size query with a table for a modest number of buckets, once more with as many buckets as
+    // lines if that table overflows, then the call with exactly the size it reported.
+    template <typename Call>
+    Buckets bucketsOf(const BucketParts& parts, const Where* where, const uint64_t* lines, Call&& call) const {
+        const std::vector<gx_bucket_part> p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
+        Buckets b;
+        gx_bucket_out query{};
+        query.max_buckets = 1024;
+        int rc = call(p.data(), np, terms.data(), nt, &query, &b.totals);
+        if (rc == GX_E_LIMIT && b.totals.n_buckets != 0 && b.totals.exact == 0) {
+            query.max_buckets = *lines;
+            rc = call(p.data(), np, terms.data(), nt, &query, &b.totals);
+        }
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t k = static_cast<size_t>(b.totals.n_buckets);
+        b.bucketNumber.assign(k, 0);
+        b.firstLine.assign(k, 0);
+        b.lines.assign(k, 0);
+        if (parts.hasValues()) b.stats.assign(k, gx_measure_stats{});
+        b.lineBucket.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        gx_bucket_out out{};
+        out.bucket_number = b.bucketNumber.data();
+        out.bucket_first_line = b.firstLine.data();
+        out.bucket_lines = b.lines.data();
+        out.bucket_stats = parts.hasValues() ? b.stats.data() : nullptr;
+        out.line_bucket = b.lineBucket.data();
+        out.max_buckets = b.totals.n_buckets;   // (the arrays' capacity; a table of twice as many slots holds them all)
+        rc = call(p.data(), np, terms.data(), nt, &out, &b.totals);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        return b;
     }
     // groupsOf with the pairs beside the keys: the size queries ask with a pair table for maxLines lines, which always suffices; the call
     // with exactly the sizes they reported delivers both.  Pair outputs are asked for only where a part has a second (the C call refuses

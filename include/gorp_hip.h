@@ -893,6 +893,86 @@ int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         const int32_t* second_groups, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
                         const gx_pairs_out* pairs, gx_pairs_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- Lines counted and measured per interval of a captured number, on the device (gx_bucket_lines) ----
+ * The reference's caller asks of a timestamp "how many per minute, and how slow were they, minute by minute" right behind the
+ * extraction (README.md:26,63-79, with a timestamp field):
+ *     r = gorp.extract(line);
+ *     if (r != null) {
+ *         long b = Math.floorDiv(Instant.parse(r.asMap().get("ts")).toEpochMilli() - origin, 60_000L);
+ *         perMinute.merge(b, 1L, Long::sum);                                            // a TreeMap: buckets in time order
+ *         latency.computeIfAbsent(b, x -> new Stats()).record(Long.parseLong(r.asMap().get("timeTakenInMsec")));
+ *     }
+ * -- GROUP BY floor((number - origin) / width).  It is no gx_group_lines call (that keys on the text: two timestamps a millisecond apart
+ * are two keys) and no gx_capture_stats histogram (at most 64 edges, known beforehand).
+ * PARTS: a part names, for the lines of one extraction, number_group -- the number that is bucketed, parsed under its gx_number_format
+ * and classed exactly as gx_capture_stats classes a value -- and optionally value_group, measured per bucket as gx_group_lines measures
+ * one per key (-1: count only).  At most one part per extraction, at most 64 parts; all parts share ONE bucket space.
+ * WHICH LINES COUNT: a line counts when its outcome is a matched extraction that has a part and every term of that extraction holds
+ * (gx_capture_stats' rule).  A line that counts is BUCKETED, or its number group is UNSET, or its value is NO NUMBER, or its bucket is
+ * OUT OF RANGE: lines == bucketed + unset + not_numbers + out_of_range.
+ * THE BUCKET: b = floor((v - origin) / width), exact for every int64 v and origin and every width >= 1 (the 65-bit difference is taken
+ * exactly).  A bucket outside [INT64_MIN + 1, INT64_MAX] is out of range and the line has no bucket.  This differs from Java on purpose:
+ * Math.subtractExact would throw where v - origin overflows, while here the difference is exact and only the bucket number is limited.
+ * Only the bucket NUMBER is delivered, never origin + b * width, which can overflow.
+ * ORDER: buckets leave in ascending order of their number.  Only occupied buckets are delivered; an empty interval has no entry.
+ * EXACT: every output is exact and the same bits on every run; all merges are unsigned integer adds and maxima.
+ * NOT IN SCOPE: a text key beside the bucket (a series per verb), empty buckets filled in, calendar widths (months, local days),
+ * quantiles per bucket.  The rule: gorp_amd/csrc/gx_bucket.hpp. */
+#define GX_BUCKET_ALL_DIGITS 2u   /* test hook beside GX_GROUP_WEAK_HASH (1u): sort all 11 digits whatever the buckets' range is */
+
+typedef struct gx_bucket_part {    /* the lines of ONE extraction: which group is the number, which (if any) is measured */
+    int32_t extraction;            /* k in [0, K); at most one part per extraction */
+    int32_t number_group;          /* g in [0, gx_num_groups(h, k)) */
+    int32_t value_group;           /* -1: count only; else a group parsed as gx_capture_stats parses one */
+    uint32_t reserved;             /* 0 */
+} gx_bucket_part;
+
+typedef struct gx_bucket_out {     /* 48 bytes; every pointer optional; device memory with opts->device_pointers, else host */
+    int64_t*  bucket_number;       /* ascending */
+    uint32_t* bucket_first_line;   /* the first input line in bucket j */
+    uint64_t* bucket_lines;        /* lines in bucket j */
+    gx_measure_stats* bucket_stats;/* per bucket, over its lines whose part has a value_group (exact 128-bit sum; no histogram) */
+    uint32_t* line_bucket;         /* n entries: the index j of every input line's bucket, 0xFFFFFFFF for a line that has none */
+    uint64_t  max_buckets;         /* capacity of the four per-bucket arrays, and the table's size; read in the size query too; <= 2^30 */
+} gx_bucket_out;
+
+typedef struct gx_bucket_totals {  /* 72 bytes; host, always */
+    uint64_t n_buckets;            /* what the outputs need */
+    uint64_t lines;                /* lines that count */
+    uint64_t bucketed, unset, not_numbers, out_of_range;   /* lines == bucketed + unset + not_numbers + out_of_range */
+    uint64_t exact;                /* 1: n_buckets is exact; 0: the table overflowed, n_buckets is only a lower bound */
+    int64_t  first_bucket, last_bucket;   /* the smallest and the largest bucket number; 0 when there is no bucket */
+} gx_bucket_totals;
+
+/* gx_bucket_lines: the batch bytes / offsets / n / ids / caps is read exactly as gx_group_lines reads it (row formats int32 + dense, u16
+ * and u8; offsets64; utf16; utf8 = 1; staging or device_pointers; the stream).  The buckets are found in a hash table on the device of
+ * the smallest power of two >= max(64, 2 * max_buckets) slots of one 64-bit word each.
+ * SIZE QUERY: every output pointer NULL (or out == NULL): only *totals is delivered, and max_buckets is still read, as the table's size.
+ * GX_E_LIMIT: a per-bucket array given and n_buckets > max_buckets -- nothing is written to any output and *totals is filled; a line that
+ * finds no free slot -- exact = 0 and n_buckets = slots + 1 (the number of lines is always a sufficient max_buckets); max_buckets above
+ * 2^30; more than 64 parts; n of 2^32 - 1 and more; a line of 2^32 code units and more (or offsets that go backwards).
+ * GX_E_ARG: parts == NULL with n_parts > 0, totals == NULL, a part's extraction or group out of range, two parts for one extraction,
+ * reserved != 0, unknown flag bits, width < 1, bucket_stats without a value_group, every refusal of a term (gx_select_lines_where),
+ * parts or terms on dense ids without caps, utf8 = 2, no_sync.  All refusals that need no device come before the device is looked at: a
+ * host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).  n == 0 and n_parts == 0 are legal: no buckets, all
+ * zeros, line_bucket all none.
+ * HOST WAITS: the call synchronises the stream once, where the host reads the totals, the number of buckets and the range of their
+ * numbers (from which it plans the sort's digits); with host outputs a second wait delivers them.  With device_pointers the sort and the
+ * emit are left running on opts->stream when the call returns (stream order delivers the outputs); the handle's next gx_bucket_lines
+ * on another stream waits for them, and the batch must stay unchanged until they have run.
+ * The device workspace stays on the handle until gx_destroy: 29 bytes per slot (93 with a value group), 4 per input line, and 24 per
+ * bucket plus 768 per 2 048 buckets for the sort. */
+int gx_bucket_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                    const gx_bucket_part* parts, uint32_t n_parts, int64_t origin, int64_t width, const gx_where_term* terms,
+                    uint32_t n_terms, uint32_t flags, const gx_bucket_out* out, gx_bucket_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with this call at its end: raw text -> lines -> the match-and-extract path -> the
+ * buckets.  counts and *n_lines as gx_text_group_lines delivers them; line_bucket holds one entry per line of the text.  Like every
+ * gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_bucket_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_bucket_part* parts, uint32_t n_parts, int64_t origin,
+                         int64_t width, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_bucket_out* out,
+                         gx_bucket_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
@@ -927,7 +1007,8 @@ int gx_set_extraction_meta(gx_handle* h, int32_t k, const char* name, const char
  * new BigDecimal(r.asMap().get("request_time")).  A FORMAT {kind, scale} is a property of group g of extraction k, kept on the
  * handle like the names of gx_set_extraction_meta.  Wherever a call parses that group as a number -- the GX_WHERE_INT_* terms of
  * gx_select_lines_where, a measure of gx_capture_stats, the value group of gx_group_lines / gx_group_quantiles / gx_top_groups /
- * gx_top_lines / gx_capture_quantiles, and their gx_text_* forms -- it parses it under the group's format, and a term's `number`,
+ * gx_top_lines / gx_capture_quantiles, both groups of a gx_bucket_lines part (origin and width are in the number group's unit), and
+ * their gx_text_* forms -- it parses it under the group's format, and a term's `number`,
  * a measure's `edges` and every min / max / sum / quantile / ranked value are in the format's unit.  Nothing else sees the format:
  * text terms, keys, the extraction itself and JSON Lines read the value as text.  The rule: gorp_amd/csrc/gx_number.hpp.
  *   GX_NUMBER_LONG     scale 0: Long.parseLong on ASCII.  The default of every group.
