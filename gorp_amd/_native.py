@@ -56,6 +56,7 @@ SYMBOLS = [
     "gx_lines_by_key", "gx_text_lines_by_key",
     "gx_group_pairs", "gx_text_group_pairs",
     "gx_bucket_lines", "gx_text_bucket_lines",
+    "gx_group_series", "gx_text_group_series",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
 
@@ -166,6 +167,16 @@ class gx_by_key_out(C.Structure):
 
 class gx_by_key_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("keys_kept", C.c_uint64), ("lines_out", C.c_uint64), ("units_out", C.c_uint64)]
+
+
+class gx_series_out(C.Structure):
+    _fields_ = [("bucket_number", C.c_void_p), ("cell_key", C.c_void_p), ("cell_bucket", C.c_void_p), ("cell_first_line", C.c_void_p), ("cell_lines", C.c_void_p),
+                ("cell_stats", C.c_void_p), ("key_cell_begin", C.c_void_p), ("line_cell", C.c_void_p), ("max_cells", C.c_uint64), ("max_buckets", C.c_uint64)]
+
+
+class gx_series_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("n_cells", C.c_uint64), ("n_buckets", C.c_uint64), ("celled", C.c_uint64), ("number_unset", C.c_uint64),
+                ("not_numbers", C.c_uint64), ("out_of_range", C.c_uint64), ("cells_exact", C.c_uint64), ("first_bucket", C.c_int64), ("last_bucket", C.c_int64)]
 
 
 class gx_pairs_out(C.Structure):
@@ -414,6 +425,14 @@ def lib():
                                       C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_pairs_out), C.POINTER(gx_pairs_totals), C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_pairs.restype = C.c_int
+    L.gx_group_series.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
+                                  C.c_int64, C.c_int64, C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_series_out),
+                                  C.POINTER(gx_series_totals), C.POINTER(gx_batch_opts)]
+    L.gx_group_series.restype = C.c_int
+    L.gx_text_group_series.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                       C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_series_out),
+                                       C.POINTER(gx_series_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_series.restype = C.c_int
     L.gx_bucket_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_bucket_part), C.c_uint32, C.c_int64, C.c_int64,
                                   C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.POINTER(gx_batch_opts)]
     L.gx_bucket_lines.restype = C.c_int

@@ -25,6 +25,7 @@
 #include "gx_group_quantile.hpp"
 #include "gx_pairs.hpp"
 #include "gx_bucket.hpp"
+#include "gx_series.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
@@ -294,6 +295,10 @@ struct gx_handle {
     // gx_group_pairs behind gx_group_lines' build: its second groups (PairsHead, gx_pairs.hpp), the pair slots' words and the per-line
     // arrays (gx_pairs.hip), covered by group_event too
     GrowBuf pairs_image, pairs_table, pairs_lines;
+    // gx_group_series behind gx_group_lines' build: its number groups (SeriesHead, gx_series.hpp) at the head of both tables' slots' words
+    // and arrays, and the lines' cell slots (gx_series.hip); behind the one wait, sized by the cells read there, the sorts' workspace.
+    // Covered by group_event too
+    GrowBuf series_table, series_lines, series_sort;
     Event group_event;
     bool group_pending = false;
     // gx_bucket_lines: its parts and terms on the device (BucketHead, gx_bucket.hpp; WhereHead behind it), the slots' words and arrays,
@@ -1924,6 +1929,21 @@ struct PairsCall {
     bool per_pair() const { return out.pair_offsets || out.pair_key || out.pair_first_line || out.pair_lines; }
     bool any() const { return per_pair() || out.pair_units || out.key_pairs || out.line_pair; }
 };
+// sc (gx_group_series; nullptr: gx_group_lines as it is): behind the build the bucket table's and the cell table's build, flags and scans
+// (launch_series_build), whose totals, buckets and cells are read in the same wait -- both sorts' digits follow from numbers known
+// there; behind the emit, which numbers the key slots, the two sorts and the series' emits.
+struct SeriesCall {
+    const int32_t* number_groups = nullptr;
+    int64_t origin = 0, width = 0;
+    bool all_digits = false;
+    const gx_series_out* asked = nullptr;   // the caller's; nullptr: the keys alone, no series tables
+    gx_series_totals* totals = nullptr;     // (its group member is the gx_group_totals the pass fills)
+    SeriesHead head{};                      // (series_refusals) the number group per entry of GroupHead::ext[]
+    bool any_number = false;
+    gx_series_out out{};
+    bool per_cell() const { return out.cell_key || out.cell_bucket || out.cell_first_line || out.cell_lines || out.cell_stats; }
+    bool any() const { return per_cell() || out.bucket_number || out.key_cell_begin || out.line_cell; }
+};
 // gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
 struct TopGroupsCall {
     uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
@@ -1936,6 +1956,7 @@ struct GroupExtras {
     std::optional<TopGroupsCall> top;
     std::optional<ByKeyCall> by_key;
     std::optional<PairsCall> pairs;
+    std::optional<SeriesCall> series;
 };
 static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
                       gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupExtras& x) {
@@ -1943,11 +1964,16 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     const GroupQuant* gq = x.quant ? &*x.quant : nullptr;
     const ByKeyCall* bk = x.by_key ? &*x.by_key : nullptr;
     const PairsCall* pc = x.pairs && x.pairs->asked ? &*x.pairs : nullptr;
+    const SeriesCall* sc = x.series && x.series->asked ? &*x.series : nullptr;
     const uint64_t n = v.n;
     if (bk) *bk->totals = gx_by_key_totals{};
     if (pc) {
         *pc->totals = gx_pairs_totals{};
         pc->totals->pairs_exact = 1;
+    }
+    if (sc) {
+        *sc->totals = gx_series_totals{};
+        sc->totals->cells_exact = 1;
     }
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
@@ -1957,7 +1983,9 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     const uint32_t n_q = q_rows ? gq->qh.n_q : 0u;
     const bool bk_out = bk && bk->any();
     const bool pc_out = pc && pc->any();
-    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out || pc_out;
+    const bool sc_out = sc && sc->any();
+    const bool any_out =
+        out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out || pc_out || sc_out;
     if (!run) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -1987,6 +2015,16 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
             if (pc->out.line_pair && n) {
                 if (host_out) memset(pc->out.line_pair, 0xFF, n * 4);
                 else GX_HIP(hipMemsetAsync(pc->out.line_pair, 0xFF, n * 4, stream));
+            }
+        }
+        if (sc_out) {   // no cells: the bounds' one entry and every line's "none"
+            if (sc->out.key_cell_begin) {
+                if (host_out) memcpy(sc->out.key_cell_begin, &zero, 8);
+                else GX_HIP(hipMemsetAsync(sc->out.key_cell_begin, 0, 8, stream));
+            }
+            if (sc->out.line_cell && n) {
+                if (host_out) memset(sc->out.line_cell, 0xFF, n * 4);
+                else GX_HIP(hipMemsetAsync(sc->out.line_cell, 0xFF, n * 4, stream));
             }
         }
         return GX_OK;
@@ -2040,6 +2078,21 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
         GX_HIP(hipMemcpyAsync(&n_pairs, pw.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
         GX_HIP(hipMemcpyAsync(&pair_units, pw.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
     }
+    // the cells of gx_group_series: a table of the buckets and a table of (key slot, bucket slot), behind the build that has left slot_of[]
+    SeriesWs sw{};
+    SeriesDev sd{};
+    uint64_t n_buckets = 0, n_cells = 0;
+    if (sc) {
+        const uint32_t s_slots = group_slots(sc->out.max_cells);
+        const size_t at_table = (sizeof(SeriesHead) + 15) & ~static_cast<size_t>(15);
+        uint8_t* d_simg = static_cast<uint8_t*>(h->series_table.get(at_table + series_table_bytes(s_slots, gi.values)));
+        GX_HIP(hipMemcpyAsync(d_simg, &sc->head, sizeof(SeriesHead), hipMemcpyHostToDevice, stream));
+        sw = series_workspace(d_simg + at_table, h->series_lines.get(series_lines_bytes(n)), s_slots, gi.values);
+        GX_HIP(launch_series_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_simg, a.formats != 0 || sc->head.formats != 0, w, sw, stream));
+        GX_HIP(hipMemcpyAsync(&sd, sw.totals, sizeof(SeriesDev), hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&n_buckets, sw.bbefore + s_slots, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&n_cells, sw.cbefore + s_slots, 8, hipMemcpyDeviceToHost, stream));
+    }
     uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
     GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
     GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -2074,6 +2127,30 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
             return fail(GX_E_LIMIT, name + ": the pair table of " + std::to_string(pw.n_slots) + " slots is full; the number of lines is always a sufficient max_pairs");
         }
     }
+    uint64_t s_min_word = 0, s_max_word = 0;
+    if (sc) {
+        gx_series_totals& t = *sc->totals;
+        t.celled = sd.celled;
+        t.number_unset = sd.number_unset;
+        t.not_numbers = sd.not_numbers;
+        t.out_of_range = sd.out_of_range;
+        t.n_cells = n_cells;
+        t.n_buckets = n_buckets;
+        s_min_word = ~sd.min_inv;
+        s_max_word = sd.max_word;
+        if (n_buckets) {
+            t.first_bucket = bucket_number(s_min_word);
+            t.last_bucket = bucket_number(s_max_word);
+        }
+        if (sd.status & 2u) {
+            t.cells_exact = 0;
+            t.n_cells = static_cast<uint64_t>(sw.n_slots) + 1u;
+            return fail(GX_E_LIMIT, name + ": a series table of " + std::to_string(sw.n_slots) + " slots is full; the number of lines is always a sufficient max_cells");
+        }
+        if (sd.celled + sd.number_unset + sd.not_numbers + sd.out_of_range != totals->keyed)
+            throw GxError(GX_E_ARG, "internal: " + name + ": the classes of the keyed lines do not add up to them");
+        if (n_buckets > n_cells || n_cells > sd.celled) throw GxError(GX_E_ARG, "internal: " + name + ": more buckets than cells, or more cells than celled lines");
+    }
     if (!any_out) return GX_OK;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || q_rows;
     if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
@@ -2096,6 +2173,13 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
             return fail(GX_E_LIMIT, name + ": " + std::to_string(pair_units) + " pair units, pair_units_cap " + std::to_string(b.pair_units_cap));
         if (b.pair_offsets && !out64 && pair_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G pair units and more need offsets64");
         if (b.key_pairs && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
+    }
+    if (sc_out) {
+        const gx_series_out& b = sc->out;
+        if (sc->per_cell() && n_cells > b.max_cells) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_cells) + " cells, max_cells " + std::to_string(b.max_cells));
+        if (b.bucket_number && n_buckets > b.max_buckets)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(n_buckets) + " buckets, max_buckets " + std::to_string(b.max_buckets));
+        if (b.key_cell_begin && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
     }
     GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
     DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey, d_rows;
@@ -2154,6 +2238,32 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
         }
         GX_HIP(launch_pairs_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_pimg, w, pw, po, n_pairs, pair_units, n_keys, stream));
     }
+    // gx_group_series: the axis, the cells' rows ordered by (key number, bucket), the keys' bounds and the lines' cells
+    SeriesOut so2{};
+    DevMem<> s_num, s_key, s_bkt, s_first, s_lines, s_stats, s_begin, s_lc;
+    if (sc_out) {
+        const gx_series_out& b = sc->out;
+        so2 = SeriesOut{b.bucket_number, b.cell_key, b.cell_bucket, b.cell_first_line, b.cell_lines, reinterpret_cast<uint64_t*>(b.cell_stats), b.key_cell_begin, b.line_cell};
+        if (host_out) {
+            if (b.bucket_number && n_buckets) { s_num = dev_alloc(n_buckets * 8); so2.bucket_number = static_cast<int64_t*>(s_num.get()); }
+            if (b.cell_key && n_cells) { s_key = dev_alloc(n_cells * 4); so2.cell_key = static_cast<uint32_t*>(s_key.get()); }
+            if (b.cell_bucket && n_cells) { s_bkt = dev_alloc(n_cells * 4); so2.cell_bucket = static_cast<uint32_t*>(s_bkt.get()); }
+            if (b.cell_first_line && n_cells) { s_first = dev_alloc(n_cells * 4); so2.cell_first_line = static_cast<uint32_t*>(s_first.get()); }
+            if (b.cell_lines && n_cells) { s_lines = dev_alloc(n_cells * 8); so2.cell_lines = static_cast<uint64_t*>(s_lines.get()); }
+            if (b.cell_stats && n_cells) { s_stats = dev_alloc(n_cells * 64); so2.cell_stats = static_cast<uint64_t*>(s_stats.get()); }
+            if (b.key_cell_begin) { s_begin = dev_alloc((n_keys + 1) * 8); so2.key_cell_begin = static_cast<uint64_t*>(s_begin.get()); }
+            if (b.line_cell) { s_lc = dev_alloc(n * 4); so2.line_cell = static_cast<uint32_t*>(s_lc.get()); }
+        }
+        if (n_cells == 0) {   // keyed lines, and none of them celled: every key's run is empty
+            if (so2.key_cell_begin) GX_HIP(hipMemsetAsync(so2.key_cell_begin, 0, (n_keys + 1) * 8, stream));
+            if (so2.line_cell) GX_HIP(hipMemsetAsync(so2.line_cell, 0xFF, n * 4, stream));
+        } else {
+            const uint32_t b_digits = sc->all_digits ? BUCKET_MAX_DIGITS : bucket_digits(s_min_word, s_max_word);
+            const uint32_t c_digits = sc->all_digits ? BUCKET_MAX_DIGITS : series_digits(n_keys, n_buckets);
+            const SeriesSortWs ssw = series_sort_workspace(h->series_sort.get(series_sort_workspace_bytes(n_cells)), n_cells);
+            GX_HIP(launch_series_emit(n, n_keys, n_buckets, n_cells, b_digits, c_digits, w, sw, ssw, so2, stream));
+        }
+    }
     if (rows_bytes) {
         if (sort && qd.candidates != 0) {
             const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, n_keys, gq_sorts_all_digits());
@@ -2186,6 +2296,17 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
             if (b.key_pairs && n_keys) GX_HIP(hipMemcpyAsync(b.key_pairs, po.key_pairs, n_keys * 8, hipMemcpyDeviceToHost, stream));
             if (b.line_pair) GX_HIP(hipMemcpyAsync(b.line_pair, po.line_pair, n * 4, hipMemcpyDeviceToHost, stream));
         }
+        if (sc_out) {
+            const gx_series_out& b = sc->out;
+            if (b.bucket_number && n_buckets) GX_HIP(hipMemcpyAsync(b.bucket_number, so2.bucket_number, n_buckets * 8, hipMemcpyDeviceToHost, stream));
+            if (b.cell_key && n_cells) GX_HIP(hipMemcpyAsync(b.cell_key, so2.cell_key, n_cells * 4, hipMemcpyDeviceToHost, stream));
+            if (b.cell_bucket && n_cells) GX_HIP(hipMemcpyAsync(b.cell_bucket, so2.cell_bucket, n_cells * 4, hipMemcpyDeviceToHost, stream));
+            if (b.cell_first_line && n_cells) GX_HIP(hipMemcpyAsync(b.cell_first_line, so2.cell_first_line, n_cells * 4, hipMemcpyDeviceToHost, stream));
+            if (b.cell_lines && n_cells) GX_HIP(hipMemcpyAsync(b.cell_lines, so2.cell_lines, n_cells * 8, hipMemcpyDeviceToHost, stream));
+            if (b.cell_stats && n_cells) GX_HIP(hipMemcpyAsync(b.cell_stats, so2.cell_stats, n_cells * 64, hipMemcpyDeviceToHost, stream));
+            if (b.key_cell_begin) GX_HIP(hipMemcpyAsync(b.key_cell_begin, so2.key_cell_begin, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
+            if (b.line_cell) GX_HIP(hipMemcpyAsync(b.line_cell, so2.line_cell, n * 4, hipMemcpyDeviceToHost, stream));
+        }
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         leave_pending(h->group_event, h->group_pending, stream);
@@ -2209,6 +2330,33 @@ static void pairs_refusals(const gx_handle* h, const GroupImage& gi, const gx_gr
     }
     if (n_parts && !pc->any_second && pc->any()) throw GxError(GX_E_ARG, name + ": pair outputs while every part's second group is -1");
     if (pc->out.max_pairs > PAIRS_MAX_PAIRS) throw GxError(GX_E_LIMIT, name + ": max_pairs above 2^30");
+}
+
+// what gx_group_series adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups, checked
+// against the handle and laid out with their formats by GroupHead::ext[] (gi: group_refusals'), then the width and the outputs
+static void series_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, SeriesCall* sc) {
+    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) sc->head.number[q] = SERIES_NO_NUMBER;
+    sc->head.origin = sc->origin;
+    sc->head.width = static_cast<uint64_t>(sc->width < 1 ? 1 : sc->width);
+    sc->head.flags = gi.head.flags | (sc->all_digits ? BUCKET_ALL_DIGITS : 0u);
+    if (sc->asked) sc->out = *sc->asked;
+    if (n_parts && !sc->number_groups) throw GxError(GX_E_ARG, name + ": number_groups is NULL");
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const int32_t ng = sc->number_groups[t];
+        if (ng < -1 || ng >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's number group is neither -1 nor one of its extraction's");
+        if (ng < 0) continue;
+        sc->any_number = true;
+        for (uint32_t q = 0; q < gi.head.n_parts; ++q) {
+            if (gi.head.ext[q] != static_cast<uint32_t>(parts[t].extraction)) continue;
+            sc->head.number[q] = ng;
+            sc->head.nfmt[q] = h->number_format_of(parts[t].extraction, ng);
+            if (sc->head.nfmt[q]) sc->head.formats = 1u;
+        }
+    }
+    if (sc->width < 1) throw GxError(GX_E_ARG, name + ": width below 1");
+    if (sc->out.cell_stats && !gi.values) throw GxError(GX_E_ARG, name + ": cell_stats without a value_group");
+    if (n_parts && !sc->any_number && sc->any()) throw GxError(GX_E_ARG, name + ": series outputs while every part's number group is -1");
+    if (sc->out.max_cells > SERIES_MAX_CELLS) throw GxError(GX_E_LIMIT, name + ": max_cells above 2^30");
 }
 
 // what gx_lines_by_key adds to the refusals of gx_group_lines, behind them and before the look at the device
@@ -2379,6 +2527,7 @@ static void extras_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (x->quant) gq_refusals(gi, name, &*x->quant);
     if (x->top) tg_refusals(gi, *x->top, name);
     if (x->pairs) pairs_refusals(h, gi, parts, n_parts, name, &*x->pairs);
+    if (x->series) series_refusals(h, gi, parts, n_parts, name, &*x->series);
     if (x->by_key) by_key_refusals(*x->by_key, name);
 }
 
@@ -2554,6 +2703,40 @@ int gx_text_group_pairs(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_pairs", h, text, size, parts, n_parts, terms, n_terms, flags, keys, totals ? &totals->group : nullptr, counts, n_lines, opts,
                            pairs_extras(second_groups, pairs, totals));
+}
+
+// gx_group_series: gx_group_lines' call with the series behind it.  totals == NULL is refused as gx_group_lines refuses it.  The flags
+// travel without GX_BUCKET_ALL_DIGITS (unknown bits stay in the flags and are refused there).
+static GroupExtras series_extras(const int32_t* number_groups, int64_t origin, int64_t width, uint32_t flags, const gx_series_out* series, gx_series_totals* totals) {
+    if (totals) {
+        *totals = gx_series_totals{};
+        totals->cells_exact = 1;
+    }
+    SeriesCall sc;
+    sc.number_groups = number_groups;
+    sc.origin = origin;
+    sc.width = width;
+    sc.all_digits = (flags & GX_BUCKET_ALL_DIGITS) != 0u;
+    sc.asked = series;
+    sc.totals = totals;
+    GroupExtras x;
+    x.series = sc;
+    return x;
+}
+static_assert(sizeof(gx_series_out) == 80 && sizeof(gx_series_totals) == sizeof(gx_group_totals) + 72, "include/gorp_hip.h states these layouts");
+
+int gx_group_series(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                    uint32_t n_parts, const int32_t* number_groups, int64_t origin, int64_t width, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                    const gx_group_out* keys, const gx_series_out* series, gx_series_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_series", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                            totals ? &totals->group : nullptr, opts, series_extras(number_groups, origin, width, flags, series, totals));
+}
+
+int gx_text_group_series(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups, int64_t origin,
+                         int64_t width, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_series_out* series,
+                         gx_series_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_series", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, series_extras(number_groups, origin, width, flags, series, totals));
 }
 
 // The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.

@@ -411,6 +411,58 @@ hipError_t launch_bucket_build(const void* ids, RowFormat fmt, uint32_t row_unit
                                const BucketWs& w, hipStream_t stream);
 hipError_t launch_bucket_emit(uint64_t n, uint64_t m, uint32_t n_digits, const BucketWs& w, const BucketSortWs& s, const BucketOut& out, hipStream_t stream);
 
+// The lines of a finished batch counted and measured per (captured text, interval of a captured number) (gx_series.hip; the rule:
+// gx_series.hpp), behind gx_group_lines' passes on the same stream: a one-word table of the distinct bucket numbers, a one-word table of
+// the distinct (key slot, bucket slot) cells with gx_group_lines' per-slot words, the buckets sorted into an axis and the cells sorted by
+// (key number, rank on the axis).  Its build pass adds to a cell slot with gx_group_dev.hpp's GroupAdd / group_add, as gx_group.hip's
+// and gx_bucket.hip's do.  Both tables have n_slots slots.  The passes' device workspace: the slots' words and arrays
+// (series_table_bytes), the lines' cell slots (series_lines_bytes) and, sized by the cells the host has read, the sorts'
+// (series_sort_workspace_bytes).
+struct SeriesWs {
+    uint32_t n_slots;             // a power of two, of EACH table
+    uint64_t* btable;             // [n_slots] the bucket slot words: group_max_word(bucket), 0 = empty
+    uint64_t* ctable;             // [n_slots] the cell slot words: cell_word(key slot, bucket slot), 0 = empty
+    uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS] of the cell slots
+    uint64_t* stats_words;        // [n_slots][GROUP_STATS_WORDS] of the cell slots, with values
+    uint64_t* totals;             // [8] SeriesDev
+    uint64_t *bbefore, *cbefore;  // [n_slots + 1] occupied slots before slot s; [n_slots]: the buckets, the cells
+    uint64_t *bsums, *csums;      // the scans'
+    uint32_t* rank_of_bslot;      // [n_slots] the bucket slot's index on the axis, written by k_series_axis
+    uint32_t* rank_of_cslot;      // [n_slots] the cell slot's cell number, written by k_series_emit
+    uint8_t *boccupied, *coccupied;   // [n_slots]
+    uint32_t* cslot_of;           // [n] the line's cell slot, GROUP_NONE: it is in no cell
+};
+struct SeriesSortWs {
+    BucketSortWs sort;            // for m cells; the buckets are sorted in it first
+    uint32_t* knum;               // [m] the sorted cells' key numbers
+};
+// what the emit passes write, each part optional (nullptr)
+struct SeriesOut {
+    int64_t* bucket_number;
+    uint32_t* cell_key;
+    uint32_t* cell_bucket;
+    uint32_t* cell_first_line;
+    uint64_t* cell_lines;
+    uint64_t* cell_stats;         // [n_cells][8]: gx_measure_stats' fields
+    uint64_t* key_cell_begin;     // [n_keys + 1]
+    uint32_t* line_cell;
+};
+size_t series_table_zero_bytes(uint32_t n_slots, bool values);
+size_t series_table_bytes(uint32_t n_slots, bool values);
+size_t series_lines_bytes(uint64_t n);
+SeriesWs series_workspace(void* table_mem, void* lines_mem, uint32_t n_slots, bool values);
+size_t series_sort_workspace_bytes(uint64_t m);
+SeriesSortWs series_sort_workspace(void* ws, uint64_t m);
+// n > 0, parts > 0, behind launch_group_build (g.slot_of); series_image: a SeriesHead on the device, 16-byte aligned; formats: a value
+// group's or a number group's format is not LONG.  Build, flags and the two scans; behind them the host reads w.totals,
+// w.bbefore[n_slots] and w.cbefore[n_slots].
+hipError_t launch_series_build(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                               const void* series_image, bool formats, const GroupWs& g, const SeriesWs& w, hipStream_t stream);
+// Behind launch_group_emit (g.keynum) and the host's check of the capacities: the two sorts (b_digits, c_digits digits), the axis, the
+// cells' rows, the keys' bounds and the lines' cells.  0 < n_buckets <= n_cells.
+hipError_t launch_series_emit(uint64_t n, uint64_t n_keys, uint64_t n_buckets, uint64_t n_cells, uint32_t b_digits, uint32_t c_digits, const GroupWs& g,
+                              const SeriesWs& w, const SeriesSortWs& s, const SeriesOut& out, hipStream_t stream);
+
 // The lines of a finished batch ranked by a number they captured (gx_top.hip; the rule: gx_top.hpp): the n_wanted largest (or smallest)
 // numbers' lines, ordered by (value, input line).
 struct TopArgs {

@@ -1746,6 +1746,180 @@ class Gorp:
         res["line_bucket"] = res["line_bucket"][:n_lines]
         return res, counts, n_lines
 
+    # -- a series per captured text: lines per (key, interval of a captured number) (gx_group_series / gx_text_group_series) ---------
+    def series_parts(self, spec):
+        """Resolves a list of (extraction, key extractor, number extractor[, value extractor]) into (GroupParts, int32 number groups):
+        the first, second and optional fourth entry as group_parts takes a part, the third the extractor whose value is the line's
+        NUMBER (None: the part's lines have a key and no number, -1).  A (GroupParts, numbers) tuple passes through."""
+        if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], GroupParts):
+            return spec
+        spec = [tuple(item) for item in spec]
+        for item in spec:
+            if len(item) not in (3, 4):
+                raise ValueError("a part is (extraction, key extractor, number extractor[, value extractor])")
+        parts = self.group_parts([(item[0], item[1]) + tuple(item[3:]) for item in spec])
+        numbers = (C.c_int32 * max(1, len(spec)))()
+        for t, item in enumerate(spec):
+            numbers[t] = -1 if item[2] is None else self._extraction_and_group(parts.array[t].extraction, item[2])[1]
+        return parts, numbers
+
+    def _series_origin(self, both, origin):
+        """origin as an int; a text is read by _bucket_origin's rule under the number format of the first part that has a number."""
+        parts, numbers = both
+        numbered = [(parts.array[t].extraction, numbers[t]) for t in range(parts.n) if numbers[t] >= 0]
+        return self._bucket_origin(self.bucket_parts(numbered[:1]), origin)
+
+    @staticmethod
+    def _series_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(n_cells=t.n_cells, n_buckets=t.n_buckets, celled=t.celled, number_unset=t.number_unset, not_numbers=t.not_numbers,
+                 out_of_range=t.out_of_range, cells_exact=bool(t.cells_exact), first_bucket=t.first_bucket, last_bucket=t.last_bucket,
+                 group=Gorp._group_totals(t.group))
+        return d
+
+    def group_series_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, width, origin=0, where=None, key_units_ptr=None, key_units_cap=0,
+                            key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0,
+                            bucket_number_ptr=None, cell_key_ptr=None, cell_bucket_ptr=None, cell_first_line_ptr=None, cell_lines_ptr=None, cell_stats_ptr=None,
+                            key_cell_begin_ptr=None, line_cell_ptr=None, max_cells=0, max_buckets=0, series=True, offsets64=False, utf16=False, compact=0,
+                            stream=None, device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_group_series on device pointers (ints): group_lines_device's keys, plus the cells (key, bucket) in the caller's buffers,
+        each optional (none at all: the size query; max_keys and max_cells still size the tables).  series=False passes series ==
+        NULL: the call is gx_group_lines.  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says
+        what the outputs need (n_keys, key_units, n_cells, n_buckets; exact / cells_exact False: that table overflowed, the number of
+        lines always suffices); every other error raises."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_series_out(bucket_number_ptr, cell_key_ptr, cell_bucket_ptr, cell_first_line_ptr, cell_lines_ptr, cell_stats_ptr, key_cell_begin_ptr, line_cell_ptr,
+                              max_cells, max_buckets)
+        totals = N.gx_series_totals()
+        rc = N.lib().gx_group_series(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, both[0].array, both[0].n, both[1], self._series_origin(both, origin),
+                                     int(width), terms.array, terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(keys), C.byref(out) if series else None,
+                                     C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._series_totals(totals)
+
+    def text_group_series_device(self, text_ptr, size, parts, width, origin=0, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                                 key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, bucket_number_ptr=None,
+                                 cell_key_ptr=None, cell_bucket_ptr=None, cell_first_line_ptr=None, cell_lines_ptr=None, cell_stats_ptr=None, key_cell_begin_ptr=None,
+                                 line_cell_ptr=None, max_cells=0, max_buckets=0, series=True, offsets64=False, stream=None, device_pointers=True, utf8=False,
+                                 weak_hash=False, all_digits=False):
+        """gx_text_group_series on a device buffer (int); outputs as group_series_device takes them (line_key and line_cell: one entry
+        per line of the text).  Returns (rc, totals, counts, n_lines)."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_series_out(bucket_number_ptr, cell_key_ptr, cell_bucket_ptr, cell_first_line_ptr, cell_lines_ptr, cell_stats_ptr, key_cell_begin_ptr, line_cell_ptr,
+                              max_cells, max_buckets)
+        totals = N.gx_series_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_series(self._h.ptr, text_ptr, size, both[0].array, both[0].n, both[1], self._series_origin(both, origin), int(width), terms.array,
+                                          terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(keys), C.byref(out) if series else None, C.byref(totals),
+                                          counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._series_totals(totals), counts, nl.value
+
+    def _series_host(self, device_call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap, max_cells, max_buckets):
+        """_group_host with the series arrays beside the key arrays.  max_cells defaults to min(the number of lines, 4 096) and
+        max_buckets to max_cells; an exact GX_E_LIMIT raises them to what it reports, an overflowed key or cell table to the number
+        of lines, which always suffices: behind any overflow the next call's tables hold everything, so three calls are enough."""
+        mc0 = min(n_lines_cap, 4096) if max_cells is None else max_cells
+        size = {"max_cells": mc0, "max_buckets": mc0 if max_buckets is None else max_buckets}
+        got = {}
+
+        def call(units, cap, koff, first, lines, stats, line_key, mk):
+            mc, mb = size["max_cells"], size["max_buckets"]
+            got.update(bucket_number=np.zeros(max(1, mb), np.int64), cell_key=np.zeros(max(1, mc), np.uint32), cell_bucket=np.zeros(max(1, mc), np.uint32),
+                       cell_first_line=np.zeros(max(1, mc), np.uint32), cell_lines=np.zeros(max(1, mc), np.uint64),
+                       cell_stats=(N.gx_measure_stats * max(1, mc))() if parts.has_values else None, key_cell_begin=np.zeros(mk + 1, np.uint64),
+                       line_cell=np.full(max(1, n_lines_cap), 0xFFFFFFFF, np.uint32))
+            r = device_call(units, cap, koff, first, lines, stats, line_key, mk, got["bucket_number"].ctypes.data, got["cell_key"].ctypes.data,
+                            got["cell_bucket"].ctypes.data, got["cell_first_line"].ctypes.data, got["cell_lines"].ctypes.data,
+                            None if got["cell_stats"] is None else C.addressof(got["cell_stats"]), got["key_cell_begin"].ctypes.data, got["line_cell"].ctypes.data, mc, mb)
+            if r[0] == N.GX_E_LIMIT and r[1]["exact"] and r[1]["cells_exact"]:
+                size.update(max_cells=max(mc, r[1]["n_cells"]), max_buckets=max(mb, r[1]["n_buckets"]))
+            elif r[0] == N.GX_E_LIMIT:
+                # A table overflowed.  The key table's overflow leaves the series totals zero, so nothing is known of the cells: both
+                # series sizes go to the number of lines with it, and the limits of keys and cells never take a call each.
+                size.update(max_cells=n_lines_cap, max_buckets=max(mb, n_lines_cap) if max_buckets is None else mb)
+            return r
+        res, rest = self._group_host(call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap)
+        c, b, k = res["totals"]["n_cells"], res["totals"]["n_buckets"], res["totals"]["n_keys"]
+        st = got["cell_stats"]
+        res.update(bucket_number=got["bucket_number"][:b], cell_key=got["cell_key"][:c], cell_bucket=got["cell_bucket"][:c], cell_first_line=got["cell_first_line"][:c],
+                   cell_lines=got["cell_lines"][:c], key_cell_begin=got["key_cell_begin"][:k + 1], line_cell=got["line_cell"],
+                   cell_stats=None if st is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                                                        "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
+                                                        "sum": (s.sum_hi << 64) + s.sum_lo} for s in st[:c]])
+        return res, rest
+
+    def group_series(self, data, offsets, ids, rows, parts, width, origin=0, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None, max_cells=None,
+                     max_buckets=None, weak_hash=False, all_digits=False):
+        """gx_group_series on host buffers: group_lines' keys, and the lines counted -- and, with a value extractor, measured -- per
+        (key, interval floor((number - origin) / width)): GROUP BY verb, minute.  parts: (extraction, key extractor, number
+        extractor[, value extractor]) each (series_parts); width and origin as bucket_lines takes them (a text origin is read under
+        the first numbered part's number format); everything else as group_lines takes it.  Returns group_lines' dict plus
+        bucket_number (the axis: int64, ascending, the buckets that hold a cell), cell_key, cell_bucket (the index into
+        bucket_number), cell_first_line, cell_lines, cell_stats (per cell, ordered by (key number, bucket); None when no part has a
+        value extractor), key_cell_begin (n_keys + 1: key j's cells are [begin[j], begin[j + 1])), line_cell (uint32 per input line,
+        0xFFFFFFFF: none) and the series totals (n_cells, n_buckets, celled, number_unset, not_numbers, out_of_range, cells_exact,
+        first_bucket, last_bucket) in totals.  On an exact GX_E_LIMIT the call is repeated once with the sizes it reported."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        both = self.series_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.group_series_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), both, width, origin, where, *outs,
+                                            offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8),
+                                            weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._series_host(device_call, n, both[0], data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap, max_cells, max_buckets)
+        res["line_key"], res["line_cell"] = res["line_key"][:n], res["line_cell"][:n]
+        return res
+
+    def text_group_series(self, text, parts, width, origin=0, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None, max_cells=None,
+                          max_buckets=None, weak_hash=False, all_digits=False):
+        """gx_text_group_series on a host buffer: raw text -> lines -> extraction -> group_series.  Returns (the dict group_series
+        returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        both = self.series_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.text_group_series_device(raw.ctypes.data if raw.size else None, raw.size, both, width, origin, where, *outs, device_pointers=False, utf8=utf8,
+                                                 weak_hash=weak_hash, all_digits=all_digits)
+        res, (counts, n_lines) = self._series_host(device_call, cap_lines, both[0], np.uint8, np.uint32, keys, decode, max_keys, key_units_cap, max_cells, max_buckets)
+        res["line_key"], res["line_cell"] = res["line_key"][:n_lines], res["line_cell"][:n_lines]
+        return res, counts, n_lines
+
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
     def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
                                key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,

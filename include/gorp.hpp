@@ -906,6 +906,79 @@ public:
         out.resize(static_cast<size_t>(size));
         return out;
     }
+    // A series per captured text (gx_group_series): the caller's
+    //     long b = Math.floorDiv(Instant.parse(r.asMap().get("ts")).toEpochMilli() - origin, 60_000L);
+    //     perVerb.computeIfAbsent(r.asMap().get("verb"), v -> new TreeMap<Long, Stats>()).computeIfAbsent(b, x -> new Stats()).record(...);
+    // (README.md:26,63-79, with a timestamp field) -- GROUP BY verb, floor((ts - origin) / width).  The parts of a call are groupParts' plus
+    // a NUMBER extractor per part (an empty name, or -1: the part's lines have a key and no number), read under its group's number format:
+    // seriesParts().of("GetRequest", "verb", "ts", "timeTakenInMsec").
+    class SeriesParts {
+    public:
+        explicit SeriesParts(const Gorp* g) : g_(g), keys_(g) {}
+        SeriesParts& of(const std::string& extraction, const std::string& key, const std::string& number, const std::string& value = std::string()) {
+            int32_t n = -1;
+            if (!number.empty()) {
+                Where at(g_);
+                at.on(extraction, number).isSet();
+                n = at.terms()[0].group;
+            }
+            keys_.of(extraction, key, value);
+            numbers_.push_back(n);
+            return *this;
+        }
+        SeriesParts& of(size_t extraction, size_t keyGroup, int32_t numberGroup, int32_t valueGroup = -1) {
+            if (numberGroup < -1 || (extraction < g_->extractions_.size() && numberGroup >= 0 &&
+                                     static_cast<size_t>(numberGroup) >= g_->extractions_[extraction].extractorNames.size()))
+                throw std::invalid_argument("no such extraction or group");
+            keys_.of(extraction, keyGroup, valueGroup);
+            numbers_.push_back(numberGroup);
+            return *this;
+        }
+        const GroupParts& keys() const { return keys_; }
+        const std::vector<int32_t>& numbers() const { return numbers_; }
+
+    private:
+        const Gorp* g_;
+        GroupParts keys_;
+        std::vector<int32_t> numbers_;
+    };
+    SeriesParts seriesParts() const { return SeriesParts(this); }
+    // groupLines' result, plus the axis (the distinct buckets that hold a cell, ascending) and the cells ordered by (key number, bucket):
+    // per cell its key's number, the index of its bucket on the axis, its first line, its lines and -- when a part has a value -- its
+    // gx_measure_stats; per key where its cells begin (keys.size() + 1 entries); per input line its cell's number (0xFFFFFFFF: none).
+    struct Series : Groups {
+        std::vector<int64_t> bucketNumber;
+        std::vector<uint32_t> cellKey, cellBucket, cellFirstLine;
+        std::vector<uint64_t> cellLines;
+        std::vector<gx_measure_stats> cellStats;   // empty when no part has a value
+        std::vector<uint64_t> keyCellBegin;
+        std::vector<uint32_t> lineCell;
+        gx_series_totals series{};
+    };
+    Series groupSeries(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const SeriesParts& parts,
+                       int64_t width, int64_t origin = 0, const Where* where = nullptr) const {
+        return seriesOf(parts, where, &n, n, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                 const gx_series_out* so, gx_series_totals* totals) {
+            return gx_group_series(h_, bytes, offsets, n, match_id, caps, p, np, s, origin, width, t, nt, 0, out, so, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same series out (gx_text_group_series).  counts (optional): lines per outcome index.
+    Series textGroupSeries(const std::string& text, const SeriesParts& parts, int64_t width, int64_t origin = 0, const Where* where = nullptr,
+                           std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0, ends = 1;   // (no more lines than line ends, plus the last)
+        for (const char c : text) ends += (c == '\n' || c == '\r') ? 1u : 0u;
+        Series r = seriesOf(parts, where, &lines, ends, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt,
+                                                            const gx_group_out* out, const gx_series_out* so, gx_series_totals* totals) {
+            return gx_text_group_series(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, s, origin, width, t, nt, 0, out, so, totals,
+                                        counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return r;
+    }
     int maxGroups() const { return gx_max_groups(h_); }
     gx_handle* handle() const { return h_; }
 
@@ -1024,6 +1097,48 @@ private:
             r.linePair.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
         }
         for (size_t j = 0; j < r.pairKey.size(); ++j) r.seconds.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
+        return r;
+    }
+    // groupsOf with the series beside the keys: the size queries ask with tables for maxLines cells, which always suffices; the call with
+    // exactly the sizes they reported delivers both.  Series outputs are asked for only where a part has a number (the C call refuses
+    // them otherwise: there is nothing they could hold).
+    template <typename Call>
+    Series seriesOf(const SeriesParts& parts, const Where* where, const uint64_t* lines, uint64_t maxLines, Call&& call) const {
+        Series r;
+        const int32_t none = -1;
+        const std::vector<int32_t>& numbers = parts.numbers();
+        bool wanted = numbers.empty();
+        for (const int32_t s : numbers) wanted = wanted || s >= 0;
+        Groups g = groupsOf(parts.keys(), where, lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                            gx_group_totals* totals) {
+            gx_series_out so{};
+            so.max_cells = maxLines < (1ull << 30) ? maxLines : (1ull << 30);
+            if (out->key_offsets != nullptr && wanted) {   // (the size query before it left the sizes in r.series)
+                const size_t m = static_cast<size_t>(r.series.n_cells);
+                r.bucketNumber.assign(static_cast<size_t>(r.series.n_buckets), 0);
+                r.cellKey.assign(m, 0);
+                r.cellBucket.assign(m, 0);
+                r.cellFirstLine.assign(m, 0);
+                r.cellLines.assign(m, 0);
+                if (parts.keys().hasValues()) r.cellStats.assign(m, gx_measure_stats{});
+                r.keyCellBegin.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+                r.lineCell.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+                so.bucket_number = r.bucketNumber.data(); so.cell_key = r.cellKey.data(); so.cell_bucket = r.cellBucket.data();
+                so.cell_first_line = r.cellFirstLine.data(); so.cell_lines = r.cellLines.data();
+                so.cell_stats = parts.keys().hasValues() ? r.cellStats.data() : nullptr;
+                so.key_cell_begin = r.keyCellBegin.data(); so.line_cell = r.lineCell.data();
+                so.max_cells = r.series.n_cells;   // (the arrays' capacity; tables of twice as many slots hold them all)
+                so.max_buckets = r.series.n_buckets;
+            }
+            const int rc = call(p, np, numbers.empty() ? &none : numbers.data(), t, nt, out, &so, &r.series);
+            *totals = r.series.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        if (!wanted) {
+            r.keyCellBegin.assign(r.keys.size() + 1, 0);
+            r.lineCell.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        }
         return r;
     }
     // groupsOf's scheme for topGroups: the size query with a table for a modest number of keys, once more with as many keys as lines if

@@ -973,6 +973,92 @@ int gx_text_bucket_lines(gx_handle* h, const uint8_t* text, uint64_t size, const
                          int64_t width, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_bucket_out* out,
                          gx_bucket_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- A series per captured text: lines counted and measured per (key, interval), on the device (gx_group_series) ----
+ * The reference's caller asks the question of gx_bucket_lines per verb, per host, per path right behind the extraction
+ * (README.md:26,63-79, with a timestamp field):
+ *     r = gorp.extract(line);
+ *     if (r != null) {
+ *         long b = Math.floorDiv(Instant.parse(r.asMap().get("ts")).toEpochMilli() - origin, 60_000L);
+ *         perVerb.computeIfAbsent(r.asMap().get("verb"), v -> new TreeMap<Long, Stats>())
+ *                .computeIfAbsent(b, x -> new Stats()).record(Long.parseLong(r.asMap().get("timeTakenInMsec")));
+ *     }
+ * -- GROUP BY verb, floor((ts - origin) / width).  gx_group_lines keys on one text, gx_group_pairs on two texts (two stamps a millisecond
+ * apart are two seconds), gx_bucket_lines has one bucket space for all lines.
+ * PARTS: gx_group_lines' parts, plus number_groups[n_parts]: per part the group whose value is the line's NUMBER, parsed under its
+ * gx_number_format, in [0, gx_num_groups(h, extraction)), or -1: the part's lines have a key and no number.  origin and width >= 1 are
+ * gx_bucket_lines'.  All parts share one key space and one bucket space.
+ * THE RULE: a line counts, is keyed or adds to `unset` exactly as in gx_group_lines; nothing of that call is reinterpreted.  A keyed line
+ * is CELLED when its part has a number group, that group's capture names a value (the rule of gx_where_term), the value parses and
+ * gx_bucket_lines' rule gives it a bucket; else it adds to number_unset (the number group is -1, or its capture names nothing), to
+ * not_numbers (the value does not parse) or to out_of_range (gx_bucket_lines' rule): keyed == celled + number_unset + not_numbers +
+ * out_of_range.  Lines without a key are never bucketed.  Two celled lines are in the same CELL when they hold the same key
+ * (gx_group_lines' equality) and the same bucket number.
+ * ORDER: cells leave ordered by (key number, bucket number): key numbers are gx_group_lines' (first appearance), buckets ascend inside a
+ * key, and every key's cells are contiguous -- a series per key, in time order.  The distinct bucket numbers that hold at least one cell
+ * leave ascending, as an axis (bucket_number), and a cell names its bucket by its index into that axis: a dense key x time matrix needs
+ * no search.
+ * EXACT: every output is exact and the same bits on every run; all merges are unsigned integer adds and maxima.
+ * NOT IN SCOPE: empty cells filled in, calendar widths, quantiles per cell, ranking cells, lines per bucket across keys (that is
+ * gx_bucket_lines), more than one text key (compose with gx_group_pairs later).  The rule: gorp_amd/csrc/gx_series.hpp. */
+typedef struct gx_series_out {     /* every pointer optional; device memory with opts->device_pointers, else host */
+    int64_t*  bucket_number;       /* the axis: distinct buckets that hold a cell, ascending */
+    uint32_t* cell_key;            /* key number (gx_group_out's order) of cell c; cells are ORDERED by (cell_key, cell_bucket) */
+    uint32_t* cell_bucket;         /* index into bucket_number */
+    uint32_t* cell_first_line;
+    uint64_t* cell_lines;
+    gx_measure_stats* cell_stats;  /* over the cell's lines whose part has a value_group; NULL where no part has one */
+    uint64_t* key_cell_begin;      /* n_keys + 1: key j's cells are [key_cell_begin[j], key_cell_begin[j+1]); capacity keys->max_keys + 1 */
+    uint32_t* line_cell;           /* n entries, 0xFFFFFFFF: none */
+    uint64_t  max_cells;           /* capacity of the per-cell arrays, and BOTH tables' size; read in the size query too; <= 2^30 */
+    uint64_t  max_buckets;         /* capacity of bucket_number only */
+} gx_series_out;
+
+typedef struct gx_series_totals {  /* host, always */
+    gx_group_totals group;         /* exactly what gx_group_lines reports for the same call */
+    uint64_t n_cells, n_buckets, celled, number_unset, not_numbers, out_of_range, cells_exact;
+    int64_t  first_bucket, last_bucket;   /* 0 without a cell */
+} gx_series_totals;
+
+/* gx_group_series: everything gx_group_lines delivers through `keys` and totals->group is delivered bit for bit.
+ * HOW THE BATCH IS READ: exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging
+ * or device_pointers; the stream).
+ * FLAGS: GX_GROUP_WEAK_HASH (it cuts the hashes of all three tables to 3 bits) and GX_BUCKET_ALL_DIGITS (it applies to both sorts).
+ * With series == NULL the call IS gx_group_lines: the series passes do not run, and the series totals are zero with cells_exact = 1.
+ * Its arguments are still checked: number_groups == NULL with n_parts > 0, a bad number group and width < 1 are GX_E_ARG there too.
+ * THE TABLES: a table of the distinct buckets and a table of the distinct cells, each of the smallest power of two >= max(64, 2 *
+ * max_cells) slots of one 64-bit word; distinct buckets never exceed distinct cells.  The number of lines is always a sufficient
+ * max_cells.
+ * SIZE QUERY: every output of `keys` and `series` NULL: only *totals is filled; keys->max_keys and series->max_cells are still read as
+ * the tables' sizes.
+ * GX_E_LIMIT: a per-cell array (cell_key, cell_bucket, cell_first_line, cell_lines, cell_stats) with n_cells > max_cells; bucket_number
+ * with n_buckets > max_buckets; key_cell_begin with n_keys > keys->max_keys; max_cells > 2^30; a full table (cells_exact = 0 and n_cells
+ * = slots + 1, while group.exact stays 1); and gx_group_lines' own limits.  In every one of these cases nothing is written to ANY
+ * output, the key outputs included, and *totals is filled (after the overflow of the KEY table the series totals are zero).
+ * GX_E_ARG: every refusal gx_group_lines makes; number_groups == NULL with n_parts > 0; a number group that is neither -1 nor one of its
+ * part's extraction's; width < 1; cell_stats where no part has a value group; an output of `series` given while n_parts > 0 and every
+ * number group is -1; unknown flag bits.  All refusals that need no device come before the device is looked at: a host-only handle
+ * gives them, and GX_E_DEVICE after them (there is no CPU path).
+ * EMPTY INPUTS: n == 0 and n_parts == 0 are legal and give all zeros (key_cell_begin: its one entry; line_cell: all none).
+ * HOST WAITS: ONE host wait before any output -- the wait in which gx_group_lines reads its totals also reads the series totals, the
+ * buckets, the cells and the range of the bucket numbers, from which both sorts' digits are planned.  With host outputs a second wait
+ * delivers them.  With device_pointers the sorts and the emits are left running on opts->stream when the call returns, as
+ * gx_bucket_lines leaves them; the handle's next group call on another stream waits for them, and the batch must stay unchanged until
+ * they have run.
+ * WORKSPACE: on the handle beside gx_group_lines', until gx_destroy: 21 bytes per bucket slot and 37 per cell slot (101 with a value
+ * group), 4 per input line, and 28 per cell plus 768 per 2 048 cells for the sorts. */
+int gx_group_series(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                    const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups, int64_t origin, int64_t width,
+                    const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_series_out* series,
+                    gx_series_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the series at its end: raw text -> lines -> the match-and-extract path -> the
+ * keys and the cells.  counts and *n_lines as gx_text_group_lines delivers them; line_cell holds one entry per line of the text.  Like
+ * every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_series(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                         const int32_t* number_groups, int64_t origin, int64_t width, const gx_where_term* terms, uint32_t n_terms,
+                         uint32_t flags, const gx_group_out* keys, const gx_series_out* series, gx_series_totals* totals, uint64_t* counts,
+                         uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
