@@ -99,6 +99,40 @@ template <typename T = void> DevMem<T> dev_alloc(size_t bytes) {
     return m;
 }
 
+// A reduction's outputs, which are the caller's device pointers or -- host_out -- host buffers: of() gives what the kernels write, the
+// caller's own pointer or a device twin of `bytes` bytes (one allocation each, 16 bytes for none) that lives as long as this object,
+// until the call's last wait; deliver() enqueues the twins' way back behind the kernels.  nullptr (not wanted) stays nullptr.
+class HostTwins {
+    struct Twin {
+        void* callers;
+        DevMem<> dev;
+        size_t bytes;
+    };
+    std::vector<Twin> twins_;
+    bool host_out_ = false;
+
+  public:
+    HostTwins() = default;
+    explicit HostTwins(bool host_out) : host_out_(host_out) {}
+    template <class T> T* of(T* callers, size_t bytes) {
+        if (!callers || !host_out_) return callers;
+        twins_.push_back(Twin{callers, dev_alloc(bytes), bytes});
+        return static_cast<T*>(twins_.back().dev.get());
+    }
+    void deliver(hipStream_t stream) const {
+        for (const Twin& t : twins_)
+            if (t.bytes) GX_HIP(hipMemcpyAsync(t.callers, t.dev.get(), t.bytes, hipMemcpyDeviceToHost, stream));
+    }
+};
+
+// The results that no kernel writes ("no keys", "no lines", "no cells"): `bytes` bytes of `byte` at an output, in host memory or, on the
+// stream, in device memory.  Nothing for an output that is not wanted or empty.
+void fill_out(void* p, int byte, size_t bytes, bool host_out, hipStream_t stream) {
+    if (!p || !bytes) return;
+    if (host_out) memset(p, byte, bytes);
+    else GX_HIP(hipMemsetAsync(p, byte, bytes, stream));
+}
+
 // Device memory kept between calls and grown as they ask (an allocation and a free per call cost more than the kernels that use it).
 struct GrowBuf {
     DevMem<> mem;
@@ -1405,36 +1439,22 @@ struct LinesOut {
 namespace {
 struct StagedLinesOut {
     SelectOut dev{};
-    DevMem<> index, bytes, offsets, ids, caps;
+    HostTwins twins;
+    // behind the copy pass, host buffers only: the twins back to the caller's buffers
+    void deliver(hipStream_t stream) const { twins.deliver(stream); }
 };
 }  // namespace
 static StagedLinesOut stage_lines_out(const gx_handle* h, const BatchView& v, const LinesOut& out, bool host, uint64_t lines, uint64_t units) {
     const size_t off_w = v.off64 ? 8 : 4, unit = v.wide ? 2 : 1, id_row = static_cast<size_t>(v.row_units) * row_unit_bytes(v.fmt);
     const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
     StagedLinesOut s;
-    s.dev.index = out.index; s.dev.bytes = out.bytes; s.dev.offsets = out.offsets;
-    void *dst_ids = out.ids, *dst_caps = out.caps;
-    if (host) {
-        if (out.index) { s.index = dev_alloc(lines * 4); s.dev.index = static_cast<uint32_t*>(s.index.get()); }
-        if (out.bytes) { s.bytes = dev_alloc(units * unit); s.dev.bytes = s.bytes.get(); }
-        if (out.offsets) { s.offsets = dev_alloc((lines + 1) * off_w); s.dev.offsets = s.offsets.get(); }
-        if (out.ids) { s.ids = dev_alloc(lines * id_row); dst_ids = s.ids.get(); }
-        if (out.caps) { s.caps = dev_alloc(lines * slots * 4); dst_caps = s.caps.get(); }
-    }
-    if (out.ids) { s.dev.col_src[0] = v.ids; s.dev.col_dst[0] = dst_ids; s.dev.col_width[0] = v.row_units; s.dev.col_unit_bytes[0] = row_unit_bytes(v.fmt); }
-    if (out.caps) { s.dev.col_src[1] = v.caps; s.dev.col_dst[1] = dst_caps; s.dev.col_width[1] = static_cast<uint32_t>(slots); s.dev.col_unit_bytes[1] = 4; }
+    s.twins = HostTwins(host);
+    s.dev.index = s.twins.of(out.index, lines * 4);
+    s.dev.bytes = s.twins.of(out.bytes, units * unit);
+    s.dev.offsets = s.twins.of(out.offsets, (lines + 1) * off_w);
+    if (out.ids) { s.dev.col_src[0] = v.ids; s.dev.col_dst[0] = s.twins.of(out.ids, lines * id_row); s.dev.col_width[0] = v.row_units; s.dev.col_unit_bytes[0] = row_unit_bytes(v.fmt); }
+    if (out.caps) { s.dev.col_src[1] = v.caps; s.dev.col_dst[1] = s.twins.of(out.caps, lines * slots * 4); s.dev.col_width[1] = static_cast<uint32_t>(slots); s.dev.col_unit_bytes[1] = 4; }
     return s;
-}
-// behind the copy pass, host buffers only: the twins back to the caller's buffers
-static void deliver_lines_out(const gx_handle* h, const BatchView& v, const LinesOut& out, const StagedLinesOut& s, uint64_t lines, uint64_t units,
-                              hipStream_t stream) {
-    const size_t off_w = v.off64 ? 8 : 4, unit = v.wide ? 2 : 1, id_row = static_cast<size_t>(v.row_units) * row_unit_bytes(v.fmt);
-    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
-    if (out.index && lines) GX_HIP(hipMemcpyAsync(out.index, s.dev.index, lines * 4, hipMemcpyDeviceToHost, stream));
-    if (out.bytes && units) GX_HIP(hipMemcpyAsync(out.bytes, s.dev.bytes, units * unit, hipMemcpyDeviceToHost, stream));
-    if (out.offsets) GX_HIP(hipMemcpyAsync(out.offsets, s.dev.offsets, (lines + 1) * off_w, hipMemcpyDeviceToHost, stream));
-    if (out.ids && lines) GX_HIP(hipMemcpyAsync(out.ids, s.dev.col_dst[0], lines * id_row, hipMemcpyDeviceToHost, stream));
-    if (out.caps && lines) GX_HIP(hipMemcpyAsync(out.caps, s.dev.col_dst[1], lines * slots * 4, hipMemcpyDeviceToHost, stream));
 }
 
 // The histogram of a batch's outcomes beside a reduction of it (k_select_flags' counting form, on the handle's select workspace, under
@@ -1513,6 +1533,19 @@ static WhereImage where_image(const gx_handle* h, const gx_where_term* terms, ui
     img.formats = head.formats != 0u;
     memcpy(img.bytes.data(), &head, sizeof(head));
     return img;
+}
+// A reduction's image on the device, in a buffer of the handle's: the head, a quantile call's QuantHead behind it, then the terms (small
+// transfers from pageable memory, which the runtime stages).  terms: nullptr when the call has none.
+struct DevImage {
+    uint8_t *head, *terms;
+};
+static DevImage upload_image(GrowBuf& buf, const void* head, size_t head_bytes, const QuantHead* second, const WhereImage& wi, hipStream_t stream) {
+    const size_t at_terms = head_bytes + (second ? sizeof(QuantHead) : 0);
+    uint8_t* d = static_cast<uint8_t*>(buf.get(at_terms + wi.bytes.size()));
+    GX_HIP(hipMemcpyAsync(d, head, head_bytes, hipMemcpyHostToDevice, stream));
+    if (second) GX_HIP(hipMemcpyAsync(d + head_bytes, second, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
+    if (!wi.none()) GX_HIP(hipMemcpyAsync(d + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
+    return {d, wi.none() ? nullptr : d + at_terms};
 }
 static Selected select_pass(gx_handle* h, const BatchView& v, const uint8_t* want, const WhereImage& where, uint64_t* counts, hipStream_t stream) {
     const uint32_t K = static_cast<uint32_t>(h->T.n_rules), bins = 2u * K + 2u;
@@ -1610,7 +1643,7 @@ static int select_lines_call(const char* fn, bool where, gx_handle* h, const voi
         const StagedLinesOut out = stage_lines_out(h, v, lo, host, s.lines, s.units);
         if (out.dev.offsets && n == 0) GX_HIP(hipMemsetAsync(out.dev.offsets, 0, v.off64 ? 8 : 4, stream));
         GX_HIP(launch_select_copy(out.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, s.w, stream));
-        if (host) deliver_lines_out(h, v, lo, out, s.lines, s.units, stream);
+        if (host) out.deliver(stream);
         // (no_sync: the copy pass still reads the workspace: whoever uses it next waits for this)
         if (o.no_sync) leave_pending(h->select_event, h->select_pending, stream);
         else GX_HIP(hipStreamSynchronize(stream));
@@ -1756,11 +1789,9 @@ static void stats_pass(gx_handle* h, const BatchView& v, const StatsImage& si, c
     std::vector<uint64_t> got(total + 2, 0);   // (the words, the bins, the status word)
     const bool run = n != 0 && n_measures != 0;
     if (run) {
-        uint8_t* d_img = static_cast<uint8_t*>(h->stats_image.get(si.bytes.size() + wi.bytes.size()));
-        GX_HIP(hipMemcpyAsync(d_img, si.bytes.data(), si.bytes.size(), hipMemcpyHostToDevice, stream));
-        if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + si.bytes.size(), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-        const StatsArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, static_cast<uint32_t>(si.bytes.size()),
-                          wi.none() ? nullptr : d_img + si.bytes.size(), static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins,
+        const DevImage img = upload_image(h->stats_image, si.bytes.data(), si.bytes.size(), nullptr, wi, stream);
+        const StatsArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), img.head, static_cast<uint32_t>(si.bytes.size()),
+                          img.terms, static_cast<uint32_t>(wi.bytes.size()), n_measures, si.n_bins,
                           (si.formats || wi.formats) ? 1u : 0u};
         void* ws = h->stats_ws.get(stats_workspace_bytes(n, n_measures, si.n_bins));
         GX_HIP(launch_capture_stats(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, ws, stream));
@@ -1892,9 +1923,73 @@ static void group_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_
     if (out.max_keys > GROUP_MAX_KEYS) throw GxError(GX_E_LIMIT, name + ": max_keys above 2^30");
 }
 
-// The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
-// totals and checks the capacities; then the emit.  out: the caller's, device or host
-// (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes (gx_text_group_lines).
+// gx_group_lines' build as group_pass and top_groups_pass run it, on the handle's buffers (under h->mu).  enqueue(): the wait for the
+// workspace's last user, the image, then the build, flags and scans.  ask(): the reads of what they left, enqueued last before the
+// caller's wait (a read into pageable memory holds the host up until the stream has come that far: what else the caller has to launch
+// goes first).  read(), behind that wait: the totals and the refusals that follow from them.  The object stays where it is from ask()
+// to the wait: the reads are into its members.
+struct GroupBuild {
+    GroupArgs a{};
+    GroupWs w{};
+    uint32_t n_slots = 0;
+    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
+    GroupBuild() = default;
+    GroupBuild(const GroupBuild&) = delete;
+    GroupBuild& operator=(const GroupBuild&) = delete;
+    void enqueue(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, uint64_t max_keys, hipStream_t stream) {
+        wait_pending(h->group_event, h->group_pending, stream);
+        n_slots = group_slots(max_keys);
+        const DevImage img = upload_image(h->group_image, &gi.head, sizeof(GroupHead), nullptr, wi, stream);
+        a = GroupArgs{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), img.head, img.terms,
+                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
+        w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(v.n)), v.n, n_slots, gi.values);
+        GX_HIP(launch_group_build(v.ids, v.fmt, v.row_units, static_cast<uint32_t>(h->T.n_rules), v.n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
+    }
+    void ask(uint64_t n, hipStream_t stream) {
+        GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&key_units, w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    }
+    int read(gx_group_totals* totals, const std::string& name) const {
+        if (got[2] & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be grouped");
+        totals->lines = got[0];
+        totals->unset = got[1];
+        totals->keyed = got[0] - got[1];
+        totals->n_keys = n_keys;
+        totals->key_units = key_units;
+        if (got[2] & 2u) {
+            totals->exact = 0;
+            totals->n_keys = static_cast<uint64_t>(n_slots) + 1u;
+            return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
+        }
+        return GX_OK;
+    }
+};
+
+// What every step of a group_pass call reads: the call's arguments and its build.
+struct GroupCtx {
+    gx_handle* h;
+    const BatchView& v;
+    const WhereImage& wi;
+    bool values, out64, host_out;   // values: a part has a value group
+    uint64_t max_keys;
+    const gx_group_totals* totals;
+    hipStream_t stream;
+    const std::string& name;
+    GroupBuild b;
+    uint32_t K() const { return static_cast<uint32_t>(h->T.n_rules); }
+};
+
+// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall) and, beside each,
+// what it keeps while the pass runs (…Run; call == nullptr: not that call), whose steps group_pass takes in this order:
+//   start()    the call's own totals as they are when nothing has run
+//   nothing()  no lines or no parts: the results that no kernel writes
+//   enqueue()  behind the build and before the ONE wait: the call's own passes and the reads of what they leave
+//   read()     behind the wait: the totals, the checks that they add up, the refusal of a full table
+//   fits()     the refusals of capacities that are smaller than the result
+//   emit()     behind launch_group_emit: the call's outputs, those of a host caller by way of the pass' twins
+// A step that a call does not need is not there.
+
 // gq (gx_group_quantiles; nullptr or n_q == 0: gx_group_lines as it is): before the read of the totals also the candidates' pairs, their
 // number and the OR and AND of their value keys (launch_gq_collect), read in the same wait; behind the emit the sort by the digit
 // plan made from them and the pick.
@@ -1906,6 +2001,37 @@ struct GroupQuant {
     QuantHead qh{};
 };
 static_assert(sizeof(gx_quantile_out) == sizeof(QuantOut), "the rows are copied as they are");
+struct GroupQuantRun {
+    const GroupQuant* call;
+    gx_quantile_out* rows;   // where the rows go; nullptr: none are wanted
+    bool sort;               // the candidates are collected: only where rows are wanted and a part has a value (else every population is empty)
+    GqWs qw{};
+    GqDev qd{};
+    uint8_t* d_qh = nullptr;   // the QuantHead on the device
+    explicit GroupQuantRun(const GroupQuant* gq) : call(gq), rows(gq && gq->qh.n_q ? gq->rows : nullptr), sort(rows && gq->ti.n_parts != 0) {}
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        const DevImage img = upload_image(c.h->gq_image, &call->ti, sizeof(TopHead), &call->qh, c.wi, c.stream);
+        d_qh = img.head + sizeof(TopHead);
+        const TopArgs ta{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(c.h->T.max_groups), img.head, img.terms,
+                         static_cast<uint32_t>(c.wi.bytes.size()), 0u, 0u, c.b.a.formats};
+        qw = gq_workspace(c.h->gq_ws.get(gq_workspace_bytes(v.n)), v.n);
+        GX_HIP(launch_gq_collect(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, ta, c.b.w.slot_of, qw, c.stream));
+        GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, c.stream));
+    }
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const uint32_t n_q = call->qh.n_q;
+        const size_t rows_bytes = static_cast<size_t>(c.b.n_keys) * n_q * sizeof(QuantOut);
+        if (!rows_bytes) return;
+        void* d_rows = twins.of(rows, rows_bytes);
+        if (sort && qd.candidates != 0) {
+            const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, c.b.n_keys, gq_sorts_all_digits());
+            GX_HIP(launch_gq_sort_pick(qw, qd.candidates, plan, c.b.w.keynum, c.b.w.n_slots, d_qh, n_q, c.b.n_keys, d_rows, c.stream));
+        } else {
+            GX_HIP(hipMemsetAsync(d_rows, 0, rows_bytes, c.stream));   // no key has a number
+        }
+    }
+};
 // bk (gx_lines_by_key; nullptr: gx_group_lines as it is): before the read of the totals also the kept flags, their scan and the kept
 // lines, units and keys (launch_by_key_kept), read in the same wait; behind the emit, which numbers the slots, the compaction, the sort
 // by key number, the bounds (launch_by_key_sort) and the copy (launch_partition_copy).
@@ -1916,6 +2042,62 @@ struct ByKeyCall {
     gx_by_key_totals* totals = nullptr;   // (its group member is the gx_group_totals the pass fills)
     bool per_line() const { return out.out_index || out.out_offsets || out.out_ids || out.out_caps; }
     bool any() const { return per_line() || out.out_bytes || out.key_out_lines || out.key_out_units; }
+};
+struct ByKeyRun {
+    const ByKeyCall* call;
+    ByKeyWs bw{};
+    ByKeyDev bd{};
+    StagedLinesOut lines;   // the kept lines' outputs (their twins are its own, and live as long as this object)
+    explicit operator bool() const { return call != nullptr; }
+    void start() const { *call->totals = gx_by_key_totals{}; }
+    void nothing(const GroupCtx& c) const {   // no kept lines: the one entry of the offsets and of the two prefixes
+        fill_out(call->out.out_offsets, 0, c.v.off64 ? 8 : 4, c.host_out, c.stream);
+        fill_out(call->out.key_out_lines, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.key_out_units, 0, 8, c.host_out, c.stream);
+    }
+    // the kept lines, their units and their keys: from the slots' line counts, which the build has left complete
+    void enqueue(const GroupCtx& c) {
+        const uint64_t n = c.v.n;
+        bw = by_key_workspace(c.h->by_key_ws.get(by_key_workspace_bytes(n)), n);
+        GX_HIP(launch_by_key_kept(n, c.v.offsets, c.v.off64 ? 1 : 0, c.b.w, call->min_lines, call->max_lines, bw, c.stream));
+        GX_HIP(hipMemcpyAsync(&bd, bw.head, sizeof(ByKeyDev), hipMemcpyDeviceToHost, c.stream));
+    }
+    void read(const GroupCtx& c) const {
+        if (bd.lines_out > c.v.n || bd.keys_kept > c.b.n_keys) throw GxError(GX_E_ARG, "internal: " + c.name + ": more kept lines or keys than there are");
+        call->totals->keys_kept = bd.keys_kept;
+        call->totals->lines_out = bd.lines_out;
+        call->totals->units_out = bd.units_out;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_by_key_out& b = call->out;
+        const std::string& name = c.name;
+        const size_t unit = c.v.wide ? 2 : 1;
+        if (call->per_line() && bd.lines_out > b.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
+        if (b.out_bytes && bd.units_out * unit > b.out_bytes_cap) return fail(GX_E_LIMIT, name + ": the kept text is larger than the capacity (see totals->units_out)");
+        if (b.out_offsets && !c.v.off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+        if ((b.key_out_lines || b.key_out_units) && c.b.n_keys > c.max_keys)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the kept lines by (key number, line) as a new batch, and the keys' bounds in it
+    void emit(const GroupCtx& c, HostTwins& twins) {
+        const gx_by_key_out& b = call->out;
+        const BatchView& v = c.v;
+        const uint64_t n = v.n, m = bd.lines_out, n_keys = c.b.n_keys;
+        lines = stage_lines_out(c.h, v, LinesOut{b.out_index, b.out_bytes, b.out_offsets, b.out_ids, b.out_caps}, c.host_out, m, bd.units_out);
+        uint64_t* kol = twins.of(b.key_out_lines, (n_keys + 1) * 8);
+        uint64_t* kou = twins.of(b.key_out_units, (n_keys + 1) * 8);
+        if (m == 0) {
+            if (lines.dev.offsets) GX_HIP(hipMemsetAsync(lines.dev.offsets, 0, v.off64 ? 8 : 4, c.stream));
+            if (kol) GX_HIP(hipMemsetAsync(kol, 0, (n_keys + 1) * 8, c.stream));
+            if (kou) GX_HIP(hipMemsetAsync(kou, 0, (n_keys + 1) * 8, c.stream));
+        } else {
+            PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
+            GX_HIP(launch_by_key_sort(n, m, n_keys, by_key_passes(n_keys, call->all_digits), c.b.w, bw, kol, kou, &pw.perm_sorted, c.stream));
+            pw.dst_off = bw.dst_off;
+            GX_HIP(launch_partition_copy(lines.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, m, pw, c.stream));
+        }
+    }
 };
 // pc (gx_group_pairs; nullptr: gx_group_lines as it is): behind the build the pair table's build, flags and scans (launch_pairs_build),
 // whose totals, pairs and units are read in the same wait; behind the emit, which numbers the key slots, the pair emit.
@@ -1928,6 +2110,69 @@ struct PairsCall {
     gx_pairs_out out{};
     bool per_pair() const { return out.pair_offsets || out.pair_key || out.pair_first_line || out.pair_lines; }
     bool any() const { return per_pair() || out.pair_units || out.key_pairs || out.line_pair; }
+};
+struct PairsRun {
+    const PairsCall* call;
+    PairsWs pw{};
+    PairsDev pd{};
+    uint64_t n_pairs = 0, pair_units = 0;
+    uint8_t* d_img = nullptr;   // the PairsHead on the device
+    explicit operator bool() const { return call != nullptr; }
+    void start() const {
+        *call->totals = gx_pairs_totals{};
+        call->totals->pairs_exact = 1;
+    }
+    void nothing(const GroupCtx& c) const {   // no pairs: the offsets' one entry and every line's "none"
+        fill_out(call->out.pair_offsets, 0, c.out64 ? 8 : 4, c.host_out, c.stream);
+        fill_out(call->out.line_pair, 0xFF, c.v.n * 4, c.host_out, c.stream);
+    }
+    // a second table keyed by (key slot, second text), behind the build that has left slot_of[] complete
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        const uint32_t p_slots = group_slots(call->out.max_pairs);
+        d_img = static_cast<uint8_t*>(c.h->pairs_image.get(sizeof(PairsHead)));
+        GX_HIP(hipMemcpyAsync(d_img, &call->head, sizeof(PairsHead), hipMemcpyHostToDevice, c.stream));
+        pw = pairs_workspace(c.h->pairs_table.get(pairs_table_bytes(p_slots, c.b.n_slots)), c.h->pairs_lines.get(pairs_lines_bytes(v.n)), v.n, p_slots, c.b.n_slots);
+        GX_HIP(launch_pairs_build(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, c.b.a, d_img, c.b.w, pw, c.stream));
+        GX_HIP(hipMemcpyAsync(&pd, pw.totals, sizeof(PairsDev), hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipMemcpyAsync(&n_pairs, pw.idx_off + v.n, 8, hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipMemcpyAsync(&pair_units, pw.dst_off + v.n, 8, hipMemcpyDeviceToHost, c.stream));
+    }
+    int read(const GroupCtx& c) const {
+        gx_pairs_totals& t = *call->totals;
+        if (pd.paired + pd.unpaired != c.totals->keyed) throw GxError(GX_E_ARG, "internal: " + c.name + ": paired and unpaired lines do not add up to the keyed lines");
+        t.paired = pd.paired;
+        t.unpaired = pd.unpaired;
+        t.n_pairs = n_pairs;
+        t.pair_units = pair_units;
+        if (pd.status & 2u) {
+            t.pairs_exact = 0;
+            t.n_pairs = static_cast<uint64_t>(pw.n_slots) + 1u;
+            return fail(GX_E_LIMIT, c.name + ": the pair table of " + std::to_string(pw.n_slots) + " slots is full; the number of lines is always a sufficient max_pairs");
+        }
+        return GX_OK;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_pairs_out& b = call->out;
+        const std::string& name = c.name;
+        if (call->per_pair() && n_pairs > b.max_pairs) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_pairs) + " pairs, max_pairs " + std::to_string(b.max_pairs));
+        if (b.pair_units && pair_units > b.pair_units_cap)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(pair_units) + " pair units, pair_units_cap " + std::to_string(b.pair_units_cap));
+        if (b.pair_offsets && !c.out64 && pair_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G pair units and more need offsets64");
+        if (b.key_pairs && c.b.n_keys > c.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the pairs' rows, their seconds, the keys' pairs and the lines' pair numbers
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const gx_pairs_out& b = call->out;
+        const BatchView& v = c.v;
+        const size_t unit = v.wide ? 2 : 1, off_w = c.out64 ? 8 : 4;
+        const uint64_t n = v.n, n_keys = c.b.n_keys;
+        const PairsOut po{twins.of(b.pair_units, pair_units * unit), twins.of(b.pair_offsets, (n_pairs + 1) * off_w), twins.of(b.pair_key, n_pairs * 4),
+                          twins.of(b.pair_first_line, n_pairs * 4), twins.of(b.pair_lines, n_pairs * 8), twins.of(b.key_pairs, n_keys * 8),
+                          twins.of(b.line_pair, n * 4), c.out64 ? 1 : 0};
+        GX_HIP(launch_pairs_emit(v.ids, v.fmt, v.row_units, c.K(), n, v.offsets, v.off64 ? 1 : 0, c.b.a, d_img, c.b.w, pw, po, n_pairs, pair_units, n_keys, c.stream));
+    }
 };
 // sc (gx_group_series; nullptr: gx_group_lines as it is): behind the build the bucket table's and the cell table's build, flags and scans
 // (launch_series_build), whose totals, buckets and cells are read in the same wait -- both sorts' digits follow from numbers known
@@ -1944,6 +2189,86 @@ struct SeriesCall {
     bool per_cell() const { return out.cell_key || out.cell_bucket || out.cell_first_line || out.cell_lines || out.cell_stats; }
     bool any() const { return per_cell() || out.bucket_number || out.key_cell_begin || out.line_cell; }
 };
+struct SeriesRun {
+    const SeriesCall* call;
+    SeriesWs sw{};
+    SeriesDev sd{};
+    uint64_t n_buckets = 0, n_cells = 0, min_word = 0, max_word = 0;
+    explicit operator bool() const { return call != nullptr; }
+    void start() const {
+        *call->totals = gx_series_totals{};
+        call->totals->cells_exact = 1;
+    }
+    void nothing(const GroupCtx& c) const {   // no cells: the bounds' one entry and every line's "none"
+        fill_out(call->out.key_cell_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.line_cell, 0xFF, c.v.n * 4, c.host_out, c.stream);
+    }
+    // a table of the buckets and a table of (key slot, bucket slot), behind the build that has left slot_of[]
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        const uint32_t s_slots = group_slots(call->out.max_cells);
+        const size_t at_table = (sizeof(SeriesHead) + 15) & ~static_cast<size_t>(15);
+        uint8_t* d_img = static_cast<uint8_t*>(c.h->series_table.get(at_table + series_table_bytes(s_slots, c.values)));
+        GX_HIP(hipMemcpyAsync(d_img, &call->head, sizeof(SeriesHead), hipMemcpyHostToDevice, c.stream));
+        sw = series_workspace(d_img + at_table, c.h->series_lines.get(series_lines_bytes(v.n)), s_slots, c.values);
+        GX_HIP(launch_series_build(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, c.b.a, d_img, c.b.a.formats != 0 || call->head.formats != 0, c.b.w, sw,
+                                   c.stream));
+        GX_HIP(hipMemcpyAsync(&sd, sw.totals, sizeof(SeriesDev), hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipMemcpyAsync(&n_buckets, sw.bbefore + s_slots, 8, hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipMemcpyAsync(&n_cells, sw.cbefore + s_slots, 8, hipMemcpyDeviceToHost, c.stream));
+    }
+    int read(const GroupCtx& c) {
+        gx_series_totals& t = *call->totals;
+        t.celled = sd.celled;
+        t.number_unset = sd.number_unset;
+        t.not_numbers = sd.not_numbers;
+        t.out_of_range = sd.out_of_range;
+        t.n_cells = n_cells;
+        t.n_buckets = n_buckets;
+        min_word = ~sd.min_inv;
+        max_word = sd.max_word;
+        if (n_buckets) {
+            t.first_bucket = bucket_number(min_word);
+            t.last_bucket = bucket_number(max_word);
+        }
+        if (sd.status & 2u) {
+            t.cells_exact = 0;
+            t.n_cells = static_cast<uint64_t>(sw.n_slots) + 1u;
+            return fail(GX_E_LIMIT, c.name + ": a series table of " + std::to_string(sw.n_slots) + " slots is full; the number of lines is always a sufficient max_cells");
+        }
+        if (sd.celled + sd.number_unset + sd.not_numbers + sd.out_of_range != c.totals->keyed)
+            throw GxError(GX_E_ARG, "internal: " + c.name + ": the classes of the keyed lines do not add up to them");
+        if (n_buckets > n_cells || n_cells > sd.celled) throw GxError(GX_E_ARG, "internal: " + c.name + ": more buckets than cells, or more cells than celled lines");
+        return GX_OK;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_series_out& b = call->out;
+        const std::string& name = c.name;
+        if (call->per_cell() && n_cells > b.max_cells) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_cells) + " cells, max_cells " + std::to_string(b.max_cells));
+        if (b.bucket_number && n_buckets > b.max_buckets)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(n_buckets) + " buckets, max_buckets " + std::to_string(b.max_buckets));
+        if (b.key_cell_begin && c.b.n_keys > c.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the axis, the cells' rows ordered by (key number, bucket), the keys' bounds and the lines' cells
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const gx_series_out& b = call->out;
+        const uint64_t n = c.v.n, n_keys = c.b.n_keys;
+        const SeriesOut so{twins.of(b.bucket_number, n_buckets * 8), twins.of(b.cell_key, n_cells * 4), twins.of(b.cell_bucket, n_cells * 4),
+                           twins.of(b.cell_first_line, n_cells * 4), twins.of(b.cell_lines, n_cells * 8),
+                           twins.of(reinterpret_cast<uint64_t*>(b.cell_stats), n_cells * 64), twins.of(b.key_cell_begin, (n_keys + 1) * 8),
+                           twins.of(b.line_cell, n * 4)};
+        if (n_cells == 0) {   // keyed lines, and none of them celled: every key's run is empty
+            if (so.key_cell_begin) GX_HIP(hipMemsetAsync(so.key_cell_begin, 0, (n_keys + 1) * 8, c.stream));
+            if (so.line_cell) GX_HIP(hipMemsetAsync(so.line_cell, 0xFF, n * 4, c.stream));
+        } else {
+            const uint32_t b_digits = call->all_digits ? BUCKET_MAX_DIGITS : bucket_digits(min_word, max_word);
+            const uint32_t c_digits = call->all_digits ? BUCKET_MAX_DIGITS : series_digits(n_keys, n_buckets);
+            const SeriesSortWs ssw = series_sort_workspace(c.h->series_sort.get(series_sort_workspace_bytes(n_cells)), n_cells);
+            GX_HIP(launch_series_emit(n, n_keys, n_buckets, n_cells, b_digits, c_digits, c.b.w, sw, ssw, so, c.stream));
+        }
+    }
+};
 // gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
 struct TopGroupsCall {
     uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
@@ -1958,355 +2283,73 @@ struct GroupExtras {
     std::optional<PairsCall> pairs;
     std::optional<SeriesCall> series;
 };
+// The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
+// totals and checks the capacities; then the emit.  out: the caller's, device or host
+// (host_out: staged, and a second wait delivers them).  counts: also the histogram of outcomes (gx_text_group_lines).
+// x: what the call adds to gx_group_lines, each in the steps that stand beside its arguments above.
 static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, const gx_group_out& out, bool out64, bool host_out,
                       gx_group_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name, const GroupExtras& x) {
-    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
-    const GroupQuant* gq = x.quant ? &*x.quant : nullptr;
-    const ByKeyCall* bk = x.by_key ? &*x.by_key : nullptr;
-    const PairsCall* pc = x.pairs && x.pairs->asked ? &*x.pairs : nullptr;
-    const SeriesCall* sc = x.series && x.series->asked ? &*x.series : nullptr;
+    GroupQuantRun gq(x.quant ? &*x.quant : nullptr);
+    ByKeyRun bk{x.by_key ? &*x.by_key : nullptr};
+    PairsRun pc{x.pairs && x.pairs->asked ? &*x.pairs : nullptr};
+    SeriesRun sc{x.series && x.series->asked ? &*x.series : nullptr};
+    GroupCtx c{h, v, wi, gi.values, out64, host_out, out.max_keys, totals, stream, name};
     const uint64_t n = v.n;
-    if (bk) *bk->totals = gx_by_key_totals{};
-    if (pc) {
-        *pc->totals = gx_pairs_totals{};
-        pc->totals->pairs_exact = 1;
-    }
-    if (sc) {
-        *sc->totals = gx_series_totals{};
-        sc->totals->cells_exact = 1;
-    }
+    if (bk) bk.start();
+    if (pc) pc.start();
+    if (sc) sc.start();
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
     totals->exact = 1;
-    const bool run = n != 0 && gi.head.n_parts != 0;
-    gx_quantile_out* q_rows = gq && gq->qh.n_q ? gq->rows : nullptr;
-    const uint32_t n_q = q_rows ? gq->qh.n_q : 0u;
-    const bool bk_out = bk && bk->any();
-    const bool pc_out = pc && pc->any();
-    const bool sc_out = sc && sc->any();
+    const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any();
     const bool any_out =
-        out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || q_rows || bk_out || pc_out || sc_out;
-    if (!run) {
+        out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || gq.rows || bk_out || pc_out || sc_out;
+    if (n == 0 || gi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
-        const uint64_t zero = 0;
-        if (out.key_offsets) {
-            if (host_out) memcpy(out.key_offsets, &zero, out64 ? 8 : 4);
-            else GX_HIP(hipMemsetAsync(out.key_offsets, 0, out64 ? 8 : 4, stream));
-        }
-        if (out.line_key && n) {
-            if (host_out) memset(out.line_key, 0xFF, n * 4);
-            else GX_HIP(hipMemsetAsync(out.line_key, 0xFF, n * 4, stream));
-        }
-        if (bk_out) {   // no kept lines: the one entry of the offsets and of the two prefixes
-            void* const one[3] = {bk->out.out_offsets, bk->out.key_out_lines, bk->out.key_out_units};
-            const size_t width[3] = {v.off64 ? size_t(8) : size_t(4), 8, 8};
-            for (int q = 0; q < 3; ++q) {
-                if (!one[q]) continue;
-                if (host_out) memcpy(one[q], &zero, width[q]);
-                else GX_HIP(hipMemsetAsync(one[q], 0, width[q], stream));
-            }
-        }
-        if (pc_out) {   // no pairs: the offsets' one entry and every line's "none"
-            if (pc->out.pair_offsets) {
-                if (host_out) memcpy(pc->out.pair_offsets, &zero, out64 ? 8 : 4);
-                else GX_HIP(hipMemsetAsync(pc->out.pair_offsets, 0, out64 ? 8 : 4, stream));
-            }
-            if (pc->out.line_pair && n) {
-                if (host_out) memset(pc->out.line_pair, 0xFF, n * 4);
-                else GX_HIP(hipMemsetAsync(pc->out.line_pair, 0xFF, n * 4, stream));
-            }
-        }
-        if (sc_out) {   // no cells: the bounds' one entry and every line's "none"
-            if (sc->out.key_cell_begin) {
-                if (host_out) memcpy(sc->out.key_cell_begin, &zero, 8);
-                else GX_HIP(hipMemsetAsync(sc->out.key_cell_begin, 0, 8, stream));
-            }
-            if (sc->out.line_cell && n) {
-                if (host_out) memset(sc->out.line_cell, 0xFF, n * 4);
-                else GX_HIP(hipMemsetAsync(sc->out.line_cell, 0xFF, n * 4, stream));
-            }
-        }
+        fill_out(out.key_offsets, 0, out64 ? 8 : 4, host_out, stream);
+        fill_out(out.line_key, 0xFF, n * 4, host_out, stream);
+        if (bk_out) bk.nothing(c);
+        if (pc_out) pc.nothing(c);
+        if (sc_out) sc.nothing(c);
         return GX_OK;
     }
-    wait_pending(h->group_event, h->group_pending, stream);
-    const uint32_t n_slots = group_slots(out.max_keys);
-    uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
-    GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
-    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
-                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
-    const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
-    GX_HIP(launch_group_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
-    // the quantiles' candidates: only where rows are wanted and a part has a value (else every population is empty)
-    const bool sort = q_rows && gq->ti.n_parts != 0;
-    GqWs qw{};
-    GqDev qd{};
-    uint8_t* d_qimg = nullptr;
-    if (sort) {
-        const size_t at_terms = sizeof(TopHead) + sizeof(QuantHead);
-        d_qimg = static_cast<uint8_t*>(h->gq_image.get(at_terms + wi.bytes.size()));
-        GX_HIP(hipMemcpyAsync(d_qimg, &gq->ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
-        GX_HIP(hipMemcpyAsync(d_qimg + sizeof(TopHead), &gq->qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
-        if (!wi.none()) GX_HIP(hipMemcpyAsync(d_qimg + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-        const TopArgs ta{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_qimg, wi.none() ? nullptr : d_qimg + at_terms,
-                         static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
-        qw = gq_workspace(h->gq_ws.get(gq_workspace_bytes(n)), n);
-        GX_HIP(launch_gq_collect(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, ta, w.slot_of, qw, stream));
-        GX_HIP(hipMemcpyAsync(&qd, qw.head, sizeof(GqDev), hipMemcpyDeviceToHost, stream));
-    }
-    // the kept lines of gx_lines_by_key, their units and their keys: from the slots' line counts, which the build has left complete
-    ByKeyWs bw{};
-    ByKeyDev bd{};
-    if (bk) {
-        bw = by_key_workspace(h->by_key_ws.get(by_key_workspace_bytes(n)), n);
-        GX_HIP(launch_by_key_kept(n, v.offsets, v.off64 ? 1 : 0, w, bk->min_lines, bk->max_lines, bw, stream));
-        GX_HIP(hipMemcpyAsync(&bd, bw.head, sizeof(ByKeyDev), hipMemcpyDeviceToHost, stream));
-    }
-    // the pairs of gx_group_pairs: a second table keyed by (key slot, second text), behind the build that has left slot_of[] complete
-    PairsWs pw{};
-    PairsDev pd{};
-    uint64_t n_pairs = 0, pair_units = 0;
-    uint8_t* d_pimg = nullptr;
-    if (pc) {
-        const uint32_t p_slots = group_slots(pc->out.max_pairs);
-        d_pimg = static_cast<uint8_t*>(h->pairs_image.get(sizeof(PairsHead)));
-        GX_HIP(hipMemcpyAsync(d_pimg, &pc->head, sizeof(PairsHead), hipMemcpyHostToDevice, stream));
-        pw = pairs_workspace(h->pairs_table.get(pairs_table_bytes(p_slots, n_slots)), h->pairs_lines.get(pairs_lines_bytes(n)), n, p_slots, n_slots);
-        GX_HIP(launch_pairs_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_pimg, w, pw, stream));
-        GX_HIP(hipMemcpyAsync(&pd, pw.totals, sizeof(PairsDev), hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&n_pairs, pw.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&pair_units, pw.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
-    }
-    // the cells of gx_group_series: a table of the buckets and a table of (key slot, bucket slot), behind the build that has left slot_of[]
-    SeriesWs sw{};
-    SeriesDev sd{};
-    uint64_t n_buckets = 0, n_cells = 0;
-    if (sc) {
-        const uint32_t s_slots = group_slots(sc->out.max_cells);
-        const size_t at_table = (sizeof(SeriesHead) + 15) & ~static_cast<size_t>(15);
-        uint8_t* d_simg = static_cast<uint8_t*>(h->series_table.get(at_table + series_table_bytes(s_slots, gi.values)));
-        GX_HIP(hipMemcpyAsync(d_simg, &sc->head, sizeof(SeriesHead), hipMemcpyHostToDevice, stream));
-        sw = series_workspace(d_simg + at_table, h->series_lines.get(series_lines_bytes(n)), s_slots, gi.values);
-        GX_HIP(launch_series_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_simg, a.formats != 0 || sc->head.formats != 0, w, sw, stream));
-        GX_HIP(hipMemcpyAsync(&sd, sw.totals, sizeof(SeriesDev), hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&n_buckets, sw.bbefore + s_slots, 8, hipMemcpyDeviceToHost, stream));
-        GX_HIP(hipMemcpyAsync(&n_cells, sw.cbefore + s_slots, 8, hipMemcpyDeviceToHost, stream));
-    }
-    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
-    GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
-    GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
-    GX_HIP(hipMemcpyAsync(&key_units, w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GroupBuild& b = c.b;
+    b.enqueue(h, v, gi, wi, out.max_keys, stream);
+    if (gq.sort) gq.enqueue(c);
+    if (bk) bk.enqueue(c);
+    if (pc) pc.enqueue(c);
+    if (sc) sc.enqueue(c);
+    b.ask(n, stream);
     GX_HIP(hipStreamSynchronize(stream));
-    if (got[2] & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be grouped");
-    totals->lines = got[0];
-    totals->unset = got[1];
-    totals->keyed = got[0] - got[1];
-    totals->n_keys = n_keys;
-    totals->key_units = key_units;
-    if (got[2] & 2u) {
-        totals->exact = 0;
-        totals->n_keys = static_cast<uint64_t>(n_slots) + 1u;
-        return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
-    }
-    if (bk) {
-        if (bd.lines_out > n || bd.keys_kept > n_keys) throw GxError(GX_E_ARG, "internal: " + name + ": more kept lines or keys than there are");
-        bk->totals->keys_kept = bd.keys_kept;
-        bk->totals->lines_out = bd.lines_out;
-        bk->totals->units_out = bd.units_out;
-    }
-    if (pc) {
-        if (pd.paired + pd.unpaired != totals->keyed) throw GxError(GX_E_ARG, "internal: " + name + ": paired and unpaired lines do not add up to the keyed lines");
-        pc->totals->paired = pd.paired;
-        pc->totals->unpaired = pd.unpaired;
-        pc->totals->n_pairs = n_pairs;
-        pc->totals->pair_units = pair_units;
-        if (pd.status & 2u) {
-            pc->totals->pairs_exact = 0;
-            pc->totals->n_pairs = static_cast<uint64_t>(pw.n_slots) + 1u;
-            return fail(GX_E_LIMIT, name + ": the pair table of " + std::to_string(pw.n_slots) + " slots is full; the number of lines is always a sufficient max_pairs");
-        }
-    }
-    uint64_t s_min_word = 0, s_max_word = 0;
-    if (sc) {
-        gx_series_totals& t = *sc->totals;
-        t.celled = sd.celled;
-        t.number_unset = sd.number_unset;
-        t.not_numbers = sd.not_numbers;
-        t.out_of_range = sd.out_of_range;
-        t.n_cells = n_cells;
-        t.n_buckets = n_buckets;
-        s_min_word = ~sd.min_inv;
-        s_max_word = sd.max_word;
-        if (n_buckets) {
-            t.first_bucket = bucket_number(s_min_word);
-            t.last_bucket = bucket_number(s_max_word);
-        }
-        if (sd.status & 2u) {
-            t.cells_exact = 0;
-            t.n_cells = static_cast<uint64_t>(sw.n_slots) + 1u;
-            return fail(GX_E_LIMIT, name + ": a series table of " + std::to_string(sw.n_slots) + " slots is full; the number of lines is always a sufficient max_cells");
-        }
-        if (sd.celled + sd.number_unset + sd.not_numbers + sd.out_of_range != totals->keyed)
-            throw GxError(GX_E_ARG, "internal: " + name + ": the classes of the keyed lines do not add up to them");
-        if (n_buckets > n_cells || n_cells > sd.celled) throw GxError(GX_E_ARG, "internal: " + name + ": more buckets than cells, or more cells than celled lines");
-    }
+    int rc = b.read(totals, name);
+    if (rc != GX_OK) return rc;
+    if (bk) bk.read(c);
+    if (pc && (rc = pc.read(c)) != GX_OK) return rc;
+    if (sc && (rc = sc.read(c)) != GX_OK) return rc;
     if (!any_out) return GX_OK;
-    const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || q_rows;
+    const uint64_t n_keys = b.n_keys, key_units = b.key_units;
+    const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || gq.rows;
     if (per_key && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
     if (out.key_units && key_units > out.key_units_cap)
         return fail(GX_E_LIMIT, name + ": " + std::to_string(key_units) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && key_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
+    if (bk_out && (rc = bk.fits(c)) != GX_OK) return rc;
+    if (pc_out && (rc = pc.fits(c)) != GX_OK) return rc;
+    if (sc_out && (rc = sc.fits(c)) != GX_OK) return rc;
     const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
-    if (bk_out) {
-        const gx_by_key_out& b = bk->out;
-        if (bk->per_line() && bd.lines_out > b.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
-        if (b.out_bytes && bd.units_out * unit > b.out_bytes_cap) return fail(GX_E_LIMIT, name + ": the kept text is larger than the capacity (see totals->units_out)");
-        if (b.out_offsets && !v.off64 && bd.units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
-        if ((b.key_out_lines || b.key_out_units) && n_keys > out.max_keys)
-            return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
-    }
-    if (pc_out) {
-        const gx_pairs_out& b = pc->out;
-        if (pc->per_pair() && n_pairs > b.max_pairs) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_pairs) + " pairs, max_pairs " + std::to_string(b.max_pairs));
-        if (b.pair_units && pair_units > b.pair_units_cap)
-            return fail(GX_E_LIMIT, name + ": " + std::to_string(pair_units) + " pair units, pair_units_cap " + std::to_string(b.pair_units_cap));
-        if (b.pair_offsets && !out64 && pair_units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G pair units and more need offsets64");
-        if (b.key_pairs && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
-    }
-    if (sc_out) {
-        const gx_series_out& b = sc->out;
-        if (sc->per_cell() && n_cells > b.max_cells) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_cells) + " cells, max_cells " + std::to_string(b.max_cells));
-        if (b.bucket_number && n_buckets > b.max_buckets)
-            return fail(GX_E_LIMIT, name + ": " + std::to_string(n_buckets) + " buckets, max_buckets " + std::to_string(b.max_buckets));
-        if (b.key_cell_begin && n_keys > out.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_keys) + " keys, max_keys " + std::to_string(out.max_keys));
-    }
-    GroupOut o{out.key_units, out.key_offsets, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_key, out64 ? 1 : 0};
-    DevMem<> d_units, d_offs, d_first, d_lines, d_stats, d_lkey, d_rows;
-    void* rows = q_rows;
-    const size_t rows_bytes = static_cast<size_t>(n_keys) * n_q * sizeof(QuantOut);
-    if (host_out && rows_bytes) { d_rows = dev_alloc(rows_bytes); rows = d_rows.get(); }
+    HostTwins twins(host_out);
+    const GroupOut o{twins.of(out.key_units, key_units * unit), twins.of(out.key_offsets, (n_keys + 1) * off_w), twins.of(out.key_first_line, n_keys * 4),
+                     twins.of(out.key_lines, n_keys * 8), twins.of(reinterpret_cast<uint64_t*>(out.key_stats), n_keys * 64), twins.of(out.line_key, n * 4),
+                     out64 ? 1 : 0};
+    GX_HIP(launch_group_emit(v.ids, v.fmt, v.row_units, c.K(), n, v.offsets, v.off64 ? 1 : 0, b.a, b.w, o, n_keys, key_units, stream));
+    if (bk_out) bk.emit(c, twins);
+    if (pc_out) pc.emit(c, twins);
+    if (sc_out) sc.emit(c, twins);
+    if (gq.rows) gq.emit(c, twins);
     if (host_out) {
-        if (out.key_units) { d_units = dev_alloc(key_units * unit); o.key_units = d_units.get(); }
-        if (out.key_offsets) { d_offs = dev_alloc((n_keys + 1) * off_w); o.key_offsets = d_offs.get(); }
-        if (out.key_first_line) { d_first = dev_alloc(n_keys * 4); o.key_first_line = static_cast<uint32_t*>(d_first.get()); }
-        if (out.key_lines) { d_lines = dev_alloc(n_keys * 8); o.key_lines = static_cast<uint64_t*>(d_lines.get()); }
-        if (out.key_stats) { d_stats = dev_alloc(n_keys * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
-        if (out.line_key) { d_lkey = dev_alloc(n * 4); o.line_key = static_cast<uint32_t*>(d_lkey.get()); }
-    }
-    GX_HIP(launch_group_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, o, n_keys, key_units, stream));
-    // gx_lines_by_key: the kept lines by (key number, line) as a new batch, and the keys' bounds in it
-    LinesOut bo{};
-    StagedLinesOut so;
-    DevMem<> b_kol, b_kou;
-    uint64_t *kol = nullptr, *kou = nullptr;
-    const uint64_t m = bd.lines_out;
-    if (bk_out) {
-        const gx_by_key_out& b = bk->out;
-        bo = LinesOut{b.out_index, b.out_bytes, b.out_offsets, b.out_ids, b.out_caps};
-        so = stage_lines_out(h, v, bo, host_out, m, bd.units_out);
-        kol = b.key_out_lines; kou = b.key_out_units;
-        if (host_out) {
-            if (kol) { b_kol = dev_alloc((n_keys + 1) * 8); kol = static_cast<uint64_t*>(b_kol.get()); }
-            if (kou) { b_kou = dev_alloc((n_keys + 1) * 8); kou = static_cast<uint64_t*>(b_kou.get()); }
-        }
-        if (m == 0) {
-            if (so.dev.offsets) GX_HIP(hipMemsetAsync(so.dev.offsets, 0, v.off64 ? 8 : 4, stream));
-            if (kol) GX_HIP(hipMemsetAsync(kol, 0, (n_keys + 1) * 8, stream));
-            if (kou) GX_HIP(hipMemsetAsync(kou, 0, (n_keys + 1) * 8, stream));
-        } else {
-            PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
-            GX_HIP(launch_by_key_sort(n, m, n_keys, by_key_passes(n_keys, bk->all_digits), w, bw, kol, kou, &pw.perm_sorted, stream));
-            pw.dst_off = bw.dst_off;
-            GX_HIP(launch_partition_copy(so.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, m, pw, stream));
-        }
-    }
-    // gx_group_pairs: the pairs' rows, their seconds, the keys' pairs and the lines' pair numbers
-    PairsOut po{};
-    DevMem<> p_units, p_offs, p_key, p_first, p_lines, p_kp, p_lp;
-    if (pc_out) {
-        const gx_pairs_out& b = pc->out;
-        po = PairsOut{b.pair_units, b.pair_offsets, b.pair_key, b.pair_first_line, b.pair_lines, b.key_pairs, b.line_pair, out64 ? 1 : 0};
-        if (host_out) {
-            if (b.pair_units) { p_units = dev_alloc(pair_units * unit); po.pair_units = p_units.get(); }
-            if (b.pair_offsets) { p_offs = dev_alloc((n_pairs + 1) * off_w); po.pair_offsets = p_offs.get(); }
-            if (b.pair_key) { p_key = dev_alloc(n_pairs * 4); po.pair_key = static_cast<uint32_t*>(p_key.get()); }
-            if (b.pair_first_line) { p_first = dev_alloc(n_pairs * 4); po.pair_first_line = static_cast<uint32_t*>(p_first.get()); }
-            if (b.pair_lines) { p_lines = dev_alloc(n_pairs * 8); po.pair_lines = static_cast<uint64_t*>(p_lines.get()); }
-            if (b.key_pairs) { p_kp = dev_alloc(n_keys * 8); po.key_pairs = static_cast<uint64_t*>(p_kp.get()); }
-            if (b.line_pair) { p_lp = dev_alloc(n * 4); po.line_pair = static_cast<uint32_t*>(p_lp.get()); }
-        }
-        GX_HIP(launch_pairs_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_pimg, w, pw, po, n_pairs, pair_units, n_keys, stream));
-    }
-    // gx_group_series: the axis, the cells' rows ordered by (key number, bucket), the keys' bounds and the lines' cells
-    SeriesOut so2{};
-    DevMem<> s_num, s_key, s_bkt, s_first, s_lines, s_stats, s_begin, s_lc;
-    if (sc_out) {
-        const gx_series_out& b = sc->out;
-        so2 = SeriesOut{b.bucket_number, b.cell_key, b.cell_bucket, b.cell_first_line, b.cell_lines, reinterpret_cast<uint64_t*>(b.cell_stats), b.key_cell_begin, b.line_cell};
-        if (host_out) {
-            if (b.bucket_number && n_buckets) { s_num = dev_alloc(n_buckets * 8); so2.bucket_number = static_cast<int64_t*>(s_num.get()); }
-            if (b.cell_key && n_cells) { s_key = dev_alloc(n_cells * 4); so2.cell_key = static_cast<uint32_t*>(s_key.get()); }
-            if (b.cell_bucket && n_cells) { s_bkt = dev_alloc(n_cells * 4); so2.cell_bucket = static_cast<uint32_t*>(s_bkt.get()); }
-            if (b.cell_first_line && n_cells) { s_first = dev_alloc(n_cells * 4); so2.cell_first_line = static_cast<uint32_t*>(s_first.get()); }
-            if (b.cell_lines && n_cells) { s_lines = dev_alloc(n_cells * 8); so2.cell_lines = static_cast<uint64_t*>(s_lines.get()); }
-            if (b.cell_stats && n_cells) { s_stats = dev_alloc(n_cells * 64); so2.cell_stats = static_cast<uint64_t*>(s_stats.get()); }
-            if (b.key_cell_begin) { s_begin = dev_alloc((n_keys + 1) * 8); so2.key_cell_begin = static_cast<uint64_t*>(s_begin.get()); }
-            if (b.line_cell) { s_lc = dev_alloc(n * 4); so2.line_cell = static_cast<uint32_t*>(s_lc.get()); }
-        }
-        if (n_cells == 0) {   // keyed lines, and none of them celled: every key's run is empty
-            if (so2.key_cell_begin) GX_HIP(hipMemsetAsync(so2.key_cell_begin, 0, (n_keys + 1) * 8, stream));
-            if (so2.line_cell) GX_HIP(hipMemsetAsync(so2.line_cell, 0xFF, n * 4, stream));
-        } else {
-            const uint32_t b_digits = sc->all_digits ? BUCKET_MAX_DIGITS : bucket_digits(s_min_word, s_max_word);
-            const uint32_t c_digits = sc->all_digits ? BUCKET_MAX_DIGITS : series_digits(n_keys, n_buckets);
-            const SeriesSortWs ssw = series_sort_workspace(h->series_sort.get(series_sort_workspace_bytes(n_cells)), n_cells);
-            GX_HIP(launch_series_emit(n, n_keys, n_buckets, n_cells, b_digits, c_digits, w, sw, ssw, so2, stream));
-        }
-    }
-    if (rows_bytes) {
-        if (sort && qd.candidates != 0) {
-            const GqPlan plan = gq_plan(qd.value_or ^ qd.value_and, n_keys, gq_sorts_all_digits());
-            GX_HIP(launch_gq_sort_pick(qw, qd.candidates, plan, w.keynum, w.n_slots, d_qimg + sizeof(TopHead), n_q, n_keys, rows, stream));
-        } else {
-            GX_HIP(hipMemsetAsync(rows, 0, rows_bytes, stream));   // no key has a number
-        }
-    }
-    if (host_out) {
-        if (rows_bytes) GX_HIP(hipMemcpyAsync(q_rows, rows, rows_bytes, hipMemcpyDeviceToHost, stream));
-        if (out.key_units && key_units) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, key_units * unit, hipMemcpyDeviceToHost, stream));
-        if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_keys + 1) * off_w, hipMemcpyDeviceToHost, stream));
-        if (out.key_first_line && n_keys) GX_HIP(hipMemcpyAsync(out.key_first_line, o.key_first_line, n_keys * 4, hipMemcpyDeviceToHost, stream));
-        if (out.key_lines && n_keys) GX_HIP(hipMemcpyAsync(out.key_lines, o.key_lines, n_keys * 8, hipMemcpyDeviceToHost, stream));
-        if (out.key_stats && n_keys) GX_HIP(hipMemcpyAsync(out.key_stats, o.key_stats, n_keys * 64, hipMemcpyDeviceToHost, stream));
-        if (out.line_key) GX_HIP(hipMemcpyAsync(out.line_key, o.line_key, n * 4, hipMemcpyDeviceToHost, stream));
-        if (bk_out) {
-            const gx_by_key_out& b = bk->out;
-            deliver_lines_out(h, v, bo, so, m, bd.units_out, stream);
-            if (b.key_out_lines) GX_HIP(hipMemcpyAsync(b.key_out_lines, kol, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
-            if (b.key_out_units) GX_HIP(hipMemcpyAsync(b.key_out_units, kou, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
-        }
-        if (pc_out) {
-            const gx_pairs_out& b = pc->out;
-            if (b.pair_units && pair_units) GX_HIP(hipMemcpyAsync(b.pair_units, po.pair_units, pair_units * unit, hipMemcpyDeviceToHost, stream));
-            if (b.pair_offsets) GX_HIP(hipMemcpyAsync(b.pair_offsets, po.pair_offsets, (n_pairs + 1) * off_w, hipMemcpyDeviceToHost, stream));
-            if (b.pair_key && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_key, po.pair_key, n_pairs * 4, hipMemcpyDeviceToHost, stream));
-            if (b.pair_first_line && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_first_line, po.pair_first_line, n_pairs * 4, hipMemcpyDeviceToHost, stream));
-            if (b.pair_lines && n_pairs) GX_HIP(hipMemcpyAsync(b.pair_lines, po.pair_lines, n_pairs * 8, hipMemcpyDeviceToHost, stream));
-            if (b.key_pairs && n_keys) GX_HIP(hipMemcpyAsync(b.key_pairs, po.key_pairs, n_keys * 8, hipMemcpyDeviceToHost, stream));
-            if (b.line_pair) GX_HIP(hipMemcpyAsync(b.line_pair, po.line_pair, n * 4, hipMemcpyDeviceToHost, stream));
-        }
-        if (sc_out) {
-            const gx_series_out& b = sc->out;
-            if (b.bucket_number && n_buckets) GX_HIP(hipMemcpyAsync(b.bucket_number, so2.bucket_number, n_buckets * 8, hipMemcpyDeviceToHost, stream));
-            if (b.cell_key && n_cells) GX_HIP(hipMemcpyAsync(b.cell_key, so2.cell_key, n_cells * 4, hipMemcpyDeviceToHost, stream));
-            if (b.cell_bucket && n_cells) GX_HIP(hipMemcpyAsync(b.cell_bucket, so2.cell_bucket, n_cells * 4, hipMemcpyDeviceToHost, stream));
-            if (b.cell_first_line && n_cells) GX_HIP(hipMemcpyAsync(b.cell_first_line, so2.cell_first_line, n_cells * 4, hipMemcpyDeviceToHost, stream));
-            if (b.cell_lines && n_cells) GX_HIP(hipMemcpyAsync(b.cell_lines, so2.cell_lines, n_cells * 8, hipMemcpyDeviceToHost, stream));
-            if (b.cell_stats && n_cells) GX_HIP(hipMemcpyAsync(b.cell_stats, so2.cell_stats, n_cells * 64, hipMemcpyDeviceToHost, stream));
-            if (b.key_cell_begin) GX_HIP(hipMemcpyAsync(b.key_cell_begin, so2.key_cell_begin, (n_keys + 1) * 8, hipMemcpyDeviceToHost, stream));
-            if (b.line_cell) GX_HIP(hipMemcpyAsync(b.line_cell, so2.line_cell, n * 4, hipMemcpyDeviceToHost, stream));
-        }
+        twins.deliver(stream);
+        if (bk_out) bk.lines.deliver(stream);
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         leave_pending(h->group_event, h->group_pending, stream);
@@ -2401,49 +2444,27 @@ static int top_groups_pass(gx_handle* h, const BatchView& v, const GroupImage& g
     totals->group.exact = 1;
     const gx_top_groups_out& out = tg.out;
     const bool any_out = out.key_units || out.key_offsets || out.key_number || out.key_first_line || out.key_lines || out.key_stats || out.line_rank;
-    const uint64_t zero = 0;
     // no keys: the offsets' one entry and every line's "none"
     auto deliver_nothing = [&]() -> int {
-        if (out.key_offsets) {
-            if (host_out) memcpy(out.key_offsets, &zero, out64 ? 8 : 4);
-            else GX_HIP(hipMemsetAsync(out.key_offsets, 0, out64 ? 8 : 4, stream));
-        }
-        if (out.line_rank && n) {
-            if (host_out) memset(out.line_rank, 0xFF, n * 4);
-            else GX_HIP(hipMemsetAsync(out.line_rank, 0xFF, n * 4, stream));
-        }
+        fill_out(out.key_offsets, 0, out64 ? 8 : 4, host_out, stream);
+        fill_out(out.line_rank, 0xFF, n * 4, host_out, stream);
         return GX_OK;
     };
     if (n == 0 || gi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
         return deliver_nothing();
     }
-    wait_pending(h->group_event, h->group_pending, stream);
-    const uint32_t n_slots = group_slots(max_keys);
-    uint8_t* d_img = static_cast<uint8_t*>(h->group_image.get(sizeof(GroupHead) + wi.bytes.size()));
-    GX_HIP(hipMemcpyAsync(d_img, &gi.head, sizeof(GroupHead), hipMemcpyHostToDevice, stream));
-    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(GroupHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(GroupHead),
-                      static_cast<uint32_t>(wi.bytes.size()), gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
-    const GroupWs w = group_workspace(h->group_table.get(group_table_bytes(n_slots, gi.values)), h->group_lines.get(group_lines_bytes(n)), n, n_slots, gi.values);
-    GX_HIP(launch_group_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
     // the first wait: gx_group_lines' totals
-    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_keys = 0, key_units = 0;
-    GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
-    GX_HIP(hipMemcpyAsync(&n_keys, w.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
-    GX_HIP(hipMemcpyAsync(&key_units, w.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    GroupBuild b;
+    b.enqueue(h, v, gi, wi, max_keys, stream);
+    b.ask(n, stream);
     GX_HIP(hipStreamSynchronize(stream));
-    if (got[2] & 1u) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be grouped");
-    totals->group.lines = got[0];
-    totals->group.unset = got[1];
-    totals->group.keyed = got[0] - got[1];
-    totals->group.n_keys = n_keys;
-    totals->group.key_units = key_units;
-    if (got[2] & 2u) {
-        totals->group.exact = 0;
-        totals->group.n_keys = static_cast<uint64_t>(n_slots) + 1u;
-        return fail(GX_E_LIMIT, name + ": the table of " + std::to_string(n_slots) + " slots is full; the number of lines is always a sufficient max_keys");
-    }
+    const int rc = b.read(&totals->group, name);
+    if (rc != GX_OK) return rc;
+    const GroupArgs& a = b.a;
+    const GroupWs& w = b.w;
+    const uint32_t n_slots = b.n_slots;
+    const uint64_t n_keys = b.n_keys;
     if (n_keys == 0) return deliver_nothing();
     if (n_keys > n) throw GxError(GX_E_ARG, "internal: " + name + ": more keys than lines");
     // the keys pass, the select, the order; the second wait: what the select found
@@ -2473,27 +2494,13 @@ static int top_groups_pass(gx_handle* h, const BatchView& v, const GroupImage& g
         return fail(GX_E_LIMIT, name + ": " + std::to_string(units_top) + " key units, key_units_cap " + std::to_string(out.key_units_cap));
     if (out.key_offsets && !out64 && units_top > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G key units and more need offsets64");
     const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
-    TopGroupsOut o{out.key_units, out.key_offsets, out.key_number, out.key_first_line, out.key_lines, reinterpret_cast<uint64_t*>(out.key_stats), out.line_rank,
-                   out64 ? 1 : 0};
-    DevMem<> d_units, d_offs, d_num, d_first, d_lines, d_stats, d_lrank;
-    if (host_out) {
-        if (out.key_units) { d_units = dev_alloc(units_top * unit); o.key_units = d_units.get(); }
-        if (out.key_offsets) { d_offs = dev_alloc((n_top + 1) * off_w); o.key_offsets = d_offs.get(); }
-        if (out.key_number) { d_num = dev_alloc(n_top * 4); o.key_number = static_cast<uint32_t*>(d_num.get()); }
-        if (out.key_first_line) { d_first = dev_alloc(n_top * 4); o.key_first_line = static_cast<uint32_t*>(d_first.get()); }
-        if (out.key_lines) { d_lines = dev_alloc(n_top * 8); o.key_lines = static_cast<uint64_t*>(d_lines.get()); }
-        if (out.key_stats) { d_stats = dev_alloc(n_top * 64); o.key_stats = static_cast<uint64_t*>(d_stats.get()); }
-        if (out.line_rank) { d_lrank = dev_alloc(n * 4); o.line_rank = static_cast<uint32_t*>(d_lrank.get()); }
-    }
+    HostTwins twins(host_out);
+    const TopGroupsOut o{twins.of(out.key_units, units_top * unit), twins.of(out.key_offsets, (n_top + 1) * off_w), twins.of(out.key_number, n_top * 4),
+                         twins.of(out.key_first_line, n_top * 4), twins.of(out.key_lines, n_top * 8), twins.of(reinterpret_cast<uint64_t*>(out.key_stats), n_top * 64),
+                         twins.of(out.line_rank, n * 4), out64 ? 1 : 0};
     GX_HIP(launch_top_groups_emit(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, tw, o, n_top, units_top, stream));
     if (host_out) {
-        if (out.key_units && units_top) GX_HIP(hipMemcpyAsync(out.key_units, o.key_units, units_top * unit, hipMemcpyDeviceToHost, stream));
-        if (out.key_offsets) GX_HIP(hipMemcpyAsync(out.key_offsets, o.key_offsets, (n_top + 1) * off_w, hipMemcpyDeviceToHost, stream));
-        if (out.key_number && n_top) GX_HIP(hipMemcpyAsync(out.key_number, o.key_number, n_top * 4, hipMemcpyDeviceToHost, stream));
-        if (out.key_first_line && n_top) GX_HIP(hipMemcpyAsync(out.key_first_line, o.key_first_line, n_top * 4, hipMemcpyDeviceToHost, stream));
-        if (out.key_lines && n_top) GX_HIP(hipMemcpyAsync(out.key_lines, o.key_lines, n_top * 8, hipMemcpyDeviceToHost, stream));
-        if (out.key_stats && n_top) GX_HIP(hipMemcpyAsync(out.key_stats, o.key_stats, n_top * 64, hipMemcpyDeviceToHost, stream));
-        if (out.line_rank) GX_HIP(hipMemcpyAsync(out.line_rank, o.line_rank, n * 4, hipMemcpyDeviceToHost, stream));
+        twins.deliver(stream);
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         leave_pending(h->group_event, h->group_pending, stream);
@@ -2809,22 +2816,15 @@ static int bucket_pass(gx_handle* h, const BatchView& v, const BucketImage& bi, 
     totals->exact = 1;
     const bool per_bucket = out.bucket_number || out.bucket_first_line || out.bucket_lines || out.bucket_stats;
     const bool any_out = per_bucket || out.line_bucket;
-    auto no_line_has_one = [&]() {
-        if (!out.line_bucket || !n) return;
-        if (host_out) memset(out.line_bucket, 0xFF, n * 4);
-        else GX_HIP(hipMemsetAsync(out.line_bucket, 0xFF, n * 4, stream));
-    };
     if (n == 0 || bi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
-        no_line_has_one();
+        fill_out(out.line_bucket, 0xFF, n * 4, host_out, stream);   // no line has a bucket
         return GX_OK;
     }
     wait_pending(h->bucket_event, h->bucket_pending, stream);
     const uint32_t n_slots = group_slots(out.max_buckets);
-    uint8_t* d_img = static_cast<uint8_t*>(h->bucket_image.get(sizeof(BucketHead) + wi.bytes.size()));
-    GX_HIP(hipMemcpyAsync(d_img, &bi.head, sizeof(BucketHead), hipMemcpyHostToDevice, stream));
-    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(BucketHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), d_img, wi.none() ? nullptr : d_img + sizeof(BucketHead),
+    const DevImage img = upload_image(h->bucket_image, &bi.head, sizeof(BucketHead), nullptr, wi, stream);
+    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), img.head, img.terms,
                       static_cast<uint32_t>(wi.bytes.size()), bi.values ? 1u : 0u, (bi.head.formats || wi.formats) ? 1u : 0u};
     const BucketWs w = bucket_workspace(h->bucket_table.get(bucket_table_bytes(n_slots, bi.values)), h->bucket_lines.get(bucket_lines_bytes(n)), n, n_slots, bi.values);
     GX_HIP(launch_bucket_build(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
@@ -2855,27 +2855,17 @@ static int bucket_pass(gx_handle* h, const BatchView& v, const BucketImage& bi, 
     if (per_bucket && n_buckets > out.max_buckets)
         return fail(GX_E_LIMIT, name + ": " + std::to_string(n_buckets) + " buckets, max_buckets " + std::to_string(out.max_buckets));
     if (n_buckets == 0) {   // lines, and none of them bucketed
-        no_line_has_one();
+        fill_out(out.line_bucket, 0xFF, n * 4, host_out, stream);
         return GX_OK;
     }
-    BucketOut o{out.bucket_number, out.bucket_first_line, out.bucket_lines, reinterpret_cast<uint64_t*>(out.bucket_stats), out.line_bucket};
-    DevMem<> d_num, d_first, d_lines, d_stats, d_lb;
-    if (host_out) {
-        if (out.bucket_number) { d_num = dev_alloc(n_buckets * 8); o.bucket_number = static_cast<int64_t*>(d_num.get()); }
-        if (out.bucket_first_line) { d_first = dev_alloc(n_buckets * 4); o.bucket_first_line = static_cast<uint32_t*>(d_first.get()); }
-        if (out.bucket_lines) { d_lines = dev_alloc(n_buckets * 8); o.bucket_lines = static_cast<uint64_t*>(d_lines.get()); }
-        if (out.bucket_stats) { d_stats = dev_alloc(n_buckets * 64); o.bucket_stats = static_cast<uint64_t*>(d_stats.get()); }
-        if (out.line_bucket) { d_lb = dev_alloc(n * 4); o.line_bucket = static_cast<uint32_t*>(d_lb.get()); }
-    }
+    HostTwins twins(host_out);
+    const BucketOut o{twins.of(out.bucket_number, n_buckets * 8), twins.of(out.bucket_first_line, n_buckets * 4), twins.of(out.bucket_lines, n_buckets * 8),
+                      twins.of(reinterpret_cast<uint64_t*>(out.bucket_stats), n_buckets * 64), twins.of(out.line_bucket, n * 4)};
     const uint32_t n_digits = (bi.head.flags & BUCKET_ALL_DIGITS) ? BUCKET_MAX_DIGITS : bucket_digits(min_word, max_word);
     const BucketSortWs sw = bucket_sort_workspace(h->bucket_sort.get(bucket_sort_workspace_bytes(n_buckets)), n_buckets);
     GX_HIP(launch_bucket_emit(n, n_buckets, n_digits, w, sw, o, stream));
     if (host_out) {
-        if (out.bucket_number) GX_HIP(hipMemcpyAsync(out.bucket_number, o.bucket_number, n_buckets * 8, hipMemcpyDeviceToHost, stream));
-        if (out.bucket_first_line) GX_HIP(hipMemcpyAsync(out.bucket_first_line, o.bucket_first_line, n_buckets * 4, hipMemcpyDeviceToHost, stream));
-        if (out.bucket_lines) GX_HIP(hipMemcpyAsync(out.bucket_lines, o.bucket_lines, n_buckets * 8, hipMemcpyDeviceToHost, stream));
-        if (out.bucket_stats) GX_HIP(hipMemcpyAsync(out.bucket_stats, o.bucket_stats, n_buckets * 64, hipMemcpyDeviceToHost, stream));
-        if (out.line_bucket) GX_HIP(hipMemcpyAsync(out.line_bucket, o.line_bucket, n * 4, hipMemcpyDeviceToHost, stream));
+        twins.deliver(stream);
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         leave_pending(h->bucket_event, h->bucket_pending, stream);
@@ -3038,20 +3028,14 @@ static int top_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const W
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_top_totals{};
     const size_t unit = v.wide ? 2 : 1, off_w = v.off64 ? 8 : 4;
-    const uint64_t zero = 0;
     if (n == 0 || ti.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
-        if (out.lines.offsets) {   // no lines: the offsets' one entry
-            if (host_out) memcpy(out.lines.offsets, &zero, off_w);
-            else GX_HIP(hipMemsetAsync(out.lines.offsets, 0, off_w, stream));
-        }
+        fill_out(out.lines.offsets, 0, off_w, host_out, stream);   // no lines: the offsets' one entry
         return GX_OK;
     }
     wait_pending(h->top_event, h->top_pending, stream);
-    uint8_t* d_img = static_cast<uint8_t*>(h->top_image.get(sizeof(TopHead) + wi.bytes.size()));
-    GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
-    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + sizeof(TopHead),
+    const DevImage img = upload_image(h->top_image, &ti, sizeof(TopHead), nullptr, wi, stream);
+    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), img.head, img.terms,
                     static_cast<uint32_t>(wi.bytes.size()), ti.smallest, n_wanted, (ti.formats || wi.formats) ? 1u : 0u};
     const TopWs w = top_workspace(h->top_ws.get(top_workspace_bytes(n)), n);
     GX_HIP(launch_top_select(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, w, stream));
@@ -3090,7 +3074,7 @@ static int top_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const W
     GX_HIP(launch_partition_copy(so.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, n_top, pw, stream));
     if (out.values && n_top) GX_HIP(hipMemcpyAsync(out.values, w.values, n_top * 8, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
     if (host_out) {
-        deliver_lines_out(h, v, out.lines, so, n_top, units, stream);
+        so.deliver(stream);
         GX_HIP(hipStreamSynchronize(stream));
     } else {
         leave_pending(h->top_event, h->top_pending, stream);
@@ -3196,15 +3180,11 @@ static int quant_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const
         return GX_OK;
     }
     // the image: the parts, the quantiles, the terms
-    const size_t at_terms = sizeof(TopHead) + sizeof(QuantHead);
-    uint8_t* d_img = static_cast<uint8_t*>(h->quant_image.get(at_terms + wi.bytes.size()));
-    GX_HIP(hipMemcpyAsync(d_img, &ti, sizeof(TopHead), hipMemcpyHostToDevice, stream));
-    GX_HIP(hipMemcpyAsync(d_img + sizeof(TopHead), &qh, sizeof(QuantHead), hipMemcpyHostToDevice, stream));
-    if (!wi.none()) GX_HIP(hipMemcpyAsync(d_img + at_terms, wi.bytes.data(), wi.bytes.size(), hipMemcpyHostToDevice, stream));
-    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), d_img, wi.none() ? nullptr : d_img + at_terms,
+    const DevImage img = upload_image(h->quant_image, &ti, sizeof(TopHead), &qh, wi, stream);
+    const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), img.head, img.terms,
                     static_cast<uint32_t>(wi.bytes.size()), 0u, 0u, (ti.formats || wi.formats) ? 1u : 0u};
     const QuantWs w = quant_workspace(h->quant_ws.get(quant_workspace_bytes(n)), n);
-    GX_HIP(launch_quantiles(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, d_img + sizeof(TopHead), qh.n_q, w, stream));
+    GX_HIP(launch_quantiles(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, img.head + sizeof(TopHead), qh.n_q, w, stream));
     struct { uint32_t counts[TOP_COUNTS]; QuantOut out[QUANT_MAX]; } got{};
     static_assert(sizeof(got) == offsetof(QuantDev, sel), "the head's first words");
     GX_HIP(hipMemcpyAsync(&got, w.head, sizeof(got), hipMemcpyDeviceToHost, stream));
@@ -3338,7 +3318,7 @@ int gx_partition_lines(gx_handle* h, const void* bytes, const void* offsets, uin
         const StagedLinesOut out = stage_lines_out(h, v, lo, host, s.lines, s.units);
         if (out.dev.offsets && s.lines == 0) GX_HIP(hipMemsetAsync(out.dev.offsets, 0, v.off64 ? 8 : 4, stream));
         GX_HIP(launch_partition_copy(out.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, s.lines, s.w, stream));
-        if (host) deliver_lines_out(h, v, lo, out, s.lines, s.units, stream);
+        if (host) out.deliver(stream);
         // (no_sync: the copy pass still reads the workspace: whoever uses it next waits for this)
         if (o.no_sync) leave_pending(h->select_event, h->select_pending, stream);
         else GX_HIP(hipStreamSynchronize(stream));
