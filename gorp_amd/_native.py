@@ -57,6 +57,7 @@ SYMBOLS = [
     "gx_group_pairs", "gx_text_group_pairs",
     "gx_bucket_lines", "gx_text_bucket_lines",
     "gx_group_series", "gx_text_group_series",
+    "gx_sort_lines", "gx_text_sort_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
 
@@ -113,6 +114,7 @@ GX_TOP_GROUPS_SMALLEST = 2
 GX_TOP_GROUPS_MAX = 4096
 GX_BY_KEY_ALL_DIGITS = 2
 GX_BUCKET_ALL_DIGITS = 2
+GX_SORT_DESCENDING, GX_SORT_CARRY, GX_SORT_REST_LAST, GX_SORT_ALL_DIGITS = 1, 2, 4, 8
 
 
 class gx_group_part(C.Structure):
@@ -167,6 +169,17 @@ class gx_by_key_out(C.Structure):
 
 class gx_by_key_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("keys_kept", C.c_uint64), ("lines_out", C.c_uint64), ("units_out", C.c_uint64)]
+
+
+class gx_sort_out(C.Structure):
+    _fields_ = [("out_index", C.c_void_p), ("out_values", C.c_void_p), ("out_class", C.c_void_p), ("out_bytes", C.c_void_p), ("out_offsets", C.c_void_p),
+                ("out_ids", C.c_void_p), ("out_caps", C.c_void_p), ("cap_lines", C.c_uint64), ("out_bytes_cap", C.c_uint64)]
+
+
+class gx_sort_totals(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("carried", C.c_uint64), ("rest", C.c_uint64),
+                ("lines_out", C.c_uint64), ("units_out", C.c_uint64), ("first_value", C.c_int64), ("last_value", C.c_int64), ("n_passes", C.c_uint32),
+                ("already_ordered", C.c_uint32)]
 
 
 class gx_series_out(C.Structure):
@@ -440,6 +453,13 @@ def lib():
                                        C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.c_void_p, C.POINTER(C.c_uint64),
                                        C.POINTER(gx_batch_opts)]
     L.gx_text_bucket_lines.restype = C.c_int
+    L.gx_sort_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_top_part), C.c_uint32, C.POINTER(gx_where_term),
+                                C.c_uint32, C.c_uint32, C.POINTER(gx_sort_out), C.POINTER(gx_sort_totals), C.POINTER(gx_batch_opts)]
+    L.gx_sort_lines.restype = C.c_int
+    L.gx_text_sort_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_top_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gx_sort_totals), C.c_void_p,
+                                     C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_sort_lines.restype = C.c_int
     L.gx_partition_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]

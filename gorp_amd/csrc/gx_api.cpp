@@ -31,6 +31,7 @@
 #include "gx_images.hpp"
 #include "gx_number.hpp"
 #include "gx_slots.hpp"
+#include "gx_sort.hpp"
 #include "gx_stats.hpp"
 #include "gx_quantile.hpp"
 #include "gx_top.hpp"
@@ -347,6 +348,12 @@ struct gx_handle {
     GrowBuf top_image, top_ws;
     Event top_event;
     bool top_pending = false;
+    // gx_sort_lines: its parts and terms on the device (TopHead; WhereHead behind it) and the passes' workspace (gx_sort.hip: SortWs).
+    // Used under `mu`.  With device pointers the sort, the finish and the copy are left running on the caller's stream and still read
+    // the workspace: the next call's stream waits for sort_event first.
+    GrowBuf sort_image, sort_ws;
+    Event sort_event;
+    bool sort_pending = false;
     // gx_capture_quantiles: its parts, quantiles and terms on the device (TopHead, QuantHead, WhereHead) and the passes' workspace
     // (gx_quantile.hip: QuantWs).  Used under `mu`; every call that uses them ends with a stream synchronisation.
     GrowBuf quant_image, quant_ws;
@@ -3138,6 +3145,177 @@ int gx_text_top_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx
         if (h->top_pending) {
             GX_HIP(hipStreamSynchronize(stream));
             h->top_pending = false;
+        }
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
+    });
+}
+
+// where gx_sort_lines' delivered lines go: the caller's pointers, device or host (host_out: staged, and a second wait delivers them)
+struct SortOut {
+    LinesOut lines;
+    int64_t* values;
+    uint8_t* cls;
+    uint64_t cap_lines, bytes_cap;
+    bool per_line() const { return lines.per_line() || values || cls; }
+    bool any() const { return lines.any() || values || cls; }
+};
+
+// what both sort calls refuse before they look at the batch: gx_top_lines' refusals of parts and terms, in its order
+static void sort_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                          uint32_t flags, bool wide, const gx_sort_totals* totals, const std::string& name, TopHead* ti, WhereImage* wi) {
+    if (!totals) throw GxError(GX_E_ARG, name + ": totals is NULL");
+    if (flags & ~SORT_FLAGS) throw GxError(GX_E_ARG, name + ": unknown flag bits");
+    *ti = top_image(h, parts, n_parts, (flags & GX_SORT_DESCENDING) ? GX_TOP_SMALLEST : 0u, name);   // (key ascending: top_key(value, descending))
+    if (o.utf8 == 2) throw GxError(GX_E_ARG, name + ": gx_batch_opts.utf8 = 1 (values are read in the units the offsets count)");
+    *wi = where_image(h, terms, n_terms, wide, name);
+    if (o.no_sync) throw GxError(GX_E_ARG, name + ": no_sync: the totals are host values");
+}
+
+// The passes on the handle's workspace (under h->mu): keys, scan, compaction, entries and totals; ONE synchronisation of the stream,
+// where the host reads the totals, plans the digits and checks the capacities; then the sort, the finish, the scan of the lengths and
+// the copy (launch_partition_copy).  counts: also the histogram of outcomes (gx_text_sort_lines).
+static int sort_pass(gx_handle* h, const BatchView& v, const TopHead& ti, const WhereImage& wi, uint32_t flags, const SortOut& out, bool host_out,
+                     gx_sort_totals* totals, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+    const uint64_t n = v.n;
+    if (counts) counts_beside(h, v, counts, stream);
+    *totals = gx_sort_totals{};
+    totals->already_ordered = 1;
+    const size_t unit = v.wide ? 2 : 1, off_w = v.off64 ? 8 : 4;
+    if (n == 0) {
+        GX_HIP(hipStreamSynchronize(stream));
+        fill_out(out.lines.offsets, 0, off_w, host_out, stream);   // no lines: the offsets' one entry
+        return GX_OK;
+    }
+    wait_pending(h->sort_event, h->sort_pending, stream);
+    const SortWs w = sort_workspace(h->sort_ws.get(sort_workspace_bytes(n)), n);
+    if (ti.n_parts) {
+        const DevImage img = upload_image(h->sort_image, &ti, sizeof(TopHead), nullptr, wi, stream);
+        const TopArgs a{v.data, v.wide ? 1 : 0, v.caps, static_cast<uint32_t>(slots), img.head, img.terms,
+                        static_cast<uint32_t>(wi.bytes.size()), ti.smallest, 0u, (ti.formats || wi.formats) ? 1u : 0u};
+        GX_HIP(launch_sort_entries(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, &a, flags, w, stream));
+    } else {
+        GX_HIP(launch_sort_entries(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, nullptr, flags, w, stream));   // (no part: every line is a rest line)
+    }
+    SortDev sd{};
+    GX_HIP(hipMemcpyAsync(&sd, w.head, sizeof(SortDev), hipMemcpyDeviceToHost, stream));
+    GX_HIP(hipStreamSynchronize(stream));
+    if (sd.counts[TOP_C_STATUS]) throw GxError(GX_E_LIMIT, "a line of 4 G code units or more cannot be sorted");
+    if (sd.entries > n || sd.rest > n - sd.entries || sd.carried > sd.entries) throw GxError(GX_E_ARG, "internal: " + name + ": more entries or rest lines than there are");
+    const bool descending = (flags & GX_SORT_DESCENDING) != 0u;
+    const uint64_t m = sd.entries, lines_out = m + ((flags & GX_SORT_REST_LAST) ? sd.rest : 0u), units = sd.units_out;
+    const SortPlan plan = sort_plan(sd.key_or, sd.key_and, m, (flags & GX_SORT_ALL_DIGITS) != 0u);
+    totals->numbers = sd.counts[TOP_C_NUMBERS];
+    totals->unset = sd.counts[TOP_C_UNSET];
+    totals->not_numbers = sd.counts[TOP_C_NOT_NUMBERS];
+    totals->lines = totals->numbers + totals->unset + totals->not_numbers;
+    totals->carried = sd.carried;
+    totals->rest = sd.rest;
+    totals->lines_out = lines_out;
+    totals->units_out = units;
+    if (m) {
+        totals->first_value = top_value(sd.key_min, descending);
+        totals->last_value = top_value(sd.key_max, descending);
+    }
+    totals->n_passes = plan.n_passes;
+    totals->already_ordered = sd.unordered ? 0u : 1u;
+    if (!out.any()) return GX_OK;   // size query
+    if (out.per_line() && lines_out > out.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
+    if (out.lines.bytes && units * unit > out.bytes_cap) return fail(GX_E_LIMIT, name + ": the delivered text is larger than the capacity (see totals->units_out)");
+    if (out.lines.offsets && !v.off64 && units > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+    if (lines_out == 0) {
+        fill_out(out.lines.offsets, 0, off_w, host_out, stream);
+        return GX_OK;
+    }
+    StagedLinesOut so = stage_lines_out(h, v, out.lines, host_out, lines_out, units);
+    int64_t* d_values = so.twins.of(out.values, lines_out * 8);
+    uint8_t* d_cls = so.twins.of(out.cls, lines_out);
+    PartWs pw{};   // (the copy pass reads the permutation and the output offsets alone)
+    GX_HIP(launch_sort_emit(n, m, lines_out, plan, flags, w, d_values, d_cls, &pw.perm_sorted, stream));
+    pw.dst_off = w.dst_off;
+    GX_HIP(launch_partition_copy(so.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, lines_out, pw, stream));
+    if (host_out) {
+        so.deliver(stream);
+        GX_HIP(hipStreamSynchronize(stream));
+    } else {
+        leave_pending(h->sort_event, h->sort_pending, stream);
+    }
+    return GX_OK;
+}
+
+int gx_sort_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_top_part* parts,
+                  uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_sort_out* out, gx_sort_totals* totals,
+                  const gx_batch_opts* opts) {
+    const std::string name = "gx_sort_lines";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        TopHead ti;
+        WhereImage wi;
+        sort_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, totals, name, &ti, &wi);
+        gx_sort_out so = out ? *out : gx_sort_out{};
+        if (so.out_caps && fmt != ROWS_DENSE) return fail(GX_E_ARG, name + ": out_caps on compact rows (out_ids holds whole rows)");
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (n > SORT_MAX_LINES) return fail(GX_E_LIMIT, name + ": the sort's places are 30 bits; split batches of more than 2^30 lines");
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "sorted");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (so.out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
+        if (!slots) so.out_caps = nullptr;
+        {
+            const uint64_t ow = o.offsets64 ? 8 : 4, un = o.utf16 ? 2 : 1, idr = static_cast<uint64_t>(row_units) * row_unit_bytes(fmt);
+            const uint64_t in_units = o.device_pointers ? (n ? 1u : 0u) : HostOffsets{offsets, o.offsets64 != 0, n}[n];
+            const uint64_t cap = std::min<uint64_t>(so.cap_lines, n);   // (no more than n lines leave, whatever the capacity says: no product wraps)
+            const std::pair<const void*, uint64_t> outs[7] = {{so.out_index, cap * 4}, {so.out_values, cap * 8}, {so.out_class, cap}, {so.out_bytes, so.out_bytes_cap},
+                                                              {so.out_offsets, (cap + 1) * ow}, {so.out_ids, cap * idr}, {so.out_caps, cap * slots * 4}};
+            const std::pair<const void*, uint64_t> ins[4] = {{bytes, in_units * un}, {offsets, (n + 1) * ow}, {ids, n * idr},
+                                                             {fmt == ROWS_DENSE ? caps : nullptr, n * slots * 4}};
+            by_key_overlaps(outs, 7, ins, 4, name);
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        const SortOut to{{so.out_index, so.out_bytes, so.out_offsets, so.out_ids, so.out_caps}, so.out_values, so.out_class, so.cap_lines, so.out_bytes_cap};
+        return sort_pass(h, in.v, ti, wi, flags, to, !o.device_pointers, totals, nullptr, stream, name);
+    });
+}
+
+int gx_text_sort_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                       uint32_t flags, uint8_t* out, uint64_t out_cap, void* out_offsets, uint32_t* out_index, int64_t* out_values, uint8_t* out_class,
+                       gx_sort_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    const std::string name = "gx_text_sort_lines";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        TopHead ti;
+        WhereImage wi;
+        sort_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, totals, name, &ti, &wi);
+        const std::pair<const void*, uint64_t> outs[5] = {{out, out_cap}, {out_offsets, 4}, {out_index, 4}, {out_values, 8}, {out_class, 1}};
+        const std::pair<const void*, uint64_t> ins[1] = {{text, size}};
+        by_key_overlaps(outs, 5, ins, 1, name);
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        if (tb.v.n > SORT_MAX_LINES) return fail(GX_E_LIMIT, name + ": the sort's places are 30 bits; split texts of more than 2^30 lines");
+        // (cap_lines: sized by the size query -- the header)
+        const SortOut to{{out_index, out, out_offsets, nullptr, nullptr}, out_values, out_class, ~0ull, out_cap};
+        const int rc = sort_pass(h, tb.v, ti, wi, flags, to, !o.device_pointers, totals, counts, stream, name);
+        // The passes behind the wait read the offsets that text_lines left in the handle's scratch buffers, which the next whole-file
+        // call on any stream overwrites: like every gx_text_* call this one returns with its work done.
+        if (h->sort_pending) {
+            GX_HIP(hipStreamSynchronize(stream));
+            h->sort_pending = false;
         }
         if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
         return rc;

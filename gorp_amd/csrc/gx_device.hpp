@@ -621,6 +621,38 @@ hipError_t launch_by_key_kept(uint64_t n, const void* offsets, int offsets64, co
 hipError_t launch_by_key_sort(uint64_t n, uint64_t m, uint64_t n_keys, uint32_t n_passes, const GroupWs& g, const ByKeyWs& w, uint64_t* key_out_lines,
                               uint64_t* key_out_units, uint32_t** perm, hipStream_t stream);
 
+// A whole batch ordered by a number its lines captured (gx_sort.hip; the rule: gx_sort.hpp).  The lines that count, their class and the
+// key are gx_top_lines': TopArgs (n_wanted is not looked at).  The passes' device workspace, cut out of one allocation of
+// sort_workspace_bytes(n) bytes:
+struct SortPlan;
+struct SortWs {
+    uint8_t* head;                // SortDev (gx_sort.hpp): the class counts, the entries' OR / AND / min / max, the totals
+    uint64_t* sums;               // the entries pass's workgroups' words
+    uint32_t* slab;               // the keys pass's counts, then a digit's counts, bin-major
+    uint64_t* bases;              // ... scanned
+    uint64_t* block_sums;         // the scans'
+    uint64_t* keys;               // [n] a stamped line's key
+    uint64_t* ckeys;              // [n] the stamped keys, dense, in line order
+    uint64_t* word[2];            // [n] the pairs' keys, ping and pong (word[1] is keys)
+    uint64_t* before;             // [n + 1] the stamped lines before line i; [n]: all of them
+    uint64_t* dst_off;            // [lines_out + 1] code units before output line j (the same memory as `before`, behind the entries pass)
+    uint32_t* line[2];            // [n] the pairs' line numbers, likewise; the rest lines behind the entries in both
+    uint32_t* len;                // [n] every line's code units
+    uint32_t* plen;               // [lines_out] the same in output order
+    uint8_t* cand;                // [n] the line is stamped
+    uint8_t* cls;                 // [n] SORT_STAMPED / SORT_CARRIED / SORT_REST
+    size_t bytes;
+};
+SortWs sort_workspace(void* ws, uint64_t n);
+size_t sort_workspace_bytes(uint64_t n);
+// 0 < n <= 2^30; a == nullptr: no parts, every line is a rest line; flags: GX_SORT_*.  Behind it the host reads SortDev at w.head.
+hipError_t launch_sort_entries(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const TopArgs* a,
+                               uint32_t flags, const SortWs& w, hipStream_t stream);
+// Behind the host's read: m entries, 0 < lines_out <= n lines that leave; out_values / out_class: lines_out each on the device, optional.
+// Behind it the copy is launch_partition_copy with *perm and w.dst_off.
+hipError_t launch_sort_emit(uint64_t n, uint64_t m, uint64_t lines_out, const SortPlan& plan, uint32_t flags, const SortWs& w, int64_t* out_values,
+                            uint8_t* out_class, uint32_t** perm, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

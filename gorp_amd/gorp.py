@@ -2300,6 +2300,128 @@ class Gorp:
         k = totals["n_top"]
         return index[:k], values[:k], out[:size].tobytes(), totals, counts, n_lines
 
+    # -- a whole batch ordered by a number its lines captured (gx_sort_lines / gx_text_sort_lines) ---------------------------------
+    @staticmethod
+    def _sort_totals(t):
+        return {"lines": t.lines, "numbers": t.numbers, "unset": t.unset, "not_numbers": t.not_numbers, "carried": t.carried, "rest": t.rest,
+                "lines_out": t.lines_out, "units_out": t.units_out, "first_value": t.first_value, "last_value": t.last_value, "n_passes": t.n_passes,
+                "already_ordered": bool(t.already_ordered)}
+
+    @staticmethod
+    def _sort_flags(descending, carry, rest, all_digits):
+        if rest not in ("drop", "last"):
+            raise ValueError('rest: "drop" or "last"')
+        return ((N.GX_SORT_DESCENDING if descending else 0) | (N.GX_SORT_CARRY if carry else 0) | (N.GX_SORT_REST_LAST if rest == "last" else 0)
+                | (N.GX_SORT_ALL_DIGITS if all_digits else 0))
+
+    def sort_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, by, descending=False, carry=False, rest="drop", where=None, out_index_ptr=None,
+                          out_values_ptr=None, out_class_ptr=None, out_data_ptr=None, out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0,
+                          out_bytes_cap=0, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, all_digits=False):
+        """gx_sort_lines on device pointers (ints); the outputs are the caller's buffers, each optional (none at all: the size query).
+        Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says what the outputs need (lines_out,
+        units_out); every other error raises."""
+        parts = self.top_parts(by)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_sort_out(out_index_ptr, out_values_ptr, out_class_ptr, out_data_ptr, out_offsets_ptr, out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap)
+        totals = N.gx_sort_totals()
+        rc = N.lib().gx_sort_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n,
+                                   self._sort_flags(descending, carry, rest, all_digits), C.byref(out), C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.lines_out):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._sort_totals(totals)
+
+    def sort_lines(self, data, offsets, ids, rows, by, descending=False, carry=False, rest="drop", where=None, utf8=None, all_digits=False):
+        """gx_sort_lines on host buffers: the batch ordered by (the number a line captured, input line) -- two hosts' logs as one
+        timeline.  by: Gorp.top_parts or its input, one (extraction, value extractor) per extraction that takes part; where: terms as
+        capture_stats takes them; data / offsets / ids / rows and utf8 as capture_stats takes them.  carry: a line without a number of
+        its own travels with the nearest earlier line that has one (stack traces kept with their line); rest: the remaining lines are
+        dropped ("drop") or follow in input order ("last").  Returns a dict: index (input line of every output line, uint32), values
+        (int64; a carried line's is its header's, a rest line's 0), line_class (uint8: 0 own number, 1 carried, 2 rest), data / offsets
+        (the lines as a CSR batch), ids and caps (their ids or whole rows; caps None for compact rows or without rows) and totals."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.top_parts(by)
+        n = len(offsets) - 1
+        total = int(offsets[n] - offsets[0]) if n else 0
+        # no ordering is larger than its input
+        index = np.zeros(max(1, n), np.uint32)
+        values = np.zeros(max(1, n), np.int64)
+        line_class = np.zeros(max(1, n), np.uint8)
+        out = np.zeros(max(1, total), data.dtype)
+        out_off = np.zeros(n + 1, offsets.dtype)
+        out_ids = np.zeros((max(1, n),) + ids.shape[1:], ids.dtype)
+        out_caps = None if caps is None else np.zeros((max(1, n), 2 * self.max_groups), np.int32)
+        rc, totals = self.sort_lines_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), parts, descending, carry, rest, where,
+                                            out_index_ptr=index.ctypes.data, out_values_ptr=values.ctypes.data, out_class_ptr=line_class.ctypes.data,
+                                            out_data_ptr=out.ctypes.data, out_offsets_ptr=out_off.ctypes.data, out_ids_ptr=out_ids.ctypes.data,
+                                            out_caps_ptr=None if out_caps is None else out_caps.ctypes.data, cap_lines=n, out_bytes_cap=total * data.itemsize,
+                                            offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8),
+                                            all_digits=all_digits)
+        if rc != N.GX_OK:
+            raise GorpError(rc, N.last_error())
+        m = totals["lines_out"]
+        return {"index": index[:m], "values": values[:m], "line_class": line_class[:m], "data": out[:totals["units_out"]], "offsets": out_off[:m + 1],
+                "ids": out_ids[:m], "caps": None if out_caps is None else out_caps[:m], "totals": totals}
+
+    def text_sort_lines_device(self, text_ptr, size, by, descending=False, carry=False, rest="drop", where=None, out_ptr=None, out_cap=0, out_offsets_ptr=None,
+                               out_index_ptr=None, out_values_ptr=None, out_class_ptr=None, stream=None, device_pointers=True, utf8=False, all_digits=False):
+        """gx_text_sort_lines on a device buffer (int); out_offsets (uint32), out_index, out_values and out_class are sized by the size
+        query (all outputs None).  Returns (rc, totals, counts, n_lines); rc as sort_lines_device returns it."""
+        parts = self.top_parts(by)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        totals = N.gx_sort_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_sort_lines(self._h.ptr, text_ptr, size, parts.array, parts.n, terms.array, terms.n, self._sort_flags(descending, carry, rest, all_digits),
+                                        out_ptr, out_cap, out_offsets_ptr, out_index_ptr, out_values_ptr, out_class_ptr, C.byref(totals), counts.ctypes.data,
+                                        C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.lines_out):
+            _check(rc)
+        return rc, self._sort_totals(totals), counts, nl.value
+
+    def text_sort_lines(self, text, by, descending=False, carry=False, rest="drop", where=None, utf8=False, all_digits=False):
+        """gx_text_sort_lines on a host buffer: raw text -> lines -> extraction -> sort_lines.  Returns (the dict sort_lines returns
+        without ids and caps: data holds the delivered lines' original bytes, each with its terminator, offsets (uint32) delimits them,
+        index holds line numbers of the text; counts uint64[2K + 2] of outcomes; n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.top_parts(by)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        index = np.zeros(cap_lines, np.uint32)
+        values = np.zeros(cap_lines, np.int64)
+        line_class = np.zeros(cap_lines, np.uint8)
+        out = np.zeros(max(1, raw.size), np.uint8)
+        out_off = np.zeros(cap_lines + 1, np.uint32)
+        rc, totals, counts, n_lines = self.text_sort_lines_device(raw.ctypes.data if raw.size else None, raw.size, parts, descending, carry, rest, where,
+                                                                  out.ctypes.data, raw.size, out_off.ctypes.data, index.ctypes.data, values.ctypes.data,
+                                                                  line_class.ctypes.data, device_pointers=False, utf8=utf8, all_digits=all_digits)
+        if rc != N.GX_OK:
+            raise GorpError(rc, N.last_error())
+        m = totals["lines_out"]
+        return ({"index": index[:m], "values": values[:m], "line_class": line_class[:m], "data": out[:totals["units_out"]], "offsets": out_off[:m + 1],
+                 "totals": totals}, counts, n_lines)
+
     # -- percentiles of a number the lines captured (gx_capture_quantiles / gx_text_capture_quantiles) -------------------------------
     @staticmethod
     def quantile_asks(quantiles):

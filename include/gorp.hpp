@@ -734,6 +734,80 @@ public:
                                      out.bytes.size(), &size, &out.totals, counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
         });
     }
+    // A whole batch ordered by a number its lines captured (gx_sort_lines): the caller's results.sort(Comparator.comparingLong(r ->
+    // Instant.parse(r.asMap().get("ts")).toEpochMilli())) (README.md:26,63-79) -- two hosts' logs as one timeline.  The lines leave by
+    // (value, input line), descending by (value descending, input line); with carry a line without a number of its own travels with the
+    // nearest earlier line that has one (stack traces kept with their line); with restLast the remaining lines follow in input order,
+    // else they are dropped.  index: the input line of every output line; values: their numbers (a carried line's is its header's, a rest
+    // line's 0); lineClass: 0 own number, 1 carried, 2 rest; bytes / offsets: the lines as a batch; ids / caps: their match ids and
+    // capture rows (textSortLines: empty; index holds lines of the text, bytes the lines' original bytes cut at offsets).
+    struct Sorted {
+        std::vector<uint32_t> index;
+        std::vector<int64_t> values;
+        std::vector<uint8_t> lineClass;
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> offsets;
+        std::vector<int32_t> ids, caps;
+        gx_sort_totals totals{};
+    };
+    static uint32_t sortFlags(bool descending, bool carry, bool restLast) {
+        return (descending ? GX_SORT_DESCENDING : 0u) | (carry ? GX_SORT_CARRY : 0u) | (restLast ? GX_SORT_REST_LAST : 0u);
+    }
+    // of the batch's lines (host buffers, Latin-1, 32-bit offsets, int32 match ids and dense capture rows; the C call takes every other layout)
+    Sorted sortLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const TopParts& parts,
+                     bool descending = false, bool carry = false, bool restLast = false, const Where* where = nullptr) const {
+        const std::vector<gx_top_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size()), flags = sortFlags(descending, carry, restLast);
+        const size_t slots = 2 * static_cast<size_t>(gx_max_groups(h_));
+        Sorted r;
+        int rc = gx_sort_lines(h_, bytes, offsets, n, match_id, caps, p.data(), np, terms.data(), nt, flags, nullptr, &r.totals, nullptr);   // the size query
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t m = static_cast<size_t>(r.totals.lines_out), units = static_cast<size_t>(r.totals.units_out);
+        r.index.assign(m, 0);
+        r.values.assign(m, 0);
+        r.lineClass.assign(m, 0);
+        r.bytes.assign(units + 1, 0);
+        r.offsets.assign(m + 1, 0);
+        r.ids.assign(m, 0);
+        r.caps.assign(m * slots + 1, 0);
+        gx_sort_out out{};
+        out.out_index = r.index.data(); out.out_values = r.values.data(); out.out_class = r.lineClass.data(); out.out_bytes = r.bytes.data();
+        out.out_offsets = r.offsets.data(); out.out_ids = r.ids.data(); out.out_caps = caps && slots ? r.caps.data() : nullptr;
+        out.cap_lines = m; out.out_bytes_cap = units;
+        rc = gx_sort_lines(h_, bytes, offsets, n, match_id, caps, p.data(), np, terms.data(), nt, flags, &out, &r.totals, nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        r.bytes.resize(units);
+        r.caps.resize(caps ? m * slots : 0);
+        return r;
+    }
+    // Whole files: raw text in, the same ordering out (gx_text_sort_lines).  counts (optional): lines per outcome index.
+    Sorted textSortLines(const std::string& text, const TopParts& parts, bool descending = false, bool carry = false, bool restLast = false,
+                         const Where* where = nullptr, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        const std::vector<gx_top_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size()), flags = sortFlags(descending, carry, restLast);
+        const uint8_t* t = reinterpret_cast<const uint8_t*>(text.data());
+        Sorted r;
+        int rc = gx_text_sort_lines(h_, t, text.size(), p.data(), np, terms.data(), nt, flags, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &r.totals, nullptr, nullptr,
+                                    utf8 ? &o : nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        const size_t m = static_cast<size_t>(r.totals.lines_out), units = static_cast<size_t>(r.totals.units_out);
+        r.index.assign(m, 0);
+        r.values.assign(m, 0);
+        r.lineClass.assign(m, 0);
+        r.bytes.assign(units + 1, 0);
+        r.offsets.assign(m + 1, 0);
+        rc = gx_text_sort_lines(h_, t, text.size(), p.data(), np, terms.data(), nt, flags, r.bytes.data(), units, r.offsets.data(), r.index.data(), r.values.data(),
+                                r.lineClass.data(), &r.totals, counts ? counts->data() : nullptr, nLines, utf8 ? &o : nullptr);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        r.bytes.resize(units);
+        return r;
+    }
     // Percentiles of a number the lines captured (gx_capture_quantiles): nearest-rank quantiles num / den of the numbers that the parts
     // name -- sorted(values)[ceil(q * numbers) - 1], in integers alone -- each with its rank and the counts of the numbers below and
     // equal to it.  captureQuantiles(..., topParts().of("GetRequest", "timeTakenInMsec"), {{50, 100}, {95, 100}, {99, 100}}) is the

@@ -825,6 +825,93 @@ int gx_text_lines_by_key(gx_handle* h, const uint8_t* text, uint64_t size, const
                          uint64_t* key_out_lines, uint64_t* key_out_units, gx_by_key_totals* totals, uint64_t* counts, uint64_t* n_lines,
                          const gx_batch_opts* opts);
 
+/* ---- A whole batch ordered by a number its lines captured, on the device (gx_sort_lines) ----
+ * The reference's caller who reads two hosts' logs, or a log written by several threads, sorts first (README.md:26,63-79):
+ *     results.sort(Comparator.comparingLong(r -> Instant.parse(r.asMap().get("ts")).toEpochMilli()));
+ * gx_top_lines ranks by a captured number but delivers GX_TOP_MAX_LINES lines at most; this call orders the whole batch.  Parts are
+ * gx_top_part records with gx_top_lines' meaning -- at most one per extraction, one number space -- and values are read under their
+ * gx_number_format (ISO-8601, CLF, decimals: gx_set_number_format).  Terms are gx_where_terms.
+ * CLASSES.  A line is STAMPED (class 0) when it counts by gx_top_lines' rule and its value is a number.  With GX_SORT_CARRY a line that
+ * is not stamped -- unmatched, an exception, an extraction without a part, a failed term, an unset group, a value that is no number, all
+ * alike -- and that has a stamped line somewhere before it in the batch is CARRIED (class 1): it takes the number of the nearest earlier
+ * stamped line, as a stack trace belongs to the line above it.  Every other line is REST (class 2): without GX_SORT_CARRY every line that
+ * is not stamped, with it only the lines before the first stamped line.
+ * ORDER.  The stamped and carried lines (the ENTRIES) leave first, ordered by (value ascending, input line ascending), with
+ * GX_SORT_DESCENDING by (value descending, input line ascending): ties go by input line in both directions, so a header and the lines it
+ * carries leave together and in order, and two records with equal stamps leave in input order.  With GX_SORT_REST_LAST the rest lines
+ * follow in input order; without it they are dropped.
+ * COPIES: each line is copied as gx_select_lines copies one: units exactly, terminator included.  out_ids and out_caps hold the lines'
+ * ids or whole result rows in the input's format, so the result is an ordinary batch for every other call.
+ * EXACT: every output is exact and the same bits on every run: places come from scans, ranks from ballots, and there is no atomic
+ * operation on global memory in any pass. */
+#define GX_SORT_DESCENDING 1u
+#define GX_SORT_CARRY      2u
+#define GX_SORT_REST_LAST  4u
+#define GX_SORT_ALL_DIGITS 8u   /* test hook: sort all eleven six-bit digits of the key whatever the keys are; results identical, only slower */
+
+typedef struct gx_sort_out {    /* every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* out_index;        /* the delivered lines' input line numbers */
+    int64_t*  out_values;       /* their numbers (a carried line: its header's); 0 for a rest line */
+    uint8_t*  out_class;        /* 0 own number, 1 carried, 2 rest */
+    void*     out_bytes;        /* gx_partition_lines' outputs, same meaning, same formats: the delivered lines as a new CSR batch */
+    void*     out_offsets;
+    void*     out_ids;
+    int32_t*  out_caps;
+    uint64_t  cap_lines, out_bytes_cap;
+} gx_sort_out;
+
+typedef struct gx_sort_totals { /* host, always */
+    uint64_t lines, numbers, unset, not_numbers;   /* gx_top_totals' four, same meaning: lines == numbers + unset + not_numbers */
+    uint64_t carried, rest;                        /* the carried lines; the rest lines, delivered or dropped */
+    uint64_t lines_out, units_out;                 /* what the outputs need: numbers + carried (+ rest with GX_SORT_REST_LAST), and their code units */
+    int64_t  first_value, last_value;              /* of the entries in output order; 0 without one */
+    uint32_t n_passes;                             /* the digits the sort takes: those in which two entries' keys differ (eleven with GX_SORT_ALL_DIGITS) */
+    uint32_t already_ordered;                      /* 1: no entry's key is below the key of the entry before it in line order (also without entries) */
+} gx_sort_totals;
+
+/* gx_sort_lines: the batch is read exactly as gx_top_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1;
+ * staging or device_pointers; the stream).  cap_lines is the capacity of out_index, out_values, out_class, out_ids, out_caps (lines) and
+ * out_offsets (cap_lines + 1, the width of the input's offsets); out_bytes_cap is in BYTES, with utf16 too.
+ * HOST WAITS: ONE host wait before any output.  Before it run gx_top_lines' keys pass, a scan of its candidate flags, the compaction of
+ * the stamped keys, the entries pass (one lane per line: class, place, the (key, line) pair, the length) and a one-workgroup totals pass;
+ * in the wait the host reads the totals and checks the capacities.  Behind it, when outputs are wanted: a stable radix sort of the
+ * entries over the six-bit digits in which their keys' OR and AND differ (none for fewer than two distinct keys, eleven at most), the
+ * values, classes and lengths in output order, a scan, the copy.  With host outputs a second wait delivers them.  With device_pointers
+ * those passes are left running on opts->stream behind an event of this call's own; the handle's next gx_sort_lines on another stream
+ * waits for them, and the batch must stay unchanged until they have run.
+ * SIZE QUERY: out == NULL, or all of out's pointers NULL: only *totals is delivered.
+ * GX_E_LIMIT with *totals filled and no output written: cap_lines < lines_out (with any per-line output), out_bytes_cap too small, 32-bit
+ * out_offsets with 2^32 units and more.
+ * GX_E_ARG, before the device is looked at: every refusal gx_top_lines makes of parts and terms; unknown flag bits; totals == NULL;
+ * no_sync; utf8 = 2; parts or terms on dense ids without caps; out_caps on compact rows or without caps; an output overlapping an input
+ * (an output's capacity in bytes -- of at most n lines, whatever cap_lines says -- against bytes, offsets, ids and caps; of device bytes
+ * only the first unit is known before the device is looked at).  GX_E_LIMIT, likewise before the device is looked at: more than 64
+ * parts or terms; n above 2^30 (what the pair sort's kernels state); with host offsets a line of 2^32 code units and more, or offsets
+ * that go backwards (with device_pointers the entries pass finds it).  A host-only handle gives all of these, and GX_E_DEVICE after them
+ * (there is no CPU path).
+ * n == 0 and n_parts == 0 are legal; with n_parts == 0 every line is a rest line, and GX_SORT_REST_LAST then copies the batch through
+ * unchanged.  With lines_out == 0 out_offsets[0] = 0 and nothing else is written.
+ * The device workspace stays on the handle, a buffer of its own: 50 bytes per INPUT line (the keys, later the sort's second key array 8;
+ * the stamped keys in line order 8; the sort's first key array 8; its two line-number arrays 8; the scan of the candidate flags, later
+ * the destination offsets 8; the lengths by line and in output order 8; the flags 1; the classes 1) plus 768 bytes of counts per 2 048
+ * lines, until gx_destroy. */
+int gx_sort_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                  const gx_top_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                  const gx_sort_out* out, gx_sort_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_top_lines' chain with the ordering at its end: raw text -> lines -> the match-and-extract path -> the
+ * ordering.  out (out_cap bytes) receives the delivered lines' original bytes one behind the other, each with its terminator as the text
+ * has it; out_offsets (optional, lines_out + 1 entries, uint32 whatever opts->offsets64 says: the text is below 4 GiB) delimits them -- a
+ * last line of the text without a terminator is copied as it is and may now lie in the middle, so the output is cut at out_offsets, not
+ * at line ends.  out_index, out_values and out_class (optional, lines_out entries each) hold line numbers of the text, the numbers and
+ * the classes.  All are sized by the size query (all five NULL); *n_lines entries (+ 1) always suffice.  counts (optional,
+ * uint64_t[2K + 2], host) and *n_lines (optional) as gx_text_top_lines delivers them.  Limits and options are gx_text_top_lines'.  Like
+ * every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_sort_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_top_part* parts, uint32_t n_parts,
+                       const gx_where_term* terms, uint32_t n_terms, uint32_t flags, uint8_t* out, uint64_t out_cap, void* out_offsets,
+                       uint32_t* out_index, int64_t* out_values, uint8_t* out_class, gx_sort_totals* totals, uint64_t* counts,
+                       uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* ---- Lines grouped by TWO captured texts, on the device (gx_group_pairs) ----
  * The reference's caller keys on two captured texts at once right behind the extraction (README.md:26,63-79):
  *     r = gorp.extract(line);
