@@ -57,6 +57,7 @@ SYMBOLS = [
     "gx_group_pairs", "gx_text_group_pairs",
     "gx_bucket_lines", "gx_text_bucket_lines",
     "gx_group_series", "gx_text_group_series",
+    "gx_group_sessions", "gx_text_group_sessions",
     "gx_sort_lines", "gx_text_sort_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
@@ -180,6 +181,17 @@ class gx_sort_totals(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("numbers", C.c_uint64), ("unset", C.c_uint64), ("not_numbers", C.c_uint64), ("carried", C.c_uint64), ("rest", C.c_uint64),
                 ("lines_out", C.c_uint64), ("units_out", C.c_uint64), ("first_value", C.c_int64), ("last_value", C.c_int64), ("n_passes", C.c_uint32),
                 ("already_ordered", C.c_uint32)]
+
+
+class gx_sessions_out(C.Structure):
+    _fields_ = [("session_key", C.c_void_p), ("session_begin", C.c_void_p), ("session_end", C.c_void_p), ("session_first_line", C.c_void_p),
+                ("session_lines", C.c_void_p), ("session_stats", C.c_void_p), ("session_entry_begin", C.c_void_p), ("key_session_begin", C.c_void_p),
+                ("entry_line", C.c_void_p), ("line_session", C.c_void_p), ("max_sessions", C.c_uint64), ("max_entries", C.c_uint64)]
+
+
+class gx_sessions_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("n_sessions", C.c_uint64), ("entries", C.c_uint64), ("number_unset", C.c_uint64), ("not_numbers", C.c_uint64),
+                ("longest_lines", C.c_uint64), ("longest_duration", C.c_uint64), ("first_time", C.c_int64), ("last_time", C.c_int64)]
 
 
 class gx_series_out(C.Structure):
@@ -446,6 +458,14 @@ def lib():
                                        C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_series_out),
                                        C.POINTER(gx_series_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_series.restype = C.c_int
+    L.gx_group_sessions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
+                                    C.c_int64, C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_sessions_out),
+                                    C.POINTER(gx_sessions_totals), C.POINTER(gx_batch_opts)]
+    L.gx_group_sessions.restype = C.c_int
+    L.gx_text_group_sessions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32), C.c_int64,
+                                         C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_sessions_out),
+                                         C.POINTER(gx_sessions_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_sessions.restype = C.c_int
     L.gx_bucket_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_bucket_part), C.c_uint32, C.c_int64, C.c_int64,
                                   C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.POINTER(gx_batch_opts)]
     L.gx_bucket_lines.restype = C.c_int

@@ -26,6 +26,7 @@
 #include "gx_pairs.hpp"
 #include "gx_bucket.hpp"
 #include "gx_series.hpp"
+#include "gx_sessions.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
@@ -334,6 +335,10 @@ struct gx_handle {
     // and arrays, and the lines' cell slots (gx_series.hip); behind the one wait, sized by the cells read there, the sorts' workspace.
     // Covered by group_event too
     GrowBuf series_table, series_lines, series_sort;
+    // gx_group_sessions behind gx_group_lines' build: its number groups (SessionsHead, gx_sessions.hpp) at the head of the per-line arrays
+    // (gx_sessions.hip: SessionsWs); behind the group's wait, sized by the entries read there, the sorts' and the sessions' workspace
+    // (SessionsSortWs).  Covered by group_event too
+    GrowBuf sessions_lines, sessions_sort;
     Event group_event;
     bool group_pending = false;
     // gx_bucket_lines: its parts and terms on the device (BucketHead, gx_bucket.hpp; WhereHead behind it), the slots' words and arrays,
@@ -1987,7 +1992,7 @@ struct GroupCtx {
     uint32_t K() const { return static_cast<uint32_t>(h->T.n_rules); }
 };
 
-// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall) and, beside each,
+// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall, SessionsCall) and, beside each,
 // what it keeps while the pass runs (…Run; call == nullptr: not that call), whose steps group_pass takes in this order:
 //   start()    the call's own totals as they are when nothing has run
 //   nothing()  no lines or no parts: the results that no kernel writes
@@ -2276,6 +2281,99 @@ struct SeriesRun {
         }
     }
 };
+// ss (gx_group_sessions; nullptr: gx_group_lines as it is): behind the build the keys pass and its scan (launch_sessions_keys), whose
+// classes, entries and time words' OR / AND / range are read in the group's wait.  n_sessions exists only behind the two sorts, so
+// read() enqueues them with the heads, their scan and the longest session (launch_sessions_sort) and takes the call's ONE further wait --
+// before launch_group_emit: a key's number is known from the build, and a capacity can be refused before any output is written.
+struct SessionsCall {
+    const int32_t* number_groups = nullptr;
+    int64_t max_gap = 0;
+    bool all_digits = false;
+    const gx_sessions_out* asked = nullptr;   // the caller's; nullptr: the keys alone, no session passes
+    gx_sessions_totals* totals = nullptr;     // (its group member is the gx_group_totals the pass fills)
+    SessionsHead head{};                      // (sessions_refusals) the number group per entry of GroupHead::ext[]
+    bool any_number = false;
+    gx_sessions_out out{};
+    bool per_session() const {
+        return out.session_key || out.session_begin || out.session_end || out.session_first_line || out.session_lines || out.session_stats ||
+               out.session_entry_begin;
+    }
+    bool any() const { return per_session() || out.key_session_begin || out.entry_line || out.line_session; }
+};
+struct SessionsRun {
+    const SessionsCall* call;
+    SessionsWs sw{};
+    SessionsSortWs ssw{};
+    SessionsDev sd{};
+    SessionsDev2 sd2{};
+    uint32_t time_buf = 0, key_buf = 0;
+    explicit operator bool() const { return call != nullptr; }
+    void start() const { *call->totals = gx_sessions_totals{}; }
+    void nothing(const GroupCtx& c) const {   // no sessions: the bounds' one entry and every line's "none"
+        fill_out(call->out.session_entry_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.key_session_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.line_session, 0xFF, c.v.n * 4, c.host_out, c.stream);
+    }
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        sw = sessions_workspace(c.h->sessions_lines.get(sessions_workspace_bytes(v.n, c.values)), v.n, c.values);
+        GX_HIP(hipMemcpyAsync(sw.image, &call->head, sizeof(SessionsHead), hipMemcpyHostToDevice, c.stream));
+        GX_HIP(launch_sessions_keys(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, c.b.a, c.b.a.formats != 0 || call->head.formats != 0, c.b.w, sw,
+                                    c.stream));
+        GX_HIP(hipMemcpyAsync(&sd, sw.dev, sizeof(SessionsDev), hipMemcpyDeviceToHost, c.stream));
+    }
+    int read(const GroupCtx& c) {
+        gx_sessions_totals& t = *call->totals;
+        t.entries = sd.entries;
+        t.number_unset = sd.number_unset;
+        t.not_numbers = sd.not_numbers;
+        if (sd.entries + sd.number_unset + sd.not_numbers != c.totals->keyed)
+            throw GxError(GX_E_ARG, "internal: " + c.name + ": the classes of the keyed lines do not add up to them");
+        if (sd.entries == 0) return GX_OK;
+        t.first_time = top_value(~sd.min_inv, false);
+        t.last_time = top_value(sd.max_word, false);
+        if (sd.entries > SESSIONS_MAX) return fail(GX_E_LIMIT, c.name + ": " + std::to_string(sd.entries) + " entries; split batches of more than 2^30");
+        const uint64_t m = sd.entries;
+        const SortPlan plan = sessions_time_plan(sd.time_or, ~sd.and_inv, m, call->all_digits);
+        const bool stats = call->out.session_stats != nullptr;
+        ssw = sessions_sort_workspace(c.h->sessions_sort.get(sessions_sort_workspace_bytes(m, stats)), m, stats);
+        GX_HIP(launch_sessions_sort(c.v.n, m, plan, sessions_key_digits(c.b.n_keys, call->all_digits), call->max_gap, c.b.w, sw, ssw, &time_buf, &key_buf, c.stream));
+        GX_HIP(hipMemcpyAsync(&sd2, ssw.dev2, sizeof(SessionsDev2), hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipStreamSynchronize(c.stream));
+        if (sd2.n_sessions == 0 || sd2.n_sessions > m) throw GxError(GX_E_ARG, "internal: " + c.name + ": entries without a session, or more sessions than entries");
+        t.n_sessions = sd2.n_sessions;
+        t.longest_lines = sd2.longest_lines;
+        t.longest_duration = sd2.longest_duration;
+        return GX_OK;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_sessions_out& b = call->out;
+        const std::string& name = c.name;
+        if (call->per_session() && sd2.n_sessions > b.max_sessions)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(sd2.n_sessions) + " sessions, max_sessions " + std::to_string(b.max_sessions));
+        if (b.entry_line && sd.entries > b.max_entries)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(sd.entries) + " entries, max_entries " + std::to_string(b.max_entries));
+        if (b.key_session_begin && c.b.n_keys > c.max_keys)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the sessions' rows ordered by (key number, begin), the keys' bounds, the entries' lines and the lines' sessions
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const gx_sessions_out& b = call->out;
+        const uint64_t n = c.v.n, n_keys = c.b.n_keys, ns = sd2.n_sessions, m = sd.entries;
+        const SessionsOut so{twins.of(b.session_key, ns * 4), twins.of(b.session_begin, ns * 8), twins.of(b.session_end, ns * 8),
+                             twins.of(b.session_first_line, ns * 4), twins.of(b.session_lines, ns * 8),
+                             twins.of(reinterpret_cast<uint64_t*>(b.session_stats), ns * 64), twins.of(b.session_entry_begin, (ns + 1) * 8),
+                             twins.of(b.key_session_begin, (n_keys + 1) * 8), twins.of(b.entry_line, m * 4), twins.of(b.line_session, n * 4)};
+        if (m == 0) {   // keyed lines, and none of them an entry: every key's run is empty
+            if (so.session_entry_begin) GX_HIP(hipMemsetAsync(so.session_entry_begin, 0, 8, c.stream));
+            if (so.key_session_begin) GX_HIP(hipMemsetAsync(so.key_session_begin, 0, (n_keys + 1) * 8, c.stream));
+            if (so.line_session) GX_HIP(hipMemsetAsync(so.line_session, 0xFF, n * 4, c.stream));
+        } else {
+            GX_HIP(launch_sessions_emit(n, m, ns, n_keys, sw, ssw, time_buf, key_buf, so, c.stream));
+        }
+    }
+};
 // gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
 struct TopGroupsCall {
     uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
@@ -2289,6 +2387,7 @@ struct GroupExtras {
     std::optional<ByKeyCall> by_key;
     std::optional<PairsCall> pairs;
     std::optional<SeriesCall> series;
+    std::optional<SessionsCall> sessions;
 };
 // The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
 // totals and checks the capacities; then the emit.  out: the caller's, device or host
@@ -2300,17 +2399,19 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     ByKeyRun bk{x.by_key ? &*x.by_key : nullptr};
     PairsRun pc{x.pairs && x.pairs->asked ? &*x.pairs : nullptr};
     SeriesRun sc{x.series && x.series->asked ? &*x.series : nullptr};
+    SessionsRun ss{x.sessions && x.sessions->asked ? &*x.sessions : nullptr};
     GroupCtx c{h, v, wi, gi.values, out64, host_out, out.max_keys, totals, stream, name};
     const uint64_t n = v.n;
     if (bk) bk.start();
     if (pc) pc.start();
     if (sc) sc.start();
+    if (ss) ss.start();
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
     totals->exact = 1;
-    const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any();
-    const bool any_out =
-        out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || gq.rows || bk_out || pc_out || sc_out;
+    const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any(), ss_out = ss && ss.call->any();
+    const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || gq.rows || bk_out || pc_out ||
+                         sc_out || ss_out;
     if (n == 0 || gi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -2319,6 +2420,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
         if (bk_out) bk.nothing(c);
         if (pc_out) pc.nothing(c);
         if (sc_out) sc.nothing(c);
+        if (ss_out) ss.nothing(c);
         return GX_OK;
     }
     GroupBuild& b = c.b;
@@ -2327,6 +2429,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (bk) bk.enqueue(c);
     if (pc) pc.enqueue(c);
     if (sc) sc.enqueue(c);
+    if (ss) ss.enqueue(c);
     b.ask(n, stream);
     GX_HIP(hipStreamSynchronize(stream));
     int rc = b.read(totals, name);
@@ -2334,6 +2437,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (bk) bk.read(c);
     if (pc && (rc = pc.read(c)) != GX_OK) return rc;
     if (sc && (rc = sc.read(c)) != GX_OK) return rc;
+    if (ss && (rc = ss.read(c)) != GX_OK) return rc;
     if (!any_out) return GX_OK;
     const uint64_t n_keys = b.n_keys, key_units = b.key_units;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || gq.rows;
@@ -2344,6 +2448,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (bk_out && (rc = bk.fits(c)) != GX_OK) return rc;
     if (pc_out && (rc = pc.fits(c)) != GX_OK) return rc;
     if (sc_out && (rc = sc.fits(c)) != GX_OK) return rc;
+    if (ss_out && (rc = ss.fits(c)) != GX_OK) return rc;
     const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
     HostTwins twins(host_out);
     const GroupOut o{twins.of(out.key_units, key_units * unit), twins.of(out.key_offsets, (n_keys + 1) * off_w), twins.of(out.key_first_line, n_keys * 4),
@@ -2353,6 +2458,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (bk_out) bk.emit(c, twins);
     if (pc_out) pc.emit(c, twins);
     if (sc_out) sc.emit(c, twins);
+    if (ss_out) ss.emit(c, twins);
     if (gq.rows) gq.emit(c, twins);
     if (host_out) {
         twins.deliver(stream);
@@ -2407,6 +2513,30 @@ static void series_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (sc->out.cell_stats && !gi.values) throw GxError(GX_E_ARG, name + ": cell_stats without a value_group");
     if (n_parts && !sc->any_number && sc->any()) throw GxError(GX_E_ARG, name + ": series outputs while every part's number group is -1");
     if (sc->out.max_cells > SERIES_MAX_CELLS) throw GxError(GX_E_LIMIT, name + ": max_cells above 2^30");
+}
+
+// what gx_group_sessions adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups,
+// checked against the handle and laid out with their formats by GroupHead::ext[] (gi: group_refusals'), then the gap and the outputs
+static void sessions_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, SessionsCall* ss) {
+    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) ss->head.number[q] = SESSIONS_NO_NUMBER;
+    if (ss->asked) ss->out = *ss->asked;
+    if (n_parts && !ss->number_groups) throw GxError(GX_E_ARG, name + ": number_groups is NULL");
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const int32_t ng = ss->number_groups[t];
+        if (ng < -1 || ng >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's number group is neither -1 nor one of its extraction's");
+        if (ng < 0) continue;
+        ss->any_number = true;
+        for (uint32_t q = 0; q < gi.head.n_parts; ++q) {
+            if (gi.head.ext[q] != static_cast<uint32_t>(parts[t].extraction)) continue;
+            ss->head.number[q] = ng;
+            ss->head.nfmt[q] = h->number_format_of(parts[t].extraction, ng);
+            if (ss->head.nfmt[q]) ss->head.formats = 1u;
+        }
+    }
+    if (ss->max_gap < 0) throw GxError(GX_E_ARG, name + ": max_gap below 0");
+    if (ss->out.session_stats && !gi.values) throw GxError(GX_E_ARG, name + ": session_stats without a value_group");
+    if (n_parts && !ss->any_number && ss->any()) throw GxError(GX_E_ARG, name + ": session outputs while every part's number group is -1");
+    if (ss->out.max_sessions > SESSIONS_MAX) throw GxError(GX_E_LIMIT, name + ": max_sessions above 2^30");
 }
 
 // what gx_lines_by_key adds to the refusals of gx_group_lines, behind them and before the look at the device
@@ -2542,6 +2672,7 @@ static void extras_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (x->top) tg_refusals(gi, *x->top, name);
     if (x->pairs) pairs_refusals(h, gi, parts, n_parts, name, &*x->pairs);
     if (x->series) series_refusals(h, gi, parts, n_parts, name, &*x->series);
+    if (x->sessions) sessions_refusals(h, gi, parts, n_parts, name, &*x->sessions);
     if (x->by_key) by_key_refusals(*x->by_key, name);
 }
 
@@ -2751,6 +2882,36 @@ int gx_text_group_series(gx_handle* h, const uint8_t* text, uint64_t size, const
                          gx_series_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_series", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
                            totals ? &totals->group : nullptr, counts, n_lines, opts, series_extras(number_groups, origin, width, flags, series, totals));
+}
+
+// gx_group_sessions: gx_group_lines' call with the sessions behind it.  totals == NULL is refused as gx_group_lines refuses it.  The flags
+// travel without GX_BUCKET_ALL_DIGITS (unknown bits stay in the flags and are refused there).
+static GroupExtras sessions_extras(const int32_t* number_groups, int64_t max_gap, uint32_t flags, const gx_sessions_out* sessions, gx_sessions_totals* totals) {
+    if (totals) *totals = gx_sessions_totals{};
+    SessionsCall ss;
+    ss.number_groups = number_groups;
+    ss.max_gap = max_gap;
+    ss.all_digits = (flags & GX_BUCKET_ALL_DIGITS) != 0u;
+    ss.asked = sessions;
+    ss.totals = totals;
+    GroupExtras x;
+    x.sessions = ss;
+    return x;
+}
+static_assert(sizeof(gx_sessions_out) == 96 && sizeof(gx_sessions_totals) == sizeof(gx_group_totals) + 64, "include/gorp_hip.h states these layouts");
+
+int gx_group_sessions(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                      uint32_t n_parts, const int32_t* number_groups, int64_t max_gap, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                      const gx_group_out* keys, const gx_sessions_out* sessions, gx_sessions_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_sessions", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                            totals ? &totals->group : nullptr, opts, sessions_extras(number_groups, max_gap, flags, sessions, totals));
+}
+
+int gx_text_group_sessions(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups,
+                           int64_t max_gap, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_sessions_out* sessions,
+                           gx_sessions_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_sessions", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, sessions_extras(number_groups, max_gap, flags, sessions, totals));
 }
 
 // The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.

@@ -653,6 +653,62 @@ hipError_t launch_sort_entries(const void* ids, RowFormat fmt, uint32_t row_unit
 hipError_t launch_sort_emit(uint64_t n, uint64_t m, uint64_t lines_out, const SortPlan& plan, uint32_t flags, const SortWs& w, int64_t* out_values,
                             uint8_t* out_class, uint32_t** perm, hipStream_t stream);
 
+// A key's lines ordered by a captured time and cut into sessions (gx_sessions.hip; the rule: gx_sessions.hpp), behind launch_group_build
+// on the same stream (g.slot_of, g.head_words, g.idx_off: a key's number is idx_off[its first line]); launch_group_emit is not needed.
+// The passes' device workspace: per line, cut out of one allocation of sessions_workspace_bytes(n, values) bytes --
+struct SessionsWs {
+    uint8_t* image;               // SessionsHead (gx_sessions.hpp), put there by the caller, 16-byte aligned
+    uint8_t* dev;                 // SessionsDev: the classes of the keyed lines, the time words' OR / AND / minimum / maximum
+    uint64_t* tword;              // [n] an entry's time word: top_key(time, false)
+    uint64_t* before;             // [n + 1] the entries before line i; [n]: all of them
+    uint64_t* sums;               // the scan's
+    int64_t* val;                 // [n] an entry's value, with a value group (else nullptr)
+    uint8_t* ent;                 // [n] the line is an entry
+    uint8_t* vcls;                // [n] an entry's value's class -- 0: a number, 1: unset, 2: no number, 3: none to measure; nullptr as val
+    size_t bytes;
+};
+// -- and per entry, sized by the m entries the host has read: sessions_sort_workspace_bytes(m, stats) bytes.
+struct SessionsSortWs {
+    uint8_t* dev2;                // SessionsDev2: the sessions, the longest
+    BucketSortWs by_time;         // (time word, line) pairs; behind the sort its other buffer holds times and lines in the final order
+    BucketSortWs by_key;          // (key number, place in time order) pairs
+    uint64_t* sbefore;            // [m + 1] the heads before entry e; [m]: the sessions
+    uint64_t* sums;               // the scans'
+    uint32_t* start;              // [m + 1] the first entry of session s; [n_sessions] = m
+    uint32_t* skey;               // [m] the sessions' key numbers
+    uint8_t* head;                // [m] entry e begins a session
+    uint64_t* col[4];             // with stats: [m] numbers | unset << 32, not_numbers, the sum's low and high halves ...
+    uint64_t* pre[4];             // ... and [m + 1] their scans
+    uint64_t *smin, *smax;        // [m] per session: group_min_word / group_max_word merged by maximum
+    size_t bytes;
+};
+// what the emit passes write, each part optional (nullptr)
+struct SessionsOut {
+    uint32_t* session_key;
+    int64_t* session_begin;
+    int64_t* session_end;
+    uint32_t* session_first_line;
+    uint64_t* session_lines;
+    uint64_t* session_stats;      // [n_sessions][8]: gx_measure_stats' fields
+    uint64_t* session_entry_begin;   // [n_sessions + 1]
+    uint64_t* key_session_begin;  // [n_keys + 1]
+    uint32_t* entry_line;         // [m]
+    uint32_t* line_session;       // [n]
+};
+SessionsWs sessions_workspace(void* ws, uint64_t n, bool values);
+size_t sessions_workspace_bytes(uint64_t n, bool values);
+SessionsSortWs sessions_sort_workspace(void* ws, uint64_t m, bool stats);
+size_t sessions_sort_workspace_bytes(uint64_t m, bool stats);
+// n > 0, parts > 0; formats: a value group's or a number group's format is not LONG.  Behind it the host reads SessionsDev at w.dev.
+hipError_t launch_sessions_keys(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                                bool formats, const GroupWs& g, const SessionsWs& w, hipStream_t stream);
+// 0 < m <= 2^30 entries; plan: sessions_time_plan's; key_digits: sessions_key_digits'.  Behind it the host reads SessionsDev2 at s.dev2.
+hipError_t launch_sessions_sort(uint64_t n, uint64_t m, const SortPlan& plan, uint32_t key_digits, int64_t max_gap, const GroupWs& g, const SessionsWs& w,
+                                const SessionsSortWs& s, uint32_t* time_buf, uint32_t* key_buf, hipStream_t stream);
+// 0 < ns <= m sessions, each output within its capacity (the host has checked it); time_buf / key_buf: launch_sessions_sort's.
+hipError_t launch_sessions_emit(uint64_t n, uint64_t m, uint64_t ns, uint64_t n_keys, const SessionsWs& w, const SessionsSortWs& s, uint32_t time_buf, uint32_t key_buf,
+                                const SessionsOut& out, hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

@@ -1920,6 +1920,160 @@ class Gorp:
         res["line_key"], res["line_cell"] = res["line_key"][:n_lines], res["line_cell"][:n_lines]
         return res, counts, n_lines
 
+    # -- sessions per captured text: a key's lines in time order, cut at gaps (gx_group_sessions / gx_text_group_sessions) ----------
+    def _sessions_gap(self, both, max_gap):
+        """max_gap as an int >= 0; a text is read as _series_origin reads an origin, under the first numbered part's number format."""
+        try:
+            gap = self._series_origin(both, max_gap)
+        except ValueError:
+            gap = -1
+        if gap < 0:
+            raise ValueError("max_gap %r: an int64 >= 0, or a text read under the first timed part's number format" % (max_gap,))
+        return gap
+
+    @staticmethod
+    def _sessions_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(n_sessions=t.n_sessions, entries=t.entries, number_unset=t.number_unset, not_numbers=t.not_numbers, longest_lines=t.longest_lines,
+                 longest_duration=t.longest_duration, first_time=t.first_time, last_time=t.last_time, group=Gorp._group_totals(t.group))
+        return d
+
+    def group_sessions_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, max_gap, where=None, key_units_ptr=None, key_units_cap=0,
+                              key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0,
+                              session_key_ptr=None, session_begin_ptr=None, session_end_ptr=None, session_first_line_ptr=None, session_lines_ptr=None,
+                              session_stats_ptr=None, session_entry_begin_ptr=None, key_session_begin_ptr=None, entry_line_ptr=None, line_session_ptr=None,
+                              max_sessions=0, max_entries=0, sessions=True, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True,
+                              utf8=False, weak_hash=False, all_digits=False):
+        """gx_group_sessions on device pointers (ints): group_lines_device's keys, plus the sessions in the caller's buffers, each
+        optional (none at all: the size query; max_keys still sizes the table).  parts as series_parts takes them: the number is the
+        line's TIME.  sessions=False passes sessions == NULL: the call is gx_group_lines.  Returns (rc, totals): rc is GX_OK or
+        GX_E_LIMIT -- then nothing was written and totals says what the outputs need (n_keys, key_units, n_sessions, entries; entries
+        always suffices for max_sessions and max_entries); every other error raises."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_sessions_out(session_key_ptr, session_begin_ptr, session_end_ptr, session_first_line_ptr, session_lines_ptr, session_stats_ptr,
+                                session_entry_begin_ptr, key_session_begin_ptr, entry_line_ptr, line_session_ptr, max_sessions, max_entries)
+        totals = N.gx_sessions_totals()
+        rc = N.lib().gx_group_sessions(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, both[0].array, both[0].n, both[1], self._sessions_gap(both, max_gap),
+                                       terms.array, terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(keys), C.byref(out) if sessions else None,
+                                       C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._sessions_totals(totals)
+
+    def text_group_sessions_device(self, text_ptr, size, parts, max_gap, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                                   key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, session_key_ptr=None,
+                                   session_begin_ptr=None, session_end_ptr=None, session_first_line_ptr=None, session_lines_ptr=None, session_stats_ptr=None,
+                                   session_entry_begin_ptr=None, key_session_begin_ptr=None, entry_line_ptr=None, line_session_ptr=None, max_sessions=0,
+                                   max_entries=0, sessions=True, offsets64=False, stream=None, device_pointers=True, utf8=False, weak_hash=False,
+                                   all_digits=False):
+        """gx_text_group_sessions on a device buffer (int); outputs as group_sessions_device takes them (line_key and line_session: one
+        entry per line of the text).  Returns (rc, totals, counts, n_lines)."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_sessions_out(session_key_ptr, session_begin_ptr, session_end_ptr, session_first_line_ptr, session_lines_ptr, session_stats_ptr,
+                                session_entry_begin_ptr, key_session_begin_ptr, entry_line_ptr, line_session_ptr, max_sessions, max_entries)
+        totals = N.gx_sessions_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_sessions(self._h.ptr, text_ptr, size, both[0].array, both[0].n, both[1], self._sessions_gap(both, max_gap), terms.array, terms.n,
+                                            self._bucket_flags(weak_hash, all_digits), C.byref(keys), C.byref(out) if sessions else None, C.byref(totals),
+                                            counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._sessions_totals(totals), counts, nl.value
+
+    def _sessions_host(self, device_call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap):
+        """_group_host with the session arrays beside the key arrays, each sized by the number of lines: no more entries than lines, no
+        more sessions than entries."""
+        got = {}
+        cap = max(1, n_lines_cap)
+
+        def call(units, ucap, koff, first, lines, stats, line_key, mk):
+            got.update(session_key=np.zeros(cap, np.uint32), session_begin=np.zeros(cap, np.int64), session_end=np.zeros(cap, np.int64),
+                       session_first_line=np.zeros(cap, np.uint32), session_lines=np.zeros(cap, np.uint64),
+                       session_stats=(N.gx_measure_stats * cap)() if parts.has_values else None, session_entry_begin=np.zeros(cap + 1, np.uint64),
+                       key_session_begin=np.zeros(mk + 1, np.uint64), entry_line=np.zeros(cap, np.uint32), line_session=np.full(cap, 0xFFFFFFFF, np.uint32))
+            return device_call(units, ucap, koff, first, lines, stats, line_key, mk, got["session_key"].ctypes.data, got["session_begin"].ctypes.data,
+                               got["session_end"].ctypes.data, got["session_first_line"].ctypes.data, got["session_lines"].ctypes.data,
+                               None if got["session_stats"] is None else C.addressof(got["session_stats"]), got["session_entry_begin"].ctypes.data,
+                               got["key_session_begin"].ctypes.data, got["entry_line"].ctypes.data, got["line_session"].ctypes.data, n_lines_cap, n_lines_cap)
+        res, rest = self._group_host(call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap)
+        s, m, k = res["totals"]["n_sessions"], res["totals"]["entries"], res["totals"]["n_keys"]
+        st = got["session_stats"]
+        res.update(session_key=got["session_key"][:s], session_begin=got["session_begin"][:s], session_end=got["session_end"][:s],
+                   session_first_line=got["session_first_line"][:s], session_lines=got["session_lines"][:s], session_entry_begin=got["session_entry_begin"][:s + 1],
+                   key_session_begin=got["key_session_begin"][:k + 1], entry_line=got["entry_line"][:m], line_session=got["line_session"],
+                   session_stats=None if st is None else [{"lines": x.lines, "numbers": x.numbers, "unset": x.unset, "not_numbers": x.not_numbers,
+                                                           "min": x.min if x.numbers else None, "max": x.max if x.numbers else None,
+                                                           "sum": (x.sum_hi << 64) + x.sum_lo} for x in st[:s]])
+        return res, rest
+
+    def group_sessions(self, data, offsets, ids, rows, parts, max_gap, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None, weak_hash=False,
+                       all_digits=False):
+        """gx_group_sessions on host buffers: group_lines' keys, and every key's lines ordered by a captured time and cut into SESSIONS: a
+        new one at the key's first entry and wherever the time exceeds the previous entry's by more than max_gap -- Splunk's
+        `transaction id maxpause=`.  parts: (extraction, key extractor, time extractor[, value extractor]) each (series_parts); max_gap
+        an int >= 0 in the time's own unit, or a text read under the first timed part's number format; everything else as group_lines
+        takes it.  Returns group_lines' dict plus session_key, session_begin, session_end, session_first_line, session_lines,
+        session_stats (per session, ordered by (key number, begin); None when no part has a value extractor), session_entry_begin
+        (n_sessions + 1: session s's entries are entry_line[begin[s]:begin[s + 1]]), key_session_begin (n_keys + 1), entry_line (the
+        entries' input lines ordered by (key, time, line)), line_session (uint32 per input line, 0xFFFFFFFF: no entry) and the session
+        totals (n_sessions, entries, number_unset, not_numbers, longest_lines, longest_duration, first_time, last_time) in totals."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        both = self.series_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.group_sessions_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), both, max_gap, where, *outs,
+                                              offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8),
+                                              weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._sessions_host(device_call, n, both[0], data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap)
+        res["line_key"], res["line_session"] = res["line_key"][:n], res["line_session"][:n]
+        return res
+
+    def text_group_sessions(self, text, parts, max_gap, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None, weak_hash=False, all_digits=False):
+        """gx_text_group_sessions on a host buffer: raw text -> lines -> extraction -> group_sessions.  Returns (the dict group_sessions
+        returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        both = self.series_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.text_group_sessions_device(raw.ctypes.data if raw.size else None, raw.size, both, max_gap, where, *outs, device_pointers=False, utf8=utf8,
+                                                   weak_hash=weak_hash, all_digits=all_digits)
+        res, (counts, n_lines) = self._sessions_host(device_call, cap_lines, both[0], np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
+        res["line_key"], res["line_session"] = res["line_key"][:n_lines], res["line_session"][:n_lines]
+        return res, counts, n_lines
+
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
     def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
                                key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,

@@ -1053,6 +1053,46 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Sessions per captured text (gx_group_sessions): the caller's
+    //     byId.computeIfAbsent(r.asMap().get("id"), k -> new ArrayList<>()).add(r);
+    //     ... per id: sort by Instant.parse(ts).toEpochMilli(); a new session wherever ts - previous ts > maxGap
+    // (README.md:26,63-79) -- Splunk's `transaction id maxpause=30s`.  The parts are seriesParts(): the NUMBER extractor is the line's
+    // TIME.  groupLines' result, plus the sessions ordered by (key number, begin): per session its key's number, the times of its first
+    // and last entry, the input line of its first entry, its entries and -- when a part has a value -- its gx_measure_stats; where its
+    // entries begin in entryLine (sessions + 1 entries); per key where its sessions begin (keys.size() + 1 entries); the entries' input
+    // lines ordered by (key, time, line); per input line its session's number (0xFFFFFFFF: the line is no entry).
+    struct Sessions : Groups {
+        std::vector<uint32_t> sessionKey, sessionFirstLine;
+        std::vector<int64_t> sessionBegin, sessionEnd;
+        std::vector<uint64_t> sessionLines;
+        std::vector<gx_measure_stats> sessionStats;   // empty when no part has a value
+        std::vector<uint64_t> sessionEntryBegin, keySessionBegin;
+        std::vector<uint32_t> entryLine, lineSession;
+        gx_sessions_totals sessions{};
+    };
+    Sessions groupSessions(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const SeriesParts& parts,
+                           int64_t maxGap, const Where* where = nullptr) const {
+        return sessionsOf(parts, where, &n, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                const gx_sessions_out* so, gx_sessions_totals* totals) {
+            return gx_group_sessions(h_, bytes, offsets, n, match_id, caps, p, np, s, maxGap, t, nt, 0, out, so, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same sessions out (gx_text_group_sessions).  counts (optional): lines per outcome index.
+    Sessions textGroupSessions(const std::string& text, const SeriesParts& parts, int64_t maxGap, const Where* where = nullptr,
+                               std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        Sessions r = sessionsOf(parts, where, &lines, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt,
+                                                          const gx_group_out* out, const gx_sessions_out* so, gx_sessions_totals* totals) {
+            return gx_text_group_sessions(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, s, maxGap, t, nt, 0, out, so, totals,
+                                          counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return r;
+    }
     int maxGroups() const { return gx_max_groups(h_); }
     gx_handle* handle() const { return h_; }
 
@@ -1212,6 +1252,51 @@ private:
         if (!wanted) {
             r.keyCellBegin.assign(r.keys.size() + 1, 0);
             r.lineCell.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        }
+        return r;
+    }
+    // groupsOf with the sessions beside the keys: the size queries leave the sessions and the entries in r.sessions; the call with
+    // exactly the sizes they reported delivers both.  Session outputs are asked for only where a part has a number (the C call refuses
+    // them otherwise: there is nothing they could hold).
+    template <typename Call>
+    Sessions sessionsOf(const SeriesParts& parts, const Where* where, const uint64_t* lines, Call&& call) const {
+        Sessions r;
+        const int32_t none = -1;
+        const std::vector<int32_t>& numbers = parts.numbers();
+        bool wanted = numbers.empty();
+        for (const int32_t s : numbers) wanted = wanted || s >= 0;
+        Groups g = groupsOf(parts.keys(), where, lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                            gx_group_totals* totals) {
+            gx_sessions_out so{};
+            if (out->key_offsets != nullptr && wanted) {   // (the size query before it left the sizes in r.sessions)
+                const size_t m = static_cast<size_t>(r.sessions.n_sessions);
+                r.sessionKey.assign(m, 0);
+                r.sessionBegin.assign(m, 0);
+                r.sessionEnd.assign(m, 0);
+                r.sessionFirstLine.assign(m, 0);
+                r.sessionLines.assign(m, 0);
+                if (parts.keys().hasValues()) r.sessionStats.assign(m, gx_measure_stats{});
+                r.sessionEntryBegin.assign(m + 1, 0);
+                r.keySessionBegin.assign(static_cast<size_t>(out->max_keys) + 1, 0);
+                r.entryLine.assign(static_cast<size_t>(r.sessions.entries), 0);
+                r.lineSession.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+                so.session_key = r.sessionKey.data(); so.session_begin = r.sessionBegin.data(); so.session_end = r.sessionEnd.data();
+                so.session_first_line = r.sessionFirstLine.data(); so.session_lines = r.sessionLines.data();
+                so.session_stats = parts.keys().hasValues() ? r.sessionStats.data() : nullptr;
+                so.session_entry_begin = r.sessionEntryBegin.data(); so.key_session_begin = r.keySessionBegin.data();
+                so.entry_line = r.entryLine.data(); so.line_session = r.lineSession.data();
+                so.max_sessions = r.sessions.n_sessions;
+                so.max_entries = r.sessions.entries;
+            }
+            const int rc = call(p, np, numbers.empty() ? &none : numbers.data(), t, nt, out, &so, &r.sessions);
+            *totals = r.sessions.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        if (!wanted) {
+            r.sessionEntryBegin.assign(1, 0);
+            r.keySessionBegin.assign(r.keys.size() + 1, 0);
+            r.lineSession.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
         }
         return r;
     }

@@ -1146,6 +1146,95 @@ int gx_text_group_series(gx_handle* h, const uint8_t* text, uint64_t size, const
                          uint32_t flags, const gx_group_out* keys, const gx_series_out* series, gx_series_totals* totals, uint64_t* counts,
                          uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- Sessions per captured text: a key's lines in time order, cut where the log falls silent, on the device (gx_group_sessions) ----
+ * The reference's caller collects a request's, a user's or a connection's lines right behind the extraction (README.md:26,63-79) and asks
+ * which of them belong together:
+ *     byId.computeIfAbsent(r.asMap().get("id"), k -> new ArrayList<>()).add(r);
+ *     ... per id: sort by Instant.parse(ts).toEpochMilli(); a new session wherever ts - previous ts > maxGap
+ * -- Splunk's `transaction id maxpause=30s`; SQL's SUM(CASE WHEN ts - LAG(ts) OVER (PARTITION BY id ORDER BY ts) > gap THEN 1 ELSE 0 END).
+ * gx_group_series cuts time into fixed intervals from an origin: it cuts a session wherever it crosses an interval's edge and joins two
+ * that share an interval.  A session depends on the ORDER of a key's lines in time.
+ * PARTS: gx_group_lines' parts, plus number_groups[n_parts] exactly as gx_group_series takes them: per part the group whose value is the
+ * line's TIME, parsed under its gx_number_format, in [0, gx_num_groups(h, extraction)), or -1: the part's lines have a key and no time.
+ * All parts share one key space.
+ * THE RULE: a line counts, is keyed or adds to `unset` exactly as in gx_group_lines; nothing of that call is reinterpreted.  A keyed line
+ * is an ENTRY when its part has a number group, that group's capture names a value (the rule of gx_where_term) and the value parses
+ * (gx_top_lines' class "number"); else it adds to number_unset (the number group is -1, or its capture names nothing) or to not_numbers
+ * (the value does not parse): keyed == entries + number_unset + not_numbers.  Key j's entries are ordered by (time ascending, input line
+ * ascending).  A SESSION begins at the key's first entry and at every entry whose time exceeds the previous entry's time by MORE than
+ * max_gap (>= 0, an int64 in the number's own unit).  The comparison is exact for every pair of int64: in that order t >= prev, so
+ * (uint64) t - (uint64) prev is the true difference (up to 2^64 - 1), compared unsigned with (uint64) max_gap.  Equal times never open a
+ * session; max_gap = INT64_MAX still splits INT64_MIN from INT64_MAX.
+ * ORDER: sessions leave ordered by (key number, begin time): key numbers are gx_group_lines' (first appearance), a key's sessions are
+ * contiguous and in time order.  Entries leave ordered by (key number, time, input line): a session's entries are contiguous.
+ * EXACT: every output is exact and the same bits on every run; ranks come from ballots, merges are integer adds, minima and maxima; no
+ * float anywhere.
+ * NOT IN SCOPE: a cap on a session's span (maxspan), start / end markers (startswith), carrying unstamped lines into a session (compose
+ * with gx_sort_lines' carry later), the sessions' text as a new CSR batch (compose entry_line with the existing copy later), quantiles
+ * of durations, ranking sessions.  The rule: gorp_amd/csrc/gx_sessions.hpp. */
+typedef struct gx_sessions_out {      /* every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* session_key;            /* key number of session s; sessions ORDERED by (session_key, session_begin) */
+    int64_t*  session_begin;          /* time of its first entry */
+    int64_t*  session_end;            /* time of its last entry: duration = end - begin as uint64 */
+    uint32_t* session_first_line;     /* input line of its first entry */
+    uint64_t* session_lines;          /* its entries */
+    gx_measure_stats* session_stats;  /* over its entries whose part has a value_group; NULL where no part has one */
+    uint64_t* session_entry_begin;    /* n_sessions + 1: session s's entries are entry_line[begin[s], begin[s+1]) */
+    uint64_t* key_session_begin;      /* n_keys + 1; capacity keys->max_keys + 1 */
+    uint32_t* entry_line;             /* the entries' input lines in (key, time, line) order; capacity max_entries */
+    uint32_t* line_session;           /* n entries, 0xFFFFFFFF: the line is no entry */
+    uint64_t  max_sessions;           /* capacity of the per-session arrays (session_entry_begin: + 1); <= 2^30 */
+    uint64_t  max_entries;            /* capacity of entry_line */
+} gx_sessions_out;
+
+typedef struct gx_sessions_totals {   /* host, always */
+    gx_group_totals group;            /* exactly what gx_group_lines reports for the same call */
+    uint64_t n_sessions, entries, number_unset, not_numbers;
+    uint64_t longest_lines;           /* the most entries in one session; 0 without one */
+    uint64_t longest_duration;        /* the largest end - begin, unsigned; 0 without one */
+    int64_t  first_time, last_time;   /* over all entries; 0 without one */
+} gx_sessions_totals;
+
+/* gx_group_sessions: everything gx_group_lines delivers through `keys` and totals->group is delivered bit for bit.
+ * HOW THE BATCH IS READ: exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging
+ * or device_pointers; the stream).
+ * FLAGS: GX_GROUP_WEAK_HASH and GX_BUCKET_ALL_DIGITS (both sorts take every digit: the same result, only slower).
+ * With sessions == NULL the call IS gx_group_lines: the session passes do not run, and the session totals are zero.  Its arguments are
+ * still checked: number_groups == NULL with n_parts > 0, a bad number group and max_gap < 0 are GX_E_ARG there too.
+ * SIZE QUERY: every output of `keys` and `sessions` NULL: only *totals is filled; keys->max_keys is still read as the table's size.
+ * entries is always a sufficient max_sessions and max_entries.
+ * GX_E_LIMIT: a per-session array (session_key, session_begin, session_end, session_first_line, session_lines, session_stats,
+ * session_entry_begin) with n_sessions > max_sessions; entry_line with entries > max_entries; key_session_begin with n_keys >
+ * keys->max_keys; max_sessions > 2^30; more than 2^30 entries; and gx_group_lines' own limits.  In every one of these cases nothing is
+ * written to ANY output, the key outputs included, and *totals is filled (after the overflow of the key table the session totals are
+ * zero; with more than 2^30 entries n_sessions and the longest are).
+ * GX_E_ARG, in this order behind every refusal gx_group_lines makes: number_groups == NULL with n_parts > 0; a number group that is
+ * neither -1 nor one of its part's extraction's; max_gap < 0; session_stats where no part has a value group; an output of `sessions`
+ * given while n_parts > 0 and every number group is -1; unknown flag bits are among gx_group_lines' refusals.  All refusals that need no
+ * device come before the device is looked at: a host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).
+ * EMPTY INPUTS: n == 0 and n_parts == 0 are legal and give all zeros (session_entry_begin and key_session_begin: their one entry;
+ * line_session: all none).
+ * HOST WAITS: TWO host waits before any output.  The wait in which gx_group_lines reads its totals also reads entries, number_unset,
+ * not_numbers, first_time, last_time and the OR and AND of the times, from which the time sort's digits are planned.  n_sessions exists
+ * only behind the two sorts: ONE more wait reads n_sessions, longest_lines and longest_duration, before the key outputs are written, so
+ * that a capacity can be refused with every output untouched.  Without an entry that wait is not taken.  With host outputs a further
+ * wait delivers them.  With device_pointers the emits are left running on opts->stream when the call returns; the handle's next group
+ * call on another stream waits for them, and the batch must stay unchanged until they have run.
+ * WORKSPACE: on the handle beside gx_group_lines', until gx_destroy: 17 bytes per input line (26 with a value group); 65 bytes per entry
+ * and 1 536 per 2 048 entries for the sorts, the heads and the sessions; with session_stats 80 more per entry. */
+int gx_group_sessions(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                      const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups, int64_t max_gap,
+                      const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_sessions_out* sessions,
+                      gx_sessions_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the sessions at its end: raw text -> lines -> the match-and-extract path -> the
+ * keys and the sessions.  counts and *n_lines as gx_text_group_lines delivers them; line_session holds one entry per line of the text.
+ * Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_sessions(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                           const int32_t* number_groups, int64_t max_gap, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                           const gx_group_out* keys, const gx_sessions_out* sessions, gx_sessions_totals* totals, uint64_t* counts,
+                           uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
