@@ -58,6 +58,7 @@ SYMBOLS = [
     "gx_bucket_lines", "gx_text_bucket_lines",
     "gx_group_series", "gx_text_group_series",
     "gx_group_sessions", "gx_text_group_sessions",
+    "gx_group_spans", "gx_text_group_spans",
     "gx_sort_lines", "gx_text_sort_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
@@ -115,6 +116,7 @@ GX_TOP_GROUPS_SMALLEST = 2
 GX_TOP_GROUPS_MAX = 4096
 GX_BY_KEY_ALL_DIGITS = 2
 GX_BUCKET_ALL_DIGITS = 2
+GX_SPAN_BEGIN, GX_SPAN_END = 1, 2
 GX_SORT_DESCENDING, GX_SORT_CARRY, GX_SORT_REST_LAST, GX_SORT_ALL_DIGITS = 1, 2, 4, 8
 
 
@@ -189,9 +191,20 @@ class gx_sessions_out(C.Structure):
                 ("entry_line", C.c_void_p), ("line_session", C.c_void_p), ("max_sessions", C.c_uint64), ("max_entries", C.c_uint64)]
 
 
+class gx_spans_out(C.Structure):
+    _fields_ = [("span_key", C.c_void_p), ("span_begin_line", C.c_void_p), ("span_end_line", C.c_void_p), ("span_begin", C.c_void_p), ("span_end", C.c_void_p),
+                ("span_duration", C.c_void_p), ("span_class", C.c_void_p), ("key_span_begin", C.c_void_p), ("key_span_stats", C.c_void_p),
+                ("key_open_line", C.c_void_p), ("line_span", C.c_void_p), ("line_state", C.c_void_p), ("max_spans", C.c_uint64)]
+
+
 class gx_sessions_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("n_sessions", C.c_uint64), ("entries", C.c_uint64), ("number_unset", C.c_uint64), ("not_numbers", C.c_uint64),
                 ("longest_lines", C.c_uint64), ("longest_duration", C.c_uint64), ("first_time", C.c_int64), ("last_time", C.c_int64)]
+
+
+class gx_spans_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("n_spans", C.c_uint64), ("begins", C.c_uint64), ("ends", C.c_uint64), ("superseded", C.c_uint64),
+                ("left_open", C.c_uint64), ("orphan_ends", C.c_uint64), ("out_of_range", C.c_uint64), ("durations", gx_measure_stats)]
 
 
 class gx_series_out(C.Structure):
@@ -466,6 +479,14 @@ def lib():
                                          C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_sessions_out),
                                          C.POINTER(gx_sessions_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_sessions.restype = C.c_int
+    L.gx_group_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_uint32), C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_spans_out),
+                                 C.POINTER(gx_spans_totals), C.POINTER(gx_batch_opts)]
+    L.gx_group_spans.restype = C.c_int
+    L.gx_text_group_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                      C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_spans_out),
+                                      C.POINTER(gx_spans_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_spans.restype = C.c_int
     L.gx_bucket_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_bucket_part), C.c_uint32, C.c_int64, C.c_int64,
                                   C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_bucket_out), C.POINTER(gx_bucket_totals), C.POINTER(gx_batch_opts)]
     L.gx_bucket_lines.restype = C.c_int

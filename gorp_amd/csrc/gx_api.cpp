@@ -27,6 +27,7 @@
 #include "gx_bucket.hpp"
 #include "gx_series.hpp"
 #include "gx_sessions.hpp"
+#include "gx_spans.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
 #include "gx_images.hpp"
@@ -339,6 +340,10 @@ struct gx_handle {
     // (gx_sessions.hip: SessionsWs); behind the group's wait, sized by the entries read there, the sorts' and the sessions' workspace
     // (SessionsSortWs).  Covered by group_event too
     GrowBuf sessions_lines, sessions_sort;
+    // gx_group_spans behind gx_group_lines' build: its number groups and roles (SpansHead, gx_spans.hpp) at the head of the per-line arrays
+    // (gx_spans.hip: SpansWs); behind the group's wait, sized by the entries and keys read there, the sort's and the pairing's workspace
+    // (SpansPairWs).  Covered by group_event too
+    GrowBuf spans_lines, spans_pair;
     Event group_event;
     bool group_pending = false;
     // gx_bucket_lines: its parts and terms on the device (BucketHead, gx_bucket.hpp; WhereHead behind it), the slots' words and arrays,
@@ -1992,7 +1997,7 @@ struct GroupCtx {
     uint32_t K() const { return static_cast<uint32_t>(h->T.n_rules); }
 };
 
-// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall, SessionsCall) and, beside each,
+// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall, SessionsCall, SpansCall) and, beside each,
 // what it keeps while the pass runs (…Run; call == nullptr: not that call), whose steps group_pass takes in this order:
 //   start()    the call's own totals as they are when nothing has run
 //   nothing()  no lines or no parts: the results that no kernel writes
@@ -2374,6 +2379,106 @@ struct SessionsRun {
         }
     }
 };
+// sp (gx_group_spans; nullptr: gx_group_lines as it is): behind the build the entries pass and its scan (launch_spans_entries), whose
+// entries are read in the group's wait.  n_spans exists only behind the sort, so read() enqueues it with the heads and their scans
+// (launch_spans_pair) and takes the call's ONE further wait -- before launch_group_emit: a key's number is known from the build, and a
+// capacity can be refused before any output is written.
+struct SpansCall {
+    const int32_t* number_groups = nullptr;
+    const uint32_t* roles = nullptr;
+    bool all_digits = false;
+    const gx_spans_out* asked = nullptr;   // the caller's; nullptr: the keys alone, no span passes
+    gx_spans_totals* totals = nullptr;     // (its group member is the gx_group_totals the pass fills)
+    SpansHead head{};                      // (spans_refusals) the number group and the role per entry of GroupHead::ext[]
+    gx_spans_out out{};
+    bool per_span() const {
+        return out.span_key || out.span_begin_line || out.span_end_line || out.span_begin || out.span_end || out.span_duration || out.span_class;
+    }
+    bool per_key() const { return out.key_span_begin || out.key_span_stats || out.key_open_line; }
+    bool any() const { return per_span() || per_key() || out.line_span || out.line_state; }
+};
+struct SpansRun {
+    const SpansCall* call;
+    SpansWs sw{};
+    SpansPairWs pw{};
+    SpansDev sd{};
+    uint64_t m = 0, n_spans = 0, sums[4] = {0, 0, 0, 0};
+    uint32_t buf = 0;
+    explicit operator bool() const { return call != nullptr; }
+    void start() const { *call->totals = gx_spans_totals{}; }
+    void nothing(const GroupCtx& c) const {   // no spans: the bounds' one entry, every line's "none" and state 0
+        fill_out(call->out.key_span_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.line_span, 0xFF, c.v.n * 4, c.host_out, c.stream);
+        fill_out(call->out.line_state, 0, c.v.n, c.host_out, c.stream);
+    }
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        sw = spans_workspace(c.h->spans_lines.get(spans_workspace_bytes(v.n)), v.n);
+        GX_HIP(hipMemcpyAsync(sw.image, &call->head, sizeof(SpansHead), hipMemcpyHostToDevice, c.stream));
+        GX_HIP(launch_spans_entries(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, c.b.a, call->head.formats != 0, c.b.w, sw, c.stream));
+        GX_HIP(hipMemcpyAsync(&m, sw.before + v.n, 8, hipMemcpyDeviceToHost, c.stream));
+    }
+    int read(const GroupCtx& c) {
+        gx_spans_totals& t = *call->totals;
+        if (m != c.totals->keyed) throw GxError(GX_E_ARG, "internal: " + c.name + ": the entries are not the keyed lines");
+        if (m == 0) return GX_OK;
+        if (m > SPANS_MAX) return fail(GX_E_LIMIT, c.name + ": " + std::to_string(m) + " entries; split batches of more than 2^30");
+        const uint64_t n_keys = c.b.n_keys;
+        pw = spans_pair_workspace(c.h->spans_pair.get(spans_pair_workspace_bytes(m, n_keys)), m, n_keys);
+        GX_HIP(launch_spans_pair(c.v.n, m, n_keys, spans_key_digits(n_keys, call->all_digits), c.b.w, sw, pw, &buf, c.stream));
+        GX_HIP(hipMemcpyAsync(&sd, pw.dev, sizeof(SpansDev), hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipMemcpyAsync(&n_spans, pw.sbefore + m, 8, hipMemcpyDeviceToHost, c.stream));
+        for (int q = 0; q < 4; ++q) GX_HIP(hipMemcpyAsync(&sums[q], pw.pre[q] + m, 8, hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipStreamSynchronize(c.stream));
+        if (sd.state[SPAN_S_BEGIN] != n_spans || sd.state[SPAN_S_END] != n_spans || n_spans > m / 2)
+            throw GxError(GX_E_ARG, "internal: " + c.name + ": the spans' begins and ends do not add up to the spans");
+        t.n_spans = n_spans;
+        t.superseded = sd.state[SPAN_S_SUPERSEDED];
+        t.left_open = sd.state[SPAN_S_OPEN];
+        t.orphan_ends = sd.state[SPAN_S_ORPHAN];
+        t.begins = n_spans + t.superseded + t.left_open;
+        t.ends = n_spans + t.orphan_ends;
+        if (t.begins + t.ends != m) throw GxError(GX_E_ARG, "internal: " + c.name + ": the states of the entries do not add up to them");
+        t.out_of_range = sums[1] >> 32;
+        uint64_t w[GROUP_STATS_WORDS];
+        w[GROUP_S_NUMBERS] = sums[0] & 0xFFFFFFFFull;
+        w[GROUP_S_UNSET] = sums[0] >> 32;
+        w[GROUP_S_NOT_NUMBERS] = sums[1] & 0xFFFFFFFFull;
+        w[GROUP_S_MIN] = sd.min_word;
+        w[GROUP_S_MAX] = sd.max_word;
+        w[GROUP_S_LO] = sums[2];
+        w[GROUP_S_HI] = sums[3];
+        w[GROUP_S_SPARE] = 0;
+        static_assert(sizeof(gx_measure_stats) == 64, "group_stats_out writes its eight words");
+        uint64_t st[8];
+        group_stats_out(w, st);
+        std::memcpy(&t.durations, st, sizeof(st));
+        return GX_OK;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_spans_out& b = call->out;
+        const std::string& name = c.name;
+        if (call->per_span() && n_spans > b.max_spans) return fail(GX_E_LIMIT, name + ": " + std::to_string(n_spans) + " spans, max_spans " + std::to_string(b.max_spans));
+        if (call->per_key() && c.b.n_keys > c.max_keys) return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the spans' rows ordered by (key number, end line), the keys' bounds, open lines and stats, the lines' spans and states
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const gx_spans_out& b = call->out;
+        const uint64_t n = c.v.n, n_keys = c.b.n_keys, ns = n_spans;
+        const SpansOut so{twins.of(b.span_key, ns * 4), twins.of(b.span_begin_line, ns * 4), twins.of(b.span_end_line, ns * 4), twins.of(b.span_begin, ns * 8),
+                          twins.of(b.span_end, ns * 8), twins.of(b.span_duration, ns * 8), twins.of(b.span_class, ns), twins.of(b.key_span_begin, (n_keys + 1) * 8),
+                          twins.of(reinterpret_cast<uint64_t*>(b.key_span_stats), n_keys * 64), twins.of(b.key_open_line, n_keys * 4), twins.of(b.line_span, n * 4),
+                          twins.of(b.line_state, n)};
+        if (m == 0) {   // counted lines, and none of them keyed: no key, no entry
+            if (so.key_span_begin) GX_HIP(hipMemsetAsync(so.key_span_begin, 0, (n_keys + 1) * 8, c.stream));
+            if (so.line_span) GX_HIP(hipMemsetAsync(so.line_span, 0xFF, n * 4, c.stream));
+            if (so.line_state) GX_HIP(hipMemsetAsync(so.line_state, 0, n, c.stream));
+        } else {
+            GX_HIP(launch_spans_emit(n, m, ns, n_keys, sw, pw, buf, so, c.stream));
+        }
+    }
+};
 // gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
 struct TopGroupsCall {
     uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
@@ -2388,6 +2493,7 @@ struct GroupExtras {
     std::optional<PairsCall> pairs;
     std::optional<SeriesCall> series;
     std::optional<SessionsCall> sessions;
+    std::optional<SpansCall> spans;
 };
 // The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
 // totals and checks the capacities; then the emit.  out: the caller's, device or host
@@ -2400,18 +2506,21 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     PairsRun pc{x.pairs && x.pairs->asked ? &*x.pairs : nullptr};
     SeriesRun sc{x.series && x.series->asked ? &*x.series : nullptr};
     SessionsRun ss{x.sessions && x.sessions->asked ? &*x.sessions : nullptr};
+    SpansRun sp{x.spans && x.spans->asked ? &*x.spans : nullptr};
     GroupCtx c{h, v, wi, gi.values, out64, host_out, out.max_keys, totals, stream, name};
     const uint64_t n = v.n;
     if (bk) bk.start();
     if (pc) pc.start();
     if (sc) sc.start();
     if (ss) ss.start();
+    if (sp) sp.start();
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
     totals->exact = 1;
-    const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any(), ss_out = ss && ss.call->any();
+    const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any(), ss_out = ss && ss.call->any(),
+               sp_out = sp && sp.call->any();
     const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || gq.rows || bk_out || pc_out ||
-                         sc_out || ss_out;
+                         sc_out || ss_out || sp_out;
     if (n == 0 || gi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -2421,6 +2530,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
         if (pc_out) pc.nothing(c);
         if (sc_out) sc.nothing(c);
         if (ss_out) ss.nothing(c);
+        if (sp_out) sp.nothing(c);
         return GX_OK;
     }
     GroupBuild& b = c.b;
@@ -2430,6 +2540,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (pc) pc.enqueue(c);
     if (sc) sc.enqueue(c);
     if (ss) ss.enqueue(c);
+    if (sp) sp.enqueue(c);
     b.ask(n, stream);
     GX_HIP(hipStreamSynchronize(stream));
     int rc = b.read(totals, name);
@@ -2438,6 +2549,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (pc && (rc = pc.read(c)) != GX_OK) return rc;
     if (sc && (rc = sc.read(c)) != GX_OK) return rc;
     if (ss && (rc = ss.read(c)) != GX_OK) return rc;
+    if (sp && (rc = sp.read(c)) != GX_OK) return rc;
     if (!any_out) return GX_OK;
     const uint64_t n_keys = b.n_keys, key_units = b.key_units;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || gq.rows;
@@ -2449,6 +2561,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (pc_out && (rc = pc.fits(c)) != GX_OK) return rc;
     if (sc_out && (rc = sc.fits(c)) != GX_OK) return rc;
     if (ss_out && (rc = ss.fits(c)) != GX_OK) return rc;
+    if (sp_out && (rc = sp.fits(c)) != GX_OK) return rc;
     const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
     HostTwins twins(host_out);
     const GroupOut o{twins.of(out.key_units, key_units * unit), twins.of(out.key_offsets, (n_keys + 1) * off_w), twins.of(out.key_first_line, n_keys * 4),
@@ -2459,6 +2572,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (pc_out) pc.emit(c, twins);
     if (sc_out) sc.emit(c, twins);
     if (ss_out) ss.emit(c, twins);
+    if (sp_out) sp.emit(c, twins);
     if (gq.rows) gq.emit(c, twins);
     if (host_out) {
         twins.deliver(stream);
@@ -2537,6 +2651,33 @@ static void sessions_refusals(const gx_handle* h, const GroupImage& gi, const gx
     if (ss->out.session_stats && !gi.values) throw GxError(GX_E_ARG, name + ": session_stats without a value_group");
     if (n_parts && !ss->any_number && ss->any()) throw GxError(GX_E_ARG, name + ": session outputs while every part's number group is -1");
     if (ss->out.max_sessions > SESSIONS_MAX) throw GxError(GX_E_LIMIT, name + ": max_sessions above 2^30");
+}
+
+// what gx_group_spans adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups, checked
+// against the handle and laid out with their formats by GroupHead::ext[] (gi: group_refusals'), then the roles likewise
+static void spans_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, SpansCall* sp) {
+    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) sp->head.number[q] = SPANS_NO_NUMBER;
+    if (sp->asked) sp->out = *sp->asked;
+    if (n_parts && !sp->number_groups) throw GxError(GX_E_ARG, name + ": number_groups is NULL");
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const int32_t ng = sp->number_groups[t];
+        if (ng < -1 || ng >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's number group is neither -1 nor one of its extraction's");
+        if (ng < 0) continue;
+        for (uint32_t q = 0; q < gi.head.n_parts; ++q) {
+            if (gi.head.ext[q] != static_cast<uint32_t>(parts[t].extraction)) continue;
+            sp->head.number[q] = ng;
+            sp->head.nfmt[q] = h->number_format_of(parts[t].extraction, ng);
+            if (sp->head.nfmt[q]) sp->head.formats = 1u;
+        }
+    }
+    if (n_parts && !sp->roles) throw GxError(GX_E_ARG, name + ": roles is NULL");
+    for (uint32_t t = 0; t < n_parts; ++t) {
+        const uint32_t role = sp->roles[t];
+        if (role != GX_SPAN_BEGIN && role != GX_SPAN_END) throw GxError(GX_E_ARG, name + ": a part's role is neither GX_SPAN_BEGIN nor GX_SPAN_END");
+        for (uint32_t q = 0; q < gi.head.n_parts; ++q)
+            if (gi.head.ext[q] == static_cast<uint32_t>(parts[t].extraction)) sp->head.role[q] = static_cast<uint8_t>(role);
+    }
+    if (sp->out.max_spans > SPANS_MAX) throw GxError(GX_E_LIMIT, name + ": max_spans above 2^30");
 }
 
 // what gx_lines_by_key adds to the refusals of gx_group_lines, behind them and before the look at the device
@@ -2673,6 +2814,7 @@ static void extras_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (x->pairs) pairs_refusals(h, gi, parts, n_parts, name, &*x->pairs);
     if (x->series) series_refusals(h, gi, parts, n_parts, name, &*x->series);
     if (x->sessions) sessions_refusals(h, gi, parts, n_parts, name, &*x->sessions);
+    if (x->spans) spans_refusals(h, gi, parts, n_parts, name, &*x->spans);
     if (x->by_key) by_key_refusals(*x->by_key, name);
 }
 
@@ -2912,6 +3054,37 @@ int gx_text_group_sessions(gx_handle* h, const uint8_t* text, uint64_t size, con
                            gx_sessions_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_sessions", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
                            totals ? &totals->group : nullptr, counts, n_lines, opts, sessions_extras(number_groups, max_gap, flags, sessions, totals));
+}
+
+// gx_group_spans: gx_group_lines' call with the spans behind it.  totals == NULL is refused as gx_group_lines refuses it.  The flags
+// travel without GX_BY_KEY_ALL_DIGITS (unknown bits stay in the flags and are refused there).
+static GroupExtras spans_extras(const int32_t* number_groups, const uint32_t* roles, uint32_t flags, const gx_spans_out* spans, gx_spans_totals* totals) {
+    if (totals) *totals = gx_spans_totals{};
+    SpansCall sp;
+    sp.number_groups = number_groups;
+    sp.roles = roles;
+    sp.all_digits = (flags & GX_BY_KEY_ALL_DIGITS) != 0u;
+    sp.asked = spans;
+    sp.totals = totals;
+    GroupExtras x;
+    x.spans = sp;
+    return x;
+}
+static_assert(sizeof(gx_spans_out) == 104 && sizeof(gx_spans_totals) == sizeof(gx_group_totals) + 120, "include/gorp_hip.h states these layouts");
+static_assert(GX_SPAN_BEGIN == SPAN_BEGIN && GX_SPAN_END == SPAN_END, "gx_spans.hpp states the roles again");
+
+int gx_group_spans(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                   uint32_t n_parts, const int32_t* number_groups, const uint32_t* roles, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                   const gx_group_out* keys, const gx_spans_out* spans, gx_spans_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_spans", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
+                            totals ? &totals->group : nullptr, opts, spans_extras(number_groups, roles, flags, spans, totals));
+}
+
+int gx_text_group_spans(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups,
+                        const uint32_t* roles, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_spans_out* spans,
+                        gx_spans_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_spans", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, spans_extras(number_groups, roles, flags, spans, totals));
 }
 
 // The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.

@@ -709,6 +709,61 @@ hipError_t launch_sessions_sort(uint64_t n, uint64_t m, const SortPlan& plan, ui
 hipError_t launch_sessions_emit(uint64_t n, uint64_t m, uint64_t ns, uint64_t n_keys, const SessionsWs& w, const SessionsSortWs& s, uint32_t time_buf, uint32_t key_buf,
                                 const SessionsOut& out, hipStream_t stream);
 
+// A key's BEGIN and END lines paired in input order (gx_spans.hip; the rule: gx_spans.hpp), behind launch_group_build on the same stream
+// (g.slot_of, g.head_words, g.idx_off: a key's number is idx_off[its first line]); launch_group_emit is not needed.  The passes' device
+// workspace: per line, cut out of one allocation of spans_workspace_bytes(n) bytes --
+struct SpansWs {
+    uint8_t* image;               // SpansHead (gx_spans.hpp), put there by the caller, 16-byte aligned
+    int64_t* tval;                // [n] an entry's time where its class is "number", else 0
+    uint64_t* before;             // [n + 1] the entries before line i; [n]: all of them
+    uint64_t* sums;               // the scan's
+    uint8_t* ent;                 // [n] the line is an entry (it is keyed)
+    uint8_t* tcr;                 // [n] an entry's time's class and its role (span_pack)
+    size_t bytes;
+};
+// -- and per entry and key, sized by the m entries and n_keys keys the host has read: spans_pair_workspace_bytes(m, n_keys) bytes.
+struct SpansPairWs {
+    uint8_t* dev;                 // SpansDev: the states' counts, the durations' minimum and maximum
+    BucketSortWs sort;            // (key number, line) pairs
+    uint64_t* sbefore;            // [m + 1] the span ends before entry e; [m]: the spans
+    uint64_t* sums;               // the scans'
+    uint64_t* col[4];             // [m] of a span's end: numbers | unset << 32, not_numbers | out_of_range << 32, the sum's low and high halves ...
+    uint64_t* pre[4];             // ... and [m + 1] their scans
+    uint64_t *kmin, *kmax;        // [n_keys] per key: group_min_word / group_max_word of its durations merged by maximum
+    uint8_t* state;               // [m] span_state of entry e
+    uint8_t* flag;                // [m] entry e ends a span
+    size_t bytes;
+};
+// what the emit passes write, each part optional (nullptr)
+struct SpansOut {
+    uint32_t* span_key;
+    uint32_t* span_begin_line;
+    uint32_t* span_end_line;
+    int64_t* span_begin;
+    int64_t* span_end;
+    int64_t* span_duration;
+    uint8_t* span_class;
+    uint64_t* key_span_begin;     // [n_keys + 1]
+    uint64_t* key_span_stats;     // [n_keys][8]: gx_measure_stats' fields
+    uint32_t* key_open_line;      // [n_keys]
+    uint32_t* line_span;          // [n]
+    uint8_t* line_state;          // [n]
+};
+SpansWs spans_workspace(void* ws, uint64_t n);
+size_t spans_workspace_bytes(uint64_t n);
+SpansPairWs spans_pair_workspace(void* ws, uint64_t m, uint64_t n_keys);
+size_t spans_pair_workspace_bytes(uint64_t m, uint64_t n_keys);
+// n > 0, parts > 0; formats: a number group's format is not LONG.  Behind it the host reads the entries at w.before[n].
+hipError_t launch_spans_entries(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                                bool formats, const GroupWs& g, const SpansWs& w, hipStream_t stream);
+// 0 < m <= 2^30 entries of 0 < n_keys keys; key_digits: spans_key_digits'.  Behind it the host reads SpansDev at s.dev, s.sbefore[m] and
+// s.pre[q][m].
+hipError_t launch_spans_pair(uint64_t n, uint64_t m, uint64_t n_keys, uint32_t key_digits, const GroupWs& g, const SpansWs& w, const SpansPairWs& s, uint32_t* buf,
+                             hipStream_t stream);
+// ns spans, each output within its capacity (the host has checked it); buf: launch_spans_pair's.
+hipError_t launch_spans_emit(uint64_t n, uint64_t m, uint64_t ns, uint64_t n_keys, const SpansWs& w, const SpansPairWs& s, uint32_t buf, const SpansOut& out,
+                             hipStream_t stream);
+
 // The partition of a finished batch by outcome (gx_partition.hip): the kept lines ordered by (outcome index, input line number).
 // The passes' device workspace, cut out of one allocation of partition_workspace_bytes(n, K) bytes:
 struct PartWs {

@@ -2074,6 +2074,177 @@ class Gorp:
         res["line_key"], res["line_session"] = res["line_key"][:n_lines], res["line_session"][:n_lines]
         return res, counts, n_lines
 
+    # -- begin/end spans per captured text: a key's start and end lines paired in input order (gx_group_spans / gx_text_group_spans) --
+    SPAN_ROLES = {"begin": N.GX_SPAN_BEGIN, "end": N.GX_SPAN_END, N.GX_SPAN_BEGIN: N.GX_SPAN_BEGIN, N.GX_SPAN_END: N.GX_SPAN_END}
+
+    def span_parts(self, spec):
+        """Resolves a list of (extraction, key extractor, time extractor, role[, value extractor]) into (GroupParts, int32 number groups,
+        uint32 roles): the first three and the optional fifth entry as series_parts takes a part (time None: the part's lines have a
+        key and no time, -1), role "begin" / "end" (or GX_SPAN_BEGIN / GX_SPAN_END).  A (GroupParts, numbers, roles) tuple passes
+        through."""
+        if isinstance(spec, tuple) and len(spec) == 3 and isinstance(spec[0], GroupParts):
+            return spec
+        spec = [tuple(item) for item in spec]
+        for item in spec:
+            if len(item) not in (4, 5):
+                raise ValueError("a part is (extraction, key extractor, time extractor, role[, value extractor])")
+            if item[3] not in self.SPAN_ROLES:
+                raise ValueError('role %r: "begin" or "end"' % (item[3],))
+        parts, numbers = self.series_parts([item[:3] + tuple(item[4:]) for item in spec])
+        roles = (C.c_uint32 * max(1, len(spec)))()
+        for t, item in enumerate(spec):
+            roles[t] = self.SPAN_ROLES[item[3]]
+        return parts, numbers, roles
+
+    @staticmethod
+    def _stats_dict(x):
+        return {"lines": x.lines, "numbers": x.numbers, "unset": x.unset, "not_numbers": x.not_numbers, "min": x.min if x.numbers else None,
+                "max": x.max if x.numbers else None, "sum": (x.sum_hi << 64) + x.sum_lo}
+
+    @staticmethod
+    def _spans_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(n_spans=t.n_spans, begins=t.begins, ends=t.ends, superseded=t.superseded, left_open=t.left_open, orphan_ends=t.orphan_ends,
+                 out_of_range=t.out_of_range, durations=Gorp._stats_dict(t.durations), group=Gorp._group_totals(t.group))
+        return d
+
+    SPAN_OUTPUTS = ("span_key", "span_begin_line", "span_end_line", "span_begin", "span_end", "span_duration", "span_class", "key_span_begin", "key_span_stats",
+                    "key_open_line", "line_span", "line_state")
+
+    def group_spans_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                           key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, span_key_ptr=None,
+                           span_begin_line_ptr=None, span_end_line_ptr=None, span_begin_ptr=None, span_end_ptr=None, span_duration_ptr=None, span_class_ptr=None,
+                           key_span_begin_ptr=None, key_span_stats_ptr=None, key_open_line_ptr=None, line_span_ptr=None, line_state_ptr=None, max_spans=0,
+                           spans=True, offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False,
+                           all_digits=False):
+        """gx_group_spans on device pointers (ints): group_lines_device's keys, plus the spans in the caller's buffers, each optional
+        (none at all: the size query; max_keys still sizes the table).  parts as span_parts takes them.  spans=False passes spans ==
+        NULL: the call is gx_group_lines.  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says
+        what the outputs need (n_keys, key_units, n_spans; keyed // 2 always suffices for max_spans); every other error raises."""
+        three = self.span_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_spans_out(span_key_ptr, span_begin_line_ptr, span_end_line_ptr, span_begin_ptr, span_end_ptr, span_duration_ptr, span_class_ptr,
+                             key_span_begin_ptr, key_span_stats_ptr, key_open_line_ptr, line_span_ptr, line_state_ptr, max_spans)
+        totals = N.gx_spans_totals()
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (N.GX_BY_KEY_ALL_DIGITS if all_digits else 0)
+        rc = N.lib().gx_group_spans(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, three[0].array, three[0].n, three[1], three[2], terms.array, terms.n,
+                                    flags, C.byref(keys), C.byref(out) if spans else None, C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._spans_totals(totals)
+
+    def text_group_spans_device(self, text_ptr, size, parts, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None, key_first_line_ptr=None,
+                                key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, span_key_ptr=None, span_begin_line_ptr=None,
+                                span_end_line_ptr=None, span_begin_ptr=None, span_end_ptr=None, span_duration_ptr=None, span_class_ptr=None,
+                                key_span_begin_ptr=None, key_span_stats_ptr=None, key_open_line_ptr=None, line_span_ptr=None, line_state_ptr=None, max_spans=0,
+                                spans=True, offsets64=False, stream=None, device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_text_group_spans on a device buffer (int); outputs as group_spans_device takes them (line_key, line_span and line_state:
+        one entry per line of the text).  Returns (rc, totals, counts, n_lines)."""
+        three = self.span_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_spans_out(span_key_ptr, span_begin_line_ptr, span_end_line_ptr, span_begin_ptr, span_end_ptr, span_duration_ptr, span_class_ptr,
+                             key_span_begin_ptr, key_span_stats_ptr, key_open_line_ptr, line_span_ptr, line_state_ptr, max_spans)
+        totals = N.gx_spans_totals()
+        nl = C.c_uint64(0)
+        flags = (N.GX_GROUP_WEAK_HASH if weak_hash else 0) | (N.GX_BY_KEY_ALL_DIGITS if all_digits else 0)
+        rc = N.lib().gx_text_group_spans(self._h.ptr, text_ptr, size, three[0].array, three[0].n, three[1], three[2], terms.array, terms.n, flags, C.byref(keys),
+                                         C.byref(out) if spans else None, C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._spans_totals(totals), counts, nl.value
+
+    def _spans_host(self, device_call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap, max_spans):
+        """_group_host with the span arrays beside the key arrays: the per-span ones sized by max_spans (None: half the lines, which
+        always suffices; a smaller one is grown once to what the call reported), the per-line ones by the number of lines."""
+        got = {}
+        cap_lines = max(1, n_lines_cap)
+        want = [n_lines_cap // 2 if max_spans is None else max_spans]
+
+        def call(units, ucap, koff, first, lines, stats, line_key, mk):
+            cap = max(1, want[0])
+            got.update(span_key=np.zeros(cap, np.uint32), span_begin_line=np.zeros(cap, np.uint32), span_end_line=np.zeros(cap, np.uint32),
+                       span_begin=np.zeros(cap, np.int64), span_end=np.zeros(cap, np.int64), span_duration=np.zeros(cap, np.int64),
+                       span_class=np.zeros(cap, np.uint8), key_span_begin=np.zeros(mk + 1, np.uint64), key_span_stats=(N.gx_measure_stats * max(1, mk))(),
+                       key_open_line=np.full(max(1, mk), 0xFFFFFFFF, np.uint32), line_span=np.full(cap_lines, 0xFFFFFFFF, np.uint32),
+                       line_state=np.zeros(cap_lines, np.uint8))
+            ptrs = [C.addressof(got[name]) if name == "key_span_stats" else got[name].ctypes.data for name in self.SPAN_OUTPUTS]
+            ret = device_call(units, ucap, koff, first, lines, stats, line_key, mk, *ptrs, want[0])
+            want[0] = max(want[0], ret[1]["n_spans"])
+            return ret
+        res, rest = self._group_host(call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap)
+        s, k = res["totals"]["n_spans"], res["totals"]["n_keys"]
+        for name in self.SPAN_OUTPUTS[:7]:
+            res[name] = got[name][:s]
+        res.update(key_span_begin=got["key_span_begin"][:k + 1], key_span_stats=[self._stats_dict(x) for x in got["key_span_stats"][:k]],
+                   key_open_line=got["key_open_line"][:k], line_span=got["line_span"], line_state=got["line_state"])
+        return res, rest
+
+    def group_spans(self, data, offsets, ids, rows, parts, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None, max_spans=None,
+                    weak_hash=False, all_digits=False):
+        """gx_group_spans on host buffers: group_lines' keys, and every key's BEGIN and END lines paired in input order -- Splunk's
+        `transaction id startswith= endswith=`: an END forms a SPAN with the entry just before it among its key's lines if and only if
+        that entry is a BEGIN.  parts: (extraction, key extractor, time extractor, "begin" | "end"[, value extractor]) each
+        (span_parts; time None: no time); everything else as group_lines takes it.  Returns group_lines' dict plus span_key,
+        span_begin_line, span_end_line, span_begin, span_end, span_duration, span_class (per span, ordered by (key number, end line);
+        class 0 duration, 1 unset, 2 not a number), key_span_begin (n_keys + 1), key_span_stats and key_open_line (per key; 0xFFFFFFFF:
+        no begin is left open), line_span (uint32 per input line, 0xFFFFFFFF: none), line_state (uint8 per input line: 0 no entry, 1 a
+        span's begin, 2 a span's end, 3 a begin superseded, 4 a begin left open, 5 an end without a begin) and the span totals (n_spans,
+        begins, ends, superseded, left_open, orphan_ends, out_of_range, durations) in totals."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        three = self.span_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.group_spans_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), three, where, *outs, offsets64=offsets.dtype == np.uint64,
+                                           utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8), weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._spans_host(device_call, n, three[0], data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap, max_spans)
+        res["line_key"], res["line_span"], res["line_state"] = res["line_key"][:n], res["line_span"][:n], res["line_state"][:n]
+        return res
+
+    def text_group_spans(self, text, parts, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None, max_spans=None, weak_hash=False,
+                         all_digits=False):
+        """gx_text_group_spans on a host buffer: raw text -> lines -> extraction -> group_spans.  Returns (the dict group_spans returns,
+        counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        three = self.span_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.text_group_spans_device(raw.ctypes.data if raw.size else None, raw.size, three, where, *outs, device_pointers=False, utf8=utf8,
+                                                weak_hash=weak_hash, all_digits=all_digits)
+        res, (counts, n_lines) = self._spans_host(device_call, cap_lines, three[0], np.uint8, np.uint32, keys, decode, max_keys, key_units_cap, max_spans)
+        res["line_key"], res["line_span"], res["line_state"] = res["line_key"][:n_lines], res["line_span"][:n_lines], res["line_state"][:n_lines]
+        return res, counts, n_lines
+
     # -- percentiles of a captured number per captured text (gx_group_quantiles / gx_text_group_quantiles) ------------------------
     def group_quantiles_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, quantiles, where=None, key_units_ptr=None, key_units_cap=0,
                                key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, key_quantiles_ptr=None,

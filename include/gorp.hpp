@@ -1093,6 +1093,76 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Begin/end spans per captured text (gx_group_spans): the caller's
+    //     if (r.name().equals("RequestStart")) { prev = open.put(id(r), r); if (prev != null) superseded.add(prev); }
+    //     if (r.name().equals("RequestEnd"))   { b = open.remove(id(r)); if (b == null) orphanEnds.add(r); else took.record(ts(r) - ts(b)); }
+    // -- Splunk's `transaction id startswith=... endswith=...`.  The parts of a call are seriesParts' (the NUMBER extractor is the line's
+    // TIME; an empty name, or -1: none) plus a ROLE per part: spanParts().begin("RequestStart", "id", "ts").end("RequestEnd", "id", "ts").
+    class SpanParts {
+    public:
+        explicit SpanParts(const Gorp* g) : timed_(g) {}
+        SpanParts& begin(const std::string& extraction, const std::string& key, const std::string& time = std::string(), const std::string& value = std::string()) {
+            timed_.of(extraction, key, time, value);
+            roles_.push_back(GX_SPAN_BEGIN);
+            return *this;
+        }
+        SpanParts& end(const std::string& extraction, const std::string& key, const std::string& time = std::string(), const std::string& value = std::string()) {
+            timed_.of(extraction, key, time, value);
+            roles_.push_back(GX_SPAN_END);
+            return *this;
+        }
+        SpanParts& of(size_t extraction, size_t keyGroup, int32_t timeGroup, uint32_t role, int32_t valueGroup = -1) {
+            if (role != GX_SPAN_BEGIN && role != GX_SPAN_END) throw std::invalid_argument("a role is GX_SPAN_BEGIN or GX_SPAN_END");
+            timed_.of(extraction, keyGroup, timeGroup, valueGroup);
+            roles_.push_back(role);
+            return *this;
+        }
+        const SeriesParts& timed() const { return timed_; }
+        const std::vector<uint32_t>& roles() const { return roles_; }
+
+    private:
+        SeriesParts timed_;
+        std::vector<uint32_t> roles_;
+    };
+    SpanParts spanParts() const { return SpanParts(this); }
+    // groupLines' result, plus the spans ordered by (key number, end line): per span its key's number, the input lines and the times of
+    // its two sides, its duration and its class (0 duration, 1 unset, 2 not a number); per key where its spans begin (keys.size() + 1
+    // entries), the gx_measure_stats of its spans' durations and the BEGIN line it leaves open (0xFFFFFFFF: none); per input line its
+    // span's number (0xFFFFFFFF: none) and its state (0 no entry, 1 a span's begin, 2 a span's end, 3 a begin superseded, 4 a begin left
+    // open, 5 an end without a begin).
+    struct Spans : Groups {
+        std::vector<uint32_t> spanKey, spanBeginLine, spanEndLine;
+        std::vector<int64_t> spanBegin, spanEnd, spanDuration;
+        std::vector<uint8_t> spanClass;
+        std::vector<uint64_t> keySpanBegin;
+        std::vector<gx_measure_stats> keySpanStats;
+        std::vector<uint32_t> keyOpenLine, lineSpan;
+        std::vector<uint8_t> lineState;
+        gx_spans_totals spans{};
+    };
+    Spans groupSpans(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const SpanParts& parts,
+                     const Where* where = nullptr) const {
+        return spansOf(parts, where, &n, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const uint32_t* roles, const gx_where_term* t, uint32_t nt,
+                                             const gx_group_out* out, const gx_spans_out* so, gx_spans_totals* totals) {
+            return gx_group_spans(h_, bytes, offsets, n, match_id, caps, p, np, s, roles, t, nt, 0, out, so, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same spans out (gx_text_group_spans).  counts (optional): lines per outcome index.
+    Spans textGroupSpans(const std::string& text, const SpanParts& parts, const Where* where = nullptr, std::vector<uint64_t>* counts = nullptr,
+                         uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        Spans r = spansOf(parts, where, &lines, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const uint32_t* roles, const gx_where_term* t, uint32_t nt,
+                                                    const gx_group_out* out, const gx_spans_out* so, gx_spans_totals* totals) {
+            return gx_text_group_spans(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, s, roles, t, nt, 0, out, so, totals,
+                                       counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return r;
+    }
     int maxGroups() const { return gx_max_groups(h_); }
     gx_handle* handle() const { return h_; }
 
@@ -1298,6 +1368,45 @@ private:
             r.keySessionBegin.assign(r.keys.size() + 1, 0);
             r.lineSession.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
         }
+        return r;
+    }
+    // groupsOf with the spans beside the keys: the size queries leave the spans in r.spans; the call with exactly the sizes they reported
+    // delivers both.
+    template <typename Call>
+    Spans spansOf(const SpanParts& parts, const Where* where, const uint64_t* lines, Call&& call) const {
+        Spans r;
+        const int32_t none = -1;
+        const uint32_t no_role = GX_SPAN_BEGIN;
+        const std::vector<int32_t>& numbers = parts.timed().numbers();
+        const std::vector<uint32_t>& roles = parts.roles();
+        Groups g = groupsOf(parts.timed().keys(), where, lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                                    gx_group_totals* totals) {
+            gx_spans_out so{};
+            if (out->key_offsets != nullptr) {   // (the size query before it left the sizes in r.spans)
+                const size_t m = static_cast<size_t>(r.spans.n_spans), k = static_cast<size_t>(out->max_keys);
+                r.spanKey.assign(m, 0);
+                r.spanBeginLine.assign(m, 0);
+                r.spanEndLine.assign(m, 0);
+                r.spanBegin.assign(m, 0);
+                r.spanEnd.assign(m, 0);
+                r.spanDuration.assign(m, 0);
+                r.spanClass.assign(m, 0);
+                r.keySpanBegin.assign(k + 1, 0);
+                r.keySpanStats.assign(k, gx_measure_stats{});
+                r.keyOpenLine.assign(k, 0xFFFFFFFFu);
+                r.lineSpan.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+                r.lineState.assign(static_cast<size_t>(*lines), 0);
+                so.span_key = r.spanKey.data(); so.span_begin_line = r.spanBeginLine.data(); so.span_end_line = r.spanEndLine.data();
+                so.span_begin = r.spanBegin.data(); so.span_end = r.spanEnd.data(); so.span_duration = r.spanDuration.data(); so.span_class = r.spanClass.data();
+                so.key_span_begin = r.keySpanBegin.data(); so.key_span_stats = r.keySpanStats.data(); so.key_open_line = r.keyOpenLine.data();
+                so.line_span = r.lineSpan.data(); so.line_state = r.lineState.data();
+                so.max_spans = r.spans.n_spans;
+            }
+            const int rc = call(p, np, numbers.empty() ? &none : numbers.data(), roles.empty() ? &no_role : roles.data(), t, nt, out, &so, &r.spans);
+            *totals = r.spans.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
         return r;
     }
     // groupsOf's scheme for topGroups: the size query with a table for a modest number of keys, once more with as many keys as lines if

@@ -1235,6 +1235,101 @@ int gx_text_group_sessions(gx_handle* h, const uint8_t* text, uint64_t size, con
                            const gx_group_out* keys, const gx_sessions_out* sessions, gx_sessions_totals* totals, uint64_t* counts,
                            uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- Begin/end spans per captured text: a key's start and end lines paired in input order, on the device (gx_group_spans) ----
+ * An application logs one line when work starts and another when it ends; two extractions capture the same id.  The reference's caller
+ * pairs them right behind the extraction:
+ *     r = gorp.extract(line);
+ *     if (r != null && r.name().equals("RequestStart")) { prev = open.put(id(r), r); if (prev != null) superseded.add(prev); }
+ *     if (r != null && r.name().equals("RequestEnd"))   { b = open.remove(id(r)); if (b == null) orphanEnds.add(r); else took.record(ts(r) - ts(b)); }
+ *     ... at the end: open.values() are the requests that started and never finished
+ * -- Splunk's `transaction id startswith=... endswith=...`.
+ * PARTS: gx_group_lines' parts, plus number_groups[n_parts] exactly as gx_group_sessions takes them (per part the group whose value is
+ * the line's TIME, parsed under its gx_number_format, in [0, gx_num_groups(h, extraction)), or -1), plus roles[n_parts]: per part
+ * GX_SPAN_BEGIN or GX_SPAN_END.  All parts share one key space.
+ * THE RULE: a line counts, is keyed or adds to `unset` exactly as in gx_group_lines; nothing of that call is reinterpreted.  Every keyed
+ * line is an ENTRY, and its role is its part's.  A key's entries are taken in INPUT order; time plays no part in pairing, which works
+ * with every number group -1.  An END entry forms a SPAN with the entry immediately before it among its key's entries if and only if that
+ * entry is a BEGIN.  This equals the put / remove loop above for every input, because put replaces and remove empties.  Every entry has
+ * one STATE: 1 a span's begin; 2 a span's end; 3 a BEGIN superseded (the next entry of its key is another BEGIN); 4 a BEGIN left open (it
+ * is its key's last entry); 5 an END without a begin (it is its key's first entry, or follows an END); 0: the line is no entry.
+ * DURATION: each side's time is classed as gx_top_lines classes a value -- 0 number, 1 unset (the number group is -1, or its capture
+ * names nothing), 2 not a number (the value does not parse); the span's class is the larger of the two.  With both sides numbers,
+ * duration = end - begin exactly: the difference is taken in uint64 and the order of the two times decides whether it lies in int64.  A
+ * duration outside int64 makes the span class 2 and adds to out_of_range; a negative duration (the end stamped earlier than the begin) is
+ * a number like any other.  span_begin, span_end and span_duration are 0 where they are not numbers.
+ * ORDER: spans leave ordered by (key number, input line of the end): key numbers are gx_group_lines' (first appearance), a key's spans
+ * are contiguous.
+ * IDENTITIES: keyed == begins + ends; begins == n_spans + superseded + left_open; ends == n_spans + orphan_ends; durations.lines ==
+ * n_spans; out_of_range <= durations.not_numbers.
+ * EXACT: every output is exact and the same bits on every run; ranks come from ballots, merges are integer adds, minima and maxima; no
+ * float anywhere.
+ * NOT IN SCOPE: pairing in time order, roles chosen by a captured value instead of by extraction, nested or re-entrant spans (a depth
+ * counter), carrying open begins into the next batch (key_open_line is what a caller needs for that), the spans' text as a CSR batch,
+ * quantiles of durations, ranking spans.  The rule: gorp_amd/csrc/gx_spans.hpp. */
+#define GX_SPAN_BEGIN 1u
+#define GX_SPAN_END   2u
+typedef struct gx_spans_out {         /* every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* span_key;               /* key number of span s; spans ORDERED by (span_key, span_end_line) */
+    uint32_t* span_begin_line;        /* input lines of the two sides */
+    uint32_t* span_end_line;
+    int64_t*  span_begin;             /* their times; 0 where the side's class is not 0 */
+    int64_t*  span_end;
+    int64_t*  span_duration;          /* end - begin where span_class is 0, else 0 */
+    uint8_t*  span_class;             /* 0 duration, 1 unset, 2 not a number (out of range included) */
+    uint64_t* key_span_begin;         /* n_keys + 1; capacity keys->max_keys + 1 */
+    gx_measure_stats* key_span_stats; /* per key over its spans' durations: lines = spans, numbers / unset / not_numbers by span_class, min,
+                                         max, exact 128-bit sum; capacity keys->max_keys */
+    uint32_t* key_open_line;          /* per key: the BEGIN line left open at the end of the batch, 0xFFFFFFFF: none; capacity keys->max_keys */
+    uint32_t* line_span;              /* n entries: the span a line begins or ends, 0xFFFFFFFF otherwise */
+    uint8_t*  line_state;             /* n entries: 0 .. 5 as above */
+    uint64_t  max_spans;              /* capacity of the per-span arrays; <= 2^30 */
+} gx_spans_out;
+
+typedef struct gx_spans_totals {      /* host, always */
+    gx_group_totals group;            /* exactly what gx_group_lines reports for the same call */
+    uint64_t n_spans, begins, ends, superseded, left_open, orphan_ends, out_of_range;
+    gx_measure_stats durations;       /* over all spans, as key_span_stats is per key */
+} gx_spans_totals;
+
+/* gx_group_spans: everything gx_group_lines delivers through `keys` and totals->group is delivered bit for bit.
+ * HOW THE BATCH IS READ: exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging
+ * or device_pointers; the stream).
+ * FLAGS: GX_GROUP_WEAK_HASH and GX_BY_KEY_ALL_DIGITS (the sort takes every digit: the same result, only slower).
+ * With spans == NULL the call IS gx_group_lines: the span passes do not run, and the span totals are zero.  Its arguments are still
+ * checked: number_groups == NULL or roles == NULL with n_parts > 0, a bad number group and a bad role are GX_E_ARG there too.
+ * SIZE QUERY: every output of `keys` and `spans` NULL: only *totals is filled; keys->max_keys is still read as the table's size.
+ * group.keyed / 2 is always a sufficient max_spans.
+ * GX_E_LIMIT: a per-span array (span_key, span_begin_line, span_end_line, span_begin, span_end, span_duration, span_class) with n_spans >
+ * max_spans; key_span_begin, key_span_stats or key_open_line with n_keys > keys->max_keys; max_spans > 2^30; more than 2^30 entries; and
+ * gx_group_lines' own limits.  In every one of these cases nothing is written to ANY output, the key outputs included, and *totals is
+ * filled (after the overflow of the key table and with more than 2^30 entries the span totals are zero).
+ * GX_E_ARG, in this order behind every refusal gx_group_lines makes: number_groups == NULL with n_parts > 0; a number group that is
+ * neither -1 nor one of its part's extraction's; roles == NULL with n_parts > 0; a role that is neither GX_SPAN_BEGIN nor GX_SPAN_END;
+ * unknown flag bits are among gx_group_lines' refusals.  Outputs of durations are legal when every number group is -1: every span is
+ * then class 1.  All refusals that need no device come before the device is looked at: a host-only handle gives them, and GX_E_DEVICE
+ * after them (there is no CPU path).
+ * EMPTY INPUTS: n == 0 and n_parts == 0 are legal and give all zeros (key_span_begin: its one entry; line_span: all none; line_state: all
+ * 0).
+ * HOST WAITS: TWO host waits before any output.  The wait in which gx_group_lines reads its totals also reads the entries.  n_spans
+ * exists only behind the sort: ONE more wait reads n_spans, the states' counts and totals->durations, before the key outputs are written,
+ * so that a capacity can be refused with every output untouched.  Without an entry that wait is not taken.  With host outputs a further
+ * wait delivers them.  With device_pointers the emits are left running on opts->stream when the call returns; the handle's next group
+ * call on another stream waits for them, and the batch must stay unchanged until they have run.
+ * WORKSPACE: on the handle beside gx_group_lines', until gx_destroy: 18 bytes per input line; 98 bytes per entry and 768 per 2 048
+ * entries for the sort, the states and the durations' columns; 16 bytes per key; nothing per span. */
+int gx_group_spans(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                   const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups, const uint32_t* roles,
+                   const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_spans_out* spans,
+                   gx_spans_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the spans at its end: raw text -> lines -> the match-and-extract path -> the keys
+ * and the spans.  counts and *n_lines as gx_text_group_lines delivers them; line_span and line_state hold one entry per line of the text.
+ * Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_spans(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                        const int32_t* number_groups, const uint32_t* roles, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                        const gx_group_out* keys, const gx_spans_out* spans, gx_spans_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                        const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
