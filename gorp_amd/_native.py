@@ -59,6 +59,7 @@ SYMBOLS = [
     "gx_group_series", "gx_text_group_series",
     "gx_group_sessions", "gx_text_group_sessions",
     "gx_group_spans", "gx_text_group_spans",
+    "gx_group_windows", "gx_text_group_windows",
     "gx_sort_lines", "gx_text_sort_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
@@ -197,9 +198,22 @@ class gx_spans_out(C.Structure):
                 ("key_open_line", C.c_void_p), ("line_span", C.c_void_p), ("line_state", C.c_void_p), ("max_spans", C.c_uint64)]
 
 
+class gx_windows_out(C.Structure):
+    _fields_ = [("entry_line", C.c_void_p), ("entry_key", C.c_void_p), ("entry_time", C.c_void_p), ("entry_window_lines", C.c_void_p),
+                ("entry_window_sum", C.c_void_p), ("key_entry_begin", C.c_void_p), ("key_peak_lines", C.c_void_p), ("key_peak_line", C.c_void_p),
+                ("line_window_lines", C.c_void_p), ("trip_key", C.c_void_p), ("trip_line", C.c_void_p), ("trip_time", C.c_void_p), ("trip_entry", C.c_void_p),
+                ("key_trip_begin", C.c_void_p), ("max_entries", C.c_uint64), ("max_trips", C.c_uint64)]
+
+
 class gx_sessions_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("n_sessions", C.c_uint64), ("entries", C.c_uint64), ("number_unset", C.c_uint64), ("not_numbers", C.c_uint64),
                 ("longest_lines", C.c_uint64), ("longest_duration", C.c_uint64), ("first_time", C.c_int64), ("last_time", C.c_int64)]
+
+
+class gx_windows_totals(C.Structure):
+    _fields_ = [("group", gx_group_totals), ("entries", C.c_uint64), ("number_unset", C.c_uint64), ("not_numbers", C.c_uint64), ("n_trips", C.c_uint64),
+                ("tripped_keys", C.c_uint64), ("peak_lines", C.c_uint64), ("peak_line", C.c_uint32), ("peak_key", C.c_uint32), ("first_time", C.c_int64),
+                ("last_time", C.c_int64)]
 
 
 class gx_spans_totals(C.Structure):
@@ -479,6 +493,14 @@ def lib():
                                          C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_sessions_out),
                                          C.POINTER(gx_sessions_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_sessions.restype = C.c_int
+    L.gx_group_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
+                                   C.c_int64, C.c_uint32, C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_windows_out),
+                                   C.POINTER(gx_windows_totals), C.POINTER(gx_batch_opts)]
+    L.gx_group_windows.restype = C.c_int
+    L.gx_text_group_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32), C.c_int64, C.c_uint32,
+                                        C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_windows_out),
+                                        C.POINTER(gx_windows_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_group_windows.restype = C.c_int
     L.gx_group_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_uint32), C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_spans_out),
                                  C.POINTER(gx_spans_totals), C.POINTER(gx_batch_opts)]

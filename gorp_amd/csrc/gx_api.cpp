@@ -27,6 +27,7 @@
 #include "gx_bucket.hpp"
 #include "gx_series.hpp"
 #include "gx_sessions.hpp"
+#include "gx_windows.hpp"
 #include "gx_spans.hpp"
 #include "gx_top_groups.hpp"
 #include "gx_hop.hpp"
@@ -340,6 +341,8 @@ struct gx_handle {
     // (gx_sessions.hip: SessionsWs); behind the group's wait, sized by the entries read there, the sorts' and the sessions' workspace
     // (SessionsSortWs).  Covered by group_event too
     GrowBuf sessions_lines, sessions_sort;
+    // gx_group_windows shares sessions_lines (the same keys pass); per entry and key its own (WindowsWs).  Covered by group_event too
+    GrowBuf windows_ws;
     // gx_group_spans behind gx_group_lines' build: its number groups and roles (SpansHead, gx_spans.hpp) at the head of the per-line arrays
     // (gx_spans.hip: SpansWs); behind the group's wait, sized by the entries and keys read there, the sort's and the pairing's workspace
     // (SpansPairWs).  Covered by group_event too
@@ -1997,7 +2000,7 @@ struct GroupCtx {
     uint32_t K() const { return static_cast<uint32_t>(h->T.n_rules); }
 };
 
-// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall, SessionsCall, SpansCall) and, beside each,
+// What a call built on gx_group_lines adds to group_pass: its arguments (GroupQuant, ByKeyCall, PairsCall, SeriesCall, SessionsCall, SpansCall, WindowsCall) and, beside each,
 // what it keeps while the pass runs (…Run; call == nullptr: not that call), whose steps group_pass takes in this order:
 //   start()    the call's own totals as they are when nothing has run
 //   nothing()  no lines or no parts: the results that no kernel writes
@@ -2479,6 +2482,112 @@ struct SpansRun {
         }
     }
 };
+// wc (gx_group_windows; nullptr: gx_group_lines as it is): behind the build gx_group_sessions' keys pass and its scan
+// (launch_sessions_keys, on the handle's same per-line workspace), read in the group's wait.  The trips exist only behind the two sorts
+// and the window pass, so read() enqueues them (launch_windows_pass) and takes the call's ONE further wait -- before launch_group_emit: a
+// capacity can be refused before any output is written.
+struct WindowsCall {
+    const int32_t* number_groups = nullptr;
+    int64_t window = 0;
+    uint32_t threshold = 0;
+    bool all_digits = false;
+    const gx_windows_out* asked = nullptr;   // the caller's; nullptr: the keys alone, no window passes
+    gx_windows_totals* totals = nullptr;     // (its group member is the gx_group_totals the pass fills)
+    SessionsHead head{};                     // (windows_refusals) the number group per entry of GroupHead::ext[]
+    bool any_number = false;
+    gx_windows_out out{};
+    bool per_entry() const { return out.entry_line || out.entry_key || out.entry_time || out.entry_window_lines || out.entry_window_sum; }
+    bool per_trip() const { return out.trip_key || out.trip_line || out.trip_time || out.trip_entry; }
+    bool per_key() const { return out.key_entry_begin || out.key_peak_lines || out.key_peak_line || out.key_trip_begin; }
+    bool any() const { return per_entry() || per_trip() || per_key() || out.line_window_lines; }
+};
+static gx_windows_totals windows_totals_of_nothing() {
+    gx_windows_totals t{};
+    t.peak_line = t.peak_key = GROUP_NONE;
+    return t;
+}
+struct WindowsRun {
+    const WindowsCall* call;
+    SessionsWs sw{};
+    WindowsWs ww{};
+    SessionsDev sd{};
+    WindowsDev2 wd{};
+    uint32_t time_buf = 0, key_buf = 0;
+    explicit operator bool() const { return call != nullptr; }
+    void start() const { *call->totals = windows_totals_of_nothing(); }
+    void nothing(const GroupCtx& c) const {   // no entries: the bounds' one entry and every line's 0
+        fill_out(call->out.key_entry_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.key_trip_begin, 0, 8, c.host_out, c.stream);
+        fill_out(call->out.line_window_lines, 0, c.v.n * 4, c.host_out, c.stream);
+    }
+    void enqueue(const GroupCtx& c) {
+        const BatchView& v = c.v;
+        sw = sessions_workspace(c.h->sessions_lines.get(sessions_workspace_bytes(v.n, c.values)), v.n, c.values);
+        GX_HIP(hipMemcpyAsync(sw.image, &call->head, sizeof(SessionsHead), hipMemcpyHostToDevice, c.stream));
+        GX_HIP(launch_sessions_keys(v.ids, v.fmt, v.row_units, c.K(), v.n, v.offsets, v.off64 ? 1 : 0, c.b.a, c.b.a.formats != 0 || call->head.formats != 0, c.b.w, sw,
+                                    c.stream));
+        GX_HIP(hipMemcpyAsync(&sd, sw.dev, sizeof(SessionsDev), hipMemcpyDeviceToHost, c.stream));
+    }
+    int read(const GroupCtx& c) {
+        gx_windows_totals& t = *call->totals;
+        t.entries = sd.entries;
+        t.number_unset = sd.number_unset;
+        t.not_numbers = sd.not_numbers;
+        if (sd.entries + sd.number_unset + sd.not_numbers != c.totals->keyed)
+            throw GxError(GX_E_ARG, "internal: " + c.name + ": the classes of the keyed lines do not add up to them");
+        if (sd.entries == 0) return GX_OK;
+        t.first_time = top_value(~sd.min_inv, false);
+        t.last_time = top_value(sd.max_word, false);
+        if (sd.entries > WINDOWS_MAX) return fail(GX_E_LIMIT, c.name + ": " + std::to_string(sd.entries) + " entries; split batches of more than 2^30");
+        const uint64_t m = sd.entries, n_keys = c.b.n_keys;
+        const SortPlan plan = sessions_time_plan(sd.time_or, ~sd.and_inv, m, call->all_digits);
+        const bool sums = call->out.entry_window_sum != nullptr;
+        ww = windows_workspace(c.h->windows_ws.get(windows_workspace_bytes(m, n_keys, sums)), m, n_keys, sums);
+        GX_HIP(launch_windows_pass(c.v.n, m, n_keys, plan, sessions_key_digits(n_keys, call->all_digits), call->window, call->threshold, c.b.w, sw, ww, &time_buf,
+                                   &key_buf, c.stream));
+        GX_HIP(hipMemcpyAsync(&wd, ww.dev2, sizeof(WindowsDev2), hipMemcpyDeviceToHost, c.stream));
+        GX_HIP(hipStreamSynchronize(c.stream));
+        const uint32_t peak = window_peak_lines(wd.peak_word);
+        if (wd.n_trips > m || wd.tripped_keys > wd.n_trips || wd.tripped_keys > n_keys || peak == 0 || peak > m || wd.peak_key >= n_keys)
+            throw GxError(GX_E_ARG, "internal: " + c.name + ": more trips than entries, more tripped keys than trips or keys, or entries without a peak");
+        t.n_trips = wd.n_trips;
+        t.tripped_keys = wd.tripped_keys;
+        t.peak_lines = peak;
+        t.peak_line = wd.peak_line;
+        t.peak_key = wd.peak_key;
+        return GX_OK;
+    }
+    int fits(const GroupCtx& c) const {
+        const gx_windows_out& b = call->out;
+        const std::string& name = c.name;
+        if (call->per_entry() && sd.entries > b.max_entries)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(sd.entries) + " entries, max_entries " + std::to_string(b.max_entries));
+        if (call->per_trip() && wd.n_trips > b.max_trips)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(wd.n_trips) + " trips, max_trips " + std::to_string(b.max_trips));
+        if (call->per_key() && c.b.n_keys > c.max_keys)
+            return fail(GX_E_LIMIT, name + ": " + std::to_string(c.b.n_keys) + " keys, max_keys " + std::to_string(c.max_keys));
+        return GX_OK;
+    }
+    // the entries' rows and the trips' ordered by (key number, time, line), the keys' bounds and peaks, the lines' window_lines
+    void emit(const GroupCtx& c, HostTwins& twins) const {
+        const gx_windows_out& b = call->out;
+        const uint64_t n = c.v.n, n_keys = c.b.n_keys, m = sd.entries, nt = wd.n_trips;
+        const WindowsOut wo{twins.of(b.entry_line, m * 4), twins.of(b.entry_key, m * 4), twins.of(b.entry_time, m * 8), twins.of(b.entry_window_lines, m * 4),
+                            twins.of(reinterpret_cast<uint64_t*>(b.entry_window_sum), m * 32), twins.of(b.key_entry_begin, (n_keys + 1) * 8),
+                            twins.of(b.key_peak_lines, n_keys * 4), twins.of(b.key_peak_line, n_keys * 4), twins.of(b.line_window_lines, n * 4),
+                            twins.of(b.trip_key, nt * 4), twins.of(b.trip_line, nt * 4), twins.of(b.trip_time, nt * 8), twins.of(b.trip_entry, nt * 4),
+                            twins.of(b.key_trip_begin, (n_keys + 1) * 8)};
+        if (m == 0) {   // keyed lines, and none of them an entry: every key's runs are empty and it has no peak
+            if (wo.key_entry_begin) GX_HIP(hipMemsetAsync(wo.key_entry_begin, 0, (n_keys + 1) * 8, c.stream));
+            if (wo.key_trip_begin) GX_HIP(hipMemsetAsync(wo.key_trip_begin, 0, (n_keys + 1) * 8, c.stream));
+            if (wo.key_peak_lines && n_keys) GX_HIP(hipMemsetAsync(wo.key_peak_lines, 0, n_keys * 4, c.stream));
+            if (wo.key_peak_line && n_keys) GX_HIP(hipMemsetAsync(wo.key_peak_line, 0xFF, n_keys * 4, c.stream));
+            if (wo.line_window_lines) GX_HIP(hipMemsetAsync(wo.line_window_lines, 0, n * 4, c.stream));
+        } else {
+            GX_HIP(launch_windows_emit(n, m, nt, n_keys, sw, ww, time_buf, key_buf, wo, c.stream));
+        }
+    }
+};
 // gx_top_groups: what the call adds to gx_group_lines' arguments (top_groups_pass takes group_pass' place)
 struct TopGroupsCall {
     uint32_t rank_by = 0, n_wanted = 0, smallest = 0;
@@ -2494,6 +2603,7 @@ struct GroupExtras {
     std::optional<SeriesCall> series;
     std::optional<SessionsCall> sessions;
     std::optional<SpansCall> spans;
+    std::optional<WindowsCall> windows;
 };
 // The passes on the handle's buffers (under h->mu): build, flags and scans; ONE synchronisation of the stream, where the host reads the
 // totals and checks the capacities; then the emit.  out: the caller's, device or host
@@ -2507,6 +2617,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     SeriesRun sc{x.series && x.series->asked ? &*x.series : nullptr};
     SessionsRun ss{x.sessions && x.sessions->asked ? &*x.sessions : nullptr};
     SpansRun sp{x.spans && x.spans->asked ? &*x.spans : nullptr};
+    WindowsRun wc{x.windows && x.windows->asked ? &*x.windows : nullptr};
     GroupCtx c{h, v, wi, gi.values, out64, host_out, out.max_keys, totals, stream, name};
     const uint64_t n = v.n;
     if (bk) bk.start();
@@ -2514,13 +2625,14 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (sc) sc.start();
     if (ss) ss.start();
     if (sp) sp.start();
+    if (wc) wc.start();
     if (counts) counts_beside(h, v, counts, stream);
     *totals = gx_group_totals{};
     totals->exact = 1;
     const bool bk_out = bk && bk.call->any(), pc_out = pc && pc.call->any(), sc_out = sc && sc.call->any(), ss_out = ss && ss.call->any(),
-               sp_out = sp && sp.call->any();
+               sp_out = sp && sp.call->any(), wc_out = wc && wc.call->any();
     const bool any_out = out.key_units || out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || out.line_key || gq.rows || bk_out || pc_out ||
-                         sc_out || ss_out || sp_out;
+                         sc_out || ss_out || sp_out || wc_out;
     if (n == 0 || gi.head.n_parts == 0) {
         GX_HIP(hipStreamSynchronize(stream));
         // no keys: the offsets' one entry and every line's "none"
@@ -2531,6 +2643,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
         if (sc_out) sc.nothing(c);
         if (ss_out) ss.nothing(c);
         if (sp_out) sp.nothing(c);
+        if (wc_out) wc.nothing(c);
         return GX_OK;
     }
     GroupBuild& b = c.b;
@@ -2541,6 +2654,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (sc) sc.enqueue(c);
     if (ss) ss.enqueue(c);
     if (sp) sp.enqueue(c);
+    if (wc) wc.enqueue(c);
     b.ask(n, stream);
     GX_HIP(hipStreamSynchronize(stream));
     int rc = b.read(totals, name);
@@ -2550,6 +2664,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (sc && (rc = sc.read(c)) != GX_OK) return rc;
     if (ss && (rc = ss.read(c)) != GX_OK) return rc;
     if (sp && (rc = sp.read(c)) != GX_OK) return rc;
+    if (wc && (rc = wc.read(c)) != GX_OK) return rc;
     if (!any_out) return GX_OK;
     const uint64_t n_keys = b.n_keys, key_units = b.key_units;
     const bool per_key = out.key_offsets || out.key_first_line || out.key_lines || out.key_stats || gq.rows;
@@ -2562,6 +2677,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (sc_out && (rc = sc.fits(c)) != GX_OK) return rc;
     if (ss_out && (rc = ss.fits(c)) != GX_OK) return rc;
     if (sp_out && (rc = sp.fits(c)) != GX_OK) return rc;
+    if (wc_out && (rc = wc.fits(c)) != GX_OK) return rc;
     const size_t unit = v.wide ? 2 : 1, off_w = out64 ? 8 : 4;
     HostTwins twins(host_out);
     const GroupOut o{twins.of(out.key_units, key_units * unit), twins.of(out.key_offsets, (n_keys + 1) * off_w), twins.of(out.key_first_line, n_keys * 4),
@@ -2573,6 +2689,7 @@ static int group_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, co
     if (sc_out) sc.emit(c, twins);
     if (ss_out) ss.emit(c, twins);
     if (sp_out) sp.emit(c, twins);
+    if (wc_out) wc.emit(c, twins);
     if (gq.rows) gq.emit(c, twins);
     if (host_out) {
         twins.deliver(stream);
@@ -2629,28 +2746,47 @@ static void series_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (sc->out.max_cells > SERIES_MAX_CELLS) throw GxError(GX_E_LIMIT, name + ": max_cells above 2^30");
 }
 
-// what gx_group_sessions adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups,
-// checked against the handle and laid out with their formats by GroupHead::ext[] (gi: group_refusals'), then the gap and the outputs
-static void sessions_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, SessionsCall* ss) {
-    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) ss->head.number[q] = SESSIONS_NO_NUMBER;
-    if (ss->asked) ss->out = *ss->asked;
-    if (n_parts && !ss->number_groups) throw GxError(GX_E_ARG, name + ": number_groups is NULL");
+// the number groups of gx_group_sessions and gx_group_windows: checked against the handle and laid out with their formats by
+// GroupHead::ext[] (gi: group_refusals')
+static void sessions_number_groups(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups,
+                                   const std::string& name, SessionsHead* head, bool* any_number) {
+    for (uint32_t q = 0; q < GROUP_MAX_PARTS; ++q) head->number[q] = SESSIONS_NO_NUMBER;
+    if (n_parts && !number_groups) throw GxError(GX_E_ARG, name + ": number_groups is NULL");
     for (uint32_t t = 0; t < n_parts; ++t) {
-        const int32_t ng = ss->number_groups[t];
+        const int32_t ng = number_groups[t];
         if (ng < -1 || ng >= gx_num_groups(h, parts[t].extraction)) throw GxError(GX_E_ARG, name + ": a part's number group is neither -1 nor one of its extraction's");
         if (ng < 0) continue;
-        ss->any_number = true;
+        *any_number = true;
         for (uint32_t q = 0; q < gi.head.n_parts; ++q) {
             if (gi.head.ext[q] != static_cast<uint32_t>(parts[t].extraction)) continue;
-            ss->head.number[q] = ng;
-            ss->head.nfmt[q] = h->number_format_of(parts[t].extraction, ng);
-            if (ss->head.nfmt[q]) ss->head.formats = 1u;
+            head->number[q] = ng;
+            head->nfmt[q] = h->number_format_of(parts[t].extraction, ng);
+            if (head->nfmt[q]) head->formats = 1u;
         }
     }
+}
+// what gx_group_sessions adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups, then
+// the gap and the outputs
+static void sessions_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, SessionsCall* ss) {
+    if (ss->asked) ss->out = *ss->asked;
+    sessions_number_groups(h, gi, parts, n_parts, ss->number_groups, name, &ss->head, &ss->any_number);
     if (ss->max_gap < 0) throw GxError(GX_E_ARG, name + ": max_gap below 0");
     if (ss->out.session_stats && !gi.values) throw GxError(GX_E_ARG, name + ": session_stats without a value_group");
     if (n_parts && !ss->any_number && ss->any()) throw GxError(GX_E_ARG, name + ": session outputs while every part's number group is -1");
     if (ss->out.max_sessions > SESSIONS_MAX) throw GxError(GX_E_LIMIT, name + ": max_sessions above 2^30");
+}
+
+// what gx_group_windows adds to the refusals of gx_group_lines, behind them and before the look at the device: gx_group_sessions' number
+// groups, then the window, the sums, the trips and the outputs
+static void windows_refusals(const gx_handle* h, const GroupImage& gi, const gx_group_part* parts, uint32_t n_parts, const std::string& name, WindowsCall* wc) {
+    if (wc->asked) wc->out = *wc->asked;
+    sessions_number_groups(h, gi, parts, n_parts, wc->number_groups, name, &wc->head, &wc->any_number);
+    if (wc->window < 0) throw GxError(GX_E_ARG, name + ": window below 0");
+    if (wc->out.entry_window_sum && !gi.values) throw GxError(GX_E_ARG, name + ": entry_window_sum without a value_group");
+    if (wc->threshold == 0 && (wc->per_trip() || wc->out.key_trip_begin)) throw GxError(GX_E_ARG, name + ": trip outputs with threshold 0");
+    if (n_parts && !wc->any_number && wc->any()) throw GxError(GX_E_ARG, name + ": window outputs while every part's number group is -1");
+    if (wc->out.max_entries > WINDOWS_MAX) throw GxError(GX_E_LIMIT, name + ": max_entries above 2^30");
+    if (wc->out.max_trips > WINDOWS_MAX) throw GxError(GX_E_LIMIT, name + ": max_trips above 2^30");
 }
 
 // what gx_group_spans adds to the refusals of gx_group_lines, behind them and before the look at the device: the number groups, checked
@@ -2815,6 +2951,7 @@ static void extras_refusals(const gx_handle* h, const GroupImage& gi, const gx_g
     if (x->series) series_refusals(h, gi, parts, n_parts, name, &*x->series);
     if (x->sessions) sessions_refusals(h, gi, parts, n_parts, name, &*x->sessions);
     if (x->spans) spans_refusals(h, gi, parts, n_parts, name, &*x->spans);
+    if (x->windows) windows_refusals(h, gi, parts, n_parts, name, &*x->windows);
     if (x->by_key) by_key_refusals(*x->by_key, name);
 }
 
@@ -3085,6 +3222,39 @@ int gx_text_group_spans(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         gx_spans_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_spans", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BY_KEY_ALL_DIGITS), keys,
                            totals ? &totals->group : nullptr, counts, n_lines, opts, spans_extras(number_groups, roles, flags, spans, totals));
+}
+
+// gx_group_windows: gx_group_lines' call with the windows behind it.  totals == NULL is refused as gx_group_lines refuses it.  The flags
+// travel without GX_BUCKET_ALL_DIGITS (unknown bits stay in the flags and are refused there).
+static GroupExtras windows_extras(const int32_t* number_groups, int64_t window, uint32_t threshold, uint32_t flags, const gx_windows_out* windows,
+                                  gx_windows_totals* totals) {
+    if (totals) *totals = windows_totals_of_nothing();
+    WindowsCall wc;
+    wc.number_groups = number_groups;
+    wc.window = window;
+    wc.threshold = threshold;
+    wc.all_digits = (flags & GX_BUCKET_ALL_DIGITS) != 0u;
+    wc.asked = windows;
+    wc.totals = totals;
+    GroupExtras x;
+    x.windows = wc;
+    return x;
+}
+static_assert(sizeof(gx_windows_out) == 128 && sizeof(gx_windows_totals) == sizeof(gx_group_totals) + 72 && sizeof(gx_window_sum) == sizeof(WindowSum),
+              "include/gorp_hip.h states these layouts");
+
+int gx_group_windows(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                     uint32_t n_parts, const int32_t* number_groups, int64_t window, uint32_t threshold, const gx_where_term* terms, uint32_t n_terms, uint32_t flags,
+                     const gx_group_out* keys, const gx_windows_out* windows, gx_windows_totals* totals, const gx_batch_opts* opts) {
+    return group_lines_call("gx_group_windows", h, bytes, offsets, n, ids, caps, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                            totals ? &totals->group : nullptr, opts, windows_extras(number_groups, window, threshold, flags, windows, totals));
+}
+
+int gx_text_group_windows(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups,
+                          int64_t window, uint32_t threshold, const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys,
+                          const gx_windows_out* windows, gx_windows_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
+    return text_group_call("gx_text_group_windows", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
+                           totals ? &totals->group : nullptr, counts, n_lines, opts, windows_extras(number_groups, window, threshold, flags, windows, totals));
 }
 
 // The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.

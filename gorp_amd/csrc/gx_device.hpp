@@ -708,6 +708,61 @@ hipError_t launch_sessions_sort(uint64_t n, uint64_t m, const SortPlan& plan, ui
 // 0 < ns <= m sessions, each output within its capacity (the host has checked it); time_buf / key_buf: launch_sessions_sort's.
 hipError_t launch_sessions_emit(uint64_t n, uint64_t m, uint64_t ns, uint64_t n_keys, const SessionsWs& w, const SessionsSortWs& s, uint32_t time_buf, uint32_t key_buf,
                                 const SessionsOut& out, hipStream_t stream);
+// The two halves of the above that gx_group_windows shares.  The ORDER: compact, time sort, key numbers, key sort and the gather; leaves
+// key numbers in by_key.word[*key_buf], times and lines in by_time.word[*time_buf] / .slot[*time_buf], and with head (nullptr: not
+// wanted) head[e] under max_gap.
+hipError_t launch_sessions_order(uint64_t n, uint64_t m, const SortPlan& plan, uint32_t key_digits, const GroupWs& g, const SessionsWs& w, const BucketSortWs& by_time,
+                                 const BucketSortWs& by_key, int64_t max_gap, uint8_t* head, uint32_t* time_buf, uint32_t* key_buf, hipStream_t stream);
+// The entries' values as four columns and their scans (col / pre as in SessionsSortWs); with head also the sessions' minima and maxima.
+hipError_t launch_sessions_value_prefix(const uint32_t* eline, const uint8_t* head, const uint64_t* sbefore, uint64_t m, uint64_t n, const SessionsWs& w,
+                                        uint64_t* const* col, uint64_t* const* pre, uint64_t* sums, uint64_t* smin, uint64_t* smax, hipStream_t stream);
+
+// Trailing time windows per key (gx_windows.hip; the rule: gx_windows.hpp): the lines of a key within `window` before each of its
+// entries, behind launch_sessions_keys (SessionsWs is shared as it is) and the host's read of SessionsDev.  The passes' device workspace
+// per entry and key, sized by the m entries and n_keys keys the host has read: windows_workspace_bytes(m, n_keys, sums) bytes.
+struct WindowsWs {
+    uint8_t* dev2;                // WindowsDev2: the trips, the tripped keys, the peak
+    BucketSortWs by_time;         // (time word, line) pairs; behind the sort its other buffer holds times and lines in the final order
+    BucketSortWs by_key;          // (key number, place in time order) pairs
+    uint64_t* tbefore;            // [m + 1] the trips before entry e; [m]: the trips
+    uint64_t* sums;               // the scans'
+    uint64_t* kpeak;              // [n_keys] window_peak_word merged by maximum; 0: the key has no entry
+    uint32_t* wl;                 // [m] window_lines(e)
+    uint32_t* ekey;               // [m] the entries' key numbers
+    uint32_t* tent;               // [m] the entry of trip t
+    uint32_t* tkey;               // [m] the key number of trip t
+    uint8_t* flag;                // [m] entry e trips
+    uint64_t* col[4];             // with sums: [m] numbers | unset << 32, not_numbers, the sum's low and high halves ...
+    uint64_t* pre[4];             // ... and [m + 1] their scans
+    size_t bytes;
+};
+// what the emit passes write, each part optional (nullptr)
+struct WindowsOut {
+    uint32_t* entry_line;         // [m]
+    uint32_t* entry_key;
+    int64_t* entry_time;
+    uint32_t* entry_window_lines;
+    uint64_t* entry_window_sum;   // [m][4]: gx_window_sum's fields
+    uint64_t* key_entry_begin;    // [n_keys + 1]
+    uint32_t* key_peak_lines;     // [n_keys]
+    uint32_t* key_peak_line;      // [n_keys]
+    uint32_t* line_window_lines;  // [n]
+    uint32_t* trip_key;           // [n_trips]
+    uint32_t* trip_line;
+    int64_t* trip_time;
+    uint32_t* trip_entry;
+    uint64_t* key_trip_begin;     // [n_keys + 1]
+};
+WindowsWs windows_workspace(void* ws, uint64_t m, uint64_t n_keys, bool sums);
+size_t windows_workspace_bytes(uint64_t m, uint64_t n_keys, bool sums);
+// 0 < m <= 2^30 entries of 0 < n_keys keys; plan: sessions_time_plan's; key_digits: sessions_key_digits'; window >= 0.  Behind it the host
+// reads WindowsDev2 at s.dev2.
+hipError_t launch_windows_pass(uint64_t n, uint64_t m, uint64_t n_keys, const SortPlan& plan, uint32_t key_digits, int64_t window, uint32_t threshold,
+                               const GroupWs& g, const SessionsWs& w, const WindowsWs& s, uint32_t* time_buf, uint32_t* key_buf, hipStream_t stream);
+// nt trips, each output within its capacity (the host has checked it); time_buf / key_buf: launch_windows_pass'.  out.entry_window_sum
+// needs a workspace made with sums and w.val / w.vcls.
+hipError_t launch_windows_emit(uint64_t n, uint64_t m, uint64_t nt, uint64_t n_keys, const SessionsWs& w, const WindowsWs& s, uint32_t time_buf, uint32_t key_buf,
+                               const WindowsOut& out, hipStream_t stream);
 
 // A key's BEGIN and END lines paired in input order (gx_spans.hip; the rule: gx_spans.hpp), behind launch_group_build on the same stream
 // (g.slot_of, g.head_words, g.idx_off: a key's number is idx_off[its first line]); launch_group_emit is not needed.  The passes' device

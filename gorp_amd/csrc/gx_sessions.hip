@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(256) k_sess_number(const uint32_t* __restrict_
 }
 
 // One lane per entry e of the (key, time, line) order: kword[e] its key number, pos[e] its place in the time order, where tword[] and
-// tline[] hold its time and line.  Gathers both into etime[e] / eline[e] and writes head[e].
+// tline[] hold its time and line.  Gathers both into etime[e] / eline[e] and, where head is asked for (gx_group_sessions), writes head[e].
 __global__ void __launch_bounds__(256) k_sess_heads(const uint64_t* __restrict__ kword, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ tword,
                                                     const uint32_t* __restrict__ tline, uint32_t m, int64_t max_gap, uint64_t* __restrict__ etime,
                                                     uint32_t* __restrict__ eline, uint8_t* __restrict__ head) {
@@ -200,19 +200,21 @@ __global__ void __launch_bounds__(256) k_sess_heads(const uint64_t* __restrict__
     for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < m; e += stride) {
         const uint32_t p = pos[e];
         if (p >= m) {   // (it is not: the places are 0 .. m - 1)
-            head[e] = 1;
+            if (head) head[e] = 1;
             etime[e] = 0ull;
             eline[e] = GROUP_NONE;
             continue;
         }
         const uint64_t w = tword[p];
-        bool h = true;
-        if (e > 0u) {
-            const uint32_t pp = pos[e - 1u];
-            const uint64_t pw = pp < m ? tword[pp] : 0ull;
-            h = session_head(false, static_cast<uint32_t>(kword[e - 1u]), static_cast<uint32_t>(kword[e]), pw, w, max_gap);
+        if (head) {
+            bool h = true;
+            if (e > 0u) {
+                const uint32_t pp = pos[e - 1u];
+                const uint64_t pw = pp < m ? tword[pp] : 0ull;
+                h = session_head(false, static_cast<uint32_t>(kword[e - 1u]), static_cast<uint32_t>(kword[e]), pw, w, max_gap);
+            }
+            head[e] = h ? 1 : 0;
         }
-        head[e] = h ? 1 : 0;
         etime[e] = w;
         eline[e] = tline[p];
     }
@@ -266,7 +268,8 @@ __global__ void __launch_bounds__(256) k_sess_longest(const uint32_t* __restrict
 }
 
 // One lane per entry e, a wave over 64 consecutive entries: the columns for the four scans, and the minimum and maximum of the values
-// per run of equal session number inside the wave, merged into smin[s] / smax[s] (zeroed; group_min_word / group_max_word).
+// per run of equal session number inside the wave, merged into smin[s] / smax[s] (zeroed; group_min_word / group_max_word).  head ==
+// nullptr (gx_group_windows, whose sums are over windows and not over sessions): the columns alone.
 __global__ void __launch_bounds__(256) k_sess_values(const uint32_t* __restrict__ eline, const uint8_t* __restrict__ head, const uint64_t* __restrict__ sbefore,
                                                      uint32_t m, uint64_t n, const int64_t* __restrict__ val, const uint8_t* __restrict__ vcls,
                                                      uint64_t* __restrict__ c_counts, uint64_t* __restrict__ c_nan, uint64_t* __restrict__ c_lo,
@@ -285,12 +288,13 @@ __global__ void __launch_bounds__(256) k_sess_values(const uint32_t* __restrict_
                 cls = vcls[i];
                 v = val[i];
             }
-            s = session_of(sbefore[e], head[e] != 0);
+            if (head) s = session_of(sbefore[e], head[e] != 0);
             c_counts[e] = (cls == 0u ? 1ull : 0ull) | (cls == 1u ? (1ull << 32) : 0ull);
             c_nan[e] = cls == 2u ? 1ull : 0ull;
             c_lo[e] = cls == 0u ? (static_cast<uint64_t>(v) & 0xFFFFFFFFull) : 0ull;
             c_hi[e] = cls == 0u ? static_cast<uint64_t>(stats_high(v)) : 0ull;   // (two's complement: adds as unsigned)
         }
+        if (!head) continue;   // (the same in every lane)
         // the maxima over the run of equal s that ends at this lane (the session numbers ascend along the wave); 0, "no number", is the
         // identity of the maximum, and group_stats_out looks at a word only where the session has a number
         uint64_t a = cls == 0u ? group_min_word(v) : 0ull, b = cls == 0u ? group_max_word(v) : 0ull;
@@ -474,30 +478,60 @@ hipError_t launch_sessions_keys(const void* ids, RowFormat fmt, uint32_t row_uni
 }
 
 // Behind launch_sessions_keys and the host's read of SessionsDev and of n_keys on `stream`: 0 < m <= min(n, 2^30) entries, the time
-// sort's plan and the key sort's digits.  Leaves the (key, time, line) order -- key numbers in s.by_key.word[*key_buf], times and lines
-// in s.by_time.word[*time_buf] / .slot[*time_buf] --, head[], sbefore[], start[] and SessionsDev2 at s.dev2.
+// sort's plan and the key sort's digits.  The ORDER, for gx_group_sessions and gx_group_windows alike: compact, time sort, key numbers,
+// key sort, and the gather of times and lines into it.  Leaves the (key, time, line) order -- key numbers in by_key.word[*key_buf],
+// times and lines in by_time.word[*time_buf] / .slot[*time_buf] -- and, with head (nullptr: not wanted), head[e] under max_gap.
+hipError_t launch_sessions_order(uint64_t n, uint64_t m, const SortPlan& plan, uint32_t key_digits, const GroupWs& g, const SessionsWs& w, const BucketSortWs& by_time,
+                                 const BucketSortWs& by_key, int64_t max_gap, uint8_t* head, uint32_t* time_buf, uint32_t* key_buf, hipStream_t stream) {
+    if (m == 0 || m > n || m > SESSIONS_MAX || plan.n_passes > SORT_MAX_PASSES || key_digits > BY_KEY_MAX_PASSES || max_gap < 0) return hipErrorInvalidValue;
+    const uint32_t m32 = static_cast<uint32_t>(m);
+    hipLaunchKernelGGL(k_sess_compact, dim3(line_blocks(n)), dim3(256), 0, stream, n, w.ent, w.before, w.tword, m32, by_time.word[0], by_time.slot[0]);
+    uint32_t ct = 0, ck = 0;
+    hipError_t e = sort_pairs(by_time, m32, plan.digit, plan.n_passes, stream, &ct);
+    if (e != hipSuccess) return e;
+    const unsigned eb = line_blocks(m);
+    hipLaunchKernelGGL(k_sess_number, dim3(eb), dim3(256), 0, stream, by_time.slot[ct], m32, n, g.slot_of, g.n_slots, reinterpret_cast<const u64*>(g.head_words),
+                       g.idx_off, by_key.word[0], by_key.slot[0]);
+    uint8_t kd[BY_KEY_MAX_PASSES];
+    for (uint32_t d = 0; d < key_digits; ++d) kd[d] = static_cast<uint8_t>(d);
+    e = sort_pairs(by_key, m32, kd, key_digits, stream, &ck);
+    if (e != hipSuccess) return e;
+    // (the time sort's other buffer is free: the entries' times and lines in the final order go there)
+    hipLaunchKernelGGL(k_sess_heads, dim3(eb), dim3(256), 0, stream, by_key.word[ck], by_key.slot[ck], by_time.word[ct], by_time.slot[ct], m32, max_gap,
+                       by_time.word[ct ^ 1u], by_time.slot[ct ^ 1u], head);
+    *time_buf = ct ^ 1u;
+    *key_buf = ck;
+    return hipGetLastError();
+}
+
+// The values of the entries in the (key, time, line) order as four columns and their four scans: pre[q][e] = the sum of col[q] over the
+// entries before e, for differences over any run of entries (a session, a window).  With head also the sessions' minima and maxima
+// (smin / smax zeroed by the caller).  w.val / w.vcls: the keys pass', with a value group.
+hipError_t launch_sessions_value_prefix(const uint32_t* eline, const uint8_t* head, const uint64_t* sbefore, uint64_t m, uint64_t n, const SessionsWs& w,
+                                        uint64_t* const* col, uint64_t* const* pre, uint64_t* sums, uint64_t* smin, uint64_t* smax, hipStream_t stream) {
+    if (m == 0 || m > SESSIONS_MAX || !col[0] || !w.val || !w.vcls) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sess_values, dim3(line_blocks(m)), dim3(256), 0, stream, eline, head, sbefore, static_cast<uint32_t>(m), n, w.val, w.vcls, col[0], col[1],
+                       col[2], col[3], reinterpret_cast<u64*>(smin), reinterpret_cast<u64*>(smax));
+    for (int q = 0; q < 4; ++q) {
+        const hipError_t e = launch_exclusive_scan<uint64_t>(col[q], m, sums, pre[q], stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+// Behind launch_sessions_keys and the host's read of SessionsDev and of n_keys on `stream`: the order (launch_sessions_order) with
+// head[], then sbefore[], start[] and SessionsDev2 at s.dev2.
 hipError_t launch_sessions_sort(uint64_t n, uint64_t m, const SortPlan& plan, uint32_t key_digits, int64_t max_gap, const GroupWs& g, const SessionsWs& w,
                                 const SessionsSortWs& s, uint32_t* time_buf, uint32_t* key_buf, hipStream_t stream) {
-    if (m == 0 || m > n || m > SESSIONS_MAX || plan.n_passes > SORT_MAX_PASSES || key_digits > BY_KEY_MAX_PASSES || max_gap < 0) return hipErrorInvalidValue;
+    if (m == 0 || m > n || m > SESSIONS_MAX) return hipErrorInvalidValue;
     const uint32_t m32 = static_cast<uint32_t>(m);
     hipError_t e = hipMemsetAsync(s.dev2, 0, sizeof(SessionsDev2), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sess_compact, dim3(line_blocks(n)), dim3(256), 0, stream, n, w.ent, w.before, w.tword, m32, s.by_time.word[0], s.by_time.slot[0]);
-    uint32_t ct = 0, ck = 0;
-    e = sort_pairs(s.by_time, m32, plan.digit, plan.n_passes, stream, &ct);
+    uint32_t tb = 0, ck = 0;
+    e = launch_sessions_order(n, m, plan, key_digits, g, w, s.by_time, s.by_key, max_gap, s.head, &tb, &ck, stream);
     if (e != hipSuccess) return e;
+    const uint32_t ct = tb ^ 1u;
     const unsigned eb = line_blocks(m);
-    hipLaunchKernelGGL(k_sess_number, dim3(eb), dim3(256), 0, stream, s.by_time.slot[ct], m32, n, g.slot_of, g.n_slots, reinterpret_cast<const u64*>(g.head_words),
-                       g.idx_off, s.by_key.word[0], s.by_key.slot[0]);
-    uint8_t kd[BY_KEY_MAX_PASSES];
-    for (uint32_t d = 0; d < key_digits; ++d) kd[d] = static_cast<uint8_t>(d);
-    e = sort_pairs(s.by_key, m32, kd, key_digits, stream, &ck);
-    if (e != hipSuccess) return e;
-    // (the time sort's other buffer is free: the entries' times and lines in the final order go there)
-    hipLaunchKernelGGL(k_sess_heads, dim3(eb), dim3(256), 0, stream, s.by_key.word[ck], s.by_key.slot[ck], s.by_time.word[ct], s.by_time.slot[ct], m32, max_gap,
-                       s.by_time.word[ct ^ 1u], s.by_time.slot[ct ^ 1u], s.head);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
     e = launch_exclusive_scan<uint8_t>(s.head, m, s.sums, s.sbefore, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_sess_starts, dim3(eb), dim3(256), 0, stream, s.head, s.sbefore, m32, s.start);
@@ -521,12 +555,8 @@ hipError_t launch_sessions_emit(uint64_t n, uint64_t m, uint64_t ns, uint64_t n_
         if (!s.col[0] || !w.val || !w.vcls) return hipErrorInvalidValue;
         hipError_t e = hipMemsetAsync(s.smin, 0, m * 16, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sess_values, dim3(eb), dim3(256), 0, stream, eline, s.head, s.sbefore, m32, n, w.val, w.vcls, s.col[0], s.col[1], s.col[2], s.col[3],
-                           reinterpret_cast<u64*>(s.smin), reinterpret_cast<u64*>(s.smax));
-        for (int q = 0; q < 4; ++q) {
-            e = launch_exclusive_scan<uint64_t>(s.col[q], m, s.sums, s.pre[q], stream);
-            if (e != hipSuccess) return e;
-        }
+        e = launch_sessions_value_prefix(eline, s.head, s.sbefore, m, n, w, s.col, s.pre, s.sums, s.smin, s.smax, stream);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_sess_emit, dim3(line_blocks(ns)), dim3(256), 0, stream, s.start, s.by_key.word[key_buf], etime, eline, m32, ns32,
                        stats ? s.pre[0] : nullptr, stats ? s.pre[1] : nullptr, stats ? s.pre[2] : nullptr, stats ? s.pre[3] : nullptr,

@@ -2074,6 +2074,166 @@ class Gorp:
         res["line_key"], res["line_session"] = res["line_key"][:n_lines], res["line_session"][:n_lines]
         return res, counts, n_lines
 
+    # -- trailing time windows per captured text: a key's lines within the last W before each (gx_group_windows / gx_text_group_windows) --
+    WINDOW_OUTS = ("entry_line", "entry_key", "entry_time", "entry_window_lines", "entry_window_sum", "key_entry_begin", "key_peak_lines", "key_peak_line",
+                   "line_window_lines", "trip_key", "trip_line", "trip_time", "trip_entry", "key_trip_begin")
+
+    def _windows_window(self, both, window):
+        """window as an int >= 0, taken as group_sessions takes max_gap."""
+        try:
+            return self._sessions_gap(both, window)
+        except ValueError:
+            raise ValueError("window %r: an int64 >= 0, or a text read under the first timed part's number format" % (window,)) from None
+
+    @staticmethod
+    def _windows_totals(t):
+        d = Gorp._group_totals(t.group)
+        d.update(entries=t.entries, number_unset=t.number_unset, not_numbers=t.not_numbers, n_trips=t.n_trips, tripped_keys=t.tripped_keys,
+                 peak_lines=t.peak_lines, peak_line=t.peak_line, peak_key=t.peak_key, first_time=t.first_time, last_time=t.last_time,
+                 group=Gorp._group_totals(t.group))
+        return d
+
+    def group_windows_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, window, threshold=0, where=None, key_units_ptr=None, key_units_cap=0,
+                             key_offsets_ptr=None, key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0,
+                             entry_line_ptr=None, entry_key_ptr=None, entry_time_ptr=None, entry_window_lines_ptr=None, entry_window_sum_ptr=None,
+                             key_entry_begin_ptr=None, key_peak_lines_ptr=None, key_peak_line_ptr=None, line_window_lines_ptr=None, trip_key_ptr=None,
+                             trip_line_ptr=None, trip_time_ptr=None, trip_entry_ptr=None, key_trip_begin_ptr=None, max_entries=0, max_trips=0, windows=True,
+                             offsets64=False, utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_group_windows on device pointers (ints): group_lines_device's keys, plus the windows in the caller's buffers, each optional
+        (none at all: the size query; max_keys still sizes the table).  parts as series_parts takes them: the number is the line's
+        TIME.  windows=False passes windows == NULL: the call is gx_group_lines.  Returns (rc, totals): rc is GX_OK or GX_E_LIMIT --
+        then nothing was written and totals says what the outputs need (n_keys, key_units, entries, n_trips; entries always suffices
+        for max_entries and max_trips); every other error raises."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_windows_out(entry_line_ptr, entry_key_ptr, entry_time_ptr, entry_window_lines_ptr, entry_window_sum_ptr, key_entry_begin_ptr, key_peak_lines_ptr,
+                               key_peak_line_ptr, line_window_lines_ptr, trip_key_ptr, trip_line_ptr, trip_time_ptr, trip_entry_ptr, key_trip_begin_ptr, max_entries,
+                               max_trips)
+        totals = N.gx_windows_totals()
+        rc = N.lib().gx_group_windows(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, both[0].array, both[0].n, both[1], self._windows_window(both, window),
+                                      int(threshold), terms.array, terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(keys),
+                                      C.byref(out) if windows else None, C.byref(totals), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._windows_totals(totals)
+
+    def text_group_windows_device(self, text_ptr, size, parts, window, threshold=0, where=None, key_units_ptr=None, key_units_cap=0, key_offsets_ptr=None,
+                                  key_first_line_ptr=None, key_lines_ptr=None, key_stats_ptr=None, line_key_ptr=None, max_keys=0, entry_line_ptr=None,
+                                  entry_key_ptr=None, entry_time_ptr=None, entry_window_lines_ptr=None, entry_window_sum_ptr=None, key_entry_begin_ptr=None,
+                                  key_peak_lines_ptr=None, key_peak_line_ptr=None, line_window_lines_ptr=None, trip_key_ptr=None, trip_line_ptr=None,
+                                  trip_time_ptr=None, trip_entry_ptr=None, key_trip_begin_ptr=None, max_entries=0, max_trips=0, windows=True, offsets64=False,
+                                  stream=None, device_pointers=True, utf8=False, weak_hash=False, all_digits=False):
+        """gx_text_group_windows on a device buffer (int); outputs as group_windows_device takes them (line_key and line_window_lines: one
+        entry per line of the text).  Returns (rc, totals, counts, n_lines)."""
+        both = self.series_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.stream = stream
+        o.utf8 = 1 if utf8 else 0
+        keys = N.gx_group_out(key_units_ptr, key_units_cap, key_offsets_ptr, key_first_line_ptr, key_lines_ptr, key_stats_ptr, line_key_ptr, max_keys)
+        out = N.gx_windows_out(entry_line_ptr, entry_key_ptr, entry_time_ptr, entry_window_lines_ptr, entry_window_sum_ptr, key_entry_begin_ptr, key_peak_lines_ptr,
+                               key_peak_line_ptr, line_window_lines_ptr, trip_key_ptr, trip_line_ptr, trip_time_ptr, trip_entry_ptr, key_trip_begin_ptr, max_entries,
+                               max_trips)
+        totals = N.gx_windows_totals()
+        nl = C.c_uint64(0)
+        rc = N.lib().gx_text_group_windows(self._h.ptr, text_ptr, size, both[0].array, both[0].n, both[1], self._windows_window(both, window), int(threshold),
+                                           terms.array, terms.n, self._bucket_flags(weak_hash, all_digits), C.byref(keys), C.byref(out) if windows else None,
+                                           C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o))
+        if not (rc == N.GX_E_LIMIT and totals.group.n_keys):
+            _check(rc)
+        return rc, self._windows_totals(totals), counts, nl.value
+
+    def _windows_host(self, device_call, n_lines_cap, parts, threshold, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap):
+        """_group_host with the window arrays beside the key arrays, each sized by the number of lines: no more entries than lines, no
+        more trips than entries.  The trip arrays are passed only with a threshold (threshold 0 has no trips: they come back empty)."""
+        got = {}
+        cap = max(1, n_lines_cap)
+        trips = int(threshold) != 0
+
+        def call(units, ucap, koff, first, lines, stats, line_key, mk):
+            got.update(entry_line=np.zeros(cap, np.uint32), entry_key=np.zeros(cap, np.uint32), entry_time=np.zeros(cap, np.int64),
+                       entry_window_lines=np.zeros(cap, np.uint32), entry_window_sum=np.zeros((cap, 4), np.uint64) if parts.has_values else None,
+                       key_entry_begin=np.zeros(mk + 1, np.uint64), key_peak_lines=np.zeros(max(1, mk), np.uint32),
+                       key_peak_line=np.full(max(1, mk), 0xFFFFFFFF, np.uint32), line_window_lines=np.zeros(cap, np.uint32),
+                       trip_key=np.zeros(cap, np.uint32), trip_line=np.zeros(cap, np.uint32), trip_time=np.zeros(cap, np.int64),
+                       trip_entry=np.zeros(cap, np.uint32), key_trip_begin=np.zeros(mk + 1, np.uint64))
+            ptrs = [None if got[name] is None or (not trips and (name.startswith("trip_") or name == "key_trip_begin")) else got[name].ctypes.data
+                    for name in self.WINDOW_OUTS]
+            return device_call(units, ucap, koff, first, lines, stats, line_key, mk, *ptrs, n_lines_cap, n_lines_cap)
+        res, rest = self._group_host(call, n_lines_cap, parts, unit_dtype, offsets_dtype, keys, decode, max_keys, key_units_cap)
+        m, t, k = res["totals"]["entries"], res["totals"]["n_trips"], res["totals"]["n_keys"]
+        ws = got["entry_window_sum"]
+        res.update(entry_line=got["entry_line"][:m], entry_key=got["entry_key"][:m], entry_time=got["entry_time"][:m],
+                   entry_window_lines=got["entry_window_lines"][:m], key_entry_begin=got["key_entry_begin"][:k + 1], key_peak_lines=got["key_peak_lines"][:k],
+                   key_peak_line=got["key_peak_line"][:k], line_window_lines=got["line_window_lines"], trip_key=got["trip_key"][:t],
+                   trip_line=got["trip_line"][:t], trip_time=got["trip_time"][:t], trip_entry=got["trip_entry"][:t], key_trip_begin=got["key_trip_begin"][:k + 1],
+                   entry_window_sum=None if ws is None else [{"numbers": int(x[0]), "sum": (int(x[2].astype(np.int64)) << 64) + int(x[1])} for x in ws[:m]])
+        return res, rest
+
+    def group_windows(self, data, offsets, ids, rows, parts, window, threshold=0, where=None, utf8=None, keys="list", max_keys=None, key_units_cap=None,
+                      weak_hash=False, all_digits=False):
+        """gx_group_windows on host buffers: group_lines' keys, and for every entry of a key (its lines ordered by a captured time) the
+        number of the key's lines within `window` before it, itself included -- Splunk's `streamstats time_window= count by`, fail2ban's
+        findtime -- and the TRIPS: the entries at which that count reaches `threshold` from below (0: no trips).  parts: (extraction, key
+        extractor, time extractor[, value extractor]) each (series_parts); window an int >= 0 in the time's own unit, or a text read as
+        group_sessions reads max_gap; everything else as group_lines takes it.  Returns group_lines' dict plus entry_line, entry_key,
+        entry_time, entry_window_lines, entry_window_sum (per entry, ordered by (key, time, line); the sums dicts of numbers and sum,
+        None when no part has a value extractor), key_entry_begin (n_keys + 1), key_peak_lines, key_peak_line (per key; 0 and
+        0xFFFFFFFF: no entry), line_window_lines (uint32 per input line, 0: no entry), trip_key, trip_line, trip_time, trip_entry (per
+        trip, in the same order), key_trip_begin (n_keys + 1) and the window totals (entries, number_unset, not_numbers, n_trips,
+        tripped_keys, peak_lines, peak_line, peak_key, first_time, last_time) in totals."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        both = self.series_parts(parts)
+        n = len(offsets) - 1
+        decode = (lambda u: u.tobytes().decode("utf-16-le", "surrogatepass")) if utf16 else (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.group_windows_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), both, window, threshold, where, *outs,
+                                             offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact, device_pointers=False, utf8=bool(utf8),
+                                             weak_hash=weak_hash, all_digits=all_digits)
+        res, _ = self._windows_host(device_call, n, both[0], threshold, data.dtype, offsets.dtype, keys, decode, max_keys, key_units_cap)
+        res["line_key"], res["line_window_lines"] = res["line_key"][:n], res["line_window_lines"][:n]
+        return res
+
+    def text_group_windows(self, text, parts, window, threshold=0, where=None, utf8=False, keys="list", max_keys=None, key_units_cap=None, weak_hash=False,
+                           all_digits=False):
+        """gx_text_group_windows on a host buffer: raw text -> lines -> extraction -> group_windows.  Returns (the dict group_windows
+        returns, counts uint64[2K + 2] of outcomes, n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        both = self.series_parts(parts)
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        decode = (lambda u: u.tobytes().decode("utf-8")) if utf8 else (lambda u: u.tobytes())
+
+        def device_call(*outs):
+            return self.text_group_windows_device(raw.ctypes.data if raw.size else None, raw.size, both, window, threshold, where, *outs, device_pointers=False,
+                                                  utf8=utf8, weak_hash=weak_hash, all_digits=all_digits)
+        res, (counts, n_lines) = self._windows_host(device_call, cap_lines, both[0], threshold, np.uint8, np.uint32, keys, decode, max_keys, key_units_cap)
+        res["line_key"], res["line_window_lines"] = res["line_key"][:n_lines], res["line_window_lines"][:n_lines]
+        return res, counts, n_lines
+
     # -- begin/end spans per captured text: a key's start and end lines paired in input order (gx_group_spans / gx_text_group_spans) --
     SPAN_ROLES = {"begin": N.GX_SPAN_BEGIN, "end": N.GX_SPAN_END, N.GX_SPAN_BEGIN: N.GX_SPAN_BEGIN, N.GX_SPAN_END: N.GX_SPAN_END}
 

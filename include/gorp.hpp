@@ -1093,6 +1093,47 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Trailing time windows per captured text (gx_group_windows): the caller's deque per key,
+    //     q.addLast(t);  while (t - q.peekFirst() > window) q.removeFirst();  if (q.size() >= threshold && !tripped.contains(user)) alert(...)
+    // -- Splunk's `streamstats time_window=60s count by user`, fail2ban's findtime and maxretry.  The parts are seriesParts(): the NUMBER
+    // extractor is the line's TIME.  groupLines' result, plus per entry -- ordered by (key, time, line) -- its input line, key number, time,
+    // the number of its key's entries within `window` before it (itself included) and, when a part has a value, that window's
+    // gx_window_sum; per key where its entries begin (keys.size() + 1 entries), its peak and the input line that first attains it (0 and
+    // 0xFFFFFFFF: the key has no entry); per input line its window_lines (0: the line is no entry); and the TRIPS, the entries at which the
+    // count reaches `threshold` from below (0: no trips), in the same order, with every key's run of them.
+    struct Windows : Groups {
+        std::vector<uint32_t> entryLine, entryKey, entryWindowLines;
+        std::vector<int64_t> entryTime;
+        std::vector<gx_window_sum> entryWindowSum;   // empty when no part has a value
+        std::vector<uint64_t> keyEntryBegin, keyTripBegin;
+        std::vector<uint32_t> keyPeakLines, keyPeakLine, lineWindowLines;
+        std::vector<uint32_t> tripKey, tripLine, tripEntry;
+        std::vector<int64_t> tripTime;
+        gx_windows_totals windows{};
+    };
+    Windows groupWindows(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const SeriesParts& parts,
+                         int64_t window, uint32_t threshold = 0, const Where* where = nullptr) const {
+        return windowsOf(parts, threshold, where, &n, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt,
+                                                          const gx_group_out* out, const gx_windows_out* wo, gx_windows_totals* totals) {
+            return gx_group_windows(h_, bytes, offsets, n, match_id, caps, p, np, s, window, threshold, t, nt, 0, out, wo, totals, nullptr);
+        });
+    }
+    // Whole files: raw text in, the same windows out (gx_text_group_windows).  counts (optional): lines per outcome index.
+    Windows textGroupWindows(const std::string& text, const SeriesParts& parts, int64_t window, uint32_t threshold = 0, const Where* where = nullptr,
+                             std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        Windows r = windowsOf(parts, threshold, where, &lines, [&](const gx_group_part* p, uint32_t np, const int32_t* s, const gx_where_term* t, uint32_t nt,
+                                                                   const gx_group_out* out, const gx_windows_out* wo, gx_windows_totals* totals) {
+            return gx_text_group_windows(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, s, window, threshold, t, nt, 0, out, wo, totals,
+                                         counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        if (nLines) *nLines = lines;
+        return r;
+    }
     // Begin/end spans per captured text (gx_group_spans): the caller's
     //     if (r.name().equals("RequestStart")) { prev = open.put(id(r), r); if (prev != null) superseded.add(prev); }
     //     if (r.name().equals("RequestEnd"))   { b = open.remove(id(r)); if (b == null) orphanEnds.add(r); else took.record(ts(r) - ts(b)); }
@@ -1367,6 +1408,60 @@ private:
             r.sessionEntryBegin.assign(1, 0);
             r.keySessionBegin.assign(r.keys.size() + 1, 0);
             r.lineSession.assign(static_cast<size_t>(*lines), 0xFFFFFFFFu);
+        }
+        return r;
+    }
+    // groupsOf with the windows beside the keys: the size queries leave the entries and the trips in r.windows; the call with exactly
+    // the sizes they reported delivers both.  Window outputs are asked for only where a part has a number, trip outputs only with a
+    // threshold (the C call refuses them otherwise: there is nothing they could hold).
+    template <typename Call>
+    Windows windowsOf(const SeriesParts& parts, uint32_t threshold, const Where* where, const uint64_t* lines, Call&& call) const {
+        Windows r;
+        const int32_t none = -1;
+        const std::vector<int32_t>& numbers = parts.numbers();
+        bool wanted = numbers.empty();
+        for (const int32_t s : numbers) wanted = wanted || s >= 0;
+        Groups g = groupsOf(parts.keys(), where, lines, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const gx_group_out* out,
+                                                            gx_group_totals* totals) {
+            gx_windows_out wo{};
+            if (out->key_offsets != nullptr && wanted) {   // (the size query before it left the sizes in r.windows)
+                const size_t m = static_cast<size_t>(r.windows.entries), nt_ = static_cast<size_t>(r.windows.n_trips), k = static_cast<size_t>(out->max_keys);
+                r.entryLine.assign(m, 0);
+                r.entryKey.assign(m, 0);
+                r.entryTime.assign(m, 0);
+                r.entryWindowLines.assign(m, 0);
+                if (parts.keys().hasValues()) r.entryWindowSum.assign(m, gx_window_sum{});
+                r.keyEntryBegin.assign(k + 1, 0);
+                r.keyPeakLines.assign(k, 0);
+                r.keyPeakLine.assign(k, 0xFFFFFFFFu);
+                r.lineWindowLines.assign(static_cast<size_t>(*lines), 0);
+                r.keyTripBegin.assign(k + 1, 0);
+                wo.entry_line = r.entryLine.data(); wo.entry_key = r.entryKey.data(); wo.entry_time = r.entryTime.data();
+                wo.entry_window_lines = r.entryWindowLines.data(); wo.entry_window_sum = parts.keys().hasValues() ? r.entryWindowSum.data() : nullptr;
+                wo.key_entry_begin = r.keyEntryBegin.data(); wo.key_peak_lines = r.keyPeakLines.data(); wo.key_peak_line = r.keyPeakLine.data();
+                wo.line_window_lines = r.lineWindowLines.data();
+                if (threshold != 0) {
+                    r.tripKey.assign(nt_, 0);
+                    r.tripLine.assign(nt_, 0);
+                    r.tripTime.assign(nt_, 0);
+                    r.tripEntry.assign(nt_, 0);
+                    wo.trip_key = r.tripKey.data(); wo.trip_line = r.tripLine.data(); wo.trip_time = r.tripTime.data(); wo.trip_entry = r.tripEntry.data();
+                    wo.key_trip_begin = r.keyTripBegin.data();
+                }
+                wo.max_entries = r.windows.entries;
+                wo.max_trips = r.windows.n_trips;
+            }
+            const int rc = call(p, np, numbers.empty() ? &none : numbers.data(), t, nt, out, &wo, &r.windows);
+            *totals = r.windows.group;
+            return rc;
+        });
+        static_cast<Groups&>(r) = std::move(g);
+        if (!wanted) {
+            r.keyEntryBegin.assign(r.keys.size() + 1, 0);
+            r.keyTripBegin.assign(r.keys.size() + 1, 0);
+            r.keyPeakLines.assign(r.keys.size(), 0);
+            r.keyPeakLine.assign(r.keys.size(), 0xFFFFFFFFu);
+            r.lineWindowLines.assign(static_cast<size_t>(*lines), 0);
         }
         return r;
     }

@@ -1330,6 +1330,117 @@ int gx_text_group_spans(gx_handle* h, const uint8_t* text, uint64_t size, const 
                         const gx_group_out* keys, const gx_spans_out* spans, gx_spans_totals* totals, uint64_t* counts, uint64_t* n_lines,
                         const gx_batch_opts* opts);
 
+/* ---- Trailing time windows per captured text: a key's lines within the last W before each of them, on the device (gx_group_windows) ----
+ * The question most log alerts ask -- five failed logins of one user within 60 s; more than 100 requests of one client within a second.
+ * The reference's caller keeps a deque per key right behind the extraction:
+ *     Deque<Long> q = recent.computeIfAbsent(r.asMap().get("user"), k -> new ArrayDeque<>());
+ *     q.addLast(t);  while (t - q.peekFirst() > window) q.removeFirst();
+ *     if (q.size() >= threshold && !tripped.contains(user)) alert(...)
+ * -- Splunk's `streamstats time_window=60s count by user`; SQL's COUNT(*) OVER (PARTITION BY user ORDER BY ts RANGE BETWEEN 60000
+ * PRECEDING AND CURRENT ROW); fail2ban's findtime and maxretry.  gx_group_series splits a burst that straddles an interval's edge;
+ * gx_group_sessions chains lines that are each close to the next.  A sliding window depends on every entry's own place in its key's
+ * time order.
+ * PARTS: gx_group_lines' parts, plus number_groups[n_parts] exactly as gx_group_sessions takes them.  All parts share one key space.
+ * THE RULE: a line counts, is keyed or adds to `unset` exactly as in gx_group_lines; a keyed line is an ENTRY exactly as in
+ * gx_group_sessions: keyed == entries + number_unset + not_numbers.  Key j's entries are ordered by (time ascending, input line
+ * ascending).  window is an int64 >= 0 in the time's own unit.  Entry e's WINDOW is the entries f of the same key with f <= e in that
+ * order and time(e) - time(f) <= window.  The comparison is exact for every pair of int64: f <= e gives time(f) <= time(e), so (uint64)
+ * time(e) - (uint64) time(f) is the true difference, compared unsigned with (uint64) window; window = INT64_MAX still keeps INT64_MIN out
+ * of INT64_MAX's window; window = 0 is the entries of the same time up to e.  An entry of the same time and a later input line is NOT in
+ * e's window (the caller's loop has not seen it yet).  The window is the contiguous run of entries [e - window_lines + 1, e];
+ * window_lines >= 1.
+ * TRIPS: threshold is a uint32, 0: no trips.  Entry e TRIPS when window_lines(e) >= threshold and e is its key's first entry or
+ * window_lines(e - 1) < threshold: the edge, not the level.  A key trips again after its count fell below the threshold.  With
+ * threshold 1 exactly the first entry of every key that has entries trips.
+ * PEAK: a key's peak is the largest window_lines among its entries, its peak_line the input line of the FIRST entry in the order that
+ * attains it; the totals' peak is the same over all entries (ties: the smallest entry index).
+ * WINDOW SUMS: where a part has a value_group, an entry's window sum is over the window's entries whose value parsed: their count and
+ * the exact 128-bit sum.
+ * ORDER: entries and trips leave ordered by (key number, time, input line): key numbers are gx_group_lines' (first appearance).
+ * EXACT: every output is exact and the same bits on every run; ranks come from ballots, merges are integer adds and maxima; no float
+ * anywhere.
+ * NOT IN SCOPE: windows by number of entries (streamstats window=N), centred or leading windows, window min / max / quantiles, a trip's
+ * lines as a new CSR batch, windows over all keys together, state carried from one batch into the next.  The rule:
+ * gorp_amd/csrc/gx_windows.hpp. */
+typedef struct gx_window_sum {
+    uint64_t numbers;                 /* the window's entries whose value parsed */
+    uint64_t sum_lo;                  /* their exact sum: sum_hi * 2^64 + sum_lo, two's complement */
+    int64_t  sum_hi;
+    uint64_t reserved;                /* 0 */
+} gx_window_sum;
+
+typedef struct gx_windows_out {       /* every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* entry_line;             /* [entries] input lines in (key, time, line) order */
+    uint32_t* entry_key;              /* [entries] */
+    int64_t*  entry_time;             /* [entries] */
+    uint32_t* entry_window_lines;     /* [entries] >= 1; entry e's window is entries [e - lines + 1, e] */
+    gx_window_sum* entry_window_sum;  /* [entries]; NULL where no part has a value_group */
+    uint64_t* key_entry_begin;        /* n_keys + 1; capacity keys->max_keys + 1 */
+    uint32_t* key_peak_lines;         /* n_keys; 0: the key has no entry */
+    uint32_t* key_peak_line;          /* n_keys; 0xFFFFFFFF: none */
+    uint32_t* line_window_lines;      /* n: 0 for a line that is no entry */
+    uint32_t* trip_key;               /* [n_trips] trips ORDERED by (key number, time, line) */
+    uint32_t* trip_line;              /* [n_trips] input line of the entry that tripped */
+    int64_t*  trip_time;              /* [n_trips] */
+    uint32_t* trip_entry;             /* [n_trips] its index among the entries */
+    uint64_t* key_trip_begin;         /* n_keys + 1; capacity keys->max_keys + 1 */
+    uint64_t  max_entries;            /* capacity of the per-entry arrays; <= 2^30 */
+    uint64_t  max_trips;              /* capacity of the per-trip arrays; <= 2^30 */
+} gx_windows_out;
+
+typedef struct gx_windows_totals {    /* host, always */
+    gx_group_totals group;            /* exactly what gx_group_lines reports for the same call */
+    uint64_t entries, number_unset, not_numbers;
+    uint64_t n_trips, tripped_keys;   /* tripped_keys: the keys with at least one trip */
+    uint64_t peak_lines;              /* the largest window_lines; 0 without an entry */
+    uint32_t peak_line, peak_key;     /* input line and key number of the first entry that attains it; 0xFFFFFFFF without an entry */
+    int64_t  first_time, last_time;   /* over all entries; 0 without one */
+} gx_windows_totals;
+
+/* gx_group_windows: everything gx_group_lines delivers through `keys` and totals->group is delivered bit for bit.
+ * HOW THE BATCH IS READ: exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging
+ * or device_pointers; the stream).
+ * FLAGS: GX_GROUP_WEAK_HASH and GX_BUCKET_ALL_DIGITS (both sorts take every digit: the same result, only slower).
+ * With windows == NULL the call IS gx_group_lines: the window passes do not run, and the window totals are zero (the peak's line and
+ * key: 0xFFFFFFFF).  Its arguments are still checked: number_groups == NULL with n_parts > 0, a bad number group and window < 0 are
+ * GX_E_ARG there too.
+ * SIZE QUERY: every output of `keys` and `windows` NULL: only *totals is filled; keys->max_keys is still read as the table's size.
+ * entries is always a sufficient max_entries and max_trips.
+ * GX_E_LIMIT: a per-entry array (entry_line, entry_key, entry_time, entry_window_lines, entry_window_sum) with entries > max_entries; a
+ * per-trip array (trip_key, trip_line, trip_time, trip_entry) with n_trips > max_trips; a per-key array (key_entry_begin,
+ * key_peak_lines, key_peak_line, key_trip_begin) with n_keys > keys->max_keys; max_entries or max_trips > 2^30; more than 2^30 entries;
+ * and gx_group_lines' own limits.  In every one of these cases nothing is written to ANY output, the key outputs included, and *totals
+ * is filled (after the overflow of the key table the window totals are zero; with more than 2^30 entries the trips and the peak are;
+ * with a capacity above 2^30 all of *totals is, since that refusal comes before the device is looked at).
+ * GX_E_ARG, in this order behind every refusal gx_group_lines makes: number_groups == NULL with n_parts > 0; a number group that is
+ * neither -1 nor one of its part's extraction's; window < 0; entry_window_sum where no part has a value group; a trip output
+ * (trip_key, trip_line, trip_time, trip_entry, key_trip_begin) with threshold == 0; an output of `windows` given while n_parts > 0 and
+ * every number group is -1; unknown flag bits are among gx_group_lines' refusals.  All refusals that need no device come before the
+ * device is looked at: a host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).
+ * EMPTY INPUTS: n == 0 and n_parts == 0 are legal and give all zeros (key_entry_begin and key_trip_begin: their one entry;
+ * line_window_lines: all 0).
+ * HOST WAITS: TWO host waits before any output.  The wait in which gx_group_lines reads its totals also reads entries, number_unset,
+ * not_numbers, first_time, last_time and the OR and AND of the times, from which the time sort's digits are planned.  The trips exist
+ * only behind the two sorts and the window pass: ONE more wait reads n_trips, tripped_keys and the peak, before the key outputs are
+ * written, so that a capacity can be refused with every output untouched.  Without an entry that wait is not taken.  With host outputs
+ * a further wait delivers them.  With device_pointers the emits are left running on opts->stream when the call returns; the handle's
+ * next group call on another stream waits for them, and the batch must stay unchanged until they have run.
+ * WORKSPACE: on the handle beside gx_group_lines', until gx_destroy: 17 bytes per input line (26 with a value group), shared with
+ * gx_group_sessions; 73 bytes per entry and 1 536 per 2 048 entries for the sorts, the window pass and the trips; 8 bytes per key; with
+ * entry_window_sum 64 more per entry. */
+int gx_group_windows(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                     const gx_group_part* parts, uint32_t n_parts, const int32_t* number_groups, int64_t window, uint32_t threshold,
+                     const gx_where_term* terms, uint32_t n_terms, uint32_t flags, const gx_group_out* keys, const gx_windows_out* windows,
+                     gx_windows_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the windows at its end: raw text -> lines -> the match-and-extract path -> the
+ * keys and the windows.  counts and *n_lines as gx_text_group_lines delivers them; line_window_lines holds one entry per line of the
+ * text.  Like every gx_text_* call it returns with all its work on opts->stream done. */
+int gx_text_group_windows(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                          const int32_t* number_groups, int64_t window, uint32_t threshold, const gx_where_term* terms, uint32_t n_terms,
+                          uint32_t flags, const gx_group_out* keys, const gx_windows_out* windows, gx_windows_totals* totals, uint64_t* counts,
+                          uint64_t* n_lines, const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
