@@ -60,6 +60,7 @@ SYMBOLS = [
     "gx_group_sessions", "gx_text_group_sessions",
     "gx_group_spans", "gx_text_group_spans",
     "gx_group_windows", "gx_text_group_windows",
+    "gx_lookup_lines", "gx_text_lookup_lines",
     "gx_sort_lines", "gx_text_sort_lines",
     "gx_set_number_format", "gx_get_number_format", "gx_parse_number",
 ]
@@ -214,6 +215,21 @@ class gx_windows_totals(C.Structure):
     _fields_ = [("group", gx_group_totals), ("entries", C.c_uint64), ("number_unset", C.c_uint64), ("not_numbers", C.c_uint64), ("n_trips", C.c_uint64),
                 ("tripped_keys", C.c_uint64), ("peak_lines", C.c_uint64), ("peak_line", C.c_uint32), ("peak_key", C.c_uint32), ("first_time", C.c_int64),
                 ("last_time", C.c_int64)]
+
+
+GX_LOOKUP_NONE, GX_LOOKUP_MISS = 0xFFFFFFFF, 0xFFFFFFFE
+GX_LOOKUP_KEEP_NOTHING, GX_LOOKUP_KEEP_HITS, GX_LOOKUP_KEEP_OTHERS = range(3)
+
+
+class gx_lookup_out(C.Structure):
+    _fields_ = [("line_entry", C.c_void_p), ("entry_same", C.c_void_p), ("entry_lines", C.c_void_p), ("entry_first_line", C.c_void_p),
+                ("entry_stats", C.c_void_p), ("out_index", C.c_void_p), ("out_bytes", C.c_void_p), ("out_offsets", C.c_void_p), ("out_ids", C.c_void_p),
+                ("out_caps", C.c_void_p), ("cap_lines", C.c_uint64), ("out_bytes_cap", C.c_uint64)]
+
+
+class gx_lookup_totals(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("distinct_entries", C.c_uint64), ("hit_entries", C.c_uint64), ("lines", C.c_uint64), ("keyed", C.c_uint64),
+                ("unset", C.c_uint64), ("hits", C.c_uint64), ("misses", C.c_uint64), ("lines_out", C.c_uint64), ("units_out", C.c_uint64)]
 
 
 class gx_spans_totals(C.Structure):
@@ -501,6 +517,14 @@ def lib():
                                         C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_windows_out),
                                         C.POINTER(gx_windows_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
     L.gx_text_group_windows.restype = C.c_int
+    L.gx_lookup_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32,
+                                  C.POINTER(gx_where_term), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(gx_lookup_out),
+                                  C.POINTER(gx_lookup_totals), C.POINTER(gx_batch_opts)]
+    L.gx_lookup_lines.restype = C.c_int
+    L.gx_text_lookup_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(gx_where_term), C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(gx_lookup_out), C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.POINTER(gx_lookup_totals), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(gx_batch_opts)]
+    L.gx_text_lookup_lines.restype = C.c_int
     L.gx_group_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(gx_group_part), C.c_uint32, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_uint32), C.POINTER(gx_where_term), C.c_uint32, C.c_uint32, C.POINTER(gx_group_out), C.POINTER(gx_spans_out),
                                  C.POINTER(gx_spans_totals), C.POINTER(gx_batch_opts)]

@@ -19,8 +19,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgorp_hip.so")
 LIB_DEV = os.path.join(HERE, "libgorp_hip_dev.so")
 SOURCES = ["gx_tile_lds.hip", "gx_tile_l2.hip", "gx_tile_rec.hip", "gx_tile_recg.hip", "gx_tile_lds_w.hip", "gx_tile_hop.hip", "gx_tile_hop_w.hip", "gx_hop.cpp", "gx_images.cpp", "gx_kernels.hip", "gx_lanes.hip", "gx_jsonl.hip", "gx_api.cpp",
-           "gx_compile.cpp", "gx_dsl.cpp", "gx_json.cpp", "gx_regex.cpp", "gx_host.cpp", "gx_tile.hip", "gx_ingest.hip", "gx_service.hip", "gx_select.hip", "gx_utf8.hip", "gx_partition.hip", "gx_where.hip", "gx_stats.hip", "gx_group.hip", "gx_top.hip", "gx_quantile.hip", "gx_group_quantile.hip", "gx_top_groups.hip", "gx_by_key.hip", "gx_pairs.hip", "gx_bucket.hip", "gx_series.hip", "gx_sort.hip", "gx_sessions.hip", "gx_spans.hip", "gx_windows.hip"]   # (the long ones first)
-HEADERS = ["gx_common.hpp", "gx_compile.hpp", "gx_device.hpp", "gx_dsl.hpp", "gx_walk.hpp", "gx_tile_body.hpp", "gx_hop.hpp", "gx_hop_dev.hpp", "gx_layout.hpp", "gx_rows.hpp", "gx_images.hpp", "gx_slots.hpp", "gx_scan.hpp", "gx_utf8.hpp", "gx_outcome.hpp", "gx_where.hpp", "gx_where_dev.hpp", "gx_stats.hpp", "gx_group.hpp", "gx_top.hpp", "gx_quantile.hpp", "gx_group_quantile.hpp", "gx_radix_dev.hpp", "gx_group_dev.hpp", "gx_top_groups.hpp", "gx_by_key.hpp", "gx_pairs.hpp", "gx_bucket.hpp", "gx_bucket_sort_dev.hpp", "gx_series.hpp", "gx_sort.hpp", "gx_sessions.hpp", "gx_spans.hpp", "gx_windows.hpp",
+           "gx_compile.cpp", "gx_dsl.cpp", "gx_json.cpp", "gx_regex.cpp", "gx_host.cpp", "gx_tile.hip", "gx_ingest.hip", "gx_service.hip", "gx_select.hip", "gx_utf8.hip", "gx_partition.hip", "gx_where.hip", "gx_stats.hip", "gx_group.hip", "gx_top.hip", "gx_quantile.hip", "gx_group_quantile.hip", "gx_top_groups.hip", "gx_by_key.hip", "gx_pairs.hip", "gx_bucket.hip", "gx_series.hip", "gx_sort.hip", "gx_sessions.hip", "gx_spans.hip", "gx_windows.hip", "gx_lookup.hip"]   # (the long ones first)
+HEADERS = ["gx_common.hpp", "gx_compile.hpp", "gx_device.hpp", "gx_dsl.hpp", "gx_walk.hpp", "gx_tile_body.hpp", "gx_hop.hpp", "gx_hop_dev.hpp", "gx_layout.hpp", "gx_rows.hpp", "gx_images.hpp", "gx_slots.hpp", "gx_scan.hpp", "gx_utf8.hpp", "gx_outcome.hpp", "gx_where.hpp", "gx_where_dev.hpp", "gx_stats.hpp", "gx_group.hpp", "gx_top.hpp", "gx_quantile.hpp", "gx_group_quantile.hpp", "gx_radix_dev.hpp", "gx_group_dev.hpp", "gx_top_groups.hpp", "gx_by_key.hpp", "gx_pairs.hpp", "gx_bucket.hpp", "gx_bucket_sort_dev.hpp", "gx_series.hpp", "gx_sort.hpp", "gx_sessions.hpp", "gx_spans.hpp", "gx_windows.hpp", "gx_lookup.hpp",
            os.path.join("..", "..", "include", "gorp_hip.h")]
 
 

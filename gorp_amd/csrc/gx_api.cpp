@@ -23,6 +23,7 @@
 #include "gx_dsl.hpp"
 #include "gx_group.hpp"
 #include "gx_group_quantile.hpp"
+#include "gx_lookup.hpp"
 #include "gx_pairs.hpp"
 #include "gx_bucket.hpp"
 #include "gx_series.hpp"
@@ -349,6 +350,12 @@ struct gx_handle {
     GrowBuf spans_lines, spans_pair;
     Event group_event;
     bool group_pending = false;
+    // gx_lookup_lines: its parts and terms on the device (GroupHead; WhereHead behind it), the dictionary's slots' words and the per-entry
+    // and per-line arrays (gx_lookup.hip: LookupWs).  Used under `mu`.  With device pointers the emit is left running on the caller's
+    // stream: the next call's stream waits for lookup_event first (its copy pass reads select_ws: select_event likewise).
+    GrowBuf lookup_image, lookup_table, lookup_lines;
+    Event lookup_event;
+    bool lookup_pending = false;
     // gx_bucket_lines: its parts and terms on the device (BucketHead, gx_bucket.hpp; WhereHead behind it), the slots' words and arrays,
     // the lines' slots and the sort's workspace (gx_bucket.hip).  Used under `mu`.  With device pointers the sort and the emit are left
     // running on the caller's stream: the next call's stream waits for bucket_event first.
@@ -3255,6 +3262,241 @@ int gx_text_group_windows(gx_handle* h, const uint8_t* text, uint64_t size, cons
                           const gx_windows_out* windows, gx_windows_totals* totals, uint64_t* counts, uint64_t* n_lines, const gx_batch_opts* opts) {
     return text_group_call("gx_text_group_windows", h, text, size, parts, n_parts, terms, n_terms, flags & ~static_cast<uint32_t>(GX_BUCKET_ALL_DIGITS), keys,
                            totals ? &totals->group : nullptr, counts, n_lines, opts, windows_extras(number_groups, window, threshold, flags, windows, totals));
+}
+
+// gx_lookup_lines: what the call adds to gx_group_lines' parts, terms and flags -- the dictionary, keep, the outputs (the text form: its
+// three kept outputs in the batch pointers' places) and the totals.
+struct LookupCall {
+    const void* entry_units = nullptr;
+    const void* entry_offsets = nullptr;
+    uint64_t m = 0;
+    uint32_t keep = 0;
+    gx_lookup_out out{};
+    gx_lookup_totals* totals = nullptr;
+    bool per_line() const { return out.out_index || out.out_offsets || out.out_ids || out.out_caps; }
+    bool batch_out() const { return per_line() || out.out_bytes; }
+    bool per_entry() const { return out.entry_same || out.entry_lines || out.entry_first_line || out.entry_stats; }
+    bool any() const { return batch_out() || per_entry() || out.line_entry; }
+};
+static_assert(sizeof(gx_lookup_out) == 96 && sizeof(gx_lookup_totals) == 80, "include/gorp_hip.h states these layouts");
+static_assert(GX_LOOKUP_NONE == LOOKUP_NONE && GX_LOOKUP_MISS == LOOKUP_MISS && GX_LOOKUP_KEEP_HITS == LOOKUP_KEEP_HITS && GX_LOOKUP_KEEP_OTHERS == LOOKUP_KEEP_OTHERS,
+              "gx_lookup.hpp states the sentinels and keep again");
+
+// what both lookup calls refuse before they look at the device: gx_group_lines' refusals of totals, flags, parts, options and terms, then
+// the call's own
+static void lookup_refusals(const gx_handle* h, const gx_batch_opts& o, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                            uint32_t flags, bool wide, const LookupCall& c, const std::string& name, GroupImage* gi, WhereImage* wi) {
+    gx_group_totals unused{};
+    group_refusals(h, o, parts, n_parts, terms, n_terms, flags, wide, gx_group_out{}, c.totals ? &unused : nullptr, name, gi, wi);
+    if (c.out.entry_stats && !gi->values) throw GxError(GX_E_ARG, name + ": entry_stats without a value_group");
+    if (c.keep >= LOOKUP_KEEPS) throw GxError(GX_E_ARG, name + ": keep is not one of GX_LOOKUP_KEEP_NOTHING .. GX_LOOKUP_KEEP_OTHERS");
+    if (c.keep == LOOKUP_KEEP_NOTHING && c.batch_out()) throw GxError(GX_E_ARG, name + ": outputs for kept lines with GX_LOOKUP_KEEP_NOTHING");
+}
+// ... and behind the refusals that only the batch form makes: the dictionary's own.  Host offsets are read here.  Returns the units the
+// offsets name, [first, last) (device offsets: unknown, 0 and 0).
+static std::pair<uint64_t, uint64_t> lookup_dict_refusals(const gx_batch_opts& o, const LookupCall& c, const std::string& name) {
+    if (c.m && !c.entry_offsets) throw GxError(GX_E_ARG, name + ": entry_offsets is NULL");
+    if (c.m > LOOKUP_MAX_ENTRIES) throw GxError(GX_E_LIMIT, name + ": more than 2^30 entries");
+    if (o.device_pointers || c.m == 0) return {0, 0};
+    const HostOffsets eo{c.entry_offsets, o.offsets64 != 0, c.m};
+    for (uint64_t j = 0; j < c.m; ++j)
+        if (eo[j + 1] - eo[j] > 0xFFFFFFFFull) throw GxError(GX_E_LIMIT, name + ": an entry of 4 G code units or more (or entry offsets that go backwards)");
+    if (eo[c.m] > eo[0] && !c.entry_units) throw GxError(GX_E_ARG, name + ": entry_units is NULL");
+    return {eo[0], eo[c.m]};
+}
+// the dictionary's ranges as by_key_overlaps takes inputs (device offsets: the units' length is not known -- their first byte stands for them)
+static void lookup_dict_ranges(const gx_batch_opts& o, const LookupCall& c, std::pair<uint64_t, uint64_t> units, std::pair<const void*, uint64_t>* ins) {
+    const uint64_t un = o.utf16 ? 2 : 1, ow = o.offsets64 ? 8 : 4;
+    ins[0] = {c.m ? c.entry_offsets : nullptr, (c.m + 1) * ow};
+    if (o.device_pointers) ins[1] = {c.m ? c.entry_units : nullptr, 1};
+    else ins[1] = {c.entry_units ? static_cast<const uint8_t*>(c.entry_units) + units.first * un : nullptr, (units.second - units.first) * un};
+}
+
+// The dictionary on the device: the caller's own pointers (device_pointers), or copies that live as long as this object -- the offsets as
+// they are, and the units they name, [first, last), so that d.units + offsets[j] is entry j wherever offsets[0] lies.
+namespace {
+struct StagedDict {
+    LookupDict d{};
+    DevMem<> units, offsets;
+};
+}  // namespace
+static StagedDict stage_dict(const LookupCall& c, const gx_batch_opts& o, std::pair<uint64_t, uint64_t> named, uint32_t flags, hipStream_t stream) {
+    StagedDict s;
+    s.d = LookupDict{c.entry_units, c.entry_offsets, o.offsets64 ? 1 : 0, c.m, (flags & GX_GROUP_WEAK_HASH) ? 1u : 0u};
+    if (o.device_pointers || c.m == 0) return s;
+    const size_t ow = o.offsets64 ? 8 : 4, un = o.utf16 ? 2 : 1;
+    const size_t bytes = static_cast<size_t>(named.second - named.first) * un;
+    s.offsets = dev_alloc((c.m + 1) * ow);
+    s.units = dev_alloc(bytes);
+    GX_HIP(hipMemcpyAsync(s.offsets.get(), c.entry_offsets, (c.m + 1) * ow, hipMemcpyHostToDevice, stream));
+    if (bytes) GX_HIP(hipMemcpyAsync(s.units.get(), static_cast<const uint8_t*>(c.entry_units) + named.first * un, bytes, hipMemcpyHostToDevice, stream));
+    s.d.offsets = s.offsets.get();
+    s.d.units = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(s.units.get()) - static_cast<uintptr_t>(named.first * un));   // (never read below offsets[0])
+    return s;
+}
+
+// The passes on the handle's buffers (under h->mu): the dictionary's build, the probe, with keep gx_select.hip's scans, the entries' count;
+// ONE synchronisation of the stream, where the host reads the totals and checks the capacities; then the emits and the copy.  The
+// caller's outputs are device or host (host_out: staged, and a second wait delivers them).  leave: with device outputs the emits are
+// left running under lookup_event (and select_event); the text form waits for them instead.  counts: also the histogram of outcomes.
+static int lookup_pass(gx_handle* h, const BatchView& v, const GroupImage& gi, const WhereImage& wi, const LookupCall& c, const LookupDict& dict, bool host_out,
+                       bool leave, uint64_t* counts, hipStream_t stream, const std::string& name) {
+    const uint32_t K = static_cast<uint32_t>(h->T.n_rules);
+    const uint64_t n = v.n, m = c.m;
+    gx_lookup_totals& t = *c.totals;
+    t = gx_lookup_totals{};
+    t.entries = m;
+    const bool sel = c.keep != LOOKUP_KEEP_NOTHING;
+    wait_pending(h->lookup_event, h->lookup_pending, stream);
+    SelectWs sw{};
+    if (sel || counts) {
+        wait_pending(h->select_event, h->select_pending, stream);
+        sw = select_workspace(h->select_ws.get(select_workspace_bytes(n, K, sel)), n, K, sel);
+        if (counts) {   // (counts_beside's pass, on the workspace that the probe's flags share)
+            GX_HIP(launch_select_flags(v.ids, v.fmt, v.row_units, K, n, nullptr, 0, sw, stream));
+            GX_HIP(hipMemcpyAsync(counts, sw.counts, static_cast<size_t>(2u * K + 2u) * 8, hipMemcpyDeviceToHost, stream));
+        }
+    }
+    const uint32_t n_slots = group_slots(m);
+    const DevImage img = upload_image(h->lookup_image, &gi.head, sizeof(GroupHead), nullptr, wi, stream);
+    const GroupArgs a{v.data, v.wide ? 1 : 0, v.caps, 2u * static_cast<uint32_t>(h->T.max_groups), img.head, img.terms, static_cast<uint32_t>(wi.bytes.size()),
+                      gi.values ? 1u : 0u, (gi.head.formats || wi.formats) ? 1u : 0u};
+    const LookupWs w = lookup_workspace(h->lookup_table.get(lookup_table_bytes(n_slots, gi.values)), h->lookup_lines.get(lookup_lines_bytes(n, m)), n, m, n_slots, gi.values);
+    GX_HIP(launch_lookup_probe(v.ids, v.fmt, v.row_units, K, n, v.offsets, v.off64 ? 1 : 0, a, dict, c.keep, w, sel ? &sw : nullptr, stream));
+    if (sel) GX_HIP(launch_select_scans(n, sw, stream));
+    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lines_out = 0, units_out = 0;
+    GX_HIP(hipMemcpyAsync(got, w.totals, sizeof(got), hipMemcpyDeviceToHost, stream));
+    if (sel) {
+        GX_HIP(hipMemcpyAsync(&lines_out, sw.idx_off + n, 8, hipMemcpyDeviceToHost, stream));
+        GX_HIP(hipMemcpyAsync(&units_out, sw.dst_off + n, 8, hipMemcpyDeviceToHost, stream));
+    }
+    GX_HIP(hipStreamSynchronize(stream));
+    if (got[2] & 1u) throw GxError(GX_E_LIMIT, name + ": a line or an entry of 4 G code units or more (or offsets that go backwards) cannot be looked up");
+    if (got[2] & 2u) throw GxError(GX_E_ARG, "internal: " + name + ": the dictionary's table is full");
+    if (got[0] != got[1] + got[3] + got[4] || lines_out > n) throw GxError(GX_E_ARG, "internal: " + name + ": the classes do not add up");
+    t.lines = got[0];
+    t.unset = got[1];
+    t.keyed = got[0] - got[1];
+    t.hits = got[3];
+    t.misses = got[4];
+    t.distinct_entries = got[5];
+    t.hit_entries = got[6];
+    t.lines_out = lines_out;
+    t.units_out = units_out;
+    if (!c.any()) return GX_OK;   // size query
+    const gx_lookup_out& o = c.out;
+    const size_t unit = v.wide ? 2 : 1;
+    if (c.per_line() && lines_out > o.cap_lines) return fail(GX_E_LIMIT, name + ": cap_lines is smaller than the result (see totals->lines_out)");
+    if (o.out_bytes && units_out * unit > o.out_bytes_cap) return fail(GX_E_LIMIT, name + ": the kept text is larger than the capacity (see totals->units_out)");
+    if (o.out_offsets && !v.off64 && units_out > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": 4 G code units and more need offsets64");
+    HostTwins twins(host_out);
+    const LookupOut lo{twins.of(o.line_entry, n * 4), twins.of(o.entry_same, m * 4), twins.of(o.entry_lines, m * 8), twins.of(o.entry_first_line, m * 4),
+                       twins.of(reinterpret_cast<uint64_t*>(o.entry_stats), m * 64)};
+    GX_HIP(launch_lookup_emit(n, m, gi.values, w, lo, stream));
+    StagedLinesOut kept;
+    if (c.batch_out()) {
+        kept = stage_lines_out(h, v, LinesOut{o.out_index, o.out_bytes, o.out_offsets, o.out_ids, o.out_caps}, host_out, lines_out, units_out);
+        if (kept.dev.offsets && n == 0) GX_HIP(hipMemsetAsync(kept.dev.offsets, 0, v.off64 ? 8 : 4, stream));
+        GX_HIP(launch_select_copy(kept.dev, v.data, v.offsets, v.off64 ? 1 : 0, v.wide ? 1 : 0, n, sw, stream));
+    }
+    if (host_out) {
+        twins.deliver(stream);
+        kept.deliver(stream);
+        GX_HIP(hipStreamSynchronize(stream));
+    } else if (leave) {
+        leave_pending(h->lookup_event, h->lookup_pending, stream);
+        if (c.batch_out()) leave_pending(h->select_event, h->select_pending, stream);
+    } else {
+        GX_HIP(hipStreamSynchronize(stream));
+    }
+    return GX_OK;
+}
+
+int gx_lookup_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps, const gx_group_part* parts,
+                    uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms, const void* entry_units, const void* entry_offsets, uint64_t n_entries,
+                    uint32_t keep, uint32_t flags, const gx_lookup_out* out, gx_lookup_totals* totals, const gx_batch_opts* opts) {
+    const std::string name = "gx_lookup_lines";
+    return guarded([&]() -> int {
+        if (!h || !offsets || (n && !ids)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        uint32_t row_units = 1;
+        const RowFormat fmt = id_format(h, o, &row_units);
+        LookupCall c{entry_units, entry_offsets, n_entries, keep, out ? *out : gx_lookup_out{}, totals};
+        GroupImage gi;
+        WhereImage wi;
+        lookup_refusals(h, o, parts, n_parts, terms, n_terms, flags, o.utf16 != 0, c, name, &gi, &wi);
+        if (c.out.out_caps && fmt != ROWS_DENSE) return fail(GX_E_ARG, name + ": out_caps on compact rows (out_ids holds whole rows)");
+        if (n >= 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": line numbers are 32 bits and two are kept for \"none\" and \"miss\"; split batches of 2^32 - 1 lines and more");
+        const std::pair<uint64_t, uint64_t> named = lookup_dict_refusals(o, c, name);
+        if ((n_parts || !wi.none()) && fmt == ROWS_DENSE && n && !caps) return fail(GX_E_ARG, name + ": parts and terms on dense ids need caps");
+        if (!o.device_pointers) refuse_long_host_lines({offsets, o.offsets64 != 0, n}, name, "looked up");
+        const size_t slots = 2 * static_cast<size_t>(h->T.max_groups);
+        if (c.out.out_caps && slots && n && !caps) return fail(GX_E_ARG, name + ": out_caps without caps");
+        if (!slots) c.out.out_caps = nullptr;
+        {
+            const gx_lookup_out& b = c.out;
+            const uint64_t ow = o.offsets64 ? 8 : 4, un = o.utf16 ? 2 : 1, idr = static_cast<uint64_t>(row_units) * row_unit_bytes(fmt), m = n_entries;
+            const uint64_t in_units = o.device_pointers ? (n ? 1u : 0u) : HostOffsets{offsets, o.offsets64 != 0, n}[n];
+            const uint64_t cap = std::min<uint64_t>(b.cap_lines, n);   // (no more than n lines leave, whatever the capacity says: n < 2^32, no product wraps)
+            const std::pair<const void*, uint64_t> outs[10] = {{b.line_entry, n * 4}, {b.entry_same, m * 4}, {b.entry_lines, m * 8}, {b.entry_first_line, m * 4},
+                                                               {b.entry_stats, m * 64}, {b.out_index, cap * 4}, {b.out_bytes, b.out_bytes_cap},
+                                                               {b.out_offsets, (cap + 1) * ow}, {b.out_ids, cap * idr}, {b.out_caps, cap * slots * 4}};
+            std::pair<const void*, uint64_t> ins[6] = {{bytes, in_units * un}, {offsets, (n + 1) * ow}, {ids, n * idr}, {fmt == ROWS_DENSE ? caps : nullptr, n * slots * 4}, {}, {}};
+            lookup_dict_ranges(o, c, named, ins + 4);
+            by_key_overlaps(outs, 10, ins, 6, name);
+        }
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        if (fmt != ROWS_DENSE) caps = nullptr;
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        const StagedLines in = stage_lines(h, bytes, offsets, n, ids, caps, o, fmt, row_units, Travels{true, caps != nullptr}, stream, name.c_str());
+        const StagedDict sd = stage_dict(c, o, named, flags, stream);
+        return lookup_pass(h, in.v, gi, wi, c, sd.d, !o.device_pointers, true, nullptr, stream, name);
+    });
+}
+
+int gx_text_lookup_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                         const void* entry_units, const void* entry_offsets, uint64_t n_entries, uint32_t keep, uint32_t flags, const gx_lookup_out* out, uint8_t* kept,
+                         uint64_t kept_cap, void* kept_offsets, uint32_t* kept_index, gx_lookup_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                         const gx_batch_opts* opts) {
+    const std::string name = "gx_text_lookup_lines";
+    return guarded([&]() -> int {
+        if (!h || (size && !text)) return fail(GX_E_ARG, name + ": bad argument");
+        const gx_batch_opts o = read_opts(opts);
+        LookupCall c{entry_units, entry_offsets, n_entries, keep, out ? *out : gx_lookup_out{}, totals};
+        if (c.batch_out()) return fail(GX_E_ARG, name + ": the five batch outputs of `out` must be NULL (kept, kept_offsets and kept_index take the kept lines)");
+        c.out.out_bytes = kept; c.out.out_offsets = kept_offsets; c.out.out_index = kept_index;
+        c.out.cap_lines = ~0ull;   // (sized by the size query: the header)
+        c.out.out_bytes_cap = kept_cap;
+        GroupImage gi;
+        WhereImage wi;
+        lookup_refusals(h, o, parts, n_parts, terms, n_terms, flags, false, c, name, &gi, &wi);
+        const std::pair<uint64_t, uint64_t> named = lookup_dict_refusals(o, c, name);
+        {
+            const gx_lookup_out& b = c.out;
+            const uint64_t m = n_entries;
+            // (the per-line arrays are as long as the text has lines, which nobody knows yet: their first bytes stand for them)
+            const std::pair<const void*, uint64_t> outs[8] = {{b.line_entry, 4}, {b.entry_same, m * 4}, {b.entry_lines, m * 8}, {b.entry_first_line, m * 4},
+                                                              {b.entry_stats, m * 64}, {b.out_bytes, b.out_bytes_cap}, {b.out_offsets, 4}, {b.out_index, 4}};
+            std::pair<const void*, uint64_t> ins[3] = {{text, size}, {}, {}};
+            lookup_dict_ranges(o, c, named, ins + 1);
+            by_key_overlaps(outs, 8, ins, 3, name);
+        }
+        if (size > 0xFFFFFFFFull) return fail(GX_E_LIMIT, name + ": split texts of 4 GiB and more at a line boundary");
+        if (!h->on_device) return fail(GX_E_DEVICE, "handle was created host-only; no device tables (there is no CPU fallback)");
+        GX_HIP(hipSetDevice(h->device));
+        std::lock_guard<std::mutex> lock(h->mu);
+        hipStream_t stream = static_cast<hipStream_t>(o.stream);
+        // the text's lines and the path; then the passes over the ids, offsets and capture rows they left on the device
+        const TextBatch tb = stage_text_lines(h, text, size, o, stream, name.c_str());
+        if (n_lines) *n_lines = tb.v.n;
+        const StagedDict sd = stage_dict(c, o, named, flags, stream);
+        // (the emits read what text_lines left in the handle's scratch buffers, which the next whole-file call overwrites: the pass waits for them)
+        const int rc = lookup_pass(h, tb.v, gi, wi, c, sd.d, !o.device_pointers, false, counts, stream, name);
+        if (promise_broken_since(h, stream)) throw GxError(GX_E_ARG, "internal: " + name + ": a line longer than the split pass reported");
+        return rc;
+    });
 }
 
 // The parts of a gx_bucket_lines call as its kernels read them (gx_bucket.hpp: BucketHead), checked against the handle.  Needs no device.

@@ -324,6 +324,46 @@ hipError_t launch_group_build(const void* ids, RowFormat fmt, uint32_t row_units
 hipError_t launch_group_emit(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
                              const GroupWs& w, const GroupOut& out, uint64_t n_keys, uint64_t key_units, hipStream_t stream);
 
+// The lines of a finished batch looked up in a dictionary the caller supplies (gx_lookup.hip; the rule: gx_lookup.hpp): a table of the
+// entries in gx_group.hpp's form, per entry the lowest entry with its text, its lines, first line and stats, per line its entry.
+struct LookupDict {
+    const void* units;            // the entries' code units (the batch's kind)
+    const void* offsets;          // [m + 1], uint64 or uint32
+    int offsets64;
+    uint64_t m;
+    uint32_t weak_hash;           // GROUP_WEAK_HASH is among the call's flags (the probe reads them from the part image, the build from here)
+};
+// The passes' device workspace: the slots' words (lookup_table_bytes), and the per-entry and per-line arrays (lookup_lines_bytes).
+struct LookupWs {
+    uint32_t n_slots;             // group_slots(m), a power of two
+    uint64_t* table;              // [n_slots] the slot words
+    uint64_t* low;                // [n_slots] the lowest entry with the slot's text (lookup_low_word)
+    uint64_t* head_words;         // [n_slots][GROUP_HEAD_WORDS]
+    uint64_t* stats_words;        // [n_slots][GROUP_STATS_WORDS], with values
+    uint64_t* totals;             // [8]: lines, unset, status bits (1: a line or an entry of 4 G units, 2: the table is full), hits, misses,
+                                  //      distinct entries, hit entries
+    uint32_t* slot_of_entry;      // [m] the entry's slot
+    uint32_t* line_slot;          // [n] the line's slot, LOOKUP_MISS or LOOKUP_NONE
+};
+// what the emit passes write, each part optional (nullptr)
+struct LookupOut {
+    uint32_t* line_entry;
+    uint32_t* entry_same;
+    uint64_t* entry_lines;
+    uint32_t* entry_first_line;
+    uint64_t* entry_stats;        // [m][8]: gx_measure_stats' fields
+};
+size_t lookup_table_zero_bytes(uint32_t n_slots, bool values);
+size_t lookup_table_bytes(uint32_t n_slots, bool values);
+size_t lookup_lines_bytes(uint64_t n, uint64_t m);
+LookupWs lookup_workspace(void* table_mem, void* lines_mem, uint64_t n, uint64_t m, uint32_t n_slots, bool values);
+// Zeroes the slots' words, then (m > 0) k_lookup_build, (n > 0) k_lookup_probe, (m > 0) k_lookup_count: leaves w.totals.  a: the batch as
+// launch_group_build takes it.  keep != 0: the probe also leaves sel->flags and sel->klen for launch_select_scans.
+hipError_t launch_lookup_probe(const void* ids, RowFormat fmt, uint32_t row_units, uint32_t K, uint64_t n, const void* offsets, int offsets64, const GroupArgs& a,
+                               const LookupDict& d, uint32_t keep, const LookupWs& w, const SelectWs* sel, hipStream_t stream);
+// Behind the host's look at w.totals: k_lookup_emit over the entries (when a per-entry output is wanted) and k_lookup_line_entry.
+hipError_t launch_lookup_emit(uint64_t n, uint64_t m, bool values, const LookupWs& w, const LookupOut& out, hipStream_t stream);
+
 // The lines of a finished batch grouped by TWO captured texts (gx_pairs.hip; the rule: gx_pairs.hpp), behind gx_group_lines' passes on
 // the same stream: a second table keyed by (key slot, second text).  The passes' device workspace: the pair slots' words
 // (pairs_table_bytes) and the per-line arrays (pairs_lines_bytes).

@@ -1430,6 +1430,158 @@ class Gorp:
                    key_out_lines=got["key_out_lines"][:k + 1], key_out_units=got["key_out_units"][:k + 1])
         return res, counts, n_lines
 
+    # -- captured texts looked up in a dictionary of the caller's (gx_lookup_lines / gx_text_lookup_lines) -------------------------
+    @staticmethod
+    def _lookup_totals(t):
+        return {f: getattr(t, f) for f, _ in N.gx_lookup_totals._fields_}
+
+    @staticmethod
+    def _lookup_keep(keep):
+        if keep is None or keep is False:
+            return N.GX_LOOKUP_KEEP_NOTHING
+        if isinstance(keep, str):
+            if keep not in ("hits", "others"):
+                raise ValueError('keep: None, "hits" or "others"')
+            return N.GX_LOOKUP_KEEP_HITS if keep == "hits" else N.GX_LOOKUP_KEEP_OTHERS
+        return int(keep)
+
+    @staticmethod
+    def lookup_entries(entries, unit_dtype=np.uint8, offsets_dtype=np.uint32, encoding="latin-1"):
+        """A dictionary for lookup_lines as a CSR pair (units, offsets): from a list of bytes or str (str is encoded: "utf-16-le" for a
+        UTF-16 batch, else `encoding`), from a (units, offsets) pair, or from the dict a group_lines(..., keys="csr") call returned.
+        The arrays are made contiguous and of the batch's unit and offset types."""
+        if isinstance(entries, dict):
+            entries = (entries["key_units"], entries["key_offsets"])
+        if isinstance(entries, tuple) and len(entries) == 2 and isinstance(entries[1], np.ndarray):
+            units = np.ascontiguousarray(entries[0], dtype=unit_dtype)
+            offsets = np.ascontiguousarray(entries[1], dtype=offsets_dtype)
+            if offsets.ndim != 1 or offsets.size < 1:
+                raise ValueError("entry offsets: m + 1 values")
+            return units, offsets
+        enc = "utf-16-le" if np.dtype(unit_dtype) == np.uint16 else encoding
+        raw = [e.encode(enc, "surrogatepass" if enc == "utf-16-le" else "strict") if isinstance(e, str) else bytes(e) for e in entries]
+        width = np.dtype(unit_dtype).itemsize
+        offsets = np.zeros(len(raw) + 1, offsets_dtype)
+        if raw:
+            offsets[1:] = np.cumsum([len(r) // width for r in raw])
+        return np.frombuffer(b"".join(raw), dtype=unit_dtype).copy(), offsets
+
+    def lookup_lines_device(self, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts, entry_units_ptr, entry_offsets_ptr, n_entries, keep=None, where=None,
+                            line_entry_ptr=None, entry_same_ptr=None, entry_lines_ptr=None, entry_first_line_ptr=None, entry_stats_ptr=None, out_index_ptr=None,
+                            out_data_ptr=None, out_offsets_ptr=None, out_ids_ptr=None, out_caps_ptr=None, cap_lines=0, out_bytes_cap=0, offsets64=False,
+                            utf16=False, compact=0, stream=None, device_pointers=True, utf8=False, weak_hash=False):
+        """gx_lookup_lines on device pointers (ints), nothing copied: the dictionary is the CSR at entry_units_ptr / entry_offsets_ptr
+        (n_entries + 1 offsets as wide as the batch's) -- e.g. the key_units / key_offsets a group_lines_device call left on the device.
+        The outputs are the caller's buffers, each optional (none at all: the size query).  keep: None, "hits" or "others".  Returns
+        (rc, totals): rc is GX_OK or GX_E_LIMIT -- then nothing was written and totals says what the kept lines need (lines_out,
+        units_out); every other error raises."""
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-16" if utf16 else "utf-8" if utf8 else "latin-1")
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.device_pointers = 1 if device_pointers else 0
+        o.offsets64 = 1 if offsets64 else 0
+        o.utf16 = 1 if utf16 else 0
+        o.utf8 = 1 if utf8 else 0
+        o.compact_results = int(compact)
+        o.stream = stream
+        out = N.gx_lookup_out(line_entry_ptr, entry_same_ptr, entry_lines_ptr, entry_first_line_ptr, entry_stats_ptr, out_index_ptr, out_data_ptr, out_offsets_ptr,
+                              out_ids_ptr, out_caps_ptr, cap_lines, out_bytes_cap)
+        totals = N.gx_lookup_totals()
+        rc = N.lib().gx_lookup_lines(self._h.ptr, data_ptr, offsets_ptr, n, ids_ptr, caps_ptr, parts.array, parts.n, terms.array, terms.n, entry_units_ptr,
+                                     entry_offsets_ptr, n_entries, self._lookup_keep(keep), N.GX_GROUP_WEAK_HASH if weak_hash else 0, C.byref(out), C.byref(totals),
+                                     C.byref(o))
+        if not (rc == N.GX_E_LIMIT and (totals.lines_out or totals.units_out)):   # (a capacity's GX_E_LIMIT says what is needed; a refusal's says nothing)
+            _check(rc)
+        return rc, self._lookup_totals(totals)
+
+    @staticmethod
+    def _lookup_result(parts, m, line_entry, same, lines, first, stats, totals):
+        return {"line_entry": line_entry, "entry_same": same[:m], "entry_lines": lines[:m], "entry_first_line": first[:m], "totals": totals,
+                "entry_stats": None if stats is None else [{"lines": s.lines, "numbers": s.numbers, "unset": s.unset, "not_numbers": s.not_numbers,
+                                                            "min": s.min if s.numbers else None, "max": s.max if s.numbers else None,
+                                                            "sum": (s.sum_hi << 64) + s.sum_lo} for s in stats[:m]]}
+
+    def lookup_lines(self, data, offsets, ids, rows, parts, entries, keep=None, where=None, utf8=None, weak_hash=False):
+        """gx_lookup_lines on host buffers: what the lines captured as their part's key, looked up in `entries` (Gorp.lookup_entries'
+        input: a list of str or bytes, a (units, offsets) CSR pair, or the dict a group_lines(..., keys="csr") call returned), of the
+        lines on which every term of `where` holds.  data / offsets / ids / rows and utf8 as group_lines takes them.  Returns a dict:
+        line_entry (uint32 per input line: the lowest entry with the line's key, 0xFFFFFFFE: a miss, 0xFFFFFFFF: none), entry_same,
+        entry_lines, entry_first_line (per entry), entry_stats (per entry, a dict as capture_stats gives one without hist; None when no
+        part has a value extractor), totals, and with keep ("hits": wanted.contains(v); "others": !blocked.contains(v), unset lines
+        included) the kept lines in input order as a batch: index, data, offsets, ids, caps (None for compact rows or without caps)."""
+        utf16 = getattr(data, "dtype", None) == np.uint16
+        data = np.ascontiguousarray(data, dtype=np.uint16 if utf16 else np.uint8)
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.dtype not in (np.uint32, np.uint64):
+            raise TypeError("offsets must be uint32 or uint64")
+        if utf8 not in (None, False, "bytes"):
+            raise ValueError('utf8: None or "bytes" (values are read in the units the offsets count)')
+        ids = np.ascontiguousarray(ids)
+        compact = self._ids_format(ids)
+        caps = None if rows is None or compact else np.ascontiguousarray(rows, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        parts = self.group_parts(parts)
+        n = len(offsets) - 1
+        eu, eo = self.lookup_entries(entries, data.dtype, offsets.dtype, "utf-8" if utf8 else "latin-1")
+        m = len(eo) - 1
+        keep = self._lookup_keep(keep)
+        total = int(offsets[n] - offsets[0]) if n else 0
+        line_entry = np.full(n, 0xFFFFFFFF, np.uint32)
+        same, lines, first = np.zeros(max(1, m), np.uint32), np.zeros(max(1, m), np.uint64), np.zeros(max(1, m), np.uint32)
+        stats = (N.gx_measure_stats * max(1, m))() if parts.has_values else None
+        kept = {}
+        if keep:   # no selection is larger than its input
+            kept = dict(index=np.zeros(n, np.uint32), data=np.zeros(total, data.dtype), offsets=np.zeros(n + 1, offsets.dtype), ids=np.zeros(ids.shape, ids.dtype),
+                        caps=None if caps is None else np.zeros((n, 2 * self.max_groups), np.int32))
+        kp = lambda k: kept[k].ctypes.data if kept.get(k) is not None else None
+        rc, totals = self.lookup_lines_device(ptr(data), offsets.ctypes.data, n, ptr(ids), ptr(caps), parts, ptr(eu), eo.ctypes.data if m else None, m, keep, where,
+                                              line_entry.ctypes.data, same.ctypes.data, lines.ctypes.data, first.ctypes.data,
+                                              None if stats is None else C.addressof(stats), kp("index"), kp("data"), kp("offsets"), kp("ids"), kp("caps"),
+                                              cap_lines=n, out_bytes_cap=total * data.itemsize, offsets64=offsets.dtype == np.uint64, utf16=utf16, compact=compact,
+                                              device_pointers=False, utf8=bool(utf8), weak_hash=weak_hash)
+        _check(rc)
+        res = self._lookup_result(parts, m, line_entry, same, lines, first, stats, totals)
+        if keep:
+            k = totals["lines_out"]
+            res.update(index=kept["index"][:k], data=kept["data"][:totals["units_out"]], offsets=kept["offsets"][:k + 1], ids=kept["ids"][:k],
+                       caps=None if kept["caps"] is None else kept["caps"][:k])
+        return res
+
+    def text_lookup_lines(self, text, parts, entries, keep=None, where=None, utf8=False, weak_hash=False):
+        """gx_text_lookup_lines on a host buffer: raw text -> lines -> extraction -> lookup_lines.  Returns (the dict lookup_lines returns
+        without ids and caps: data holds the kept lines' original bytes, offsets (uint32) delimits them, index holds line numbers of
+        the text; counts uint64[2K + 2] of outcomes; n_lines)."""
+        raw = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        parts = self.group_parts(parts)
+        terms = self.where_terms([] if where is None else where, units="utf-8" if utf8 else "latin-1")
+        cap_lines = int(np.count_nonzero(raw == 10)) + int(np.count_nonzero(raw == 13)) + 1   # (no more lines than line ends, plus the last)
+        eu, eo = self.lookup_entries(entries, np.uint8, np.uint32, "utf-8" if utf8 else "latin-1")
+        m = len(eo) - 1
+        keep = self._lookup_keep(keep)
+        line_entry = np.full(cap_lines, 0xFFFFFFFF, np.uint32)
+        same, lines, first = np.zeros(max(1, m), np.uint32), np.zeros(max(1, m), np.uint64), np.zeros(max(1, m), np.uint32)
+        stats = (N.gx_measure_stats * max(1, m))() if parts.has_values else None
+        index, data, koff = np.zeros(cap_lines, np.uint32), np.zeros(max(1, raw.size), np.uint8), np.zeros(cap_lines + 1, np.uint32)
+        counts = np.zeros(2 * self.num_extractions + 2, np.uint64)
+        o = N.gx_batch_opts()
+        o.struct_size = C.sizeof(N.gx_batch_opts)
+        o.utf8 = 1 if utf8 else 0
+        out = N.gx_lookup_out(line_entry.ctypes.data, same.ctypes.data, lines.ctypes.data, first.ctypes.data, None if stats is None else C.addressof(stats),
+                              None, None, None, None, None, 0, 0)
+        totals = N.gx_lookup_totals()
+        nl = C.c_uint64(0)
+        _check(N.lib().gx_text_lookup_lines(self._h.ptr, raw.ctypes.data if raw.size else None, raw.size, parts.array, parts.n, terms.array, terms.n,
+                                            eu.ctypes.data if eu.size else None, eo.ctypes.data if m else None, m, keep, N.GX_GROUP_WEAK_HASH if weak_hash else 0,
+                                            C.byref(out), data.ctypes.data if keep else None, raw.size, koff.ctypes.data if keep else None,
+                                            index.ctypes.data if keep else None, C.byref(totals), counts.ctypes.data, C.byref(nl), C.byref(o)))
+        totals = self._lookup_totals(totals)
+        res = self._lookup_result(parts, m, line_entry[:nl.value], same, lines, first, stats, totals)
+        if keep:
+            k = totals["lines_out"]
+            res.update(index=index[:k], data=data[:totals["units_out"]], offsets=koff[:k + 1])
+        return res, counts, nl.value
+
     # -- lines grouped by two captured texts (gx_group_pairs / gx_text_group_pairs) ----------------------------------------------
     def pair_parts(self, spec):
         """Resolves a list of (extraction, key extractor, second extractor[, value extractor]) into (GroupParts, int32 second groups):

@@ -539,6 +539,66 @@ public:
         if (nLines) *nLines = lines;
         return r;
     }
+    // Captured texts looked up in a dictionary of the caller's (gx_lookup_lines): the caller's wanted.contains(r.asMap().get("user")) and
+    // meta = byHost.get(r.asMap().get("host")) (README.md:26,63-79).  Parts are groupParts'; entries are the dictionary's texts, and the
+    // lowest of several equal entries stands for them all (entrySame).  lineEntry: per input line the entry its key equals,
+    // GX_LOOKUP_MISS or GX_LOOKUP_NONE; entryLines, entryFirstLine and -- when a part has a value -- entryStats per entry.  With keep the
+    // kept lines leave in input order as a new batch (index, bytes, offsets, ids, caps; textLookupLines: ids and caps stay empty and index
+    // holds lines of the text).
+    struct Lookup {
+        std::vector<uint32_t> lineEntry, entrySame;
+        std::vector<uint64_t> entryLines;
+        std::vector<uint32_t> entryFirstLine;
+        std::vector<gx_measure_stats> entryStats;   // empty when no part has a value
+        std::vector<uint32_t> index;
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> offsets;
+        std::vector<int32_t> ids, caps;
+        gx_lookup_totals totals{};
+    };
+    Lookup lookupLines(const uint8_t* bytes, const uint32_t* offsets, uint64_t n, const int32_t* match_id, const int32_t* caps, const GroupParts& parts,
+                       const std::vector<std::string>& entries, uint32_t keep = GX_LOOKUP_KEEP_NOTHING, const Where* where = nullptr) const {
+        const size_t slots = 2 * static_cast<size_t>(gx_max_groups(h_));
+        return lookupOf(parts, entries, keep, where, n, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const void* eu, const void* eo,
+                                                             Lookup& r, bool deliver) {
+            gx_lookup_out out = lookupOut(r, deliver);
+            if (deliver && keep != GX_LOOKUP_KEEP_NOTHING) {
+                const size_t m = static_cast<size_t>(r.totals.lines_out);
+                r.ids.assign(m + 1, 0);
+                r.caps.assign(m * slots + 1, 0);
+                out.out_index = r.index.data(); out.out_bytes = r.bytes.data(); out.out_offsets = r.offsets.data(); out.out_ids = r.ids.data();
+                out.out_caps = caps && slots ? r.caps.data() : nullptr;
+                out.cap_lines = m; out.out_bytes_cap = r.totals.units_out;
+            }
+            const int rc = gx_lookup_lines(h_, bytes, offsets, n, match_id, caps, p, np, t, nt, eu, eo, entries.size(), keep, 0, deliver ? &out : nullptr, &r.totals, nullptr);
+            if (deliver) {
+                r.ids.resize(static_cast<size_t>(r.totals.lines_out));
+                r.caps.resize(caps ? r.ids.size() * slots : 0);
+            }
+            return rc;
+        });
+    }
+    // Whole files: raw text in, the same lookup out (gx_text_lookup_lines); bytes holds the kept lines' original bytes, cut at offsets.
+    Lookup textLookupLines(const std::string& text, const GroupParts& parts, const std::vector<std::string>& entries, uint32_t keep = GX_LOOKUP_KEEP_NOTHING,
+                           const Where* where = nullptr, std::vector<uint64_t>* counts = nullptr, uint64_t* nLines = nullptr, bool utf8 = false) const {
+        if (counts) counts->assign(2 * extractions_.size() + 2, 0);
+        gx_batch_opts o{};
+        o.struct_size = sizeof(o);
+        o.utf8 = utf8 ? 1u : 0u;
+        uint64_t lines = 0;
+        for (char c : text) lines += (c == '\n' || c == '\r') ? 1u : 0u;   // (no more lines than line ends, plus the last)
+        Lookup r = lookupOf(parts, entries, keep, where, lines + 1, [&](const gx_group_part* p, uint32_t np, const gx_where_term* t, uint32_t nt, const void* eu,
+                                                                         const void* eo, Lookup& l, bool deliver) {
+            const gx_lookup_out out = lookupOut(l, deliver);
+            const bool kept = deliver && keep != GX_LOOKUP_KEEP_NOTHING;
+            return gx_text_lookup_lines(h_, reinterpret_cast<const uint8_t*>(text.data()), text.size(), p, np, t, nt, eu, eo, entries.size(), keep, 0,
+                                        deliver ? &out : nullptr, kept ? l.bytes.data() : nullptr, l.totals.units_out, kept ? l.offsets.data() : nullptr,
+                                        kept ? l.index.data() : nullptr, &l.totals, counts ? counts->data() : nullptr, &lines, utf8 ? &o : nullptr);
+        });
+        r.lineEntry.resize(static_cast<size_t>(lines));
+        if (nLines) *nLines = lines;
+        return r;
+    }
     // Lines grouped by TWO captured texts (gx_group_pairs): the caller's seen.computeIfAbsent(r.asMap().get("verb"), v -> new
     // HashSet<>()).add(r.asMap().get("path")) and byBoth.merge(List.of(verb, path), 1L, Long::sum) (README.md:26,63-79).  The parts of a
     // call are groupParts' plus a SECOND extractor per part (an empty name, or -1: the part's lines have a key and no second):
@@ -1249,6 +1309,60 @@ private:
         if (rc != GX_OK) throw GorpError(rc, gx_last_error());
         for (size_t j = 0; j < k; ++j) g.keys.emplace_back(reinterpret_cast<const char*>(units.data()) + offsets[j], offsets[j + 1] - offsets[j]);
         return g;
+    }
+    // lookupLines and textLookupLines: the entries as a CSR; with keep the size query, then the call with exactly the sizes it reported
+    // (linesCap: the lines, or no fewer).  call(parts, n, terms, n, entry units, entry offsets, result, deliver).
+    static gx_lookup_out lookupOut(Lookup& r, bool deliver) {
+        gx_lookup_out out{};
+        if (!deliver) return out;
+        out.line_entry = r.lineEntry.data();
+        out.entry_same = r.entrySame.data();
+        out.entry_lines = r.entryLines.data();
+        out.entry_first_line = r.entryFirstLine.data();
+        out.entry_stats = r.entryStats.empty() ? nullptr : r.entryStats.data();
+        return out;
+    }
+    template <typename Call>
+    Lookup lookupOf(const GroupParts& parts, const std::vector<std::string>& entries, uint32_t keep, const Where* where, uint64_t linesCap, Call&& call) const {
+        const std::vector<gx_group_part>& p = parts.parts();
+        const std::vector<gx_where_term> terms = where ? where->terms() : std::vector<gx_where_term>();
+        const uint32_t np = static_cast<uint32_t>(p.size()), nt = static_cast<uint32_t>(terms.size());
+        std::string units;
+        std::vector<uint32_t> eoff(1, 0);
+        for (const std::string& e : entries) {
+            units += e;
+            eoff.push_back(static_cast<uint32_t>(units.size()));
+        }
+        const size_t m = entries.size();
+        Lookup r;
+        int rc = GX_OK;
+        if (keep != GX_LOOKUP_KEEP_NOTHING) {
+            rc = call(p.data(), np, terms.data(), nt, units.data(), eoff.data(), r, false);   // the size query
+            if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        }
+        const size_t kept = static_cast<size_t>(r.totals.lines_out);
+        r.lineEntry.assign(static_cast<size_t>(linesCap) + 1, GX_LOOKUP_NONE);
+        r.entrySame.assign(m + 1, 0);
+        r.entryLines.assign(m + 1, 0);
+        r.entryFirstLine.assign(m + 1, 0xFFFFFFFFu);
+        if (parts.hasValues()) r.entryStats.assign(m + 1, gx_measure_stats{});
+        if (keep != GX_LOOKUP_KEEP_NOTHING) {
+            r.index.assign(kept + 1, 0);
+            r.bytes.assign(static_cast<size_t>(r.totals.units_out) + 1, 0);
+            r.offsets.assign(kept + 1, 0);
+        }
+        rc = call(p.data(), np, terms.data(), nt, units.data(), eoff.data(), r, true);
+        if (rc != GX_OK) throw GorpError(rc, gx_last_error());
+        r.lineEntry.resize(static_cast<size_t>(linesCap));
+        r.entrySame.resize(m);
+        r.entryLines.resize(m);
+        r.entryFirstLine.resize(m);
+        if (!r.entryStats.empty()) r.entryStats.resize(m);
+        if (keep != GX_LOOKUP_KEEP_NOTHING) {
+            r.index.resize(kept);
+            r.bytes.resize(static_cast<size_t>(r.totals.units_out));
+        }
+        return r;
     }
     // groupsOf's scheme for bucketLines: the size query with a table for a modest number of buckets, once more with as many buckets as
     // lines if that table overflows, then the call with exactly the size it reported.

@@ -1441,6 +1441,93 @@ int gx_text_group_windows(gx_handle* h, const uint8_t* text, uint64_t size, cons
                           uint32_t flags, const gx_group_out* keys, const gx_windows_out* windows, gx_windows_totals* totals, uint64_t* counts,
                           uint64_t* n_lines, const gx_batch_opts* opts);
 
+/* ---- Captured texts looked up in a dictionary of the caller's, on the device.  The reference's caller does this right behind the
+ * extraction, against a set or a map that it holds from elsewhere (README.md:26,63-79):
+ *     if (r != null && wanted.contains(r.asMap().get("user"))) ...        meta = byHost.get(r.asMap().get("host"));
+ * membership ("the requests of these 40 000 customers", "drop every line whose client ip is on the blocklist"), enrichment (the row of
+ * the line's value in a dimension table) and ONE key space across batches (the keys that gx_group_lines left for batch A, looked up
+ * for batch B).
+ * THE DICTIONARY is n_entries texts, 0 <= n_entries <= 2^30, as a CSR: entry j is entry_units[entry_offsets[j], entry_offsets[j + 1])
+ * in the batch's own code units (bytes; 16-bit units with opts->utf16; UTF-8 bytes with utf8 = 1); entry_offsets holds n_entries + 1
+ * offsets, uint32 or uint64 as opts->offsets64 says, and entry_offsets[0] need not be 0 -- exactly how gx_group_out.key_units and
+ * key_offsets leave.  With device_pointers both arrays lie on the device, else they are host memory and staged.  The empty entry is an
+ * entry like any other.  Two entries with the same units are DUPLICATES and the lowest entry number stands for them all
+ * (index.putIfAbsent(entry[j], j) for ascending j): entry_same[j] is that number, j itself for the first entry with a text.
+ * PARTS are gx_group_part as they are (extraction, key_group, optional value_group; at most one part per extraction; all parts share the
+ * ONE dictionary), TERMS gx_where_term as they are; "a line counts", the key's pair, its set-or-unset test (a pair that names no value
+ * is never dereferenced) and key equality (the same number of units and the same units) are gx_group_lines' word for word.  A line that
+ * counts is exactly one of: UNSET (its key pair names no value), a HIT (its key is some entry's text) or a MISS (the pair is set and no
+ * entry has its text; every keyed line when n_entries == 0).  lines == keyed + unset, keyed == hits + misses.
+ * Every output is exact and the same bits on every run.  GX_GROUP_WEAK_HASH is accepted as the same test hook: identical results. */
+#define GX_LOOKUP_NONE 0xFFFFFFFFu   /* line_entry: the line does not count, or its key pair names no value */
+#define GX_LOOKUP_MISS 0xFFFFFFFEu   /* line_entry: the line's key is set and is no entry */
+enum { GX_LOOKUP_KEEP_NOTHING = 0, GX_LOOKUP_KEEP_HITS = 1, GX_LOOKUP_KEEP_OTHERS = 2 };
+
+typedef struct gx_lookup_out {       /* 96 bytes; every pointer optional; device memory with opts->device_pointers, else host */
+    uint32_t* line_entry;            /* n: entry_same of the entry the line's key equals, else GX_LOOKUP_MISS / GX_LOOKUP_NONE */
+    uint32_t* entry_same;            /* m: the lowest entry with entry j's text */
+    uint64_t* entry_lines;           /* m: lines that hit entry j; 0 where entry_same[j] != j */
+    uint32_t* entry_first_line;      /* m: the first input line that hits entry j, 0xFFFFFFFF: none */
+    gx_measure_stats* entry_stats;   /* m: over entry j's lines whose part has a value_group (gx_group_out.key_stats' rule) */
+    uint32_t* out_index;             /* with keep != 0: the kept lines as a new CSR batch, gx_select_lines_where's five outputs */
+    void*     out_bytes;
+    void*     out_offsets;
+    void*     out_ids;
+    int32_t*  out_caps;
+    uint64_t  cap_lines, out_bytes_cap;   /* as in gx_by_key_out: lines; BYTES */
+} gx_lookup_out;
+
+typedef struct gx_lookup_totals {    /* 80 bytes; host, always */
+    uint64_t entries, distinct_entries, hit_entries;   /* m; entries with entry_same[j] == j; ... of those with at least one line */
+    uint64_t lines, keyed, unset, hits, misses;
+    uint64_t lines_out, units_out;   /* what keep keeps; 0 with GX_LOOKUP_KEEP_NOTHING */
+} gx_lookup_totals;
+
+/* gx_lookup_lines.
+ * HOW THE BATCH IS READ: exactly as gx_group_lines reads it (row formats int32 + dense, u16 and u8; offsets64; utf16; utf8 = 1; staging
+ * or device_pointers; the stream).
+ * KEEP: GX_LOOKUP_KEEP_HITS keeps the lines that count and hit (wanted.contains(v)); GX_LOOKUP_KEEP_OTHERS keeps the lines that count
+ * and do not hit, misses and unset alike (!blocked.contains(v), v == null included).  Lines that do not count are never kept.  Kept lines
+ * leave in input order, copied as gx_select_lines copies one: out_index, out_bytes, out_offsets (the width of the input's), out_ids and
+ * out_caps in the input's row format -- an ordinary batch for every other call.  With GX_LOOKUP_KEEP_NOTHING the five must be NULL.
+ * entry_stats: gx_group_out.key_stats' rule (lines == numbers + unset + not_numbers; min and max INT64_MAX and INT64_MIN without a
+ * number; the 128-bit sum exact; the parts' number formats honoured); an entry with entry_same[j] != j has the stats of nothing.
+ * SIZE QUERY: out == NULL or every pointer NULL: only *totals is filled.  n is always a sufficient cap_lines.
+ * GX_E_LIMIT with nothing written to any output and *totals filled: cap_lines < lines_out with a per-line batch output; out_bytes_cap
+ * too small; 32-bit out_offsets with 2^32 units and more.  GX_E_LIMIT before the device is looked at: n_entries > 2^30; n >= 2^32 - 1;
+ * more than 64 parts or terms.  GX_E_LIMIT from the offsets: a line or an entry of 2^32 units and more, or offsets that go backwards --
+ * found on the host for host offsets, with device_pointers by the pass that reads them.
+ * GX_E_ARG, in this order: h, offsets or (n > 0) ids NULL; every refusal gx_group_lines makes of totals == NULL, flags, parts, utf8 = 2,
+ * terms and no_sync; entry_stats where no part has a value_group; keep > 2; a batch output with GX_LOOKUP_KEEP_NOTHING; out_caps on
+ * compact rows; entry_offsets == NULL with n_entries > 0; [the limits above]; parts or terms on dense ids without caps; out_caps
+ * without caps; entry_units == NULL where host offsets name a unit; an output that overlaps an input or the dictionary.  All of these
+ * come before the device is looked at: a host-only handle gives them, and GX_E_DEVICE after them (there is no CPU path).
+ * EMPTY INPUTS: n == 0, n_parts == 0 and n_entries == 0 are legal (entry_same is delivered whatever the lines are).
+ * HOST WAITS: ONE wait, in which the host reads the totals, lines_out and units_out among them (gx_select.hip's scans run behind the
+ * probe on the same stream).  With host outputs a second wait delivers them.  With device_pointers the emit and the copy are left
+ * running on opts->stream when the call returns; the handle's next call on another stream waits for them, and the batch and the
+ * dictionary must stay unchanged until they have run.
+ * WORKSPACE: on the handle until gx_destroy: two to four table slots per entry (64 at least) of 32 bytes each, 96 with a value group;
+ * 4 bytes per entry; 4 per line; with keep gx_select_lines' 21 per line. */
+int gx_lookup_lines(gx_handle* h, const void* bytes, const void* offsets, uint64_t n, const void* ids, const int32_t* caps,
+                    const gx_group_part* parts, uint32_t n_parts, const gx_where_term* terms, uint32_t n_terms,
+                    const void* entry_units, const void* entry_offsets, uint64_t n_entries, uint32_t keep, uint32_t flags,
+                    const gx_lookup_out* out, gx_lookup_totals* totals, const gx_batch_opts* opts);
+
+/* The whole-file form, gx_text_group_lines' chain with the lookup at its end: raw text -> lines -> the match-and-extract path -> the
+ * lookup.  `out` carries the per-line and per-entry arrays only (its five batch pointers must be NULL: GX_E_ARG); line_entry holds one
+ * entry per line of the text.  kept, kept_offsets and kept_index are gx_text_lines_by_key's out, out_offsets and out_index -- the kept
+ * lines' original bytes one after the other, terminators included, as gx_text_select writes them (kept_cap BYTES; units_out counts
+ * them), their lines + 1 offsets (32-bit) and their line numbers in the text -- sized by the size query (all three NULL:
+ * totals->lines_out and units_out); they must be NULL with GX_LOOKUP_KEEP_NOTHING.  The dictionary's
+ * offsets are as wide as opts->offsets64 says.  counts and *n_lines as gx_text_group_lines delivers them.  Like every gx_text_* call it
+ * returns with all its work on opts->stream done. */
+int gx_text_lookup_lines(gx_handle* h, const uint8_t* text, uint64_t size, const gx_group_part* parts, uint32_t n_parts,
+                         const gx_where_term* terms, uint32_t n_terms, const void* entry_units, const void* entry_offsets,
+                         uint64_t n_entries, uint32_t keep, uint32_t flags, const gx_lookup_out* out, uint8_t* kept, uint64_t kept_cap,
+                         void* kept_offsets, uint32_t* kept_index, gx_lookup_totals* totals, uint64_t* counts, uint64_t* n_lines,
+                         const gx_batch_opts* opts);
+
 /* The whole-file form, next to gx_text_to_jsonl: one homogeneous JSON Lines stream per extraction.  The output is what
  * gx_text_to_jsonl writes with its lines regrouped stably by extraction: extraction 0's objects first, in the order of their lines,
  * then extraction 1's, and so on.  group_out (host, optional, uint64_t[K + 1]): extraction k's objects are
